@@ -25,6 +25,17 @@
            `python bench.py --gpus N` from a bare shell starts its N ranks itself (the parent never
            touches the GPU); under torch.distributed.run it uses the ranks it is given.
 
+A plain run sets up (context, scene, structure builds, pt_tune), runs the --warmup steps (repeated until the
+device has been busy --clock-warmup-ms), times the --steps steps and prints the line: `value`, `ms_per_step`, the
+workload, `segments` and `roofline` from the timed launches' own HIP events (`executed` and the model `frac` of a
+walk kernel are null: they need the measuring twin).  `--full` adds every leg that runs or checks anything else,
+each after the timed region except `first_frame`: `first_frame`, `gather_check` (the digest verdict),
+`roofline.executed`, `list_walk`, `cpu_baseline` and, N > 1, `weak_series`; the --no-* switches leave single legs
+out of a --full run.  `--dump-outputs DIR` writes what the timed steps computed — `accum.npy` (height, width, 4)
+fp32, the frame's radiance sums with spp in the 4th channel, and `segments.npy`; `--config default`: `canvas.npy`,
+the last frame's RGBA8 canvas as fp32 — at most 64 MB in all (a larger frame: a fixed, seeded sample of its pixels
+and `accum_index.npy`).  The inputs depend on the flags alone, so two builds can be compared file for file.
+
 Prints ONE JSON line on rank 0.  `roofline` prices the path-tracing kernel against the FP32
 vector peak (the path has no dense contraction and ~1e5 FLOP per HBM byte):
 `frac` is EXECUTED lane-level fp32 work (from the kernel's own tallies, measuring twin run after
@@ -258,6 +269,37 @@ def frame_digest(full):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float32).tobytes()).hexdigest()
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: all files together, headers included
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: {name: array} as out_dir/<name>.npy, float64 arrays as float64, everything else as float32, smallest first.
+    An array that does not fit in what is left of `budget` is written as a fixed, seeded sample of its pixels (the leading axes
+    flattened; same seed, same pixels, in ascending order) with their flat indices beside it in <name>_index.npy (float64).
+    Returns {file name: shape}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    header = 128  # one .npy header (numpy writes 128 bytes for these shapes)
+    left = budget
+    written = {}
+    for name in sorted(arrs, key=lambda k: (arrs[k].nbytes, k)):
+        a = arrs[name]
+        if a.nbytes + header > left:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            k = max(0, min(len(rows), (left - 2 * header) // (rows.itemsize * rows.shape[1] + 8)))
+            idx = np.sort(np.random.default_rng(seed).choice(len(rows), size=k, replace=False))
+            a = rows[idx] if a.ndim > 1 else rows[idx, 0]
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            written[name + "_index.npy"] = idx.shape
+            left -= idx.size * 8 + header
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name + ".npy"] = a.shape
+        left -= a.nbytes + header
+    return written
+
+
 def load_digests():
     try:
         return json.load(open(os.path.join(ROOT, "tests", "golden", "full_frame_digests.json")))
@@ -358,7 +400,16 @@ def main():
                     help="self-started ranks (--gpus N from a bare shell): end the job after this many seconds (0 = never)")
     ap.add_argument("--spawn-selftest", default="", choices=["", "ok", "fail", "die-early", "die-in-collective", "hang"],
                     help="CPU-only check of the self-launch path: ranks rendezvous over gloo and report (tests/test_dist_cpu.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the cold first frame, the digest check of the frame, the measuring twin, "
+                         "the list walk, the CPU baseline, N > 1's weak-scaling point; --config default: the host-issued and paused legs and "
+                         "the group's trace launch on its own.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (rank 0) as DIR/<name>.npy: float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if not args.full:  # a plain run: only what the headline needs (the --no-* switches below say what --full adds)
+        args.no_first_frame = args.no_work_count = args.no_list_walk = args.no_cpu_baseline = True
+        args.no_weak_series = args.no_extra_legs = True
 
     ipc_env()  # before torch / HIP is loaded, for every launch style
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -523,6 +574,8 @@ def main():
     wall = float(elapsed.item())
     segments = float(sum(float(x[0]) for x in per_rank))
     per_rank_kernel_ms = [round(float(x[1]), 3) for x in per_rank]
+    if args.dump_outputs and rank == 0:  # before any leg below reuses the accumulation buffer
+        dump_outputs(args.dump_outputs, {"accum": full[: p.height].detach().cpu().numpy(), "segments": np.array([segments])})
 
     # RCCL parity: the gathered frame against the committed single-GPU digest of the config's converged frame
     # (passes of 16 spp, decorrelated pass times, 50 bounces: tests/golden/full_frame_digests.json).  When the timed
@@ -535,7 +588,7 @@ def main():
     digest_sized = (width == cfg["width"] and height == cfg["height"] and args.spp_per_pass == 16 and args.max_depth == 50)
     timed_is_digest = digest_sized and not weak and total_passes * args.spp_per_pass == converged_spp
     want = load_digests().get(cfg["digest"]) if digest_sized else None
-    if want:
+    if want and args.full:
         if timed_is_digest:
             check_frame, check_seg, check_src = full, segments, "the timed region's frame"
         else:
@@ -557,7 +610,7 @@ def main():
                             "matches": got == want["sha256"],
                             "segments_match": int(check_seg) == int(want["segments"]),
                             "frame": check_src}
-    elif rank == 0:
+    elif rank == 0 and args.full:
         gather_check = {"matches": None, "frame": "no committed digest for this size / pass shape (non-default --width/--height/--spp-per-pass/--max-depth)"}
 
     # the other scaling mode, timed after the main region with the same barriers (N > 1 only)
@@ -788,6 +841,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": "%s: %s (%d spheres), %dx%d, %d bounces, %d spp/step (%d passes x %d spp) x %d steps = %d spp"
                             % (cfg["name"], cfg["what"], n_sph, p.width, p.height, args.max_depth, spp_step, pps, args.spp_per_pass, steps, spp_step * steps),
@@ -908,10 +962,21 @@ def frame_loop_bench(args):
     25-spp paused mode (src/webgl.rs:342-346) is timed beside it.  Like the main line it carries
     `roofline` (the trace launch of one group of 64 frames: pt_trace_kernel_small_t1, a LIST kernel, so
     executed work = algorithmic work) and `cpu_baseline` (the oracle replaying the same ticks: one
-    1-spp pass + the shader's blend per tick, on this host's cores)."""
+    1-spp pass + the shader's blend per tick, on this host's cores).  `--steps` (else `--frames`) sets the number of timed
+    frames; without --full the line has the animation loop alone (no other legs, no roofline, no cpu_baseline)."""
     from ray_tracer_webgl_amd.app import frame_loop_benchmark
 
-    out = frame_loop_benchmark(args.frames, args.warmup, extra_legs=not args.no_extra_legs)
+    def dump(loop):  # the canvas after the last timed frame: RGBA8, what the reference puts on screen
+        dump_outputs(args.dump_outputs, {"canvas": loop.canvas})
+
+    n_frames = args.steps if args.steps is not None else args.frames
+    out = frame_loop_benchmark(n_frames, args.warmup, extra_legs=not args.no_extra_legs, kernel_leg=args.full,
+                               after_timed=dump if args.dump_outputs else None)
+    out["full"] = args.full
+    if not args.full:
+        out["build"] = build_identity()
+        print(json.dumps(out), flush=True)
+        return 0
     g = out["group_trace_kernel"]
     t_launch = g["avg_launch_ms"] * 1e-3
     # a list kernel tests every sphere for every segment (static/shader.frag:175-196): 20 FLOP each, + ~150 per segment of scatter / RNG / camera

@@ -12,12 +12,12 @@ export TMPDIR=/tmp
 # know fails only its own pass (see pmc6.log).
 PT_PMC_CLASSES=${PT_PMC_CLASSES:-SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_ADD_F16 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_FMA_F64}
 if [ "${PT_COLLECT_MAIN:-1}" = "1" ]; then
-BENCH="python3 bench.py --no-cpu-baseline --no-work-count"   # the default workload (config 2, 16 steps = 1024 spp); keeps the list-walk leg: the scalar list kernel is in the same trace
+BENCH="python3 bench.py --full --no-cpu-baseline --no-work-count"   # the default workload (config 2, 16 steps = 1024 spp); keeps the list-walk leg: the scalar list kernel is in the same trace
 timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- $BENCH > $OUT/kt.log 2>&1
 # the other BASELINE configs (one launch each after pt_tune): kernel trace only
 timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_configs -- python3 tools/config_sweep.py config3 config4 config5 default > $OUT/kt_configs.log 2>&1
 # the reference's own operating point: the animation loop replayed from a hipGraph (bench.py --config default)
-timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_frames -- python3 bench.py --config default --frames 200 > $OUT/kt_frames.log 2>&1
+timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_frames -- python3 bench.py --full --config default --frames 200 > $OUT/kt_frames.log 2>&1
 i=0
 for grp in \
   "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_LDS SQ_INSTS_SALU" \
@@ -38,10 +38,10 @@ fi  # PT_COLLECT_MAIN=0 skips the config-2 part (PT_COLLECT_CONFIGS="4" re-colle
 for CFG in ${PT_COLLECT_CONFIGS-3 4 5 default}; do  # (PT_COLLECT_CONFIGS="" collects config 2 only)
   OC=gpurun_out/prof_${TAG}_c$CFG
   mkdir -p $OC
-  BC="python3 bench.py --config $CFG --no-cpu-baseline --no-work-count --no-list-walk --no-first-frame"
+  BC="python3 bench.py --full --config $CFG --no-cpu-baseline --no-work-count --no-list-walk --no-first-frame"
   # the reference's own operating point: only the replayed animation loop + the group's trace launch on its own
   # (the longest pt_trace_kernel_small_t1 dispatches are then the groups of 16 frames, which summarize.py keeps)
-  if [ "$CFG" = "default" ]; then BC="python3 bench.py --config default --no-cpu-baseline --no-extra-legs --frames 640"; fi
+  if [ "$CFG" = "default" ]; then BC="python3 bench.py --full --config default --no-cpu-baseline --no-extra-legs --frames 640"; fi
   timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OC/kt -- $BC > $OC/kt.log 2>&1
   i=0
   for grp in \

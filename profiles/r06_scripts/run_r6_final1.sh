@@ -9,16 +9,16 @@ tail -4 $O/pytest.txt
 [ $rc -eq 0 ] || exit 1
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { tail -20 $O/smoke.txt; exit 1; }
 tail -4 $O/smoke.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err || { tail -20 $O/bench_driver_flags.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err || { tail -20 $O/bench_driver_flags.err; exit 1; }
 echo "driver flags done" >> $O/progress.txt
-timeout -k 10 300 python bench.py > $O/bench_config2.json 2> $O/bench_config2.err || { tail -20 $O/bench_config2.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench_config2.json 2> $O/bench_config2.err || { tail -20 $O/bench_config2.err; exit 1; }
 echo "config 2 done" >> $O/progress.txt
 for cfg in 3 4 5 default; do
-  timeout -k 10 500 python bench.py --config $cfg > $O/bench_config$cfg.json 2> $O/bench_config$cfg.err || { tail -20 $O/bench_config$cfg.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --config $cfg > $O/bench_config$cfg.json 2> $O/bench_config$cfg.err || { tail -20 $O/bench_config$cfg.err; exit 1; }
   echo "config $cfg done" >> $O/progress.txt
 done
 for N in 4 6; do
-  timeout -k 10 500 python bench.py --gpus $N --backend gloo --same-device --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${N}ranks_one_device.json 2> $O/bench_${N}ranks.err || { tail -20 $O/bench_${N}ranks.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --gpus $N --backend gloo --same-device --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${N}ranks_one_device.json 2> $O/bench_${N}ranks.err || { tail -20 $O/bench_${N}ranks.err; exit 1; }
   echo "$N ranks done" >> $O/progress.txt
 done
 timeout -k 10 600 python tools/rehearse_ranks.py --ranks 8 --config 2 --steps 20 --warmup 5 --again > $O/rehearse_8ranks_config2.json 2> $O/rehearse8.err || { tail -20 $O/rehearse8.err; exit 1; }

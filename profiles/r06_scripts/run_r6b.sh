@@ -6,7 +6,7 @@ timeout -k 10 1100 python -m pytest tests -x -q -m gpu --durations=12 > $O/pytes
 tail -16 $O/pytest_gpu.txt
 # (a) bench.py's N > 1 path with as many rank processes as the box admits on its card (six), uneven shares at 4, the driver's flags
 for N in 4 6; do
-  timeout -k 10 500 python bench.py --gpus $N --backend gloo --same-device --steps 20 --warmup 5 > $O/bench_${N}ranks_one_device.json 2> $O/bench_${N}ranks.err || { tail -20 $O/bench_${N}ranks.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --gpus $N --backend gloo --same-device --steps 20 --warmup 5 > $O/bench_${N}ranks_one_device.json 2> $O/bench_${N}ranks.err || { tail -20 $O/bench_${N}ranks.err; exit 1; }
   python - $O/bench_${N}ranks_one_device.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

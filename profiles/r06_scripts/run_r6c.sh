@@ -16,7 +16,7 @@ done
 AB_CASES=c2grid,c5grid16,c4small,defsmall,def1small,c2rank8_0 timeout -k 10 900 python tools/ab_kernels.py ray_tracer_webgl_amd/libptrace.so build_ab/libptrace_nt.so 3 > $O/ab_nt_store.txt 2>&1
 cat $O/ab_nt_store.txt
 for rep in 1 2; do for L in ray_tracer_webgl_amd/libptrace.so build_ab/libptrace_nt.so; do
-  PT_LIB=$L timeout -k 10 300 python bench.py --config default --no-cpu-baseline --no-extra-legs --frames 1920 2>/dev/null | python -c "
+  PT_LIB=$L timeout -k 10 300 python bench.py --full --config default --no-cpu-baseline --no-extra-legs --frames 1920 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('$L frames/s', d['value'], 'group trace ms', d['roofline']['avg_launch_ms'])" >> $O/ab_nt_frames.txt
 done; done

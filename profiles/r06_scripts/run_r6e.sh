@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests/test_gpu_fuzz.py tests/test_gpu_properties.py -x -q -m gpu -s -k "fixed_slice or config5_as_bench" > $O/pytest_tune.txt 2>&1 || { tail -60 $O/pytest_tune.txt; exit 1; }
 grep -E "pt_tune kept|passed|failed" $O/pytest_tune.txt
 for cfg in 5 2; do
-  timeout -k 10 400 python bench.py --config $cfg --no-cpu-baseline --no-list-walk > $O/bench_config$cfg.json 2> $O/bench_config$cfg.err || { tail -20 $O/bench_config$cfg.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --config $cfg --no-cpu-baseline --no-list-walk > $O/bench_config$cfg.json 2> $O/bench_config$cfg.err || { tail -20 $O/bench_config$cfg.err; exit 1; }
   python - $O/bench_config$cfg.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

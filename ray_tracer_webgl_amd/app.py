@@ -139,12 +139,15 @@ class FrameLoop:
         return n
 
 
-def frame_loop_benchmark(n_frames=400, warmup=16, width=1280, height=702, device=0, extra_legs=True):
+def frame_loop_benchmark(n_frames=400, warmup=16, width=1280, height=702, device=0, extra_legs=True, kernel_leg=True,
+                         after_timed=None):
     """bench.py --config default: the reference at its own operating point (State::default, 9 spheres,
     1280x702 = images/14.png, depth 8; src/state.rs:127-135).  Times (i) the animation loop — 1 spp per
     tick, blended into the RGBA8 textures, replayed from hipGraphs in groups of 64 — and (ii) the 25-spp frames the
     reference draws while paused (src/webgl.rs:342-346), plus (iii) the same ticks issued one by one
-    from the host (uniform upload + three launches per frame) for comparison.  Returns the JSON dict."""
+    from the host (uniform upload + three launches per frame) for comparison.  `kernel_leg`: time the trace launch
+    of one group on its own afterwards (`group_trace_kernel`, else None); `after_timed(loop)` is called right after
+    the animation loop's timed frames.  Returns the JSON dict."""
     from . import abi
 
     out = {}
@@ -194,6 +197,8 @@ def frame_loop_benchmark(n_frames=400, warmup=16, width=1280, height=702, device
         }
 
     anim = run("graph", n_frames)
+    if after_timed is not None:
+        after_timed(loop)
     anim_host = run("host", min(n_frames, 200)) if extra_legs else None
     paused = run("paused", max(8, n_frames // 8)) if extra_legs else None
     st.set_flags(is_paused=False)
@@ -202,25 +207,27 @@ def frame_loop_benchmark(n_frames=400, warmup=16, width=1280, height=702, device
     # pass k at u_time = now + k * interval, exactly the launch pt_render_frames captures), timed with HIP events on the
     # launch stream around that kernel alone (PtStats.render_kernel_ms) — what bench.py's `roofline` prices.
     group = 64
-    p = st.to_params(3000.0)
-    p.time_step, p.first_pass = 16.7, 0
-    loop.tracer.set_params(p)
-    loop.tracer.reserve_passes(group)
-    for rep in range(3):
-        loop.tracer.reset()
-        n_launch = 4 if rep < 2 else 24
-        for _ in range(n_launch):
-            loop.tracer.render_passes(group)
-        loop.tracer.synchronize()
-    sg = loop.tracer.stats()
-    n_pix = width * height
-    group_kernel = {
-        "kernel": "pt_trace_kernel_small_t%d" % (n_sph % 4),
-        "passes_per_launch": group, "spp_per_pass": 1, "launches": int(sg.render_launches),
-        "avg_launch_ms": round(sg.render_kernel_ms / max(sg.render_launches, 1), 5),
-        "segments_per_launch": round(sg.segments / max(sg.render_launches, 1), 1),
-        "n_spheres": int(n_sph), "pixels": n_pix,
-    }
+    group_kernel = None
+    if kernel_leg:
+        p = st.to_params(3000.0)
+        p.time_step, p.first_pass = 16.7, 0
+        loop.tracer.set_params(p)
+        loop.tracer.reserve_passes(group)
+        for rep in range(3):
+            loop.tracer.reset()
+            n_launch = 4 if rep < 2 else 24
+            for _ in range(n_launch):
+                loop.tracer.render_passes(group)
+            loop.tracer.synchronize()
+        sg = loop.tracer.stats()
+        n_pix = width * height
+        group_kernel = {
+            "kernel": "pt_trace_kernel_small_t%d" % (n_sph % 4),
+            "passes_per_launch": group, "spp_per_pass": 1, "launches": int(sg.render_launches),
+            "avg_launch_ms": round(sg.render_kernel_ms / max(sg.render_launches, 1), 5),
+            "segments_per_launch": round(sg.segments / max(sg.render_launches, 1), 1),
+            "n_spheres": int(n_sph), "pixels": n_pix,
+        }
     loop.close()
     out = {
         "metric": "frames/s of the reference's animation loop (1 spp per tick, temporal blend) at %dx%d" % (width, height),

@@ -161,6 +161,32 @@ def test_bench_workload_plan_and_digest_helpers():
     assert ap_default and 'default="strong"' in ap_default[0]
 
 
+def test_bench_dump_outputs_keeps_to_its_budget(tmp_path):
+    """bench.py --dump-outputs: float64 arrays stay float64, everything else becomes float32 (an RGBA8 canvas exactly); an
+    array too large for what is left of the budget is written as a fixed, seeded sample of its pixels, in ascending order,
+    with their flat indices beside it — the same pixels every time, all files together within the budget.  CPU only."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10**6
+    canvas = np.random.default_rng(1).integers(0, 256, (54, 96, 4), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "c"), {"canvas": canvas, "segments": np.array([5.0])})
+    c, s = np.load(tmp_path / "c" / "canvas.npy"), np.load(tmp_path / "c" / "segments.npy")
+    assert c.dtype == np.float32 and np.array_equal(c, canvas) and s.dtype == np.float64 and s.tolist() == [5.0]
+    big = np.arange(100 * 200 * 4, dtype=np.float32).reshape(100, 200, 4)  # 320 000 bytes
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), {"accum": big, "segments": np.array([7.0])}, budget=100_000)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["accum.npy", "accum_index.npy", "segments.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 100_000
+    part, idx = np.load(tmp_path / "b1" / "accum.npy"), np.load(tmp_path / "b1" / "accum_index.npy")
+    assert part.dtype == np.float32 and idx.dtype == np.float64 and part.shape == (len(idx), 4) and len(idx) > 3000
+    assert np.all(np.diff(idx) > 0) and np.array_equal(part, big.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "b2" / "accum.npy"), part) and np.array_equal(np.load(tmp_path / "b2" / "accum_index.npy"), idx)
+
+
 def _pids_started(err):
     import re
 

@@ -244,13 +244,14 @@ def test_config4_as_benchmarked_whole_frame_vs_oracle(ora):
     t.close()
 
 
-def _bench(*extra, timeout=900):
+def _bench(*extra, timeout=900, full=True):
+    """One bench.py line; --full by default: the tests below read the legs a plain run leaves out."""
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + list(extra),
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + (["--full"] if full else []) + list(extra),
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -335,7 +336,42 @@ def test_bench_single_gpu_line_matches_the_committed_digest():
     assert d["roofline"]["frac"] and 0 < d["roofline"]["frac"] <= 1
 
 
-@pytest.mark.parametrize("config,kernels", [("4", ("pt_trace_kernel_small_t1", "pt_trace_kernel", "pt_trace_kernel_scalar")),
+def test_a_plain_bench_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """Without --full the line is the headline alone (no leg beside it) and --steps sets the timed steps; --dump-outputs
+    writes what those steps accumulated: (height, width, 4) fp32 with steps x 64 spp in every pixel's 4th channel and the
+    line's segment count, the same bits again from a second run with the same flags.  At a reduced size."""
+    import numpy as np
+
+    flags = ("--width", "192", "--height", "108", "--steps", "3", "--warmup", "2")
+    d = _bench(*flags, "--dump-outputs", str(tmp_path / "a"), full=False)
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "Mray/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["_stdout_lines"] == 1
+    assert all(d[k] is None for k in ("first_frame", "gather_check", "list_walk", "cpu_baseline", "weak_series"))
+    assert d["roofline"]["executed"] is None
+    acc = np.load(tmp_path / "a" / "accum.npy")
+    assert acc.dtype == np.float32 and acc.shape == (108, 192, 4) and np.all(acc[..., 3] == 3 * 64)
+    seg = np.load(tmp_path / "a" / "segments.npy")
+    assert seg.dtype == np.float64 and seg.tolist() == [float(d["segments"])]
+    _bench(*flags, "--dump-outputs", str(tmp_path / "b"), full=False)
+    assert np.array_equal(np.load(tmp_path / "b" / "accum.npy").view(np.uint32), acc.view(np.uint32))
+    assert np.array_equal(np.load(tmp_path / "b" / "segments.npy"), seg)
+
+
+def test_a_plain_frame_loop_bench_run_times_its_steps_and_dumps_the_canvas(tmp_path):
+    """`--config default` without --full: the replayed animation loop alone, --steps timed frames, and the canvas of the last
+    one (RGBA8 as fp32) from --dump-outputs."""
+    import numpy as np
+
+    d = _bench("--config", "default", "--steps", "70", "--warmup", "16", "--dump-outputs", str(tmp_path), full=False)
+    assert d["full"] is False and d["steps"] == 70 and d["animation"]["frames"] == 70 and d["ms_per_step"] > 0
+    assert d["unit"] == "frames/s" and d["group_trace_kernel"] is None and "roofline" not in d and "cpu_baseline" not in d
+    assert d["animation_issued_per_frame_from_the_host"] is None and d["paused_25spp"] is None
+    c = np.load(tmp_path / "canvas.npy")
+    assert c.dtype == np.float32 and c.shape == (702, 1280, 4)
+    assert np.array_equal(c, np.round(c)) and c.min() >= 0 and c.max() <= 255 and np.all(c[..., 3] == 255)
+
+
+@pytest.mark.parametrize("config,kernels", [("4",("pt_trace_kernel_small_t1", "pt_trace_kernel", "pt_trace_kernel_scalar")),
                                             ("5", ("pt_trace_kernel_grid_cells", "pt_trace_kernel_bvh_nodes"))])
 def test_bench_lines_of_the_stress_configs(config, kernels):
     """`bench.py --config 4 / 5`: BASELINE's closed room and 10 000-sphere field through the same line

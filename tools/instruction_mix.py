@@ -212,7 +212,7 @@ def classify(op):
         return "s_waitcnt"
     if op.startswith(("s_cbranch", "s_branch")):
         return "branch"
-    if op.startswith(("s_load", "s_buffer_load", "s_memtime", "s_memrealtime", "s_dcache", "s_store", "s_atomic")):
+    if op.startswith(("s_load", "s_buffer_load", "s_memtime", "s_memrealtime")):  # (the kernels issue no other scalar memory op)
         return "scalar load"
     if "saveexec" in op:
         return "exec-mask region"
