@@ -11,6 +11,9 @@ could not have produced the winning root, so these tests check
 No GPU needed: pt_build_grid is the host half of the C ABI.
 """
 import ctypes as C
+import os
+import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -24,36 +27,63 @@ MIN_T = np.float32(0.001)
 MAX_T = np.float32(1e5)
 
 
-def build(spheres, runs=False):
-    """runs=True: the layout of the kernels that gather entries from global memory (pt_build_grid_runs,
-    include/ptrace_dev.h: the cells' runs in Morton order of their cells)"""
-    lib = _lib.load()
-    build_fn = lib.pt_build_grid
-    if runs:
-        build_fn = lib.pt_build_grid_runs
-        build_fn.restype, build_fn.argtypes = lib.pt_build_grid.restype, lib.pt_build_grid.argtypes
+# the margin classes d_near / s0 the grid is built for (csrc/pt_api.hip kNearFactors: pt_set_spheres builds class 3, pt_tune and
+# pt_refit_grid rebuild it for the class the view needs); the margin's first term grows with d_near^2
+CLASSES = (2.5, 3.0, 4.0, 5.5, 8.0, 12.0, 16.0)
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+SHIM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "grid_class_shim.cpp")
+_SHIM = []
+
+
+def compile_shim(out_dir, flags=("-O2",)):
+    """grid_class_shim.cpp (ptgrid::build for any margin class) as a shared object in out_dir"""
+    so = os.path.join(out_dir, "libgrid_class_shim.so")
+    subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] + list(flags) + [SHIM, "-o", so])
+    return so
+
+
+def _build_grid_class():
+    if not _SHIM:
+        fn = C.CDLL(compile_shim(tempfile.mkdtemp(prefix="grid_class_"))).grid_class_build
+        fn.restype = C.c_int
+        fn.argtypes = [C.POINTER(abi.PtSphere), C.c_uint32, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        _SHIM.append(fn)
+    return _SHIM[0]
+
+
+def build(spheres, runs=False, near_factor=3.0):
+    """The grid for margin class near_factor (the library's builder through grid_class_shim.cpp; class 3 is what
+    pt_build_grid returns) with the walk constants of that same grid.  runs=True: the layout of the kernels that gather entries from
+    global memory (the cells' runs in Morton order of their cells, pt_build_grid_runs)."""
+    build_fn = _build_grid_class()
     ptr, n, keep = abi.spheres_as_ctypes(spheres)
     counts = np.zeros(8, np.uint32)
     geom = np.zeros(12, np.float32)
     margin = np.zeros(4, np.float32)
+    consts = np.zeros(10, np.float32)  # what pt_render_passes copies into the launch arguments
     dg = C.c_float(0)
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    rc = build_fn(ptr, n, vp(counts), vp(geom), vp(margin), C.byref(dg), None, 0, None, 0, None, 0)
+    layout = 1 if runs else 0
+    rc = build_fn(ptr, n, near_factor, layout, _vp(counts), _vp(geom), _vp(margin), C.byref(dg), _vp(consts), None, 0, None, 0,
+                  None, 0)
     if rc != 0:
         return rc, None
     nc = int(counts[0]) * int(counts[1]) * int(counts[2])
     cells = np.zeros(nc, np.uint32)
     entries = np.zeros((counts[5], 4), np.float32)
     index = np.zeros(counts[5], np.uint32)
-    rc = build_fn(ptr, n, vp(counts), vp(geom), vp(margin), C.byref(dg), vp(cells), cells.size, vp(entries),
-                  entries.size, vp(index), index.size)
-    consts = np.zeros(10, np.float32)  # what pt_render_passes copies into the launch arguments
-    assert lib.pt_grid_walk_constants(ptr, n, vp(consts)) == 0
+    rc = build_fn(ptr, n, near_factor, layout, _vp(counts), _vp(geom), _vp(margin), C.byref(dg), _vp(consts), _vp(cells),
+                  cells.size, _vp(entries), entries.size, _vp(index), index.size)
     return rc, dict(r2_near=consts[0], lo_n=consts[1:4].copy(), hi_n=consts[4:7].copy(), inv_h=consts[7:10].copy(),
                     n=counts[:3].astype(np.int64), n_cell_entries=int(counts[3]), n_always=int(counts[4]),
                     n_entries=int(counts[5]), max_entries=int(counts[6]), nonempty=int(counts[7]), lo=geom[0:3], h=geom[3:6],
                     hi=geom[6:9], c0=geom[9:12], s0=margin[0], rmin=margin[1], rmax=margin[2], d_near=margin[3],
-                    delta_g=np.float32(dg.value), cells=cells, entries=entries, index=index)
+                    delta_g=np.float32(dg.value), cells=cells, entries=entries, index=index, near_factor=near_factor)
 
 
 def delta_of(rmin, rmax, D):
@@ -88,11 +118,32 @@ def _flat():
     return s
 
 
-@pytest.mark.parametrize("name", sorted(GRID_SCENES))
-def test_structure(name):
+# scenes every margin class is checked on: two of BASELINE's, fields, a flat one, mixed radii, and fields far from the origin
+# (eps_dda scales with d_near + |c0|)
+CLASS_SCENES = ["config2", "config5", "field300", "flat", "mixed_radii", "field300_far", "flat_far", "config2_far"]
+
+
+def over_classes(at3, names=CLASS_SCENES):
+    """(scene, class) cases: the scenes `at3` at the default class under their plain names, `names` at the six others"""
+    return ([pytest.param(n, 3.0, id=n) for n in at3] +
+            [pytest.param(n, f, id="%s@%g" % (n, f)) for f in CLASSES if f != 3.0 for n in names])
+
+
+def test_every_class_builds_on_baselines_scenes():
+    """No case of the tests over the classes may pass for want of a grid: every class builds on config 2 and config 5 (and
+    on the other scenes of CLASS_SCENES, as it does today); a grid the builder gives up on says so by its return code."""
+    for name in CLASS_SCENES:
+        sph = GRID_SCENES[name]()
+        for f in CLASSES:
+            rc, g = build(sph, near_factor=f)
+            assert rc == 0, (name, f, rc)
+
+
+@pytest.mark.parametrize("name,f", over_classes(sorted(GRID_SCENES)))
+def test_structure(name, f):
     sph = GRID_SCENES[name]()
-    rc, g = build(sph)
-    assert rc == 0
+    rc, g = build(sph, near_factor=f)
+    assert rc == 0, (name, f, rc)
     n = len(sph)
     c = np.asarray(sph["center"], np.float64)
     r = np.abs(np.asarray(sph["radius"], np.float64))
@@ -121,18 +172,22 @@ def test_structure(name):
     c0, s0 = g["c0"].astype(np.float64), float(g["s0"])
     reach = np.linalg.norm(c[gridded] - c0, axis=1) + r[gridded]
     assert reach.max() <= s0 and r[gridded].min() >= g["rmin"] and r[gridded].max() <= g["rmax"]
-    assert g["d_near"] >= 3.0 * s0
+    assert g["d_near"] >= f * s0 and float(g["d_near"]) <= f * s0 * (1.0 + 2.0 ** -23)  # the class asked for, rounded up once
     # the registration inflation covers delta(d_near) as the KERNEL bounds it (25 % slack on E') ...
     dk = np.sqrt(float(g["rmin"]) ** 2 + 40.0 * U * float(g["d_near"]) ** 2) - float(g["rmin"]) + 16.0 * U * float(g["rmax"])
     assert g["delta_g"] >= dk and g["delta_g"] >= delta_of(float(g["rmin"]), float(g["rmax"]), float(g["d_near"]))
-    # ... and is not absurd next to a cell
-    assert g["delta_g"] < 0.6 * float(g["h"].min()) or name in ("clumps",) or name.endswith("_far")
+    # ... and is not absurd next to a cell (a matter of speed: asserted for the classes up to the default, reported beyond)
+    ratio = float(g["delta_g"]) / float(g["h"].min())
+    if f <= 3.0:
+        assert g["delta_g"] < 0.6 * float(g["h"].min()) or name in ("clumps",) or name.endswith("_far")
+    else:
+        print("%s class %g: delta_g / min cell edge %.3f, %d cell entries for %d spheres" % (name, f, ratio, g["n_cell_entries"], n))
     # registration: a sphere is an entry of EVERY cell its box inflated by ITS delta touches: the kernel's bound with the
     # sphere's own radius in the square root (sqrt(r^2 + x) - r decreases with r) and its own distance bound D_i = d_near - s0
     # + |C_i - c0| (a walking ray starts within d_near - s0 of c0: the kernel's near test, r2_near) + what delta_g carries
     # beyond that term (16 u rmax and the walk's rounding, eps_dda); at r = rmin, |C - c0| = s0 - r that is delta_g itself
     d_near = float(g["d_near"])
-    assert float(g["r2_near"]) <= (d_near - s0) ** 2
+    assert float(g["r2_near"]) <= (d_near - s0) ** 2 and float(g["r2_near"]) > (0.9998 * f * s0 - s0) ** 2
     dg_walk = float(g["delta_g"]) - (np.sqrt(float(g["rmin"]) ** 2 + 40.0 * U * d_near ** 2) - float(g["rmin"]))
     assert dg_walk >= 16.0 * U * float(g["rmax"])
     D_i = np.minimum(d_near, d_near - s0 + np.linalg.norm(c - c0, axis=1))
@@ -153,8 +208,9 @@ def test_structure(name):
     # all registered boxes lie inside [lo, hi]: near rays need no inflation of the entry test
     assert np.all(c[gridded] - r[gridded, None] - float(g["delta_g"]) >= lo - 1e-9)
     assert np.all(c[gridded] + r[gridded, None] + float(g["delta_g"]) <= g["hi"].astype(np.float64) + 1e-9)
-    # cells of about one sphere each, a bounded number of copies
-    assert g["n_cell_entries"] <= 8 * len(gridded) + 64 or name.endswith("_far")
+    # cells of about one sphere each, a bounded number of copies (speed again: up to the default class)
+    if f <= 3.0:
+        assert g["n_cell_entries"] <= 8 * len(gridded) + 64 or name.endswith("_far")
 
 
 def test_giants_and_big_spheres_are_tested_for_every_ray():
@@ -401,40 +457,89 @@ def dda_discrepancy(g, o, d, rng):
     return worst_cross / unit, worst_entry / unit
 
 
-@pytest.mark.parametrize("name", ["config2", "config5", "mixed_radii", "flat", "clumps", "field300", "field300_far", "flat_far", "config2_far"])
-def test_the_walks_boundary_times_stay_within_the_rounding_budget_of_the_registration(name):
+# where ray origins stand relative to the near region of the class, in units of sqrt(r2_near): the last one is just beyond it,
+# where rays take the far path
+RIM = (0.3, 0.9, 0.99, 0.9999, 1.0001)
+
+
+def near_of(g, o):
+    """the kernel's near test (pt_grid_walk.hpp), fp32: which rays walk the cells"""
+    p = f32(o - g["c0"][None, :])
+    r2 = fma(p[:, 2], p[:, 2], fma(p[:, 1], p[:, 1], f32(p[:, 0] * p[:, 0])))
+    return r2 <= g["r2_near"]
+
+
+def rim_rays(g, sph, n, seed):
+    """Origins across the whole near region of the grid's class, |o - c0| = k sqrt(r2_near) for k in RIM (the walk's rounding
+    budget and the margin's first term both grow with the distance a walking ray comes from), aimed at sphere rims or
+    anywhere; unnormalised directions.  Returns o, d (float32) and the RIM level of each ray."""
+    rng = np.random.default_rng(seed)
+    c = np.asarray(sph["center"], np.float64)
+    r = np.abs(np.asarray(sph["radius"], np.float64))
+    c0 = g["c0"].astype(np.float64)
+    level = np.arange(n) % len(RIM)
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1)[:, None]
+    o = c0 + u * (np.asarray(RIM)[level] * np.sqrt(float(g["r2_near"])))[:, None]
+    j = rng.integers(0, len(sph), n)
+    v = rng.normal(size=(n, 3))
+    v /= np.linalg.norm(v, axis=1)[:, None]
+    target = c[j] + v * r[j, None] * rng.choice([0.999999, 1.0, 1.000001, 1.001, 0.5], (n, 1))
+    d = (target - o) * rng.choice([1.0, 0.01, 3.0], (n, 1))
+    wild = rng.random(n) < 0.3
+    d[wild] = rng.normal(size=(int(wild.sum()), 3)) * rng.choice([1e-3, 1.0, 30.0], (int(wild.sum()), 1))
+    return f32(o), f32(d), level
+
+
+def _regular(o, d):
+    a = np.einsum("ij,ij->i", d.astype(np.float64), d.astype(np.float64))
+    return (a > 1e-12) & (a < 1e6)  # the kernel's regular rays; the others take the literal loop
+
+
+@pytest.mark.parametrize("name,f", over_classes(["config2", "config5", "mixed_radii", "flat", "clumps", "field300", "field300_far",
+                                                   "flat_far", "config2_far"]))
+def test_the_walks_boundary_times_stay_within_the_rounding_budget_of_the_registration(name, f):
     """eps_dda (pt_grid.hpp) is 8 x u (n_sum + 8) (d_near + diag + |c0|) — a first-order bound of the DDA's accumulated
     rounding (derivation in the header) times a safety factor.  Measured here: the fp32 walk against float64 on bounce, camera
     and far-but-walking rays, scenes at the origin and thousands of units away from it: the worst boundary discrepancy is
     0.03 ... 0.065 of the bound WITHOUT its factor (asserted: below a quarter of it, i.e. the factor leaves more than 32 x).
     The entry point may lie outside its (clamped) entry cell by the slab's deliberate widening, 1e-6 (d_near + |c0|) — no
-    sphere's box is out there; it stays below the bound without its factor as well."""
+    sphere's box is out there; it stays below the bound without its factor as well.  Every margin class, with origins
+    across its whole near region (rim_rays) beside the scene's own rays."""
     sph = GRID_SCENES[name]()
-    rc, g = build(sph)
+    rc, g = build(sph, near_factor=f)
     assert rc == 0
     rng = np.random.default_rng(5)
     worst = [0.0, 0.0]
+    n_near = n_far = 0
     for seed in range(3):
         o, d = rays_for(sph, 4000, seed)
-        a = np.einsum("ij,ij->i", d.astype(np.float64), d.astype(np.float64))
-        ok = (a > 1e-12) & (a < 1e6)
+        ok = _regular(o, d)
         wc, we = dda_discrepancy(g, o[ok], d[ok], rng)
         worst = [max(worst[0], wc), max(worst[1], we)]
+        o, d, level = rim_rays(g, sph, 2000, 50 + seed)
+        ok = _regular(o, d)
+        near = near_of(g, o[ok])
+        assert np.array_equal(near, level[ok] < len(RIM) - 1)  # the rim's last level, and only it, takes the far path
+        n_near += int(near.sum()); n_far += int((~near).sum())
+        wc, we = dda_discrepancy(g, o[ok], d[ok], rng)
+        worst = [max(worst[0], wc), max(worst[1], we)]
+    assert n_near > 1000 and n_far > 300, (n_near, n_far)
     assert 0.0 < worst[0] < 0.25 and worst[1] < 1.0, worst
 
 
-@pytest.mark.parametrize("name", ["config2", "field300", "clumps", "field17_no_giant", "config5", "mixed_radii", "flat",
-                                  "field300_far", "flat_far", "config2_far"])
-def test_walk_returns_the_pair_hit_world_returns(name):
+@pytest.mark.parametrize("name,f", over_classes(["config2", "field300", "clumps", "field17_no_giant", "config5", "mixed_radii", "flat",
+                                                   "field300_far", "flat_far", "config2_far"]))
+def test_walk_returns_the_pair_hit_world_returns(name, f):
     sph = GRID_SCENES[name]()
-    rc, g = build(sph)
+    rc, g = build(sph, near_factor=f)
     assert rc == 0
     n_rays = 3000 if len(sph) < 2000 else 400
     total_hits = total_looked = total_lit = 0
+    rim_near = rim_far = rim_hits = 0
     for seed in range(4):
         o, d = rays_for(sph, n_rays, seed)
-        a = np.einsum("ij,ij->i", d.astype(np.float64), d.astype(np.float64))
-        ok = (a > 1e-12) & (a < 1e6)  # the kernel's regular rays; the others take the literal loop
+        ok = _regular(o, d)
         o, d = o[ok], d[ok]
         ref_t, ref_i = brute_force(o, d, sph)
         got_t, got_i, looked, literal = walk(g, o, d, sph)
@@ -444,6 +549,18 @@ def test_walk_returns_the_pair_hit_world_returns(name):
         total_hits += int((ref_i >= 0).sum())
         total_looked += int(looked[chk].sum())
         total_lit += int(literal.sum())
+        # ... and from across the class's whole near region, and just beyond it
+        o, d, level = rim_rays(g, sph, n_rays // 3, 70 + seed)
+        ok = _regular(o, d)
+        o, d = o[ok], d[ok]
+        near = near_of(g, o)
+        ref_t, ref_i = brute_force(o, d, sph)
+        got_t, got_i, looked, literal = walk(g, o, d, sph)
+        assert not (literal & near).any()
+        chk = ~literal
+        bad = chk & ((got_i != ref_i) | (got_t.view(np.uint32) != ref_t.view(np.uint32)))
+        assert not bad.any(), (name, f, seed, np.nonzero(bad)[0][:5], got_i[bad][:5], ref_i[bad][:5], got_t[bad][:5], ref_t[bad][:5])
+        rim_near += int(near.sum()); rim_far += int((~near).sum()); rim_hits += int((ref_i[near] >= 0).sum())
     assert total_hits > 300
     # the walk does cull: it looks at a small part of the scene per ray
     # (`clumps` is the grid's bad case — a dense clump inside one cell of a sparse field; PT_GEOM_AUTO
@@ -451,6 +568,7 @@ def test_walk_returns_the_pair_hit_world_returns(name):
     if len(sph) >= 100 and name != "clumps":
         assert total_looked < 0.1 * 4 * n_rays * len(sph)
     assert total_lit < 0.2 * 4 * n_rays
+    assert rim_near > 0.5 * 4 * (n_rays // 3) and rim_far > 0.1 * 4 * (n_rays // 3) and rim_hits > 50, (rim_near, rim_far, rim_hits)
 
 
 def test_walk_with_each_spheres_own_inflation_at_the_rims_of_the_big_ones_from_far_origins():
@@ -542,3 +660,207 @@ def test_morton_runs_hold_the_same_spheres_in_the_same_order(name):
     # the always-tested group: unchanged, behind the cells' entries
     assert np.array_equal(g["index"][g["n_cell_entries"]:], r["index"][r["n_cell_entries"]:])
     assert np.array_equal(g["entries"][g["n_cell_entries"]:].view(np.uint32), r["entries"][r["n_cell_entries"]:].view(np.uint32))
+
+
+def test_the_class_builder_at_the_default_class_is_pt_build_grid():
+    """The tests' class builder (grid_class_shim.cpp) at class 3 is the library's pt_build_grid (layout 0) and
+    pt_build_grid_runs (layout 1), byte for byte, and its walk10 is pt_grid_walk_constants; it refuses a class outside
+    [2, 16]."""
+    lib = _lib.load()
+    fn = _build_grid_class()
+    runs = lib.pt_build_grid_runs
+    runs.restype, runs.argtypes = lib.pt_build_grid.restype, lib.pt_build_grid.argtypes
+    for name in ("config2", "config5", "flat_far", "clumps", "field17_no_giant"):
+        sph = GRID_SCENES[name]()
+        ptr, n, keep = abi.spheres_as_ctypes(sph)
+        for layout, old_fn in ((0, lib.pt_build_grid), (1, runs)):
+            out = []
+            for new in (True, False):
+                counts = np.zeros(8, np.uint32); geom = np.zeros(12, np.float32); margin = np.zeros(4, np.float32)
+                dg = C.c_float(0); walk10 = np.zeros(10, np.float32)
+                head = (_vp(counts), _vp(geom), _vp(margin), C.byref(dg))
+                rc0 = fn(ptr, n, 3.0, layout, *head, _vp(walk10), None, 0, None, 0, None, 0) if new else old_fn(ptr, n, *head, None, 0, None, 0, None, 0)
+                assert rc0 == 0
+                cells = np.zeros(int(counts[0]) * int(counts[1]) * int(counts[2]), np.uint32)
+                entries = np.zeros(int(counts[5]) * 4, np.float32); index = np.zeros(int(counts[5]), np.uint32)
+                tail = (_vp(cells), cells.size, _vp(entries), entries.size, _vp(index), index.size)
+                if new:
+                    assert fn(ptr, n, 3.0, layout, *head, None, *tail[:-1], index.size - 1) == abi.PT_ERR_CAPACITY
+                    rc = fn(ptr, n, 3.0, layout, *head, _vp(walk10), *tail)
+                else:
+                    rc = old_fn(ptr, n, *head, *tail)
+                    assert lib.pt_grid_walk_constants(ptr, n, _vp(walk10)) == 0
+                assert rc == 0
+                out.append(b"".join(a.tobytes() for a in (counts, geom, margin, np.float32(dg.value), walk10, cells, entries, index)))
+            assert out[0] == out[1], (name, layout)
+    sph = GRID_SCENES["config2"]()
+    ptr, n, keep = abi.spheres_as_ctypes(sph)
+    for bad in (float("nan"), float("inf"), -float("inf"), 1.999, 16.001, 0.0, -3.0):
+        assert fn(ptr, n, bad, 0, None, None, None, None, None, None, 0, None, 0, None, 0) == abi.PT_ERR_INVALID, bad
+    assert fn(ptr, n, 3.0, 2, None, None, None, None, None, None, 0, None, 0, None, 0) == abi.PT_ERR_INVALID
+    for f in (2.0, 16.0):
+        assert fn(ptr, n, f, 0, None, None, None, None, None, None, 0, None, 0, None, 0) == 0
+    small = scenes.default_scene(64, 36, 1, 8).spheres  # 9 spheres: no grid, whatever the class
+    ptr, n, keep = abi.spheres_as_ctypes(small)
+    for f in CLASSES:
+        assert fn(ptr, n, f, 0, None, None, None, None, None, None, 0, None, 0, None, 0) == abi.PT_ERR_NOT_READY
+
+
+# ---- (iv) phantom hits: what the margin of every class is for --------------------------------------
+def sphere_inflation(g, sph):
+    """delta_i, the inflation pt_grid.hpp registers sphere i with (the kernel's bound with ITS radius and distance bound)"""
+    c = np.asarray(sph["center"], np.float64); r = np.abs(np.asarray(sph["radius"], np.float64))
+    c0, s0, d_near = g["c0"].astype(np.float64), float(g["s0"]), float(g["d_near"])
+    rmin = float(g["rmin"])
+    dg_walk = float(g["delta_g"]) - (np.sqrt(rmin ** 2 + 40.0 * U * d_near ** 2) - rmin)
+    D_i = np.minimum(d_near, d_near - s0 + np.linalg.norm(c - c0, axis=1))
+    return np.minimum(float(g["delta_g"]), np.sqrt(r * r + 40.0 * U * D_i ** 2) - r + dg_walk)
+
+
+def gridded_of(g):
+    idx = g["index"][:g["n_cell_entries"]]
+    return np.unique(idx[idx != PAD]).astype(np.int64)
+
+
+def phantom_rays(g, sph, n, seed):
+    """Rays that graze small gridded spheres from across the class's near region (and from just beyond it): each passes
+    sphere j at a miss distance m in (r, r + delta_j], delta_j the sphere's own registration inflation — the band where the
+    shader's fp32 test can accept a sphere the exact geometry misses (the cancellation in c = |oc|^2 - r^2 grows with
+    |o - C|^2).  Most are offset along a cell axis and run parallel to that axis's planes, half of them just beyond the cell
+    plane next to the sphere's bare box: where a phantom hit lands in a cell that only the inflation registers the sphere in.
+    Returns o, d (float32), the grazed sphere and the RIM level of each ray (not yet filtered by the fp32 test)."""
+    rng = np.random.default_rng(seed)
+    c = np.asarray(sph["center"], np.float64); r = np.abs(np.asarray(sph["radius"], np.float64))
+    c0 = g["c0"].astype(np.float64)
+    lo, h, nn = g["lo"].astype(np.float64), g["h"].astype(np.float64), g["n"]
+    infl = sphere_inflation(g, sph)
+    gridded = gridded_of(g)
+    small = gridded[r[gridded] <= np.quantile(r[gridded], 0.4)]
+    j = rng.choice(small, n)
+    k = rng.integers(0, 3, n)
+    sgn = rng.choice([-1.0, 1.0], n)
+    # gap between the sphere's bare box face and the next cell plane beyond it, along axis k
+    face = c[j, k] + sgn * r[j]
+    cell = np.floor((face - lo[k]) / h[k])
+    plane = lo[k] + (cell + (sgn > 0)) * h[k]
+    gap = np.abs(plane - face)
+    level = np.arange(n) % len(RIM)
+    rho = np.asarray(RIM)[level] * np.sqrt(float(g["r2_near"]))
+    D = rho + np.linalg.norm(c[j] - c0, axis=1)
+    y = np.exp(rng.uniform(np.log(0.2), np.log(12.0), n))
+    m = np.sqrt(r[j] ** 2 + y * U * D * D)
+    cross = rng.random(n) < 0.5   # half of them: just beyond the next cell plane
+    m = np.where(cross, np.maximum(m, r[j] + gap * 1.001), m)
+    m = np.minimum(m, r[j] + infl[j])
+    # offset direction e (axis for most), direction w perpendicular to it
+    e = np.zeros((n, 3)); e[np.arange(n), k] = sgn
+    generic = rng.random(n) < 0.25
+    eg = rng.normal(size=(n, 3)); eg /= np.linalg.norm(eg, axis=1)[:, None]
+    e[generic] = eg[generic]
+    w = rng.normal(size=(n, 3))
+    w[~generic, k[~generic]] = 0.0
+    w -= np.einsum("ij,ij->i", w, e)[:, None] * e
+    w[~generic, k[~generic]] = 0.0
+    w /= np.linalg.norm(w, axis=1)[:, None]
+    P0 = c[j] + e * m[:, None]
+    q = P0 - c0
+    wq = np.einsum("ij,ij->i", w, q)
+    disc = wq * wq - np.einsum("ij,ij->i", q, q) + rho * rho
+    s = wq + np.sqrt(np.maximum(disc, 0.0))
+    ok = (disc > 0) & (s > 4.0 * m)
+    o = P0 - s[:, None] * w
+    d = w * rng.choice([1.0, 0.05, 7.0], (n, 1))
+    return f32(o[ok]), f32(d[ok]), j[ok], level[ok]
+
+
+def bare_grid(g, sph):
+    """the same grid (lo, h, n, always-tested group) with every gridded sphere registered only in the cells of its BARE box"""
+    c = np.asarray(sph["center"], np.float64); r = np.abs(np.asarray(sph["radius"], np.float64))
+    lo, h, nn = g["lo"].astype(np.float64), g["h"].astype(np.float64), g["n"]
+    lists = {}
+    for i in gridded_of(g):
+        a = np.clip(np.floor((c[i] - r[i] - lo) / h), 0, nn - 1).astype(np.int64)
+        b = np.clip(np.floor((c[i] + r[i] - lo) / h), 0, nn - 1).astype(np.int64)
+        for z in range(a[2], b[2] + 1):
+            for yy in range(a[1], b[1] + 1):
+                for x in range(a[0], b[0] + 1):
+                    lists.setdefault((z * nn[1] + yy) * nn[0] + x, []).append(i)
+    ncell = int(np.prod(nn))
+    cells = np.zeros(ncell, np.uint32)
+    idx = []
+    for cc in range(ncell):
+        members = lists.get(cc, [])
+        cells[cc] = len(idx) | (len(members) << 24)
+        idx += members
+    tail = g["index"][g["n_cell_entries"]:]
+    index = np.concatenate([np.asarray(idx, np.uint32), tail])
+    cs = np.asarray(sph["center"], np.float32); rr = np.asarray(sph["radius"], np.float32)
+    entries = np.concatenate([np.column_stack([cs[idx], (rr * rr)[idx]]).astype(np.float32), g["entries"][g["n_cell_entries"]:]])
+    b = dict(g)
+    b.update(cells=cells, entries=entries, index=index, n_cell_entries=len(idx), n_entries=len(index))
+    return b
+
+
+def one_sphere(o, d, sph, j):
+    """hit_sphere of sphere j per ray, as brute_force runs it: (root, accepted)"""
+    cs = np.asarray(sph["center"], np.float32)[j]; rr = np.asarray(sph["radius"], np.float32)[j]
+    v, ok = exact_root(o, d, cs, f32(rr * rr))
+    return v, ok & (v <= MAX_T)
+
+PHANTOM_SCENES = {"config2": GRID_SCENES["config2"], "config5": GRID_SCENES["config5"],
+                  "field1500": lambda: scenes.field_spheres(1500)}
+
+
+@pytest.mark.parametrize("f", CLASSES)
+@pytest.mark.parametrize("name", sorted(PHANTOM_SCENES))
+def test_phantom_hits_land_in_registered_cells_and_a_bare_grid_misses_them(name, f):
+    """A phantom hit is a root the fp32 test accepts on a ray that the exact geometry (float64, the ray's float32 numbers)
+    shows passing the sphere by.  For rays grazing small spheres from anywhere in the class's near region (phantom_rays):
+    (a) phantom hits occur, in numbers; (b) every accepted point of a walking ray lies inside the grid, in a cell that
+    registers the sphere — the registration invariant itself, no walk in between; (c) the fp32 walk returns brute force's
+    pair bit for bit; (d) the same walk over cell lists built from the BARE sphere boxes (same lo, h, n, no inflation) does
+    not: from class 8 on it disagrees with brute force on config 5 and on the 1 500-sphere field — these rays exercise the
+    margin, which rays aimed at the rims of big spheres (the test above) do not."""
+    sph = PHANTOM_SCENES[name]()
+    rc, g = build(sph, near_factor=f)
+    assert rc == 0
+    keep = 1500 if len(sph) > 2000 else 3000
+    o, d, j, level = phantom_rays(g, sph, 20 * keep, 1)
+    ok = _regular(o, d)
+    o, d, j, level = o[ok], d[ok], j[ok], level[ok]
+    v, acc = one_sphere(o, d, sph, j)
+    o, d, j, level, v = o[acc][:keep], d[acc][:keep], j[acc][:keep], level[acc][:keep], v[acc][:keep]
+    near = near_of(g, o)
+    assert np.array_equal(near, level < len(RIM) - 1)
+    assert near.sum() > 0.6 * len(o) and (~near).sum() > 0.1 * len(o)
+    # (a) the exact geometry misses: distance from the centre to the ray's line, in float64
+    c = np.asarray(sph["center"], np.float32).astype(np.float64)
+    r = np.abs(np.asarray(sph["radius"], np.float32).astype(np.float64))
+    o64, d64 = o.astype(np.float64), d.astype(np.float64)
+    oc = c[j] - o64
+    tca = np.einsum("ij,ij->i", oc, d64) / np.einsum("ij,ij->i", d64, d64)
+    miss = np.linalg.norm(oc - tca[:, None] * d64, axis=1) - r[j]
+    phantom = miss > 0
+    assert phantom.sum() > 0.8 * keep, (name, f, int(phantom.sum()))
+    # (b) the accepted point of every walking ray is in a cell that registers the sphere
+    lo, h, nn, hi = g["lo"].astype(np.float64), g["h"].astype(np.float64), g["n"], g["hi"].astype(np.float64)
+    P = o64 + d64 * v.astype(np.float64)[:, None]
+    first, count = (g["cells"] & 0xFFFFFF).astype(np.int64), (g["cells"] >> 24).astype(np.int64)
+    for i in np.nonzero(near)[0]:
+        assert np.all(P[i] >= lo) and np.all(P[i] < hi), (name, f, i, P[i], lo, hi)
+        x, y, z = np.minimum(np.floor((P[i] - lo) / h).astype(np.int64), nn - 1)
+        cell = (z * nn[1] + y) * nn[0] + x
+        assert j[i] in g["index"][first[cell]:first[cell] + count[cell]], (name, f, i, j[i], (x, y, z), miss[i])
+    # (c) the walk returns hit_world's pair
+    ref_t, ref_i = brute_force(o, d, sph)
+    got_t, got_i, looked, literal = walk(g, o, d, sph)
+    assert not (literal & near).any()
+    bad = ~literal & ((got_i != ref_i) | (got_t.view(np.uint32) != ref_t.view(np.uint32)))
+    assert not bad.any(), (name, f, np.nonzero(bad)[0][:5], got_i[bad][:5], ref_i[bad][:5], got_t[bad][:5], ref_t[bad][:5])
+    # (d) ... and a grid without the margin does not
+    bt, bi, _, bl = walk(bare_grid(g, sph), o, d, sph)
+    bare_bad = int((~bl & ((bi != ref_i) | (bt.view(np.uint32) != ref_t.view(np.uint32)))).sum())
+    print("%s class %g: %d grazing rays, %d phantom hits (worst %.3g radii off), %d walking; bare-box grid disagrees on %d, "
+          "the real grid on 0" % (name, f, len(o), int(phantom.sum()), float((miss / r[j]).max()), int(near.sum()), bare_bad))
+    if f >= 8.0 and name in ("config5", "field1500"):
+        assert bare_bad > 0, (name, f)

@@ -29,12 +29,14 @@ def test_oracle_and_host_code_under_asan_ubsan(tmp_path):
                           [os.path.join(ROOT, "oracle", "pt_oracle.c"), "-o", ora_so, "-lm", "-lpthread"])
     subprocess.check_call(["g++", "-std=c++17"] + san +
                           [os.path.join(ROOT, "ray_tracer_webgl_amd", "csrc", "pt_host.cpp"), "-o", host_so])
+    grid_so = str(tmp_path / "libgrid_class_shim_asan.so")  # ptgrid::build at any margin class (tests/grid_class_shim.cpp)
+    subprocess.check_call(["g++", "-std=c++17"] + san + [os.path.join(ROOT, "tests", "grid_class_shim.cpp"), "-o", grid_so])
     script = textwrap.dedent('''
         import ctypes as C, sys
         import numpy as np
         sys.path.insert(0, %r)
         from ray_tracer_webgl_amd import abi
-        O = C.CDLL(%r); H = C.CDLL(%r)
+        O = C.CDLL(%r); H = C.CDLL(%r); G = C.CDLL(%r)
         fp = C.POINTER(C.c_float)
         # host: State lifecycle, movement with autofocus, uniforms, scene narrowing, pick ray
         h = C.c_void_p()
@@ -100,8 +102,45 @@ def test_oracle_and_host_code_under_asan_ubsan(tmp_path):
             assert rc == 0 and sorted(idx[idx != 0xFFFFFFFF].tolist()) == list(range(n))
             built += 1
         assert built >= 5
+        # host: the grid builder (registration, Morton runs) at every margin class, size query then filled call, plus the
+        # walk constants, on the same scenes and the 10 000-sphere field
+        G.grid_class_build.restype = C.c_int
+        G.grid_class_build.argtypes = [C.POINTER(abi.PtSphere), C.c_uint32, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp,
+                                          C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
+        H.pt_grid_walk_constants.argtypes = [C.POINTER(abi.PtSphere), C.c_uint32, vp]
+        field = scenes.config5(64, 36, 1, 1, 8).spheres
+        per_class = {}
+        capacity_seen = 0
+        for sph in (cover, same, huge, tiny, flat, cover[:15], cover[:16], field):
+            ptr, n, keep = abi.spheres_as_ctypes(sph)
+            w10 = np.zeros(10, np.float32)
+            rc = H.pt_grid_walk_constants(ptr, n, w10.ctypes.data)
+            assert rc in (0, abi.PT_ERR_NOT_READY), rc
+            for f in (2.5, 3.0, 4.0, 5.5, 8.0, 12.0, 16.0):
+                for layout in (0, 1):
+                    cnt = np.zeros(8, np.uint32); geo = np.zeros(12, np.float32); mar = np.zeros(4, np.float32)
+                    dg = np.zeros(1, np.float32)
+                    rc = G.grid_class_build(ptr, n, f, layout, cnt.ctypes.data, geo.ctypes.data, mar.ctypes.data, dg.ctypes.data,
+                                               w10.ctypes.data, None, 0, None, 0, None, 0)
+                    if rc != 0:
+                        assert rc == abi.PT_ERR_NOT_READY, rc
+                        continue
+                    cells = np.zeros(int(cnt[0]) * int(cnt[1]) * int(cnt[2]), np.uint32)
+                    ent = np.zeros(int(cnt[5]) * 4, np.float32); idx = np.zeros(int(cnt[5]), np.uint32)
+                    if capacity_seen < 3:  # undersized arrays: refused, nothing written past them
+                        short = [(cells.size - 1, ent.size, idx.size), (cells.size, ent.size - 4, idx.size), (cells.size, ent.size, idx.size - 1)][capacity_seen]
+                        rc = G.grid_class_build(ptr, n, f, layout, None, None, None, None, None, cells.ctypes.data, short[0],
+                                                   ent.ctypes.data, short[1], idx.ctypes.data, short[2])
+                        assert rc == abi.PT_ERR_CAPACITY, rc
+                        capacity_seen += 1
+                    rc = G.grid_class_build(ptr, n, f, layout, cnt.ctypes.data, geo.ctypes.data, mar.ctypes.data, dg.ctypes.data,
+                                               w10.ctypes.data, cells.ctypes.data, cells.size, ent.ctypes.data, ent.size,
+                                               idx.ctypes.data, idx.size)
+                    assert rc == 0 and int((cells >> 24).sum()) == int(cnt[3]), rc
+                    per_class[f] = per_class.get(f, 0) + 1
+        assert len(per_class) == 7 and capacity_seen == 3, (per_class, capacity_seen)
         print("SANITIZED-OK", int(seg))
-    ''') % (ROOT, ora_so, host_so)
+    ''') % (ROOT, ora_so, host_so, grid_so)
     env = dict(os.environ, LD_PRELOAD=asan + ":" + ubsan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, env=env, timeout=300)
