@@ -17,6 +17,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/ptrace.h"
@@ -35,34 +36,87 @@
 
 static thread_local std::string g_create_error;
 
+// A device buffer and its capacity in elements; the one owner of every allocation the library makes, freed with it.
+template <class T>
+struct DevBuf {
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
+  ~DevBuf() { if (p_) (void)hipFree(p_); }
+  // room for exactly n elements, contents undefined: the old buffer is freed BEFORE the new one is allocated (the two need
+  // not fit on the device together); on failure it holds nothing and has capacity 0
+  hipError_t reserve(size_t n) {
+    hipError_t e = hipSuccess;
+    if (p_) e = hipFree(p_);
+    p_ = nullptr;
+    cap_ = 0;
+    if (e == hipSuccess) e = hipMalloc(&p_, n * sizeof(T));
+    if (e != hipSuccess) { p_ = nullptr; return e; }
+    cap_ = n;
+    return hipSuccess;
+  }
+  T* get() const { return p_; }
+  size_t capacity() const { return cap_; }
+
+ private:
+  T* p_ = nullptr;
+  size_t cap_ = 0;
+};
+
+// Everything a trace-kernel launch needs, decided from the context's scene and uniforms: the
+// argument block, which kernel walks the sphere list, launch geometry.  No HIP call in here that
+// enqueues work, allocates or synchronises (capture-safe).
+struct Launch {
+  PtKernelArgs A;
+  const void* kfn = nullptr;
+  uint32_t grid = 1, block = 256;
+  size_t lds = 0;
+  int path = 0;
+  int trial = -1;  // k when this launch is the autotune measurement of trial_paths[k]
+};
+
+// Everything a frame bakes into its launches: decided BEFORE anything is enqueued (prepare_launch queries
+// occupancy and the autotuner's events — not things to do inside a stream capture), and what the cached graph of
+// pt_render_frames is keyed on.  Zeroed with memset and compared bytewise, padding included (plan_frame).
+struct FramePlan {
+  Launch L;
+  const uint32_t* ctr = nullptr;  // the device cell holding a frame's number in its series
+  uint32_t even_odd0 = 0;
+  int max_render_count = 0, render_count0 = 0, should_average = 0;
+  float last_frame_weight = 0.f;
+  hipStream_t stream = nullptr;
+  float4* slab = nullptr;
+  uint32_t* tex0 = nullptr; uint32_t* tex1 = nullptr; uint32_t* canvas = nullptr;
+  uint32_t n_frames = 1;  // frames traced by the one launch (as its passes), blended one after the other
+};
+
 struct pt_ctx {
   int device = 0;
   uint32_t width = 0, height = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr; // own_stream or the caller's
   // scene
-  float* d_geom = nullptr;
-  PtMatRec* d_mat = nullptr;
+  DevBuf<float> d_geom;
+  DevBuf<char> d_mat;  // sphere_cap shading records, then their r0 pairs (PtKernelArgs::mat_r0)
   uint32_t n_spheres = 0, sphere_cap = 0;
   bool scene_regular = true;
   bool have_spheres = false, have_params = false;
   PtParams params{};
   uint32_t local_rows = 0;
   // accumulation
-  float4* own_accum = nullptr;
-  size_t own_accum_pixels = 0;
-  float4* accum = nullptr; // own_accum or caller-bound
+  DevBuf<float4> own_accum;
+  float4* accum = nullptr; // own_accum or caller-bound (never freed here)
   size_t accum_pixels = 0;
   bool accum_bound = false;
   uint32_t total_spp = 0;   // enqueued directly (not through graph replays)
   bool captured = false;    // some launch was captured into a hipGraph: only the device knows the spp
-  // per-pass slabs
-  float4* d_slab = nullptr;
-  size_t slab_pixels = 0; // capacity in pixels (passes * local pixels)
+  // per-pass slabs (passes * local pixels)
+  DevBuf<float4> d_slab;
   uint32_t reserved_passes = 1;
   // read-out staging
-  float4* d_resolve = nullptr;
-  size_t resolve_pixels = 0;
+  DevBuf<float4> d_resolve;
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   int geom_policy = PT_GEOM_AUTO;
   int geom_tuned = 0;              // the path PT_GEOM_AUTO settled on, 0 while measuring
@@ -75,12 +129,11 @@ struct pt_ctx {
   double trial_samples[4] = {0.0, 0.0, 0.0, 0.0};
   // culling hierarchy (PT_GEOM_BVH), rebuilt by pt_set_spheres; absent for tiny / irregular scenes
   bool have_bvh = false;
-  uint32_t* d_bvh_nodes = nullptr;
-  float* d_bvh_nodes32 = nullptr;
-  float* d_bvh_slots = nullptr;
-  uint32_t* d_bvh_index = nullptr;
-  PtMatRec* d_bvh_mat = nullptr;   // per slot: the material of the slot's sphere
-  size_t bvh_node_cap = 0, bvh_slot_cap = 0;
+  DevBuf<uint32_t> d_bvh_nodes;
+  DevBuf<float> d_bvh_nodes32;
+  DevBuf<float> d_bvh_slots;
+  DevBuf<uint32_t> d_bvh_index;
+  DevBuf<PtMatRec> d_bvh_mat;   // per slot: the material of the slot's sphere
   uint32_t bvh_n_nodes = 0, bvh_n_slots = 0, bvh_n_tree_slots = 0, bvh_n_outliers = 0, bvh_depth = 0;
   float bvh_c0[3] = {0, 0, 0}, bvh_s0 = 0, bvh_kinv = 1;
   // uniform grid (PT_GEOM_GRID), rebuilt by pt_set_spheres; absent for tiny / irregular scenes
@@ -88,26 +141,24 @@ struct pt_ctx {
   // host copies of what the grid is built from: pt_tune rebuilds it for the view (fit_grid_to_view)
   std::vector<float> h_geom, h_radii;
   std::vector<PtMatRec> h_mat;
-  uint32_t* d_grid_cells = nullptr;
-  float* d_grid_entries = nullptr;
-  uint32_t* d_grid_index = nullptr;
-  PtMatRec* d_grid_mat = nullptr;
-  size_t grid_cell_cap = 0, grid_entry_cap = 0;
+  DevBuf<uint32_t> d_grid_cells;
+  DevBuf<float> d_grid_entries;  // 16 B per entry
+  DevBuf<uint32_t> d_grid_index;
+  DevBuf<PtMatRec> d_grid_mat;
   ptgrid::Grid grid;  // host copy of the scalars (the arrays are released after upload)
   bool grid_cells_build = false;  // pt_tune measured the build that gathers its entries from L2 faster than the LDS-staged one on this scene and view
   int grid_fit_mode = 0;  // PT_OPT_GRID_FIT: 0 pt_tune measures the margin classes, 1 it takes the one the camera needs unmeasured
   int count_work = 0; // PT_OPT_COUNT_WORK: launch the measuring twin of the walk kernel
-  uint32_t* d_cell_hist = nullptr;           // grid twins: leaf-round lanes per entry run + coherence bins (pt_debug_cell_hist)
-  size_t cell_hist_cap = 0, cell_hist_n = 0;
-  unsigned long long* d_wave_log = nullptr;  // measuring twins: per-wave {start, queue dry, end}
-  size_t wave_log_cap = 0, wave_log_n = 0;
+  DevBuf<uint32_t> d_cell_hist;           // grid twins: leaf-round lanes per entry run + coherence bins (pt_debug_cell_hist)
+  size_t cell_hist_n = 0;
+  DevBuf<unsigned long long> d_wave_log;  // measuring twins: per-wave {start, queue dry, end}
+  size_t wave_log_n = 0;
   uint32_t carry_lanes = 12;
   uint32_t refill_min = 4;
   int rr_min_depth = 0;  // PT_OPT_RUSSIAN_ROULETTE: 0 = off (the reference's estimator, bit-exact against the oracle)
-  // work-queue ordering feedback
-  uint32_t* d_tile_cost = nullptr;
-  uint32_t* d_tile_order = nullptr;
-  size_t tile_cap = 0;
+  // work-queue ordering feedback, one entry per tile
+  DevBuf<uint32_t> d_tile_cost;
+  DevBuf<uint32_t> d_tile_order;
   bool tile_order_valid = false;  // d_tile_order holds an order for the current tile count
   // the frames' cost-sorted tile order (ensure_cost_order): which view and scene it was probed for, frames drawn since
   bool order_probed = false;
@@ -116,19 +167,17 @@ struct pt_ctx {
   uint32_t frames_since_probe = 0;
   // the reference's frame (pt_render_frame / pt_render_frames): two RGBA8 textures + canvas, the
   // device-side frame counter ([0] frames replayed since the series began, [1] a cell that stays 0)
-  uint32_t* d_tex[2] = {nullptr, nullptr};
-  uint32_t* d_canvas = nullptr;
-  size_t tex_pixels = 0;
-  uint32_t* d_frame_ctr = nullptr;
+  DevBuf<uint32_t> d_tex[2];
+  DevBuf<uint32_t> d_canvas;
+  DevBuf<uint32_t> d_frame_ctr;
   // captured frames, one graph per group size (kFrameGroups: 64, 16, 4, 1 frames — a group is ONE trace launch of that many passes,
   // one kernel for their blends, one advance; a single frame is trace + blend + advance), each captured once per plan
   hipGraphExec_t frame_exec[4] = {nullptr, nullptr, nullptr, nullptr};
-  unsigned char frame_plan[4][1024] = {{0}, {0}, {0}, {0}};  // the FramePlan each cached graph was captured from (compared bytewise)
-  float4* d_frame_slab = nullptr;        // a group's slabs (up to 16 passes), allocated by the first pt_render_frames that needs them
-  size_t frame_slab_pixels = 0;
+  FramePlan frame_plan[4];               // the plan each cached graph was captured from (copied and compared bytewise)
+  DevBuf<float4> d_frame_slab;           // a group's slabs (up to 16 passes), allocated by the first pt_render_frames that needs them
   uint64_t epoch = 0;                    // bumped by everything a captured frame bakes in
   // counters + timing
-  unsigned long long* d_counters = nullptr;
+  DevBuf<unsigned long long> d_counters;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events; // pool
   size_t events_used = 0;
   double kernel_ms = 0.0;
@@ -140,6 +189,14 @@ struct pt_ctx {
   // host-clock durations of the set-up calls, ms (include/ptrace_dev.h pt_debug_setup_times: where a first frame's time goes)
   double setup_ms[PT_SETUP_COUNT] = {0};
   std::string error;
+
+  // what the context owns besides its buffers (those free themselves); the caller's stream is left alone
+  ~pt_ctx() {
+    for (auto& ev : events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+    for (hipEvent_t e : trial_ev) if (e) (void)hipEventDestroy(e);
+    for (hipGraphExec_t e : frame_exec) if (e) (void)hipGraphExecDestroy(e);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
 };
 
 namespace {
@@ -147,8 +204,8 @@ namespace {
 // the work queue's heads start a launch at zero: the shared head, or the grouped queue's (pt_refill.hpp)
 inline hipError_t zero_queue_heads(pt_ctx* c, uint32_t queue_static) {
   if (queue_static == 2u)
-    return hipMemsetAsync(&c->d_counters[PT_CTR_GROUP_HEADS], 0, 8 * PT_QUEUE_GROUPS_MAX * sizeof(unsigned long long), c->stream);
-  if (queue_static == 0u) return hipMemsetAsync(&c->d_counters[PT_CTR_HEAD], 0, sizeof(unsigned long long), c->stream);
+    return hipMemsetAsync(c->d_counters.get() + PT_CTR_GROUP_HEADS, 0, 8 * PT_QUEUE_GROUPS_MAX * sizeof(unsigned long long), c->stream);
+  if (queue_static == 0u) return hipMemsetAsync(c->d_counters.get() + PT_CTR_HEAD, 0, sizeof(unsigned long long), c->stream);
   return hipSuccess;
 }
 
@@ -200,63 +257,43 @@ int ensure_buffers(pt_ctx* c) {
   size_t pix = (size_t)c->local_rows * c->width;
   if (pix == 0) pix = 1;
   if (!c->accum_bound) {
-    if (c->own_accum_pixels < pix) {
-      if (c->own_accum) PT_HIP(c, hipFree(c->own_accum));
-      c->own_accum = nullptr;
-      PT_HIP(c, hipMalloc(&c->own_accum, pix * sizeof(float4)));
-      c->own_accum_pixels = pix;
-      PT_HIP(c, hipMemsetAsync(c->own_accum, 0, pix * sizeof(float4), c->stream));
+    if (c->own_accum.capacity() < pix) {
+      PT_HIP(c, c->own_accum.reserve(pix));
+      PT_HIP(c, hipMemsetAsync(c->own_accum.get(), 0, pix * sizeof(float4), c->stream));
       c->total_spp = 0;
     }
-    c->accum = c->own_accum;
-    c->accum_pixels = c->own_accum_pixels;
+    c->accum = c->own_accum.get();
+    c->accum_pixels = c->own_accum.capacity();
   }
-  size_t need = pix * (size_t)c->reserved_passes;
-  if (c->slab_pixels < need) {
-    if (c->d_slab) PT_HIP(c, hipFree(c->d_slab));
-    c->d_slab = nullptr;
-    PT_HIP(c, hipMalloc(&c->d_slab, need * sizeof(float4)));
-    c->slab_pixels = need;
-  }
+  const size_t need = pix * (size_t)c->reserved_passes;
+  if (c->d_slab.capacity() < need) PT_HIP(c, c->d_slab.reserve(need));
   size_t tiles = (size_t)((c->width + 7) / 8) * ((c->local_rows + 7) / 8);
   if (tiles == 0) tiles = 1;
-  if (c->tile_cap != tiles) {
-    if (c->d_tile_cost) PT_HIP(c, hipFree(c->d_tile_cost));
-    if (c->d_tile_order) PT_HIP(c, hipFree(c->d_tile_order));
-    c->d_tile_cost = nullptr; c->d_tile_order = nullptr;
-    PT_HIP(c, hipMalloc(&c->d_tile_cost, tiles * sizeof(uint32_t)));
-    PT_HIP(c, hipMalloc(&c->d_tile_order, tiles * sizeof(uint32_t)));
-    PT_HIP(c, hipMemsetAsync(c->d_tile_cost, 0, tiles * sizeof(uint32_t), c->stream));
+  // reallocated and re-seeded whenever the tile count CHANGES, not only when it grows: an order left from another count would
+  // name tiles that do not exist, or miss some
+  if (c->d_tile_cost.capacity() != tiles || c->d_tile_order.capacity() != tiles) {
+    PT_HIP(c, c->d_tile_cost.reserve(tiles));
+    PT_HIP(c, c->d_tile_order.reserve(tiles));
+    PT_HIP(c, hipMemsetAsync(c->d_tile_cost.get(), 0, tiles * sizeof(uint32_t), c->stream));
     {
       // the identity order from the start: a launch that skips the order kernel (because an earlier one was only
       // CAPTURED into a caller's hipGraph and has not run yet) must still find every tile exactly once
       std::vector<uint32_t> ident(tiles);
       for (size_t i = 0; i < tiles; i++) ident[i] = (uint32_t)i;
-      PT_HIP(c, hipMemcpy(c->d_tile_order, ident.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+      PT_HIP(c, hipMemcpy(c->d_tile_order.get(), ident.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    c->tile_cap = tiles;
     c->tile_order_valid = false;
     c->order_probed = false;
   }
-  if (c->tex_pixels < pix) {  // create_texture x2 (src/webgl.rs:82-123), cleared: alpha 0 = "no data" (shader.frag:391)
+  if (c->d_canvas.capacity() < pix) {  // create_texture x2 (src/webgl.rs:82-123), cleared: alpha 0 = "no data" (shader.frag:391)
     for (int k = 0; k < 2; k++) {
-      if (c->d_tex[k]) PT_HIP(c, hipFree(c->d_tex[k]));
-      c->d_tex[k] = nullptr;
-      PT_HIP(c, hipMalloc(&c->d_tex[k], pix * sizeof(uint32_t)));
-      PT_HIP(c, hipMemsetAsync(c->d_tex[k], 0, pix * sizeof(uint32_t), c->stream));
+      PT_HIP(c, c->d_tex[k].reserve(pix));
+      PT_HIP(c, hipMemsetAsync(c->d_tex[k].get(), 0, pix * sizeof(uint32_t), c->stream));
     }
-    if (c->d_canvas) PT_HIP(c, hipFree(c->d_canvas));
-    c->d_canvas = nullptr;
-    PT_HIP(c, hipMalloc(&c->d_canvas, pix * sizeof(uint32_t)));
-    PT_HIP(c, hipMemsetAsync(c->d_canvas, 0, pix * sizeof(uint32_t), c->stream));
-    c->tex_pixels = pix;
+    PT_HIP(c, c->d_canvas.reserve(pix));  // (last: its capacity says all three are in place)
+    PT_HIP(c, hipMemsetAsync(c->d_canvas.get(), 0, pix * sizeof(uint32_t), c->stream));
   }
-  if (c->resolve_pixels < pix) {
-    if (c->d_resolve) PT_HIP(c, hipFree(c->d_resolve));
-    c->d_resolve = nullptr;
-    PT_HIP(c, hipMalloc(&c->d_resolve, pix * sizeof(float4)));
-    c->resolve_pixels = pix;
-  }
+  if (c->d_resolve.capacity() < pix) PT_HIP(c, c->d_resolve.reserve(pix));
   return PT_OK;
 }
 
@@ -268,6 +305,40 @@ int fold_events(pt_ctx* c) {
     c->kernel_ms += (double)ms;
   }
   c->events_used = 0;
+  return PT_OK;
+}
+
+// the next pair of the timing event pool: a new pair while the pool holds fewer than 512, else the pool is drained first
+// (this synchronises, but only once per 512 launches)
+int next_events(pt_ctx* c, std::pair<hipEvent_t, hipEvent_t>** ev) {
+  if (c->events_used == c->events.size()) {
+    if (c->events.size() >= 512) {
+      PT_HIP(c, hipStreamSynchronize(c->stream));
+      int rc = fold_events(c);
+      if (rc != PT_OK) return rc;
+    } else {
+      hipEvent_t a, b;
+      PT_HIP(c, hipEventCreate(&a));
+      PT_HIP(c, hipEventCreate(&b));
+      c->events.emplace_back(a, b);
+    }
+  }
+  *ev = &c->events[c->events_used++];
+  return PT_OK;
+}
+
+// is the context's stream being captured into a hipGraph (its own or a caller's)?
+bool is_capturing(const pt_ctx* c) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(c->stream, &cap);
+  return cap != hipStreamCaptureStatusNone;
+}
+
+// the queue order of the tiles from their costs (the identity while every cost is zero)
+int launch_tile_order(pt_ctx* c) {
+  hipLaunchKernelGGL(pt_tile_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tile_cost.get(), c->d_tile_order.get(),
+                     ((c->width + 7) / 8) * ((c->local_rows + 7) / 8));
+  PT_HIP(c, hipGetLastError());
   return PT_OK;
 }
 
@@ -412,7 +483,7 @@ static int create_common(pt_ctx** out, int device, uint32_t width, uint32_t heig
   c->local_rows = height;
   auto bail = [&](hipError_t e, const char* what) {
     fail(nullptr, PT_ERR_HIP, "pt_create: %s: %s", what, hipGetErrorString(e));
-    delete c;
+    delete c;  // (frees whatever was made before the failure)
     return PT_ERR_HIP;
   };
   hipError_t e;
@@ -430,30 +501,21 @@ static int create_common(pt_ctx** out, int device, uint32_t width, uint32_t heig
     c->stream = c->own_stream;
   }
   const double t_stream = host_ms();
-  if ((e = hipMalloc(&c->d_counters, PT_CTR_ALLOC * sizeof(unsigned long long))) != hipSuccess)
-    return bail(e, "hipMalloc(counters)");
+  if ((e = c->d_counters.reserve(PT_CTR_ALLOC)) != hipSuccess) return bail(e, "hipMalloc(counters)");
   const double t_first_malloc = host_ms();
-  if ((e = hipMemsetAsync(c->d_counters, 0, PT_CTR_ALLOC * sizeof(unsigned long long), c->stream)) != hipSuccess)
+  if ((e = hipMemsetAsync(c->d_counters.get(), 0, PT_CTR_ALLOC * sizeof(unsigned long long), c->stream)) != hipSuccess)
     return bail(e, "hipMemsetAsync(counters)");
   const double t_first_memset = host_ms();
-  if ((e = hipMalloc(&c->d_frame_ctr, 2 * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMalloc(frame counter)");
-  if ((e = hipMemsetAsync(c->d_frame_ctr, 0, 2 * sizeof(uint32_t), c->stream)) != hipSuccess)
+  if ((e = c->d_frame_ctr.reserve(2)) != hipSuccess) return bail(e, "hipMalloc(frame counter)");
+  if ((e = hipMemsetAsync(c->d_frame_ctr.get(), 0, 2 * sizeof(uint32_t), c->stream)) != hipSuccess)
     return bail(e, "hipMemsetAsync(frame counter)");
   const double t_small_allocs = host_ms();
-  // allow the trace kernel to use the CU's whole 160 KiB LDS for big sphere lists
+  // allow the trace kernels to use the CU's whole 160 KiB LDS for big sphere lists
   // (the first hipFuncSetAttribute of a process also LOADS this translation unit's code object onto the device)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pt_trace_kernel),
-                      hipFuncAttributeMaxDynamicSharedMemorySize, PT_LDS_ENTRIES(PT_MAX_SPHERES_LDS) * 16);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pt_trace_kernel_scalar),
-                      hipFuncAttributeMaxDynamicSharedMemorySize, PT_LDS_ENTRIES(PT_MAX_SPHERES_LDS) * 16);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pt_trace_kernel_bvh),
-                      hipFuncAttributeMaxDynamicSharedMemorySize, PT_LDS_ENTRIES(PT_MAX_SPHERES_LDS) * 16);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pt_trace_kernel_bvh_nodes),
-                      hipFuncAttributeMaxDynamicSharedMemorySize, PT_LDS_ENTRIES(PT_MAX_SPHERES_LDS) * 16);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pt_trace_kernel_bvh_gmem),
-                      hipFuncAttributeMaxDynamicSharedMemorySize, PT_LDS_ENTRIES(PT_MAX_SPHERES_LDS) * 16);
-  for (const void* k : {PT_KFN(pt_trace_kernel_grid), PT_KFN(pt_trace_kernel_grid_cells), PT_KFN(pt_trace_kernel_grid_gmem)})
-    (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, PT_LDS_ENTRIES(PT_MAX_SPHERES_LDS) * 16);
+  for (const void* k : {PT_KFN(pt_trace_kernel), PT_KFN(pt_trace_kernel_scalar), PT_KFN(pt_trace_kernel_bvh),
+                        PT_KFN(pt_trace_kernel_bvh_nodes), PT_KFN(pt_trace_kernel_bvh_gmem), PT_KFN(pt_trace_kernel_grid),
+                        PT_KFN(pt_trace_kernel_grid_cells), PT_KFN(pt_trace_kernel_grid_gmem)})
+    (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
   (void)hipGetLastError(); // a refused attribute only limits that kernel to the default 64 KiB; the launch code checks sizes
   const double t_code = host_ms();
   int rc = ensure_buffers(c);
@@ -483,33 +545,6 @@ PT_API int pt_destroy(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  for (auto& ev : c->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-  for (hipEvent_t e : c->trial_ev) if (e) (void)hipEventDestroy(e);
-  if (c->d_geom) (void)hipFree(c->d_geom);
-  if (c->d_mat) (void)hipFree(c->d_mat);
-  if (c->d_bvh_nodes) (void)hipFree(c->d_bvh_nodes);
-  if (c->d_bvh_nodes32) (void)hipFree(c->d_bvh_nodes32);
-  if (c->d_bvh_slots) (void)hipFree(c->d_bvh_slots);
-  if (c->d_bvh_index) (void)hipFree(c->d_bvh_index);
-  if (c->d_bvh_mat) (void)hipFree(c->d_bvh_mat);
-  if (c->d_wave_log) (void)hipFree(c->d_wave_log);
-  if (c->d_cell_hist) (void)hipFree(c->d_cell_hist);
-  if (c->d_grid_cells) (void)hipFree(c->d_grid_cells);
-  if (c->d_grid_entries) (void)hipFree(c->d_grid_entries);
-  if (c->d_grid_index) (void)hipFree(c->d_grid_index);
-  if (c->d_grid_mat) (void)hipFree(c->d_grid_mat);
-  if (c->own_accum) (void)hipFree(c->own_accum);
-  if (c->d_slab) (void)hipFree(c->d_slab);
-  if (c->d_resolve) (void)hipFree(c->d_resolve);
-  if (c->d_counters) (void)hipFree(c->d_counters);
-  for (hipGraphExec_t e : c->frame_exec) if (e) (void)hipGraphExecDestroy(e);
-  if (c->d_frame_slab) (void)hipFree(c->d_frame_slab);
-  if (c->d_frame_ctr) (void)hipFree(c->d_frame_ctr);
-  for (int k = 0; k < 2; k++) if (c->d_tex[k]) (void)hipFree(c->d_tex[k]);
-  if (c->d_canvas) (void)hipFree(c->d_canvas);
-  if (c->d_tile_cost) (void)hipFree(c->d_tile_cost);
-  if (c->d_tile_order) (void)hipFree(c->d_tile_order);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return PT_OK;
 }
@@ -547,35 +582,23 @@ bool build_grid(const float* geom, const float* radii, uint32_t n, double near_f
 int install_grid(pt_ctx* c, ptgrid::Grid& grid, const PtMatRec* mat, uint32_t n) {
   c->have_grid = false;  // (until everything below has succeeded: a failed allocation must not leave a grid that points nowhere)
   const size_t n_cells_pad = (grid.cells.size() + 3u) & ~(size_t)3u;  // the kernels stage 16 B at a time
-  if (n_cells_pad > c->grid_cell_cap) {
-    if (c->d_grid_cells) PT_HIP(c, hipFree(c->d_grid_cells));
-    c->d_grid_cells = nullptr; c->grid_cell_cap = 0;
-    PT_HIP(c, hipMalloc(&c->d_grid_cells, n_cells_pad * sizeof(uint32_t)));
-    c->grid_cell_cap = n_cells_pad;
-  }
+  if (c->d_grid_cells.capacity() < n_cells_pad) PT_HIP(c, c->d_grid_cells.reserve(n_cells_pad));
   // + four entries of slack: a leaf round reads four consecutive entries whatever the cell's
   // count (and lanes without a cell under test read, and discard, wherever their stale record points)
   const size_t n_ent_pad = (size_t)grid.n_entries + 4u;
-  if (n_ent_pad > c->grid_entry_cap) {
-    if (c->d_grid_entries) PT_HIP(c, hipFree(c->d_grid_entries));
-    if (c->d_grid_index) PT_HIP(c, hipFree(c->d_grid_index));
-    if (c->d_grid_mat) PT_HIP(c, hipFree(c->d_grid_mat));
-    c->d_grid_entries = nullptr; c->d_grid_index = nullptr; c->d_grid_mat = nullptr; c->grid_entry_cap = 0;
-    PT_HIP(c, hipMalloc(&c->d_grid_entries, n_ent_pad * 16));
-    PT_HIP(c, hipMalloc(&c->d_grid_index, n_ent_pad * sizeof(uint32_t)));
-    PT_HIP(c, hipMalloc(&c->d_grid_mat, n_ent_pad * sizeof(PtMatRec)));
-    c->grid_entry_cap = n_ent_pad;
-  }
-  PT_HIP(c, hipMemset(c->d_grid_cells, 0, n_cells_pad * sizeof(uint32_t)));
-  PT_HIP(c, hipMemcpy(c->d_grid_cells, grid.cells.data(), grid.cells.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  PT_HIP(c, hipMemset(c->d_grid_entries, 0, n_ent_pad * 16));
-  PT_HIP(c, hipMemcpy(c->d_grid_entries, grid.entries.data(), (size_t)grid.n_entries * 16, hipMemcpyHostToDevice));
-  PT_HIP(c, hipMemset(c->d_grid_index, 0xff, n_ent_pad * sizeof(uint32_t)));
-  PT_HIP(c, hipMemcpy(c->d_grid_index, grid.entry_index.data(), (size_t)grid.n_entries * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (c->d_grid_entries.capacity() < n_ent_pad * 4) PT_HIP(c, c->d_grid_entries.reserve(n_ent_pad * 4));
+  if (c->d_grid_index.capacity() < n_ent_pad) PT_HIP(c, c->d_grid_index.reserve(n_ent_pad));
+  if (c->d_grid_mat.capacity() < n_ent_pad) PT_HIP(c, c->d_grid_mat.reserve(n_ent_pad));
+  PT_HIP(c, hipMemset(c->d_grid_cells.get(), 0, n_cells_pad * sizeof(uint32_t)));
+  PT_HIP(c, hipMemcpy(c->d_grid_cells.get(), grid.cells.data(), grid.cells.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  PT_HIP(c, hipMemset(c->d_grid_entries.get(), 0, n_ent_pad * 16));
+  PT_HIP(c, hipMemcpy(c->d_grid_entries.get(), grid.entries.data(), (size_t)grid.n_entries * 16, hipMemcpyHostToDevice));
+  PT_HIP(c, hipMemset(c->d_grid_index.get(), 0xff, n_ent_pad * sizeof(uint32_t)));
+  PT_HIP(c, hipMemcpy(c->d_grid_index.get(), grid.entry_index.data(), (size_t)grid.n_entries * sizeof(uint32_t), hipMemcpyHostToDevice));
   {
     std::vector<PtMatRec> sm(n_ent_pad);
     for (size_t k = 0; k < (size_t)grid.n_entries; k++) sm[k] = grid.entry_index[k] < n ? mat[grid.entry_index[k]] : PtMatRec{};
-    PT_HIP(c, hipMemcpy(c->d_grid_mat, sm.data(), sm.size() * sizeof(PtMatRec), hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->d_grid_mat.get(), sm.data(), sm.size() * sizeof(PtMatRec), hipMemcpyHostToDevice));
   }
   grid.cells.clear(); grid.cells.shrink_to_fit();
   grid.entries.clear(); grid.entries.shrink_to_fit();
@@ -594,12 +617,10 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
                 n, PT_MAX_SPHERES);
   PT_HIP(c, hipSetDevice(c->device));
   const double t_begin = host_ms();
-  if (n > c->sphere_cap || !c->d_geom) {
-    if (c->d_geom) PT_HIP(c, hipFree(c->d_geom));
-    if (c->d_mat) PT_HIP(c, hipFree(c->d_mat));
-    c->d_geom = nullptr; c->d_mat = nullptr;
-    PT_HIP(c, hipMalloc(&c->d_geom, (size_t)PT_LDS_ENTRIES(n) * 16));
-    PT_HIP(c, hipMalloc(&c->d_mat, (size_t)(n ? n : 1) * (sizeof(PtMatRec) + 2 * sizeof(float))));  // (+ the r0 pairs behind the records)
+  if (n > c->sphere_cap || !c->d_geom.get() || !c->d_mat.get()) {
+    c->sphere_cap = 0;
+    PT_HIP(c, c->d_geom.reserve((size_t)PT_LDS_ENTRIES(n) * 4));
+    PT_HIP(c, c->d_mat.reserve((size_t)(n ? n : 1) * (sizeof(PtMatRec) + 2 * sizeof(float))));  // (+ the r0 pairs behind the records)
     c->sphere_cap = n;
   }
   // split into the 16-byte geometry record the intersection loop stages into LDS and the 32-byte
@@ -647,10 +668,10 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
   {
     // the stream may still be reading the previous scene
     PT_HIP(c, hipStreamSynchronize(c->stream));
-    PT_HIP(c, hipMemcpy(c->d_geom, geom.data(), (size_t)n_pad * 16, hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->d_geom.get(), geom.data(), (size_t)n_pad * 16, hipMemcpyHostToDevice));
   }
   if (n) {
-    PT_HIP(c, hipMemcpy(c->d_mat, mat.data(), (size_t)n * sizeof(PtMatRec), hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->d_mat.get(), mat.data(), (size_t)n * sizeof(PtMatRec), hipMemcpyHostToDevice));
     // reflectance()'s r0 = ((1 - ratio) / (1 + ratio))^2 (static/shader.frag:205) for both ratios a GLASS sphere is entered
     // with, 1 / ri (front face) and ri: a subtraction, an addition, an IEEE division and a product in fp32 under
     // -ffp-contract=off give the same bits here as in the kernel.  Read by the small-list kernels only (pt_shade.hpp): in
@@ -664,37 +685,24 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
       r0[2 * i] = qf * qf;
       r0[2 * i + 1] = qb * qb;
     }
-    PT_HIP(c, hipMemcpy(reinterpret_cast<char*>(c->d_mat) + (size_t)c->sphere_cap * sizeof(PtMatRec), r0.data(), r0.size() * sizeof(float), hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->d_mat.get() + (size_t)c->sphere_cap * sizeof(PtMatRec), r0.data(), r0.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   c->have_bvh = false;
   if (have_bvh) {
-    if (bvh.nodes16.size() > c->bvh_node_cap) {
-      if (c->d_bvh_nodes) PT_HIP(c, hipFree(c->d_bvh_nodes));
-      if (c->d_bvh_nodes32) PT_HIP(c, hipFree(c->d_bvh_nodes32));
-      c->d_bvh_nodes = nullptr; c->d_bvh_nodes32 = nullptr; c->bvh_node_cap = 0;
-      PT_HIP(c, hipMalloc(&c->d_bvh_nodes, bvh.nodes16.size() * sizeof(uint32_t)));
-      PT_HIP(c, hipMalloc(&c->d_bvh_nodes32, bvh.nodes32.size() * sizeof(float)));
-      c->bvh_node_cap = bvh.nodes16.size();
-    }
-    if (bvh.slots.size() > c->bvh_slot_cap) {
-      if (c->d_bvh_slots) PT_HIP(c, hipFree(c->d_bvh_slots));
-      if (c->d_bvh_index) PT_HIP(c, hipFree(c->d_bvh_index));
-      if (c->d_bvh_mat) PT_HIP(c, hipFree(c->d_bvh_mat));
-      c->d_bvh_slots = nullptr; c->d_bvh_index = nullptr; c->d_bvh_mat = nullptr; c->bvh_slot_cap = 0;
-      PT_HIP(c, hipMalloc(&c->d_bvh_slots, bvh.slots.size() * sizeof(float)));
-      PT_HIP(c, hipMalloc(&c->d_bvh_index, bvh.slot_index.size() * sizeof(uint32_t)));
-      PT_HIP(c, hipMalloc(&c->d_bvh_mat, bvh.slot_index.size() * sizeof(PtMatRec)));
-      c->bvh_slot_cap = bvh.slots.size();
-    }
-    PT_HIP(c, hipMemcpy(c->d_bvh_nodes, bvh.nodes16.data(), bvh.nodes16.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->d_bvh_nodes32, bvh.nodes32.data(), bvh.nodes32.size() * sizeof(float), hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->d_bvh_slots, bvh.slots.data(), bvh.slots.size() * sizeof(float), hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->d_bvh_index, bvh.slot_index.data(), bvh.slot_index.size() * sizeof(uint32_t),
+    if (c->d_bvh_nodes.capacity() < bvh.nodes16.size()) PT_HIP(c, c->d_bvh_nodes.reserve(bvh.nodes16.size()));
+    if (c->d_bvh_nodes32.capacity() < bvh.nodes32.size()) PT_HIP(c, c->d_bvh_nodes32.reserve(bvh.nodes32.size()));
+    if (c->d_bvh_slots.capacity() < bvh.slots.size()) PT_HIP(c, c->d_bvh_slots.reserve(bvh.slots.size()));
+    if (c->d_bvh_index.capacity() < bvh.slot_index.size()) PT_HIP(c, c->d_bvh_index.reserve(bvh.slot_index.size()));
+    if (c->d_bvh_mat.capacity() < bvh.slot_index.size()) PT_HIP(c, c->d_bvh_mat.reserve(bvh.slot_index.size()));
+    PT_HIP(c, hipMemcpy(c->d_bvh_nodes.get(), bvh.nodes16.data(), bvh.nodes16.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->d_bvh_nodes32.get(), bvh.nodes32.data(), bvh.nodes32.size() * sizeof(float), hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->d_bvh_slots.get(), bvh.slots.data(), bvh.slots.size() * sizeof(float), hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->d_bvh_index.get(), bvh.slot_index.data(), bvh.slot_index.size() * sizeof(uint32_t),
                         hipMemcpyHostToDevice));
     {
       std::vector<PtMatRec> sm(bvh.slot_index.size());
       for (size_t k = 0; k < sm.size(); k++) sm[k] = bvh.slot_index[k] < n ? mat[bvh.slot_index[k]] : PtMatRec{};
-      PT_HIP(c, hipMemcpy(c->d_bvh_mat, sm.data(), sm.size() * sizeof(PtMatRec), hipMemcpyHostToDevice));
+      PT_HIP(c, hipMemcpy(c->d_bvh_mat.get(), sm.data(), sm.size() * sizeof(PtMatRec), hipMemcpyHostToDevice));
     }
     c->bvh_n_nodes = bvh.n_nodes; c->bvh_n_slots = bvh.n_slots; c->bvh_n_tree_slots = bvh.n_tree_slots;
     c->bvh_n_outliers = bvh.n_outliers; c->bvh_depth = bvh.depth;
@@ -815,7 +823,7 @@ PT_API int pt_reset_accum(pt_ctx* c) {
   PT_HIP(c, hipSetDevice(c->device));
   if (c->accum)
     PT_HIP(c, hipMemsetAsync(c->accum, 0, (size_t)c->local_rows * c->width * sizeof(float4), c->stream));
-  PT_HIP(c, hipMemsetAsync(c->d_counters, 0, PT_CTR_COUNT * sizeof(unsigned long long), c->stream));
+  PT_HIP(c, hipMemsetAsync(c->d_counters.get(), 0, PT_CTR_COUNT * sizeof(unsigned long long), c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   c->events_used = 0;
   c->kernel_ms = 0.0;
@@ -879,10 +887,10 @@ PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
   // the first and the last pixel must agree — is checked there, and only then does it replace the
   // accumulation.  A refused checkpoint leaves the context as it was.
   const size_t n_pix = (size_t)c->local_rows * c->width;
-  PT_HIP(c, hipMemcpyAsync(c->d_resolve, src, need, hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipMemcpyAsync(c->d_resolve.get(), src, need, hipMemcpyDefault, c->stream));
   float4 ends[2];
-  PT_HIP(c, hipMemcpyAsync(&ends[0], c->d_resolve, sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  PT_HIP(c, hipMemcpyAsync(&ends[1], c->d_resolve + (n_pix - 1), sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipMemcpyAsync(&ends[0], c->d_resolve.get(), sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipMemcpyAsync(&ends[1], c->d_resolve.get() + (n_pix - 1), sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   const float w = ends[0].w;
   if (!(w >= 0.0f) || w >= 16777216.0f || w != std::floor(w))
@@ -890,7 +898,7 @@ PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
   if (ends[1].w != w)
     return fail(c, PT_ERR_INVALID, "pt_load_accum: sample counts differ across the buffer (%g ... %g): not an accumulation of whole passes",
                 (double)w, (double)ends[1].w);
-  PT_HIP(c, hipMemcpyAsync(c->accum, c->d_resolve, need, hipMemcpyDeviceToDevice, c->stream));
+  PT_HIP(c, hipMemcpyAsync(c->accum, c->d_resolve.get(), need, hipMemcpyDeviceToDevice, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   // the host-side mirrors follow the loaded state
   c->total_spp = (uint32_t)w;
@@ -898,18 +906,6 @@ PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
   c->captured = false;
   return PT_OK;
 }
-
-// Everything a trace-kernel launch needs, decided from the context's scene and uniforms: the
-// argument block, which kernel walks the sphere list, launch geometry.  No HIP call in here that
-// enqueues work, allocates or synchronises (capture-safe).
-struct Launch {
-  PtKernelArgs A;
-  const void* kfn = nullptr;
-  uint32_t grid = 1, block = 256;
-  size_t lds = 0;
-  int path = 0;
-  int trial = -1;  // k when this launch is the autotune measurement of trial_paths[k]
-};
 
 // the shader's uniforms (static/shader.frag:79-99) + this launch's share of the image, as the kernels read them
 static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
@@ -960,13 +956,13 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   A.div_per_tile = pt_div_make(64u * n_passes);
   A.div_tiles_x = pt_div_make(A.tiles_x);
   A.div_band_rows = pt_div_make(A.band_rows);
-  A.geom = c->d_geom;
-  A.mat = c->d_mat;
-  A.mat_r0 = reinterpret_cast<const float*>(reinterpret_cast<const char*>(c->d_mat) + (size_t)c->sphere_cap * sizeof(PtMatRec));
-  A.slab = reinterpret_cast<float*>(c->d_slab);
-  A.counters = c->d_counters;
-  A.tile_order = c->d_tile_order;
-  A.tile_cost = c->d_tile_cost;
+  A.geom = c->d_geom.get();
+  A.mat = reinterpret_cast<const PtMatRec*>(c->d_mat.get());
+  A.mat_r0 = reinterpret_cast<const float*>(c->d_mat.get() + (size_t)c->sphere_cap * sizeof(PtMatRec));
+  A.slab = reinterpret_cast<float*>(c->d_slab.get());
+  A.counters = c->d_counters.get();
+  A.tile_order = c->d_tile_order.get();
+  A.tile_cost = c->d_tile_cost.get();
   A.coop_max_live = 16;
   A.carry_lanes = c->carry_lanes;
   A.refill_min = c->refill_min;
@@ -979,7 +975,7 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   // SHORT pass (the reference's 1-spp frame) would report from every item — the 64 lanes of a tile on
   // one address — and stall its waves on the atomics (vmcnt completes in order): none there.
   A.cost_feedback = (n_passes >= 2u || p.samples_per_pixel >= 8) ? 1u : 0u;
-  A.frame_ctr = c->d_frame_ctr + 1;  // the cell that stays 0 (pt_render_frames points at [0])
+  A.frame_ctr = c->d_frame_ctr.get() + 1;  // the cell that stays 0 (pt_render_frames points at [0])
   return PT_OK;
 }
 
@@ -1010,11 +1006,11 @@ static int choose_path(pt_ctx* c, bool allow_trials, int* trial) {
 // hierarchy walk: the tree's arrays and constants; which build of the kernel (everything / the nodes
 // / nothing staged in the LDS); returns the staged bytes
 static size_t bind_hierarchy(pt_ctx* c, bool rr, size_t lds_room, PtKernelArgs& A, const void** kfn) {
-  A.bvh_nodes = c->d_bvh_nodes;
-  A.bvh_nodes32 = c->d_bvh_nodes32;
-  A.bvh_slots = c->d_bvh_slots;
-  A.bvh_slot_index = c->d_bvh_index;
-  A.slot_mat = c->d_bvh_mat;
+  A.bvh_nodes = c->d_bvh_nodes.get();
+  A.bvh_nodes32 = c->d_bvh_nodes32.get();
+  A.bvh_slots = c->d_bvh_slots.get();
+  A.bvh_slot_index = c->d_bvh_index.get();
+  A.slot_mat = c->d_bvh_mat.get();
   A.n_nodes = c->bvh_n_nodes;
   A.n_tree_slots = c->bvh_n_tree_slots;
   A.n_slots = c->bvh_n_slots;
@@ -1039,10 +1035,10 @@ static size_t bind_hierarchy(pt_ctx* c, bool rr, size_t lds_room, PtKernelArgs& 
 // grid walk: likewise (cells + entries / the cell records / nothing staged)
 static size_t bind_grid(pt_ctx* c, bool rr, size_t lds_room, PtKernelArgs& A, const void** kfn) {
   const ptgrid::Grid& g = c->grid;
-  A.bvh_slots = c->d_grid_entries;
-  A.bvh_slot_index = c->d_grid_index;
-  A.slot_mat = c->d_grid_mat;
-  A.grid_cells = c->d_grid_cells;
+  A.bvh_slots = c->d_grid_entries.get();
+  A.bvh_slot_index = c->d_grid_index.get();
+  A.slot_mat = c->d_grid_mat.get();
+  A.grid_cells = c->d_grid_cells.get();
   A.n_cells = g.n[0] * g.n[1] * g.n[2];
   A.n_tree_slots = g.n_cell_entries;
   A.n_slots = g.n_entries;
@@ -1318,60 +1314,37 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
 
   // inside a stream capture (hipGraph) nothing may synchronise or allocate and timing events are
   // meaningless: the launch sequence itself is capture-safe, the measuring twins' set-up is not
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(c->stream, &cap);
-  const bool capturing = cap != hipStreamCaptureStatusNone;
+  const bool capturing = is_capturing(c);
   if (capturing && c->count_work)
     return fail(c, PT_ERR_INVALID, "pt_render_passes: PT_OPT_COUNT_WORK (measuring twin: allocates its wave log) cannot be captured into a hipGraph");
   A.wave_log = nullptr;
   A.cell_hist = nullptr;
   if (c->count_work && (path == PT_GEOM_BVH || path == PT_GEOM_GRID || path == PT_GEOM_SMALL)) { // measuring twin: not a product launch, may allocate
     const size_t n_waves = (size_t)grid * (block / 64);
-    if (n_waves * PT_WAVE_LOG_WORDS > c->wave_log_cap) {
-      if (c->d_wave_log) PT_HIP(c, hipFree(c->d_wave_log));
-      c->d_wave_log = nullptr; c->wave_log_cap = 0;
-      PT_HIP(c, hipMalloc(&c->d_wave_log, n_waves * PT_WAVE_LOG_WORDS * sizeof(unsigned long long)));
-      c->wave_log_cap = n_waves * PT_WAVE_LOG_WORDS;
-    }
-    PT_HIP(c, hipMemsetAsync(c->d_wave_log, 0, n_waves * PT_WAVE_LOG_WORDS * sizeof(unsigned long long), c->stream));
+    if (c->d_wave_log.capacity() < n_waves * PT_WAVE_LOG_WORDS) PT_HIP(c, c->d_wave_log.reserve(n_waves * PT_WAVE_LOG_WORDS));
+    PT_HIP(c, hipMemsetAsync(c->d_wave_log.get(), 0, n_waves * PT_WAVE_LOG_WORDS * sizeof(unsigned long long), c->stream));
     c->wave_log_n = n_waves;
-    A.wave_log = c->d_wave_log;
+    A.wave_log = c->d_wave_log.get();
     if (path == PT_GEOM_GRID && c->count_work >= 2) {  // which entry runs the leaf rounds gather (config 5's cache model, tools/config5_cache_model.py)
       const size_t n_hist = (size_t)A.n_slots + PT_COH_BINS;
-      if (n_hist > c->cell_hist_cap) {
-        if (c->d_cell_hist) PT_HIP(c, hipFree(c->d_cell_hist));
-        c->d_cell_hist = nullptr; c->cell_hist_cap = 0;
-        PT_HIP(c, hipMalloc(&c->d_cell_hist, n_hist * sizeof(uint32_t)));
-        c->cell_hist_cap = n_hist;
-      }
-      PT_HIP(c, hipMemsetAsync(c->d_cell_hist, 0, n_hist * sizeof(uint32_t), c->stream));
+      if (c->d_cell_hist.capacity() < n_hist) PT_HIP(c, c->d_cell_hist.reserve(n_hist));
+      PT_HIP(c, hipMemsetAsync(c->d_cell_hist.get(), 0, n_hist * sizeof(uint32_t), c->stream));
       c->cell_hist_n = n_hist;
-      A.cell_hist = c->d_cell_hist;
+      A.cell_hist = c->d_cell_hist.get();
     }
   }
-  // (capturing: skip the timing event pair)
-  if (!capturing && c->events_used == c->events.size()) {
-    if (c->events.size() >= 512) {
-      // pool full: drain (this synchronises, but only once per 512 launches)
-      PT_HIP(c, hipStreamSynchronize(c->stream));
-      int rc = fold_events(c);
-      if (rc != PT_OK) return rc;
-    } else {
-      hipEvent_t a, b;
-      PT_HIP(c, hipEventCreate(&a));
-      PT_HIP(c, hipEventCreate(&b));
-      c->events.emplace_back(a, b);
-    }
+  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;  // (capturing: no timing event pair)
+  if (!capturing) {
+    int rc = next_events(c, &ev);
+    if (rc != PT_OK) return rc;
   }
-  std::pair<hipEvent_t, hipEvent_t>* ev = capturing ? nullptr : &c->events[c->events_used++];
 
   PT_HIP(c, zero_queue_heads(c, A.queue_static));  // (a statically dealt launch takes no reservations from any head)
   // queue order from the previous launch's per-tile cost (identity when there is none yet); launches
   // that report no cost keep the order they find
   if (A.cost_feedback || !c->tile_order_valid) {
-    hipLaunchKernelGGL(pt_tile_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tile_cost,
-                       c->d_tile_order, A.tiles_x * A.tiles_y);
-    PT_HIP(c, hipGetLastError());
+    int rc = launch_tile_order(c);
+    if (rc != PT_OK) return rc;
     if (!capturing) c->tile_order_valid = true;  // (a captured order kernel has not run: the next direct launch runs its own)
   }
   if (capturing) trial = -1;
@@ -1394,7 +1367,7 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
 
   uint32_t n_pix = c->local_rows * c->width;
   hipLaunchKernelGGL(pt_accumulate_kernel, dim3(grid_for(n_pix, 256, 2048)), dim3(256), 0, c->stream,
-                     c->accum, c->d_slab, n_pix, n_passes);
+                     c->accum, c->d_slab.get(), n_pix, n_passes);
   PT_HIP(c, hipGetLastError());
 
   // Host-side tallies describe work enqueued directly.  A captured launch runs as often as its
@@ -1419,22 +1392,6 @@ PT_API int pt_render(pt_ctx* c) { return pt_render_passes(c, 1); }
 // other texture.  Nothing crosses PCIe: the textures of src/webgl.rs:82-123 live in HBM.
 namespace {
 
-// Everything a frame bakes into its launches: decided BEFORE anything is enqueued (prepare_launch queries
-// occupancy and the autotuner's events — not things to do inside a stream capture), and what the cached graph of
-// pt_render_frames is keyed on.
-struct FramePlan {
-  Launch L;
-  const uint32_t* ctr = nullptr;  // the device cell holding a frame's number in its series
-  uint32_t even_odd0 = 0;
-  int max_render_count = 0, render_count0 = 0, should_average = 0;
-  float last_frame_weight = 0.f;
-  hipStream_t stream = nullptr;
-  float4* slab = nullptr;
-  uint32_t* tex0 = nullptr; uint32_t* tex1 = nullptr; uint32_t* canvas = nullptr;
-  uint32_t n_frames = 1;  // frames traced by the one launch (as its passes), blended one after the other
-};
-static_assert(sizeof(FramePlan) <= sizeof(pt_ctx::frame_plan[0]), "pt_ctx::frame_plan must hold a FramePlan");
-
 int plan_frame(pt_ctx* c, const uint32_t* ctr, uint32_t even_odd0, int max_render_count, uint32_t n_frames, float4* slab, FramePlan* F) {
   memset(static_cast<void*>(F), 0, sizeof *F);  // (padding too: plans are compared bytewise)
   // frames k .. k + n - 1 are the passes 0 .. n - 1 of ONE launch: pass p renders at u_time = time + float(first_pass + p + k) *
@@ -1454,7 +1411,7 @@ int plan_frame(pt_ctx* c, const uint32_t* ctr, uint32_t even_odd0, int max_rende
   F->last_frame_weight = c->params.last_frame_weight;
   F->L.A.slab = reinterpret_cast<float*>(slab);
   F->stream = c->stream; F->slab = slab;
-  F->tex0 = c->d_tex[0]; F->tex1 = c->d_tex[1]; F->canvas = c->d_canvas;
+  F->tex0 = c->d_tex[0].get(); F->tex1 = c->d_tex[1].get(); F->canvas = c->d_canvas.get();
   F->n_frames = n_frames;
   return PT_OK;
 }
@@ -1470,18 +1427,18 @@ int enqueue_frame(pt_ctx* c, FramePlan& F, bool advance) {
   const uint32_t n_pix = c->local_rows * c->width;
   if (F.n_frames > 1u) {  // a group: its blends as one pass over the pixels
     hipLaunchKernelGGL(pt_frames_blend_kernel, dim3(grid_for(n_pix, 256, 2048)), dim3(256), 0, c->stream, F.slab, F.n_frames,
-                       c->d_tex[0], c->d_tex[1], c->d_canvas, n_pix, F.ctr, F.render_count0, F.even_odd0, F.max_render_count,
+                       c->d_tex[0].get(), c->d_tex[1].get(), c->d_canvas.get(), n_pix, F.ctr, F.render_count0, F.even_odd0, F.max_render_count,
                        F.should_average, F.last_frame_weight);
     PT_HIP(c, hipGetLastError());
   }
   for (uint32_t f = 0; f < (F.n_frames > 1u ? 0u : 1u); f++) {
     hipLaunchKernelGGL(pt_frame_blend_kernel, dim3(grid_for(n_pix, 256, 2048)), dim3(256), 0, c->stream, F.slab + (size_t)f * n_pix,
-                       c->d_tex[0], c->d_tex[1], c->d_canvas, n_pix, F.ctr, f, F.render_count0, F.even_odd0, F.max_render_count,
+                       c->d_tex[0].get(), c->d_tex[1].get(), c->d_canvas.get(), n_pix, F.ctr, f, F.render_count0, F.even_odd0, F.max_render_count,
                        F.should_average, F.last_frame_weight);
     PT_HIP(c, hipGetLastError());
   }
   if (advance) {
-    hipLaunchKernelGGL(pt_frame_advance_kernel, dim3(1), dim3(PT_QUEUE_GROUPS_MAX), 0, c->stream, c->d_frame_ctr, c->d_counters, F.n_frames);
+    hipLaunchKernelGGL(pt_frame_advance_kernel, dim3(1), dim3(PT_QUEUE_GROUPS_MAX), 0, c->stream, c->d_frame_ctr.get(), c->d_counters.get(), F.n_frames);
     PT_HIP(c, hipGetLastError());
   }
   return PT_OK;
@@ -1490,9 +1447,8 @@ int enqueue_frame(pt_ctx* c, FramePlan& F, bool advance) {
 // the tile order a frame finds must exist (frames report no costs and never run the order kernel themselves)
 int ensure_tile_order(pt_ctx* c) {
   if (c->tile_order_valid) return PT_OK;
-  hipLaunchKernelGGL(pt_tile_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tile_cost, c->d_tile_order,
-                     ((c->width + 7) / 8) * ((c->local_rows + 7) / 8));
-  PT_HIP(c, hipGetLastError());
+  int rc = launch_tile_order(c);
+  if (rc != PT_OK) return rc;
   c->tile_order_valid = true;
   return PT_OK;
 }
@@ -1522,7 +1478,7 @@ int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
                             // zero, a pt_render_passes with cost feedback since then does not: cleared here)
       c->order_probed = false;
       c->tile_order_valid = false;
-      PT_HIP(c, hipMemsetAsync(c->d_tile_cost, 0, c->tile_cap * sizeof(uint32_t), c->stream));
+      PT_HIP(c, hipMemsetAsync(c->d_tile_cost.get(), 0, c->d_tile_cost.capacity() * sizeof(uint32_t), c->stream));
     }
     return ensure_tile_order(c);
   }
@@ -1532,29 +1488,24 @@ int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
   if (fresh) return PT_OK;
   int rc = ensure_tile_order(c);
   if (rc != PT_OK) return rc;
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(c->stream, &cap);
-    if (cap != hipStreamCaptureStatusNone) return PT_OK;  // (a caller capturing single frames: no probe inside its graph)
-  }
+  if (is_capturing(c)) return PT_OK;  // (a caller capturing single frames: no probe inside its graph)
   Launch L;
   rc = prepare_launch(c, 1, false, &L);
   if (rc != PT_OK) return rc;
   L.A.cost_feedback = 1u;
   L.A.wave_log = nullptr;
   L.A.cell_hist = nullptr;
-  L.A.slab = reinterpret_cast<float*>(c->d_slab);  // scratch: a frame's own slab is written before it is read
-  unsigned long long* seg = &c->d_counters[PT_CTR_SEGMENTS];
-  PT_HIP(c, hipMemcpyAsync(&c->d_counters[PT_CTR_SCRATCH], seg, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
+  L.A.slab = reinterpret_cast<float*>(c->d_slab.get());  // scratch: a frame's own slab is written before it is read
+  unsigned long long* seg = c->d_counters.get() + PT_CTR_SEGMENTS;
+  PT_HIP(c, hipMemcpyAsync(c->d_counters.get() + PT_CTR_SCRATCH, seg, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
   PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
   {
     void* kargs[] = {&L.A};
     PT_HIP(c, hipLaunchKernel(L.kfn, dim3(L.grid), dim3(L.block), kargs, L.lds, c->stream));
   }
-  hipLaunchKernelGGL(pt_tile_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tile_cost, c->d_tile_order,
-                     ((c->width + 7) / 8) * ((c->local_rows + 7) / 8));
-  PT_HIP(c, hipGetLastError());
-  PT_HIP(c, hipMemcpyAsync(seg, &c->d_counters[PT_CTR_SCRATCH], sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
+  rc = launch_tile_order(c);
+  if (rc != PT_OK) return rc;
+  PT_HIP(c, hipMemcpyAsync(seg, c->d_counters.get() + PT_CTR_SCRATCH, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
   c->order_probed = true;
   c->order_view = c->params;
   c->order_scene_gen = c->scene_gen;
@@ -1577,8 +1528,8 @@ PT_API int pt_clear_textures(pt_ctx* c) {
   PT_HIP(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)c->local_rows * c->width * sizeof(uint32_t);
   if (bytes == 0) return PT_OK;
-  for (int k = 0; k < 2; k++) PT_HIP(c, hipMemsetAsync(c->d_tex[k], 0, bytes, c->stream));
-  PT_HIP(c, hipMemsetAsync(c->d_canvas, 0, bytes, c->stream));
+  for (int k = 0; k < 2; k++) PT_HIP(c, hipMemsetAsync(c->d_tex[k].get(), 0, bytes, c->stream));
+  PT_HIP(c, hipMemsetAsync(c->d_canvas.get(), 0, bytes, c->stream));
   return PT_OK;
 }
 
@@ -1588,7 +1539,7 @@ PT_API int pt_render_frame(pt_ctx* c, uint32_t even_odd_count) {
   if (c->local_rows == 0) return PT_OK;
   PT_HIP(c, hipSetDevice(c->device));
   FramePlan F;
-  rc = plan_frame(c, c->d_frame_ctr + 1, even_odd_count, 0x7fffffff, 1, c->d_slab, &F);  // frame 0 of a series of one
+  rc = plan_frame(c, c->d_frame_ctr.get() + 1, even_odd_count, 0x7fffffff, 1, c->d_slab.get(), &F);  // frame 0 of a series of one
   if (rc != PT_OK) return rc;
   rc = ensure_cost_order(c, 1);
   if (rc != PT_OK) return rc;
@@ -1606,9 +1557,7 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
   if (n_frames == 0 || c->local_rows == 0) return PT_OK;
   if (max_render_count > 0x7fffffffu) max_render_count = 0x7fffffffu;
   PT_HIP(c, hipSetDevice(c->device));
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(c->stream, &cap);
-  if (cap != hipStreamCaptureStatusNone)
+  if (is_capturing(c))
     return fail(c, PT_ERR_INVALID, "pt_render_frames: the stream is being captured already (this call replays its own graph)");
   // hipStreamBeginCapture is refused on the legacy default stream (PT_STREAM_LEGACY, what a context bound to
   // torch's default stream runs on): say so instead of failing inside the capture
@@ -1636,13 +1585,10 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
   for (int g = 0; g < kFrameLevels - 1; g++) {
     if (!counts[g]) continue;
     const size_t need = (size_t)c->local_rows * c->width * kFrameGroups[g];
-    if (c->frame_slab_pixels >= need) break;
+    if (c->d_frame_slab.capacity() >= need) break;
     PT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->d_frame_slab) PT_HIP(c, hipFree(c->d_frame_slab));
-    c->d_frame_slab = nullptr; c->frame_slab_pixels = 0;
-    if (hipMalloc(&c->d_frame_slab, need * sizeof(float4)) == hipSuccess) { c->frame_slab_pixels = need; break; }
+    if (c->d_frame_slab.reserve(need) == hipSuccess) break;
     (void)hipGetLastError();  // out of memory is not an error of this call: deal this group's frames to the next smaller one
-    c->d_frame_slab = nullptr;
     counts[g + 1] += counts[g] * (kFrameGroups[g] / kFrameGroups[g + 1]);
     counts[g] = 0;
   }
@@ -1653,11 +1599,11 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
   auto graph_for = [&](int g) -> int {
     const uint32_t frames = kFrameGroups[g];
     hipGraphExec_t* exec = &c->frame_exec[g];
-    unsigned char* plan_store = c->frame_plan[g];
+    FramePlan* plan_store = &c->frame_plan[g];
     FramePlan F;
-    int r = plan_frame(c, c->d_frame_ctr, even_odd_count, (int)max_render_count, frames, frames > 1u ? c->d_frame_slab : c->d_slab, &F);
+    int r = plan_frame(c, c->d_frame_ctr.get(), even_odd_count, (int)max_render_count, frames, frames > 1u ? c->d_frame_slab.get() : c->d_slab.get(), &F);
     if (r != PT_OK) return r;
-    if (*exec && memcmp(&F, plan_store, sizeof F) == 0) return PT_OK;
+    if (*exec && memcmp(&F, plan_store, sizeof F) == 0) return PT_OK;  // (bytewise, padding included: plan_frame zeroed it)
     if (*exec) { (void)hipGraphExecDestroy(*exec); *exec = nullptr; }
     hipGraph_t graph = nullptr;
     PT_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
@@ -1668,32 +1614,22 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
     e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) { *exec = nullptr; return fail(c, PT_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e)); }
-    memcpy(static_cast<void*>(plan_store), &F, sizeof F);
+    memcpy(static_cast<void*>(plan_store), &F, sizeof F);  // (not an assignment, which need not copy the padding)
     return PT_OK;
   };
   for (int g = 0; g < kFrameLevels; g++)
     if (counts[g]) { rc = graph_for(g); if (rc != PT_OK) return rc; }
   // the series starts at frame 0 with an empty queue; every replay leaves both ready for the next
-  PT_HIP(c, hipMemsetAsync(c->d_frame_ctr, 0, sizeof(uint32_t), c->stream));
-  PT_HIP(c, hipMemsetAsync(&c->d_counters[PT_CTR_HEAD], 0, sizeof(unsigned long long), c->stream));
+  PT_HIP(c, hipMemsetAsync(c->d_frame_ctr.get(), 0, sizeof(uint32_t), c->stream));
+  PT_HIP(c, hipMemsetAsync(c->d_counters.get() + PT_CTR_HEAD, 0, sizeof(unsigned long long), c->stream));
   PT_HIP(c, zero_queue_heads(c, 2u));
-  if (c->events_used == c->events.size()) {
-    if (c->events.size() >= 512) {
-      PT_HIP(c, hipStreamSynchronize(c->stream));
-      rc = fold_events(c);
-      if (rc != PT_OK) return rc;
-    } else {
-      hipEvent_t a, b;
-      PT_HIP(c, hipEventCreate(&a));
-      PT_HIP(c, hipEventCreate(&b));
-      c->events.emplace_back(a, b);
-    }
-  }
-  std::pair<hipEvent_t, hipEvent_t>& ev = c->events[c->events_used++];
-  PT_HIP(c, hipEventRecord(ev.first, c->stream));
+  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+  rc = next_events(c, &ev);
+  if (rc != PT_OK) return rc;
+  PT_HIP(c, hipEventRecord(ev->first, c->stream));
   for (int g = 0; g < kFrameLevels; g++)
     for (uint32_t k = 0; k < counts[g]; k++) PT_HIP(c, hipGraphLaunch(c->frame_exec[g], c->stream));
-  PT_HIP(c, hipEventRecord(ev.second, c->stream));
+  PT_HIP(c, hipEventRecord(ev->second, c->stream));
   c->launches += n_frames;
   c->samples += (uint64_t)n_frames * c->local_rows * c->width * (uint64_t)c->params.samples_per_pixel;
   return PT_OK;
@@ -1707,17 +1643,17 @@ static int read_rgba8(pt_ctx* c, const uint32_t* src, uint8_t* out, const char* 
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
-PT_API int pt_read_canvas(pt_ctx* c, uint8_t* rgba_out) { return read_rgba8(c, c ? c->d_canvas : nullptr, rgba_out, "pt_read_canvas"); }
+PT_API int pt_read_canvas(pt_ctx* c, uint8_t* rgba_out) { return read_rgba8(c, c ? c->d_canvas.get() : nullptr, rgba_out, "pt_read_canvas"); }
 PT_API int pt_read_texture(pt_ctx* c, int index, uint8_t* rgba_out) {
   if (c && (index < 0 || index > 1)) return fail(c, PT_ERR_INVALID, "pt_read_texture: index %d", index);
-  return read_rgba8(c, c ? c->d_tex[index] : nullptr, rgba_out, "pt_read_texture");
+  return read_rgba8(c, c ? c->d_tex[index].get() : nullptr, rgba_out, "pt_read_texture");
 }
 PT_API int pt_write_texture(pt_ctx* c, int index, const uint8_t* rgba_in) {
   if (!c || !rgba_in) return fail(c, PT_ERR_INVALID, "pt_write_texture: NULL argument");
   if (index < 0 || index > 1) return fail(c, PT_ERR_INVALID, "pt_write_texture: index %d", index);
   PT_HIP(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)c->local_rows * c->width * 4;
-  if (bytes) PT_HIP(c, hipMemcpyAsync(c->d_tex[index], rgba_in, bytes, hipMemcpyDefault, c->stream));
+  if (bytes) PT_HIP(c, hipMemcpyAsync(c->d_tex[index].get(), rgba_in, bytes, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
@@ -1728,7 +1664,7 @@ PT_API long pt_debug_counters(pt_ctx* c, unsigned long long* out, size_t cap) {
   if (!c || !out) return -1;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return -2;
   const size_t n = cap < (size_t)PT_CTR_COUNT ? cap : (size_t)PT_CTR_COUNT;
-  if (hipMemcpy(out, c->d_counters, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -2;
+  if (hipMemcpy(out, c->d_counters.get(), n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -2;
   return (long)n;
 }
 
@@ -1736,18 +1672,18 @@ PT_API long pt_debug_counters(pt_ctx* c, unsigned long long* out, size_t cap) {
 // of the last counted launch, in 100 MHz ticks, and where it ran (HW_ID | XCC_ID << 32): four u64 per wave.
 // Returns the number of waves, or < 0.
 PT_API long pt_debug_wave_log(pt_ctx* c, unsigned long long* out, size_t cap_waves) {
-  if (!c || !c->d_wave_log || !out) return -1;
+  if (!c || !c->d_wave_log.get() || !out) return -1;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return -2;
   const size_t n = c->wave_log_n < cap_waves ? c->wave_log_n : cap_waves;
-  if (hipMemcpy(out, c->d_wave_log, n * PT_WAVE_LOG_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -2;
+  if (hipMemcpy(out, c->d_wave_log.get(), n * PT_WAVE_LOG_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -2;
   return (long)n;
 }
 
 PT_API long pt_debug_cell_hist(pt_ctx* c, uint32_t* out, size_t cap) {
-  if (!c || !c->d_cell_hist || !out) return -1;
+  if (!c || !c->d_cell_hist.get() || !out) return -1;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return -2;
   const size_t n = c->cell_hist_n < cap ? c->cell_hist_n : cap;
-  if (hipMemcpy(out, c->d_cell_hist, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return -2;
+  if (hipMemcpy(out, c->d_cell_hist.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return -2;
   return (long)n;
 }
 
@@ -1795,16 +1731,16 @@ static int resolve_common(pt_ctx* c, void* out, int gamma, int mode, const uint8
   uint32_t grid = grid_for(n_pix, 256, 2048);
   size_t bytes;
   if (mode == 0) {
-    hipLaunchKernelGGL(pt_resolve_kernel, dim3(grid), dim3(256), 0, c->stream, c->accum, c->d_resolve,
+    hipLaunchKernelGGL(pt_resolve_kernel, dim3(grid), dim3(256), 0, c->stream, c->accum, c->d_resolve.get(),
                        n_pix, gamma);
     bytes = (size_t)n_pix * sizeof(float4);
   } else if (mode == 1) {
     hipLaunchKernelGGL(pt_resolve_rgba8_kernel, dim3(grid), dim3(256), 0, c->stream, c->accum,
-                       reinterpret_cast<uint32_t*>(c->d_resolve), n_pix, gamma);
+                       reinterpret_cast<uint32_t*>(c->d_resolve.get()), n_pix, gamma);
     bytes = (size_t)n_pix * 4;
   } else {
     // stage prev into the upper half of the resolve buffer (16 B/pixel holds 4 B in + 4 B out)
-    uint32_t* d_out = reinterpret_cast<uint32_t*>(c->d_resolve);
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(c->d_resolve.get());
     uint32_t* d_prev = d_out + n_pix;
     PT_HIP(c, hipMemcpyAsync(d_prev, prev, (size_t)n_pix * 4, hipMemcpyDefault, c->stream));
     hipLaunchKernelGGL(pt_blend_rgba8_kernel, dim3(grid), dim3(256), 0, c->stream, c->accum, d_prev, d_out,
@@ -1813,7 +1749,7 @@ static int resolve_common(pt_ctx* c, void* out, int gamma, int mode, const uint8
     bytes = (size_t)n_pix * 4;
   }
   PT_HIP(c, hipGetLastError());
-  PT_HIP(c, hipMemcpyAsync(out, c->d_resolve, bytes, hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipMemcpyAsync(out, c->d_resolve.get(), bytes, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
@@ -1832,7 +1768,7 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
   int rc = fold_events(c);
   if (rc != PT_OK) return rc;
   unsigned long long ctr[PT_CTR_COUNT];
-  PT_HIP(c, hipMemcpy(ctr, c->d_counters, sizeof ctr, hipMemcpyDeviceToHost));
+  PT_HIP(c, hipMemcpy(ctr, c->d_counters.get(), sizeof ctr, hipMemcpyDeviceToHost));
   memset(out, 0, sizeof *out);
   out->segments = ctr[PT_CTR_SEGMENTS];
   out->samples = c->samples;
@@ -2013,12 +1949,12 @@ int tune_grid_to_view(pt_ctx* c, uint32_t n_passes, bool* launched) {
       rc = hipStreamSynchronize(c->stream) == hipSuccess ? fold_events(c) : PT_ERR_HIP;
       if (rc != PT_OK) break;
       const double ms0 = c->kernel_ms;
-      if (hipMemcpy(before, c->d_counters, sizeof before, hipMemcpyDeviceToHost) != hipSuccess) { rc = PT_ERR_HIP; break; }
+      if (hipMemcpy(before, c->d_counters.get(), sizeof before, hipMemcpyDeviceToHost) != hipSuccess) { rc = PT_ERR_HIP; break; }
       rc = pt_render_passes(c, k == 0 ? 1u : n_timed);
       if (rc != PT_OK) break;
       rc = hipStreamSynchronize(c->stream) == hipSuccess ? fold_events(c) : PT_ERR_HIP;
       if (rc != PT_OK) break;
-      if (hipMemcpy(after, c->d_counters, sizeof after, hipMemcpyDeviceToHost) != hipSuccess) { rc = PT_ERR_HIP; break; }
+      if (hipMemcpy(after, c->d_counters.get(), sizeof after, hipMemcpyDeviceToHost) != hipSuccess) { rc = PT_ERR_HIP; break; }
       const double ms = c->kernel_ms - ms0;
       if (k == 0 && probes.empty()) {  // the yardstick (an over-estimate: it carries the code load — so the timed launches come out shorter, never longer)
         const double want = ms > 0.0 ? std::ceil(4.0 / ms) : (double)n_most;
@@ -2110,16 +2046,14 @@ PT_API int pt_probe(pt_ctx* c, int kind, const float* in, size_t n_in, float* ou
                     uint32_t n) {
   if (!c || !in || !out || n == 0) return fail(c, PT_ERR_INVALID, "pt_probe: bad argument");
   PT_HIP(c, hipSetDevice(c->device));
-  float *d_in = nullptr, *d_out = nullptr;
-  PT_HIP(c, hipMalloc(&d_in, n_in * sizeof(float)));
-  PT_HIP(c, hipMalloc(&d_out, n_out * sizeof(float)));
-  PT_HIP(c, hipMemcpy(d_in, in, n_in * sizeof(float), hipMemcpyHostToDevice));
-  PT_HIP(c, hipMemsetAsync(d_out, 0, n_out * sizeof(float), c->stream));
-  hipLaunchKernelGGL(pt_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, kind, d_in, d_out, n);
+  DevBuf<float> d_in, d_out;  // (freed on every return)
+  PT_HIP(c, d_in.reserve(n_in));
+  PT_HIP(c, d_out.reserve(n_out));
+  PT_HIP(c, hipMemcpy(d_in.get(), in, n_in * sizeof(float), hipMemcpyHostToDevice));
+  PT_HIP(c, hipMemsetAsync(d_out.get(), 0, n_out * sizeof(float), c->stream));
+  hipLaunchKernelGGL(pt_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, kind, d_in.get(), d_out.get(), n);
   PT_HIP(c, hipGetLastError());
   PT_HIP(c, hipStreamSynchronize(c->stream));
-  PT_HIP(c, hipMemcpy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost));
-  PT_HIP(c, hipFree(d_in));
-  PT_HIP(c, hipFree(d_out));
+  PT_HIP(c, hipMemcpy(out, d_out.get(), n_out * sizeof(float), hipMemcpyDeviceToHost));
   return PT_OK;
 }
