@@ -26,6 +26,7 @@
 #include "pt_grid.hpp"
 #include "pt_extra.h"
 #include "pt_kernel_args.h"
+#include "pt_launch_plan.hpp"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -427,8 +428,6 @@ int grid_build_kind(const pt_ctx* c, size_t lds_room) {
 constexpr size_t kWalkLdsMax = (size_t)PT_LDS_ENTRIES(PT_MAX_SPHERES_LDS) * 16;
 constexpr size_t walk_lds_room() { return kWalkLdsMax - (size_t)PT_PARK_STRIDE * 4 * 1024; }
 
-#define PT_KFN(name) reinterpret_cast<const void*>(name)
-
 // a kernel of pt_kernels_extra.hip; its first use loads that code object and lifts its dynamic-LDS limit
 const void* extra_kernel(int device, int id) {
   static std::once_flag once[64][PT_X_COUNT];  // (function attributes belong to a device: the context's is current here)
@@ -440,8 +439,38 @@ const void* extra_kernel(int device, int id) {
     });
   return k;
 }
-// the Russian-roulette build of a kernel when the option is on
-#define PT_PICK(rr, name, id) ((rr) ? extra_kernel(c->device, id) : PT_KFN(name))
+
+// Every trace kernel, by how it reads the list (row) and which build runs (column), with the wave count it is built for
+// (its PT_BUILT_FOR).  A kernel of this object has `main`; one of pt_kernels_extra.hip a PT_X_* id (`extra`), one of
+// pt_kernels_small.hip the list length's remainder modulo four (`small`): those two objects are loaded only when one of
+// their kernels is first launched, so their handles are taken when an entry is chosen, not here.  Where a way to read the
+// list has no roulette build or no measuring twin, its column holds the plain build, which then runs.
+struct TraceKernel { const void* main; int extra, small, waves; };
+// ROW_SMALL + list length % 4; ROW_BVH / ROW_GRID + what is staged in the LDS (bind_hierarchy, bind_grid)
+enum TraceRow { ROW_LIST_LDS, ROW_SCALAR, ROW_SCALAR_NOLDS, ROW_SMALL, ROW_BVH = ROW_SMALL + 4, ROW_GRID = ROW_BVH + 3, ROW_COUNT = ROW_GRID + 3 };
+enum TraceBuild { BUILD_PLAIN, BUILD_RR, BUILD_TWIN, BUILD_COUNT };
+
+template <class K>
+TraceKernel in_main(K* k, int waves) { return {reinterpret_cast<const void*>(k), -1, -1, waves}; }
+TraceKernel in_extra(int id, int waves = PT_WAVES_WALK) { return {nullptr, id, -1, waves}; }
+TraceKernel in_small(int rem) { return {nullptr, -1, rem, PT_WAVES_SMALL}; }
+
+const TraceKernel kTraceKernels[ROW_COUNT][BUILD_COUNT] = {
+    // plain                                                roulette                                         measuring twin
+    {in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),           in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),     in_main(pt_trace_kernel, PT_WAVES_LIST_LDS)},
+    {in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),        in_extra(PT_X_SCALAR_RR, PT_WAVES_LIST),         in_main(pt_trace_kernel_scalar, PT_WAVES_LIST)},
+    {in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_extra(PT_X_SCALAR_NOLDS_RR, PT_WAVES_LIST),   in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST)},
+    {in_small(0),                                           in_extra(PT_X_SMALL_RR + 0, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL)},
+    {in_small(1),                                           in_extra(PT_X_SMALL_RR + 1, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL)},
+    {in_small(2),                                           in_extra(PT_X_SMALL_RR + 2, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL)},
+    {in_small(3),                                           in_extra(PT_X_SMALL_RR + 3, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL)},
+    {in_main(pt_trace_kernel_bvh, PT_WAVES_WALK),           in_extra(PT_X_BVH_RR),                           in_extra(PT_X_BVH_COUNT)},
+    {in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),     in_extra(PT_X_BVH_NODES_RR),                     in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK)},
+    {in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),      in_extra(PT_X_BVH_GMEM_RR),                      in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK)},
+    {in_main(pt_trace_kernel_grid, PT_WAVES_WALK),          in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_COUNT)},
+    {in_main(pt_trace_kernel_grid_cells, PT_WAVES_WALK),    in_extra(PT_X_GRID_CELLS_RR),                    in_extra(PT_X_GRID_CELLS_COUNT, PT_WAVES_TWIN_CELLS)},
+    {in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),     in_extra(PT_X_GRID_GMEM_RR),                     in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK)},
+};
 
 inline uint32_t grid_for(uint32_t n, uint32_t block, uint32_t cap) {
   uint32_t g = (n + block - 1) / block;
@@ -512,10 +541,8 @@ static int create_common(pt_ctx** out, int device, uint32_t width, uint32_t heig
   const double t_small_allocs = host_ms();
   // allow the trace kernels to use the CU's whole 160 KiB LDS for big sphere lists
   // (the first hipFuncSetAttribute of a process also LOADS this translation unit's code object onto the device)
-  for (const void* k : {PT_KFN(pt_trace_kernel), PT_KFN(pt_trace_kernel_scalar), PT_KFN(pt_trace_kernel_bvh),
-                        PT_KFN(pt_trace_kernel_bvh_nodes), PT_KFN(pt_trace_kernel_bvh_gmem), PT_KFN(pt_trace_kernel_grid),
-                        PT_KFN(pt_trace_kernel_grid_cells), PT_KFN(pt_trace_kernel_grid_gmem)})
-    (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
+  for (const auto& row : kTraceKernels)
+    if (row[BUILD_PLAIN].main) (void)hipFuncSetAttribute(row[BUILD_PLAIN].main, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
   (void)hipGetLastError(); // a refused attribute only limits that kernel to the default 64 KiB; the launch code checks sizes
   const double t_code = host_ms();
   int rc = ensure_buffers(c);
@@ -963,18 +990,8 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   A.counters = c->d_counters.get();
   A.tile_order = c->d_tile_order.get();
   A.tile_cost = c->d_tile_cost.get();
-  A.coop_max_live = 16;
   A.carry_lanes = c->carry_lanes;
   A.refill_min = c->refill_min;
-#ifdef PT_DEV_KNOBS // A/B builds only (tools/sweep_knobs.py); libptrace.so as shipped reads no environment variable (the Python
-                    // harness has two, both loader matters of ray_tracer_webgl_amd/_lib.py: PT_LIB — which build of this library it
-                    // loads — and PT_NO_TORCH_HIP_PRELOAD — do not map PyTorch's copy of the HIP runtime before it)
-  if (const char* e = getenv("PT_CARRY_LANES")) A.carry_lanes = (uint32_t)atoi(e);
-#endif
-  // cost feedback for the next launch's tile order: one atomicMax per item of pass 0.  A launch of one
-  // SHORT pass (the reference's 1-spp frame) would report from every item — the 64 lanes of a tile on
-  // one address — and stall its waves on the atomics (vmcnt completes in order): none there.
-  A.cost_feedback = (n_passes >= 2u || p.samples_per_pixel >= 8) ? 1u : 0u;
   A.frame_ctr = c->d_frame_ctr.get() + 1;  // the cell that stays 0 (pt_render_frames points at [0])
   return PT_OK;
 }
@@ -1003,9 +1020,9 @@ static int choose_path(pt_ctx* c, bool allow_trials, int* trial) {
   return path;
 }
 
-// hierarchy walk: the tree's arrays and constants; which build of the kernel (everything / the nodes
-// / nothing staged in the LDS); returns the staged bytes
-static size_t bind_hierarchy(pt_ctx* c, bool rr, size_t lds_room, PtKernelArgs& A, const void** kfn) {
+// hierarchy walk: the tree's arrays and constants; what is staged in the LDS (`*staging`: 0 everything, 1 the nodes,
+// 2 nothing: the kernel's row past ROW_BVH); returns the staged bytes
+static size_t bind_hierarchy(pt_ctx* c, size_t lds_room, PtKernelArgs& A, int* staging) {
   A.bvh_nodes = c->d_bvh_nodes.get();
   A.bvh_nodes32 = c->d_bvh_nodes32.get();
   A.bvh_slots = c->d_bvh_slots.get();
@@ -1020,20 +1037,12 @@ static size_t bind_hierarchy(pt_ctx* c, bool rr, size_t lds_room, PtKernelArgs& 
   A.bvh_kinv = c->bvh_kinv;
   const size_t need_all = PT_BVH_LDS_BYTES32(c->bvh_n_nodes, c->bvh_n_slots);
   const size_t need_nodes = PT_BVH_LDS_BYTES16(c->bvh_n_nodes);
-  if (need_all <= lds_room) {
-    *kfn = c->count_work ? extra_kernel(c->device, PT_X_BVH_COUNT) : PT_PICK(rr, pt_trace_kernel_bvh, PT_X_BVH_RR);
-    return need_all;
-  }
-  if (need_nodes <= lds_room) {
-    *kfn = PT_PICK(rr, pt_trace_kernel_bvh_nodes, PT_X_BVH_NODES_RR);
-    return need_nodes;
-  }
-  *kfn = PT_PICK(rr, pt_trace_kernel_bvh_gmem, PT_X_BVH_GMEM_RR);
-  return 0;
+  *staging = need_all <= lds_room ? 0 : (need_nodes <= lds_room ? 1 : 2);
+  return *staging == 0 ? need_all : (*staging == 1 ? need_nodes : 0);
 }
 
-// grid walk: likewise (cells + entries / the cell records / nothing staged)
-static size_t bind_grid(pt_ctx* c, bool rr, size_t lds_room, PtKernelArgs& A, const void** kfn) {
+// grid walk: likewise (cells + entries / the cell records / nothing staged: grid_build_kind - 1)
+static size_t bind_grid(pt_ctx* c, size_t lds_room, PtKernelArgs& A, int* staging) {
   const ptgrid::Grid& g = c->grid;
   A.bvh_slots = c->d_grid_entries.get();
   A.bvh_slot_index = c->d_grid_index.get();
@@ -1054,22 +1063,13 @@ static size_t bind_grid(pt_ctx* c, bool rr, size_t lds_room, PtKernelArgs& A, co
   A.grid_r2_near = g.r2_near;
   const size_t need_cells = PT_GRID_LDS_CELLS(A.n_cells);
   const size_t need_all = need_cells + (size_t)g.n_entries * 16;
-  const int build = grid_build_kind(c, lds_room);
-  if (build == 1) {
-    *kfn = c->count_work ? extra_kernel(c->device, PT_X_GRID_COUNT) : PT_PICK(rr, pt_trace_kernel_grid, PT_X_GRID_RR);
-    return need_all;
-  }
-  if (build == 2) {
-    *kfn = c->count_work ? extra_kernel(c->device, PT_X_GRID_CELLS_COUNT) : PT_PICK(rr, pt_trace_kernel_grid_cells, PT_X_GRID_CELLS_RR);
-    return need_cells;
-  }
-  *kfn = PT_PICK(rr, pt_trace_kernel_grid_gmem, PT_X_GRID_GMEM_RR);
-  return 0;
+  *staging = grid_build_kind(c, lds_room) - 1;
+  return *staging == 0 ? need_all : (*staging == 1 ? need_cells : 0);
 }
 
 // Workgroups of `block` threads really RESIDENT on a CU at once: the occupancy query (LDS, VGPRs, and an SGPR rule
-// that leaves out the trap handler's 16 per wave) capped by what the kernel is BUILT FOR (pt_kernel_args.h PT_WAVES_*,
-// the kernel's amdgpu_waves_per_eu).  A launch of more workgroups than this is not wrong, but the extra ones start
+// that leaves out the trap handler's 16 per wave) capped by what the kernel is BUILT FOR (`built_for`: its entry's wave
+// count, the kernel's amdgpu_waves_per_eu).  A launch of more workgroups than this is not wrong, but the extra ones start
 // only when others end: for the shared queue that is an empty wave at the end, for a statically dealt launch a share
 // of the frame that begins when everybody else is done (the reference's 25-spp paused frame x 4: 2.98 -> 2.44 ms).
 static hipError_t resident_blocks(const void* kfn, uint32_t block, size_t lds, int built_for, int* out) {
@@ -1080,17 +1080,10 @@ static hipError_t resident_blocks(const void* kfn, uint32_t block, size_t lds, i
   *out = n < cap ? n : cap;
   return hipSuccess;
 }
-// what a trace kernel is built for, by how it looks at the list (every build of a path shares its figure; the one twin
-// whose tallies cost it two waves has its own)
-static int built_for_waves(int path, const void* kfn) {
-  if (path == PT_GEOM_SMALL) return PT_WAVES_SMALL;
-  if (path == PT_GEOM_BVH || path == PT_GEOM_GRID) return kfn == pt_extra_kernel(PT_X_GRID_CELLS_COUNT) ? PT_WAVES_TWIN_CELLS : PT_WAVES_WALK;
-  return path == PT_GEOM_LDS ? PT_WAVES_LIST_LDS : PT_WAVES_LIST;
-}
 
 // walk kernels: whichever of 256 / 512 / 1024 threads puts the most waves on a CU (the staged scene is
 // paid once per workgroup, the parked path state and the VGPRs per wave)
-static uint32_t walk_block_threads(const void* kfn, int built_for, size_t scene, size_t lds_max) {
+static uint32_t walk_block_threads(const void* kfn, int built_for, size_t scene, size_t lds_max, std::optional<uint32_t> knob) {
   uint32_t block = 0;
   int best_waves = -1;
   for (uint32_t b = 256; b <= 1024; b *= 2) {
@@ -1104,13 +1097,23 @@ static uint32_t walk_block_threads(const void* kfn, int built_for, size_t scene,
     const int waves = n * (int)(b / 64);
     if (waves > best_waves) { best_waves = waves; block = b; }
   }
-#ifdef PT_DEV_KNOBS
-  if (const char* e = getenv("PT_BVH_BLOCK")) {
-    uint32_t b = (uint32_t)atoi(e);
-    if (b >= 64u && b <= 1024u && b % 64u == 0u) block = b;
-  }
-#endif
+  if (knob && *knob >= 64u && *knob <= 1024u && *knob % 64u == 0u) block = *knob;
   return block ? block : 1024u;
+}
+
+// The launch path's dev knobs (pt_launch_plan.hpp), read per launch: tools/sweep_knobs.py starts a process per point.
+// libptrace.so as shipped reads no environment variable (the Python harness has two, both loader matters of
+// ray_tracer_webgl_amd/_lib.py: PT_LIB and PT_NO_TORCH_HIP_PRELOAD)
+static LaunchKnobs read_launch_knobs() {
+  LaunchKnobs k;
+#ifdef PT_DEV_KNOBS
+  auto knob = [](const char* name, auto& field) { if (const char* e = getenv(name)) field = atoi(e); };
+  knob("PT_CARRY_LANES", k.carry_lanes), knob("PT_BVH_BLOCK", k.bvh_block), knob("PT_COOP_MAX", k.coop_max);
+  knob("PT_PER_CU", k.per_cu), knob("PT_QUEUE_CHUNK", k.queue_chunk), knob("PT_GRID_PERCENT", k.grid_percent);
+  knob("PT_QUEUE_STATIC", k.queue_static), knob("PT_COST_FEEDBACK", k.cost_feedback), knob("PT_QUEUE_GROUPED", k.queue_grouped);
+  knob("PT_FEWER_X10_1", k.fewer_x10_1), knob("PT_FEWER_X10_2", k.fewer_x10_2);
+#endif
+  return k;
 }
 
 static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launch* L) {
@@ -1119,7 +1122,8 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
     int rc = fill_uniforms(c, n_passes, A);
     if (rc != PT_OK) return rc;
   }
-  const unsigned long long items = A.n_items;
+  const LaunchKnobs knobs = read_launch_knobs();
+  if (knobs.carry_lanes) A.carry_lanes = *knobs.carry_lanes;
   int trial = -1;
   const int path = choose_path(c, allow_trials, &trial);
   const bool rr = c->rr_min_depth > 0;
@@ -1128,163 +1132,42 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
 
   // the kernel, its workgroup size and its dynamic LDS (staged scene + the parked path state of every
   // lane of a walk kernel's workgroup)
-  size_t lds = 0;
-  const void* kfn = nullptr;
-  uint32_t block = 256;
-  if (path == PT_GEOM_BVH || path == PT_GEOM_GRID) {
-    const size_t lds_max = kWalkLdsMax;
-    const size_t lds_room = walk_lds_room();
-    const size_t scene = path == PT_GEOM_BVH ? bind_hierarchy(c, rr, lds_room, A, &kfn) : bind_grid(c, rr, lds_room, A, &kfn);
+  const bool walk = path == PT_GEOM_BVH || path == PT_GEOM_GRID;
+  size_t scene = 0;
+  int row = 0;
+  if (walk) {
+    int staging = 0;
+    scene = path == PT_GEOM_BVH ? bind_hierarchy(c, walk_lds_room(), A, &staging) : bind_grid(c, walk_lds_room(), A, &staging);
+    row = (path == PT_GEOM_BVH ? ROW_BVH : ROW_GRID) + staging;
     A.lds_scene_bytes = (uint32_t)scene;
-    A.coop_max_live = 0;  // (the walk kernels have no tail mode: pt_trace_body.hpp)
-    block = walk_block_threads(kfn, built_for_waves(path, kfn), scene, lds_max);
-    lds = scene + (size_t)PT_PARK_STRIDE * 4 * block;
   } else {
     // the LDS copy exists whenever the list fits; the scalar and small-list walks only change how the
     // SCAN reads (their per-lane gathers — shading, tail mode — still come from the copy)
     const bool have_lds = c->n_spheres <= PT_MAX_SPHERES_LDS;
-    lds = have_lds ? (size_t)PT_LDS_ENTRIES(c->n_spheres) * 16 : 0;
-    kfn = path == PT_GEOM_SMALL ? (c->count_work ? extra_kernel(c->device, PT_X_SMALL_COUNT) : (rr ? extra_kernel(c->device, PT_X_SMALL_RR + (int)(c->n_spheres & 3u)) : pt_small_kernel(c->n_spheres)))
-          : path == PT_GEOM_LDS ? PT_KFN(pt_trace_kernel)
-                                : (have_lds ? PT_PICK(rr, pt_trace_kernel_scalar, PT_X_SCALAR_RR)
-                                            : PT_PICK(rr, pt_trace_kernel_scalar_nolds, PT_X_SCALAR_NOLDS_RR));
-    // tail mode (list kernels only): a turn-around costs ~(n / 64 + 1) x 60 + 60 issue slots per live ray, a step of the
-    // scan ~12 n + 700 for the wave: it pays while the live rays are fewer than the ratio (484 spheres: 12 — measured
-    // 155.7 / 17.21 ms per 16-pass / 1-pass launch against 157.5 / 17.46 at 16 and 158.2 / 18.10 without it)
-    {
-      const uint32_t per_ray = (c->n_spheres / 64u + 1u) * 60u + 60u;
-      const uint32_t lim = (12u * c->n_spheres + 700u) / per_ray;
-      A.coop_max_live = lim > 16u ? 16u : lim;
-#ifdef PT_DEV_KNOBS
-      if (const char* e = getenv("PT_COOP_MAX")) A.coop_max_live = (uint32_t)atoi(e);
-#endif
-    }
-    // 256-thread workgroups while several fit per CU; one 1024-thread workgroup per CU when the list
-    // takes most of the 160 KiB LDS
-    block = lds > 40 * 1024 ? 1024u : 256u;
+    scene = have_lds ? (size_t)PT_LDS_ENTRIES(c->n_spheres) * 16 : 0;
+    row = path == PT_GEOM_SMALL ? ROW_SMALL + (int)(c->n_spheres & 3u)
+                                : (path == PT_GEOM_LDS ? ROW_LIST_LDS : (have_lds ? ROW_SCALAR : ROW_SCALAR_NOLDS));
   }
+  const TraceKernel& tk = kTraceKernels[row][rr ? BUILD_RR : (c->count_work ? BUILD_TWIN : BUILD_PLAIN)];
+  const void* kfn = tk.main ? tk.main : (tk.extra >= 0 ? extra_kernel(c->device, tk.extra) : pt_small_kernel((unsigned)tk.small));
+  const uint32_t block = walk ? walk_block_threads(kfn, tk.waves, scene, kWalkLdsMax, knobs.bvh_block) : list_block_threads(scene);
+  const size_t lds = walk ? scene + (size_t)PT_PARK_STRIDE * 4 * block : scene;
   A.block_threads = block;
   int per_cu = 0;
-  PT_HIP(c, resident_blocks(kfn, block, lds, built_for_waves(path, kfn), &per_cu));
-  if (per_cu < 1) per_cu = 1;
-#ifdef PT_DEV_KNOBS
-  if (const char* e = getenv("PT_PER_CU")) { const int v = atoi(e); if (v >= 1 && v <= 32) per_cu = v; }
-#endif
+  PT_HIP(c, resident_blocks(kfn, block, lds, tk.waves, &per_cu));
 
-  // Items a wave reserves per queue atomic.  Items are numbered tile-major, so a reservation is
-  // also a run of neighbouring pixels: big reservations keep a wave's lanes on one tile (more
-  // coherent walks, fewer atomics), small ones deal the tail of a short launch finely.
-  // Measured on config 2, grid walk, 64 passes of 16 spp: the whole frame (225 items per resident
-  // lane) 153.6 / 149.9 / 148.0 / 147.3 ms with 64 / 128 / 256 / 512 items; one rank's band of eight
-  // (28 items per lane) 24.0 / 22.0 / 21.1 / 21.0 / 21.1 / 21.5 / 22.9 ms with 16 ... 1024.
-  {
-    const unsigned long long lanes = (unsigned long long)c->num_cus * (unsigned)per_cu * block;
-    A.queue_chunk = items >= 192ull * lanes ? 512u : (items >= 64ull * lanes ? 128u : (items >= 16ull * lanes ? 64u : 32u));
-    // ... and to the ITEMS (round 4): the queue head is one address and takes a reservation every ~13 ns (77 M/s: a 16-pass
-    // launch of 1-spp items at the reference's size never ran faster than 2.9 ms through it, 0.65 ms dealt statically); an item
-    // of s samples is ~s x 27 us of a lane's time, so reservations of at least 1100 / s items keep the head below half
-    // of that rate
-    {
-      const uint32_t spp = (uint32_t)(c->params.samples_per_pixel > 0 ? c->params.samples_per_pixel : 1);
-      uint32_t c_min = 32u;
-      while (c_min * spp < 1100u && c_min < 1024u) c_min *= 2u;
-      if (A.queue_chunk < c_min) A.queue_chunk = c_min;
-    }
-#ifdef PT_DEV_KNOBS
-    if (const char* e = getenv("PT_QUEUE_CHUNK")) {
-      uint32_t v = (uint32_t)atoi(e);
-      if (v >= 1u && v <= 4096u) A.queue_chunk = v;
-    }
-#endif
-  }
-  const unsigned long long want = (items + block - 1) / block;
-  const unsigned long long resident = (unsigned long long)c->num_cus * (unsigned)per_cu;
-  uint32_t grid = (uint32_t)(want < resident ? want : resident);
-#ifdef PT_DEV_KNOBS
-  if (const char* e = getenv("PT_GRID_PERCENT")) grid = (uint32_t)((unsigned long long)grid * (unsigned)atoi(e) / 100ull);
-#endif
-  if (grid < 1) grid = 1;
-  // Launches of a few items per lane (the reference's 1-spp frame: two) cannot afford the shared
-  // queue: its head is ONE address, the reservations' atomics take their turn there (~25 ns each), and
-  // 28 000 of them are the frame's whole 0.78 ms.  Such launches deal reservations of one tile's 64
-  // items round-robin to the waves instead (no atomic; the cost-ordered tile list still spreads the
-  // heavy tiles over the waves).
-  A.n_waves = grid * (block / 64u);
-  // WHEN to deal statically: by the SAMPLES a lane gets, not only by its items.  The queue's balance is worth its atomics once
-  // a lane's share is long enough for the streams' lengths to spread; below that the static deal wins, and the reservations
-  // sized for the queue head (>= 1100 / spp items) would leave most waves of a short launch without any.  Measured on the
-  // reference's scene and size (7 168 waves) and on the cover scene (6 144), static / queue in ms (profiles/r05_ab_runs.txt):
-  //   4 spp x 4 passes  (31 samples per lane) 0.53 / 0.78      8 spp x 4  (63) 0.99 / 1.07      25 spp x 2  (98) 1.48 / 1.47
-  //   25 spp x 4 (196) 2.84 / 2.62     25 spp x 8 (392) 5.48 / 4.64     cover scene 16 spp x 1 (84) 3.50 / 3.92     x 2 (169) 5.72 / 4.68
-  // -> statically below 112 samples per lane (rounds 2-4: below 8 ITEMS per lane whatever their length, which dealt the
-  // paused mode's 25-spp frames statically up to 200 samples per lane: 4 of them 2.84 -> 2.62 ms).  Items of one or two
-  // samples keep round 4's bound of 64 items per lane (16 passes of 1 / 2 spp at the reference's size: 0.59 / 1.08 ms
-  // against 2.89 / 2.89 through the queue, whose head was the limit).
-  const unsigned long long lanes_all = (unsigned long long)A.n_waves * 64ull;
-  const unsigned long long spp_u = (unsigned long long)(c->params.samples_per_pixel > 0 ? c->params.samples_per_pixel : 1);
-  const bool short_items = c->params.samples_per_pixel <= 2 && items < 64ull * lanes_all;
-  // (round 5, with the GROUPED queue below taking the statically dealt launches from 16 samples per lane on: the shared queue
-  // only wins from ~450 samples per lane — grouped / shared: 25 spp x 4 (196) 2.52 / 2.61, 64 spp x 2 (250) 3.21 / 3.42, cover
-  // scene 16 spp x 2 (169) 4.47 / 4.70, x 4 (337) 8.04 / 8.31, but x 8 (674) 15.25 / 14.69 and the full frame 120.8 / 110.0:
-  // long launches want the shared queue's big reservations and its balance across ALL waves)
-  A.queue_static = (short_items || items * spp_u < 448ull * lanes_all) ? 1u : 0u;
-#ifdef PT_DEV_KNOBS
-  if (const char* e = getenv("PT_QUEUE_STATIC")) A.queue_static = atoi(e) ? 1u : 0u;
-  if (const char* e = getenv("PT_COST_FEEDBACK")) A.cost_feedback = atoi(e) ? 1u : 0u;
-#endif
-  if (A.queue_static) {
-    A.queue_chunk = 64u;
-    // a statically dealt launch of ONE-sample items keeps the tile order it finds: the feedback's one atomic per pixel of pass 0
-    // costs such a launch more than the order gives it (4 passes of 1 spp at the reference's size: 0.206 -> 0.185 ms; with 2, 4, 8
-    // spp the cost-ordered tiles pay: 0.318 / 0.557 / 1.03 ms with feedback against 0.333 / 0.608 / 1.13 without)
-    if (c->params.samples_per_pixel < 2) A.cost_feedback = 0u;
-    // FEWER WAVES for the shortest launches.  A launch of a lane-step or two per resident lane is all drain: a wave ends when
-    // its slowest lane does, and with fewer waves on a SIMD each step is faster and each wave deals more items to its lanes.
-    // One-sample items want ~4.6 per lane, two-sample items ~3.4 — in WHOLE workgroups per CU, so that no CU carries one more
-    // than its neighbours (the reference's 1280x702 frame, 1 spp: three of the seven resident workgroups per CU, 0.115 ->
-    // 0.081 ms; 2 spp: four, 0.132 -> 0.116; from 4 spp on the full grid wins; re-swept in round 5 on the corrected grid:
-    // 3.8 / 4.2 / 4.6 / 5.0 / 5.4 items per lane -> 0.089 / 0.088 / 0.082 / 0.091 / 0.087 ms).  Scheduling only.
-    if (c->params.samples_per_pixel <= 2) {
-      unsigned long long x10 = c->params.samples_per_pixel == 1 ? 46ull : 34ull;
-#ifdef PT_DEV_KNOBS
-      if (const char* e = getenv(c->params.samples_per_pixel == 1 ? "PT_FEWER_X10_1" : "PT_FEWER_X10_2")) { const int v = atoi(e); if (v >= 1) x10 = (unsigned long long)v; }
-#endif
-      const unsigned long long per_wg = (unsigned long long)block * x10 / 10ull;
-      unsigned long long fewer = (items + per_wg - 1) / per_wg;
-      const unsigned long long cus = (unsigned long long)c->num_cus;
-      if (fewer > cus) fewer = (fewer + cus / 2) / cus * cus;  // whole workgroups per CU
-      if (fewer >= 1 && fewer < grid) {
-        grid = (uint32_t)fewer;
-        A.n_waves = grid * (block / 64u);
-      }
-    }
-  }
+  const LaunchPlan P = plan_launch({A.n_items, c->params.samples_per_pixel, n_passes, block, per_cu, (uint32_t)c->num_cus, walk,
+                                    c->n_spheres, knobs});
+  A.queue_chunk = P.queue_chunk; A.queue_static = (uint32_t)P.deal; A.queue_groups = P.queue_groups;
+  A.n_waves = P.n_waves; A.cost_feedback = P.cost_feedback; A.coop_max_live = P.coop_max_live;
+  L->kfn = kfn; L->grid = P.grid; L->block = block; L->lds = lds; L->path = path; L->trial = trial;
+  return PT_OK;
+}
 
-  // ... and between the two lies the GROUPED queue (round 5; pt_refill.hpp): G groups of waves, each with a head of its own,
-  // wave w in group w % G, group g owning the reservations g, g + G, ... — a queue's balance among a group's ~28 waves at one
-  // atomic per reservation on one of G = 256 addresses.  It replaces the static deal from 16 SAMPLES per lane on: below that
-  // a wave takes so few reservations that the atomic's round trip, which finds the whole wave idle (all lanes of a
-  // short-item launch run dry together), costs more than the balance gives.  Measured static / grouped, ms
-  // (profiles/r05_ab_runs.txt): the reference's scene 16 x 1 spp 0.579 / 0.533, groups of 1- / 2-spp frames 0.0384 / 0.0351 and
-  // 0.0697 / 0.0598 per frame, 8 spp x 4 0.958 / 0.889, cover scene 16 x 1 spp 2.93 / 2.55, 4 spp x 2 1.62 / 1.41; but 4 x 1 spp
-  // 0.164 / 0.203, the single 1-spp frame 0.079 / 0.088, the single 4-spp frame 0.172 / 0.186.  G is the largest power of
-  // two that is neither above the CU count nor above the launch's wave count (every group needs a wave: nobody else hands
-  // out its reservations).
-  if (A.queue_static) {
-    const unsigned long long lanes_now = (unsigned long long)A.n_waves * 64ull;
-    bool grouped = items * spp_u >= 16ull * lanes_now;
-#ifdef PT_DEV_KNOBS
-    if (const char* e = getenv("PT_QUEUE_GROUPED")) grouped = atoi(e) != 0;
-#endif
-    if (grouped) {
-      uint32_t g = 1u;
-      while (2u * g <= (uint32_t)c->num_cus && 2u * g <= (uint32_t)PT_QUEUE_GROUPS_MAX && 2u * g <= A.n_waves) g *= 2u;
-      A.queue_groups = g;
-      A.queue_static = 2u;
-    }
-  }
-
-  L->kfn = kfn; L->grid = grid; L->block = block; L->lds = lds; L->path = path; L->trial = trial;
+// the trace kernel of a prepared launch (capture-safe: a launch only)
+static int launch_trace(pt_ctx* c, const Launch& L) {
+  void* kargs[] = {const_cast<PtKernelArgs*>(&L.A)};
+  PT_HIP(c, hipLaunchKernel(L.kfn, dim3(L.grid), dim3(L.block), kargs, L.lds, c->stream));
   return PT_OK;
 }
 
@@ -1306,9 +1189,7 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
   }
   PtKernelArgs& A = L.A;
   const PtParams& p = c->params;
-  const void* kfn = L.kfn;
   const uint32_t grid = L.grid, block = L.block;
-  const size_t lds = L.lds;
   const int path = L.path;
   int trial = L.trial;
 
@@ -1354,10 +1235,7 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
     PT_HIP(c, hipEventRecord(c->trial_ev[2 * trial], c->stream));
   }
   if (ev) PT_HIP(c, hipEventRecord(ev->first, c->stream));
-  {
-    void* kargs[] = {&A};
-    PT_HIP(c, hipLaunchKernel(kfn, dim3(grid), dim3(block), kargs, lds, c->stream));
-  }
+  if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
   if (ev) PT_HIP(c, hipEventRecord(ev->second, c->stream));
   if (trial >= 0) {
     PT_HIP(c, hipEventRecord(c->trial_ev[2 * trial + 1], c->stream));
@@ -1418,10 +1296,7 @@ int plan_frame(pt_ctx* c, const uint32_t* ctr, uint32_t even_odd0, int max_rende
 
 // enqueue one planned frame — or group of frames — (capture-safe: launches only)
 int enqueue_frame(pt_ctx* c, FramePlan& F, bool advance) {
-  {
-    void* kargs[] = {&F.L.A};
-    PT_HIP(c, hipLaunchKernel(F.L.kfn, dim3(F.L.grid), dim3(F.L.block), kargs, F.L.lds, c->stream));
-  }
+  if (int rc = launch_trace(c, F.L); rc != PT_OK) return rc;
   // a frame's one pass sits in its slab ({sum r, g, b, spp} per pixel): blend straight from there, frame after frame
   // (each blend reads the texture the one before it wrote)
   const uint32_t n_pix = c->local_rows * c->width;
@@ -1499,10 +1374,8 @@ int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
   unsigned long long* seg = c->d_counters.get() + PT_CTR_SEGMENTS;
   PT_HIP(c, hipMemcpyAsync(c->d_counters.get() + PT_CTR_SCRATCH, seg, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
   PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
-  {
-    void* kargs[] = {&L.A};
-    PT_HIP(c, hipLaunchKernel(L.kfn, dim3(L.grid), dim3(L.block), kargs, L.lds, c->stream));
-  }
+  rc = launch_trace(c, L);
+  if (rc != PT_OK) return rc;
   rc = launch_tile_order(c);
   if (rc != PT_OK) return rc;
   PT_HIP(c, hipMemcpyAsync(seg, c->d_counters.get() + PT_CTR_SCRATCH, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));

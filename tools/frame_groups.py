@@ -1,11 +1,12 @@
 """Dev tool: the reference's frame loop (State::default, 1280x702, depth 8) at several samples per frame — ms per frame
 when a series is replayed from hipGraphs in groups (pt_render_frames) and when single frames are issued from the host.
 
-    PT_LIB=build_ab/libptrace_knobs.so PT_GROUP_STATIC=0 python tools/frame_groups.py [spp ...]
+    PT_LIB=build_ab/libptrace_knobs.so PT_QUEUE_STATIC=1 python tools/frame_groups.py [spp ...]
 
-With the PT_DEV_KNOBS build: PT_GROUP_STATIC=0 sends a group's items through the shared queue whenever the launch's own
-rule would (prepare_launch), =1 (the default) deals every group statically; PT_FEWER_X10_1 / _2 = items per lane (x 10)
-a statically dealt launch of 1- / 2-sample items is sized for.
+A group is dealt like any other launch of its shape (pt_launch_plan.hpp).  With the PT_DEV_KNOBS build: PT_QUEUE_STATIC=1
+deals every launch statically, =0 sends it through a queue; PT_QUEUE_GROUPED=0 / 1 turns the grouped queue of a statically
+dealt launch off / on; PT_FEWER_X10_1 / _2 = items per lane (x 10) a statically dealt launch of 1- / 2-sample items is
+sized for.
 """
 import os
 import sys
