@@ -26,6 +26,7 @@
 #include "pt_grid.hpp"
 #include "pt_extra.h"
 #include "pt_kernel_args.h"
+#include "pt_geom_plan.hpp"
 #include "pt_launch_plan.hpp"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
@@ -75,7 +76,7 @@ struct Launch {
   uint32_t grid = 1, block = 256;
   size_t lds = 0;
   int path = 0;
-  int trial = -1;  // k when this launch is the autotune measurement of trial_paths[k]
+  int trial = -1;  // k when this launch is the autotune measurement of PathTuner::paths[k]
 };
 
 // Everything a frame bakes into its launches: decided BEFORE anything is enqueued (prepare_launch queries
@@ -119,15 +120,8 @@ struct pt_ctx {
   // read-out staging
   DevBuf<float4> d_resolve;
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
-  int geom_policy = PT_GEOM_AUTO;
-  int geom_tuned = 0;              // the path PT_GEOM_AUTO settled on, 0 while measuring
-  int geom_last = PT_GEOM_LDS;     // path of the most recent launch
-  int trial_paths[4] = {0, 0, 0, 0};  // the paths this scene can use, in measuring order
-  int n_trials = 0;
-  int trial_state = 0;             // 0: unmeasured first launch (cold), k in 1..n_trials: the next
-                                   // launch measures trial_paths[k-1], n_trials+1: all enqueued
+  PathTuner geom;
   hipEvent_t trial_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // begin/end per trial
-  double trial_samples[4] = {0.0, 0.0, 0.0, 0.0};
   // culling hierarchy (PT_GEOM_BVH), rebuilt by pt_set_spheres; absent for tiny / irregular scenes
   bool have_bvh = false;
   DevBuf<uint32_t> d_bvh_nodes;
@@ -147,7 +141,7 @@ struct pt_ctx {
   DevBuf<uint32_t> d_grid_index;
   DevBuf<PtMatRec> d_grid_mat;
   ptgrid::Grid grid;  // host copy of the scalars (the arrays are released after upload)
-  bool grid_cells_build = false;  // pt_tune measured the build that gathers its entries from L2 faster than the LDS-staged one on this scene and view
+  bool grid_cells_build = false;  // pt_tune measured the build that gathers its entries from L2 faster than the LDS-staged one on this scene and view (grid_staging)
   int grid_fit_mode = 0;  // PT_OPT_GRID_FIT: 0 pt_tune measures the margin classes, 1 it takes the one the camera needs unmeasured
   int count_work = 0; // PT_OPT_COUNT_WORK: launch the measuring twin of the walk kernel
   DevBuf<uint32_t> d_cell_hist;           // grid twins: leaf-round lanes per entry run + coherence bins (pt_debug_cell_hist)
@@ -346,87 +340,37 @@ int launch_tile_order(pt_ctx* c) {
 // PT_GEOM_AUTO: once every trial launch has finished (non-blocking query), keep the path with
 // the lowest time per camera sample.  Images do not depend on the choice.
 void try_finish_tuning(pt_ctx* c) {
-  if (c->geom_tuned || c->n_trials == 0 || c->trial_state <= c->n_trials) return;
-  for (int k = 0; k < c->n_trials; k++)
+  if (!c->geom.awaiting_times()) return;
+  for (int k = 0; k < c->geom.n_paths; k++)
     if (hipEventQuery(c->trial_ev[2 * k + 1]) != hipSuccess) return;
-  double best = 0.0;
-  int best_path = 0;
-  for (int k = 0; k < c->n_trials; k++) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->trial_ev[2 * k], c->trial_ev[2 * k + 1]) != hipSuccess) return;
-    double per = (double)ms / (c->trial_samples[k] > 0 ? c->trial_samples[k] : 1.0);
-    if (best_path == 0 || per < best) { best = per; best_path = c->trial_paths[k]; }
+  double ms[4];
+  for (int k = 0; k < c->geom.n_paths; k++) {
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, c->trial_ev[2 * k], c->trial_ev[2 * k + 1]) != hipSuccess) return;
+    ms[k] = (double)t;
   }
-  c->geom_tuned = best_path;
+  c->geom.settle(ms);
 }
 
-// the geometry paths a scene can use, in measuring order (the first is also the default while
-// PT_GEOM_AUTO has not decided)
-void list_paths(pt_ctx* c) {
-  c->n_trials = 0;
-  // The list walks test every sphere for every ray: beside a culling structure they can only win
-  // on very short lists (measured: 484 spheres 4x, 10 001 spheres 14x slower than the grid), so
-  // beyond 64 spheres PT_GEOM_AUTO does not spend launches on measuring them.
-  const bool structured = c->have_bvh || c->have_grid;
-  if (c->n_spheres <= PT_MAX_SPHERES_SMALL) c->trial_paths[c->n_trials++] = PT_GEOM_SMALL;  // the reference's own scene size
-  if (!structured || c->n_spheres <= 64u) {
-    if (c->n_spheres <= PT_MAX_SPHERES_LDS && c->n_trials < 4) c->trial_paths[c->n_trials++] = PT_GEOM_LDS;
-    if (c->n_trials < 4) c->trial_paths[c->n_trials++] = PT_GEOM_SCALAR;
-  }
-  // The hierarchy beats the grid where a uniform grid is the wrong structure: a dense clump inside one
-  // cell of a sparse field (many entries in a cell), or many spheres too large to be gridded (every ray
-  // tests those first).  On an even field the grid won every measurement (config 2: 112 against 185 ms,
-  // config 5: 123 against 365), and a trial of the hierarchy costs the first frame of such a scene more
-  // than anything else (config 5: two 0.4-s launches): not measured there.
-  const bool grid_even = c->have_grid && c->grid.max_cell_entries <= 16u && c->grid.n_always <= 8u;
-  if (c->have_bvh && !grid_even && c->n_trials < 4) c->trial_paths[c->n_trials++] = PT_GEOM_BVH;
-  if (c->have_grid && c->n_trials < 4) c->trial_paths[c->n_trials++] = PT_GEOM_GRID;
-  if (c->n_trials == 1) c->geom_tuned = c->trial_paths[0];  // nothing to measure
+PathScene path_scene(const pt_ctx* c) {
+  return {c->n_spheres, c->have_bvh, c->have_grid, c->grid.max_cell_entries, c->grid.n_always};
 }
 
-// The margin classes a grid is built for (d_near / s0: rays that start within (factor - 1) s0 of the scene's middle walk the
-// cells; pt_grid.hpp) and the smallest one that covers the camera of the current uniforms with its lens; 0 = no grid / no
-// uniforms / a camera that is not finite.  A camera farther out than the largest class gets the largest: its primary rays
-// take the far path as before (it sees the scene under a small angle: few of them reach the grid's box).
-constexpr double kNearFactors[] = {2.5, 3.0, 4.0, 5.5, 8.0, 12.0, 16.0};
-double view_need_factor(const pt_ctx* c) {
-  if (!c->have_grid || !c->have_params) return 0.0;
-  const PtParams& p = c->params;
-  double rho = 0.0, reach = 0.0;
-  for (int k = 0; k < 3; k++) {
-    const double dk = (double)p.camera_origin[k] - (double)c->grid.c0[k];
-    rho += dk * dk;
-    reach += std::fabs((double)p.lens_radius) * (std::fabs((double)p.u[k]) + std::fabs((double)p.v[k]));
-  }
-  rho = std::sqrt(rho) + reach;
-  if (!std::isfinite(rho)) return 0.0;
-  const double need = ((rho / 0.9999 + (double)c->grid.s0) / (double)c->grid.s0) * 1.01;
-  double factor = kNearFactors[sizeof kNearFactors / sizeof kNearFactors[0] - 1];
-  for (double f : kNearFactors) if (f >= need) { factor = f; break; }
-  return factor;
-}
-int grid_fit_state(const pt_ctx* c);  // (below, beside fit_grid_to_view)
-
-// Which build of the grid kernel the next launch gets (PtStats.grid_kernel_build): 1 = cells AND entries staged in the LDS
-// (pt_trace_kernel_grid), 2 = the cell records staged, the entries gathered from L2 (…_grid_cells), 3 = nothing staged (…_grid_gmem),
-// 0 = no grid.  What fits goes into the LDS — with two exceptions (round 6).  (i) A camera OUTSIDE the near region (grid_fit_state 1:
-// the host has not refitted yet) turns every primary ray into a far ray, and the LDS-staged build runs a far ray through the literal
-// loop for ONE lane (~12 instructions per sphere of the list), while its siblings hand it to the whole wave, 64 spheres at a time:
-// the 1 500-sphere field from five scene radii out renders in 2.2-2.9 ms through the cells build against 8-10 ms (and 0.55 ms once
-// refitted).  (ii) pt_tune times both builds on scenes whose entries take a good part of the LDS (fewer workgroups per CU) and
-// keeps the faster (the same field seen from inside: 1.37 against 1.48 ms; config 2, 14 KB of entries: the LDS build by 6 %,
-// not measured there).  Scheduling only: the same entries, the same tests, the same bits.
-int grid_build_kind(const pt_ctx* c, size_t lds_room) {
-  if (!c->have_grid) return 0;
-  const size_t need_cells = PT_GRID_LDS_CELLS((size_t)c->grid.n[0] * c->grid.n[1] * c->grid.n[2]);
-  const size_t need_all = need_cells + (size_t)c->grid.n_entries * 16;
-  if (need_all <= lds_room && !c->grid_cells_build && grid_fit_state(c) != 1) return 1;
-  return need_cells <= lds_room ? 2 : 3;
+// the margin class the current uniforms need of the grid (pt_geom_plan.hpp); 0 = no grid / no uniforms / a camera that is not finite
+double need_factor(const pt_ctx* c) {
+  return c->have_grid && c->have_params ? view_need_factor(c->params, c->grid.c0, c->grid.s0) : 0.0;
 }
 
-// LDS a walk kernel may fill with its staged scene: what is left beside a 1024-thread workgroup's parked path state
-constexpr size_t kWalkLdsMax = (size_t)PT_LDS_ENTRIES(PT_MAX_SPHERES_LDS) * 16;
-constexpr size_t walk_lds_room() { return kWalkLdsMax - (size_t)PT_PARK_STRIDE * 4 * 1024; }
+// does the grid in place fit the view (PtStats.grid_fit_stale, pt_grid_fit)?
+int fit_state(const pt_ctx* c) {
+  return grid_fit_state(c->geom.grid_in_use(c->have_grid), need_factor(c), (double)c->grid.near_factor);
+}
+
+// the build of the grid kernel the next launch gets and the bytes it stages (with a grid)
+Staging grid_build(const pt_ctx* c) {
+  const ptgrid::Grid& g = c->grid;
+  return grid_staging((uint64_t)g.n[0] * g.n[1] * g.n[2], g.n_entries, walk_lds_room(), c->grid_cells_build, fit_state(c));
+}
 
 // a kernel of pt_kernels_extra.hip; its first use loads that code object and lifts its dynamic-LDS limit
 const void* extra_kernel(int device, int id) {
@@ -751,11 +695,10 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
   c->grid_cells_build = false;  // (a measurement of the previous scene)
   c->epoch++;
   c->scene_gen++;
-  c->geom_tuned = 0;  // a new scene: PT_GEOM_AUTO measures again
-  c->trial_state = 0;
+  c->geom.reset();  // a new scene: PT_GEOM_AUTO measures again
   c->scene_regular = regular;
   c->have_spheres = true;
-  list_paths(c);
+  c->geom.list_paths(path_scene(c));
   {
     const double t_end = host_ms();
     c->setup_ms[PT_SETUP_SPHERES_UPLOAD] = t_end - t_grid;
@@ -996,33 +939,8 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   return PT_OK;
 }
 
-// which way PHASE 1 looks at the sphere list (bit-identical results whichever way): the forced path,
-// or PT_GEOM_AUTO's tuned one / the trial this launch is (`*trial` = k when it measures trial_paths[k])
-static int choose_path(pt_ctx* c, bool allow_trials, int* trial) {
-  int path = c->geom_policy;
-  *trial = -1;
-  if (path == PT_GEOM_AUTO && !allow_trials) {
-    try_finish_tuning(c);
-    path = c->geom_tuned ? c->geom_tuned : c->trial_paths[0];
-  } else if (path == PT_GEOM_AUTO) {
-    try_finish_tuning(c);
-    if (c->geom_tuned) path = c->geom_tuned;
-    else if (c->trial_state == 0) { path = c->trial_paths[0]; c->trial_state = 1; } // cold launch: not measured
-    else if (c->trial_state <= c->n_trials) { *trial = c->trial_state - 1; path = c->trial_paths[*trial]; }
-    else path = c->trial_paths[0]; // trials still in flight
-  }
-  // a forced path the scene cannot use falls back to the nearest one it can
-  if (path == PT_GEOM_GRID && !c->have_grid) path = c->have_bvh ? PT_GEOM_BVH : PT_GEOM_SCALAR;
-  if (path == PT_GEOM_BVH && !c->have_bvh) path = PT_GEOM_SCALAR;
-  if (path == PT_GEOM_SMALL && c->n_spheres > PT_MAX_SPHERES_SMALL) path = PT_GEOM_SCALAR;
-  if (path == PT_GEOM_LDS && c->n_spheres > PT_MAX_SPHERES_LDS) path = PT_GEOM_SCALAR;
-  if (c->rr_min_depth > 0 && path == PT_GEOM_LDS) path = PT_GEOM_SCALAR;  // the roulette builds exist for the other four ways to read the list
-  return path;
-}
-
-// hierarchy walk: the tree's arrays and constants; what is staged in the LDS (`*staging`: 0 everything, 1 the nodes,
-// 2 nothing: the kernel's row past ROW_BVH); returns the staged bytes
-static size_t bind_hierarchy(pt_ctx* c, size_t lds_room, PtKernelArgs& A, int* staging) {
+// hierarchy walk: the tree's arrays and constants; returns what is staged in the LDS (hierarchy_staging)
+static Staging bind_hierarchy(pt_ctx* c, PtKernelArgs& A) {
   A.bvh_nodes = c->d_bvh_nodes.get();
   A.bvh_nodes32 = c->d_bvh_nodes32.get();
   A.bvh_slots = c->d_bvh_slots.get();
@@ -1035,14 +953,11 @@ static size_t bind_hierarchy(pt_ctx* c, size_t lds_room, PtKernelArgs& A, int* s
   for (int k = 0; k < 3; k++) A.bvh_c0[k] = c->bvh_c0[k];
   A.bvh_s0 = c->bvh_s0;
   A.bvh_kinv = c->bvh_kinv;
-  const size_t need_all = PT_BVH_LDS_BYTES32(c->bvh_n_nodes, c->bvh_n_slots);
-  const size_t need_nodes = PT_BVH_LDS_BYTES16(c->bvh_n_nodes);
-  *staging = need_all <= lds_room ? 0 : (need_nodes <= lds_room ? 1 : 2);
-  return *staging == 0 ? need_all : (*staging == 1 ? need_nodes : 0);
+  return hierarchy_staging(c->bvh_n_nodes, c->bvh_n_slots, walk_lds_room());
 }
 
-// grid walk: likewise (cells + entries / the cell records / nothing staged: grid_build_kind - 1)
-static size_t bind_grid(pt_ctx* c, size_t lds_room, PtKernelArgs& A, int* staging) {
+// grid walk: likewise (grid_staging)
+static Staging bind_grid(pt_ctx* c, PtKernelArgs& A) {
   const ptgrid::Grid& g = c->grid;
   A.bvh_slots = c->d_grid_entries.get();
   A.bvh_slot_index = c->d_grid_index.get();
@@ -1061,10 +976,7 @@ static size_t bind_grid(pt_ctx* c, size_t lds_room, PtKernelArgs& A, int* stagin
   }
   A.bvh_s0 = g.s0;
   A.grid_r2_near = g.r2_near;
-  const size_t need_cells = PT_GRID_LDS_CELLS(A.n_cells);
-  const size_t need_all = need_cells + (size_t)g.n_entries * 16;
-  *staging = grid_build_kind(c, lds_room) - 1;
-  return *staging == 0 ? need_all : (*staging == 1 ? need_cells : 0);
+  return grid_build(c);
 }
 
 // Workgroups of `block` threads really RESIDENT on a CU at once: the occupancy query (LDS, VGPRs, and an SGPR rule
@@ -1124,11 +1036,12 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
   }
   const LaunchKnobs knobs = read_launch_knobs();
   if (knobs.carry_lanes) A.carry_lanes = *knobs.carry_lanes;
-  int trial = -1;
-  const int path = choose_path(c, allow_trials, &trial);
+  if (c->geom.policy == PT_GEOM_AUTO) try_finish_tuning(c);
   const bool rr = c->rr_min_depth > 0;
+  const PathChoice choice = c->geom.choose(path_scene(c), allow_trials, rr);
+  const int path = choice.path;
   if (rr && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and PT_OPT_RUSSIAN_ROULETTE exclude each other");
-  c->geom_last = path;
+  c->geom.last = path;
 
   // the kernel, its workgroup size and its dynamic LDS (staged scene + the parked path state of every
   // lane of a walk kernel's workgroup)
@@ -1136,9 +1049,9 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
   size_t scene = 0;
   int row = 0;
   if (walk) {
-    int staging = 0;
-    scene = path == PT_GEOM_BVH ? bind_hierarchy(c, walk_lds_room(), A, &staging) : bind_grid(c, walk_lds_room(), A, &staging);
-    row = (path == PT_GEOM_BVH ? ROW_BVH : ROW_GRID) + staging;
+    const Staging st = path == PT_GEOM_BVH ? bind_hierarchy(c, A) : bind_grid(c, A);
+    scene = st.bytes;
+    row = path == PT_GEOM_BVH ? ROW_BVH + st.kind : ROW_GRID + st.kind - 1;
     A.lds_scene_bytes = (uint32_t)scene;
   } else {
     // the LDS copy exists whenever the list fits; the scalar and small-list walks only change how the
@@ -1160,7 +1073,7 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
                                     c->n_spheres, knobs});
   A.queue_chunk = P.queue_chunk; A.queue_static = (uint32_t)P.deal; A.queue_groups = P.queue_groups;
   A.n_waves = P.n_waves; A.cost_feedback = P.cost_feedback; A.coop_max_live = P.coop_max_live;
-  L->kfn = kfn; L->grid = P.grid; L->block = block; L->lds = lds; L->path = path; L->trial = trial;
+  L->kfn = kfn; L->grid = P.grid; L->block = block; L->lds = lds; L->path = path; L->trial = choice.trial;
   return PT_OK;
 }
 
@@ -1239,8 +1152,7 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
   if (ev) PT_HIP(c, hipEventRecord(ev->second, c->stream));
   if (trial >= 0) {
     PT_HIP(c, hipEventRecord(c->trial_ev[2 * trial + 1], c->stream));
-    c->trial_samples[trial] = (double)c->local_rows * c->width * n_passes * (double)p.samples_per_pixel;
-    c->trial_state = trial + 2;
+    c->geom.enqueued(trial, (double)c->local_rows * c->width * n_passes * (double)p.samples_per_pixel);
   }
 
   uint32_t n_pix = c->local_rows * c->width;
@@ -1657,8 +1569,8 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
   out->n_spheres = c->n_spheres;
   try_finish_tuning(c);
   out->local_rows = c->local_rows;
-  out->geometry_path = (uint32_t)c->geom_last;
-  out->geometry_tuned = c->geom_tuned ? 1u : 0u;
+  out->geometry_path = (uint32_t)c->geom.last;
+  out->geometry_tuned = c->geom.tuned ? 1u : 0u;
   for (int k = 0; k < 8; k++) out->work[k] = ctr[PT_CTR_WORK + k];
   out->far_rays = ctr[PT_CTR_FAR_RAYS];
   if (c->have_grid) {
@@ -1666,9 +1578,9 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
     out->grid_entries = c->grid.n_entries;
     out->grid_always = c->grid.n_always;
     out->grid_near_factor = c->grid.near_factor;
-    out->grid_need_factor = (float)view_need_factor(c);
-    out->grid_fit_stale = (uint32_t)grid_fit_state(c);
-    out->grid_kernel_build = (uint32_t)grid_build_kind(c, walk_lds_room());
+    out->grid_need_factor = (float)need_factor(c);
+    out->grid_fit_stale = (uint32_t)fit_state(c);
+    out->grid_kernel_build = (uint32_t)grid_build(c).kind;
   }
   if (c->have_bvh) {
     out->bvh_nodes = c->bvh_n_nodes;
@@ -1686,7 +1598,7 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     if (value != PT_GEOM_AUTO && value != PT_GEOM_LDS && value != PT_GEOM_SCALAR && value != PT_GEOM_BVH &&
         value != PT_GEOM_GRID && value != PT_GEOM_SMALL)
       return fail(c, PT_ERR_INVALID, "pt_set_option: bad geometry path %d", value);
-    c->geom_policy = value;
+    c->geom.policy = value;
     return PT_OK;
   }
   if (key == PT_OPT_COUNT_WORK) { // measuring twin of the walk kernels (PtStats.work); slower, never timed
@@ -1729,24 +1641,16 @@ namespace {
 // hipGraph (its arguments hold the old grid's numbers).  Whether the grid in place still fits is host arithmetic on the
 // uniforms (grid_fit_state: PtStats.grid_fit_stale, pt_grid_fit): pt_set_params never rebuilds — a rebuild synchronises the
 // stream and moves device buffers.
-bool grid_in_use(const pt_ctx* c) {  // can the grid be what the next launch walks?
-  if (!c->have_grid) return false;
-  if (c->geom_policy == PT_GEOM_GRID) return true;
-  return c->geom_policy == PT_GEOM_AUTO && (c->geom_tuned == 0 || c->geom_tuned == PT_GEOM_GRID);
-}
-
-constexpr double kDefaultNearFactor = 3.0;  // what pt_set_spheres builds for: rays that start within 2 s0 of the scene's middle
-
-int grid_fit_state(const pt_ctx* c) {
-  if (!grid_in_use(c) || !c->have_params) return 0;
-  const double need = view_need_factor(c);
-  if (need <= 0.0) return 0;
-  const double have = (double)c->grid.near_factor;
-  if (have < need - 1e-6) return 1;  // the camera stands outside the near region: every primary ray takes the far path
-  // looser than needed — measured against the default class, not against a class BELOW it: whether 2.5 s0 beats 3 s0 depends on
-  // where BOUNCE rays start (a camera that sees the ground out to the horizon sends them back from beyond any near region),
-  // which only a measurement knows (pt_tune); a refit never goes below the default
-  return have > std::max(need, kDefaultNearFactor) + 1e-6 ? 2 : 0;
+// (the decisions: pt_geom_plan.hpp)
+// May the grid be rebuilt for the view at all: there is one, with uniforms and the host copies it is built from, no launch
+// captured into a caller's hipGraph holds its numbers, and no A/B build fixes its factor (PT_GRID_DNEAR, PT_DEV_KNOBS builds only:
+// pt_grid.hpp builds every grid for it)?
+bool grid_refittable(const pt_ctx* c) {
+  if (!c->have_grid || !c->have_params || c->captured || c->h_geom.empty()) return false;
+#ifdef PT_DEV_KNOBS
+  if (getenv("PT_GRID_DNEAR")) return false;  // (the A/B build's own factor stands)
+#endif
+  return true;
 }
 
 // replace the grid in place by one built for d_near = factor * s0 (the caller has decided that it should be)
@@ -1756,66 +1660,40 @@ int rebuild_grid(pt_ctx* c, double factor, bool keep_tuned) {
   if (!build_grid(c->h_geom.data(), c->h_radii.data(), n, factor, &grid)) return PT_OK;  // (no grid for that factor: the one in place stays)
   PT_HIP(c, hipSetDevice(c->device));
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight read the grid in place
-  const int tuned = c->geom_tuned;
+  const int tuned = c->geom.tuned;
   int rc = install_grid(c, grid, c->h_mat.data(), n);
   c->epoch++;
-  list_paths(c);  // (which kernels the grid can feed, and whether PT_GEOM_AUTO has anything to measure, follow its size — or its absence, had the upload failed)
-  if (keep_tuned && rc == PT_OK && tuned == PT_GEOM_GRID && c->have_grid) c->geom_tuned = tuned;  // a refit keeps the settled choice
+  c->geom.list_paths(path_scene(c));  // (which kernels the grid can feed, and whether PT_GEOM_AUTO has anything to measure, follow its size — or its absence, had the upload failed)
+  if (keep_tuned && rc == PT_OK && tuned == PT_GEOM_GRID && c->have_grid) c->geom.tuned = tuned;  // a refit keeps the settled choice
   return rc;
 }
 
-// policy: 0 = rebuild whenever another class fits better, 1 = only when the class in place is too SMALL (pt_refit_grid: never below
-// the default class either way)
+// policy: 0 = rebuild whenever another class fits better, 1 = only when the class in place is too SMALL (refit_factor)
 int fit_grid_to_view(pt_ctx* c, int policy) {
-  if (!c->have_grid || !c->have_params || c->captured || c->h_geom.empty()) return PT_OK;
-  if (!grid_in_use(c)) return PT_OK;  // (a forced list / hierarchy walk never reads the grid: no rebuild, no stream synchronisation)
-  const int state = grid_fit_state(c);
-  if (state == 0 || (policy == 1 && state != 1)) return PT_OK;
-#ifdef PT_DEV_KNOBS
-  if (getenv("PT_GRID_DNEAR")) return PT_OK;  // (the A/B build's own factor stands)
-#endif
-  return rebuild_grid(c, std::max(view_need_factor(c), kDefaultNearFactor), true);
+  if (!grid_refittable(c)) return PT_OK;
+  const double factor = refit_factor(policy, fit_state(c), need_factor(c));
+  return factor > 0.0 ? rebuild_grid(c, factor, true) : PT_OK;
 }
 
-// pt_tune's part (i).  The smallest class that covers the CAMERA is a lower bound, not the answer: bounce rays start wherever the
-// camera's rays end, and those that start on an always-tested giant (the ground under a field) beyond the near region and come
-// back into the grid's box take the far path — one of them costs what hundreds of walked segments cost (the literal loop over
-// the list for one lane, or the whole wave 64 spheres at a time).  Measured on a 1 500-sphere field, camera inside it looking
-// across: the grid for 2.5 s0 renders the frame in 1.8 ms, the one for 3 s0 in 0.9 (profiles/r06_ab_runs.txt); on config 5
-// (camera above the field looking down) 2.5 s0 is 3 % faster.  So pt_tune MEASURES (PT_OPT_GRID_FIT 0, the default): one timed
-// launch of n_passes passes per candidate — the class the camera needs, the default class when that is smaller, and up to two
-// classes wider while the launch's own far-ray tally says such rays matter and a wider class keeps winning — and the fastest
-// stays.  PT_OPT_GRID_FIT 1: the class the camera needs, unmeasured (no launches here).
+// pt_tune's part (i): the grid's margin class (GridClassSearch) and build
 int tune_grid_to_view(pt_ctx* c, uint32_t n_passes, bool* launched) {
   *launched = false;
-  if (!c->have_grid || !c->have_params || c->captured || c->h_geom.empty()) return PT_OK;
-  bool grid_tried = c->geom_policy == PT_GEOM_GRID;
-  if (c->geom_policy == PT_GEOM_AUTO)
-    for (int k = 0; k < c->n_trials; k++) grid_tried = grid_tried || c->trial_paths[k] == PT_GEOM_GRID;
-  if (!grid_tried) return PT_OK;
-#ifdef PT_DEV_KNOBS
-  if (getenv("PT_GRID_DNEAR")) return PT_OK;
-#endif
-  const double need = view_need_factor(c);
+  if (!grid_refittable(c) || !c->geom.grid_tried()) return PT_OK;
+  const double need = need_factor(c);
   if (need <= 0.0) return PT_OK;
-  auto at = [&](double f) { return std::fabs(f - (double)c->grid.near_factor) < 1e-6; };
-  if (c->grid_fit_mode == 1 || n_passes > c->reserved_passes) {  // unmeasured: the class the camera needs
+  auto at = [&](double f) { return same_class(f, (double)c->grid.near_factor); };
+  if (grid_class_unmeasured(c->grid_fit_mode, n_passes, c->reserved_passes)) {  // the class the camera needs
     return at(need) ? PT_OK : rebuild_grid(c, need, false);
   }
-  // one timed launch through the grid walk on the grid in place: kernel time from the launch's events, far share from its tallies
-  const int policy_kept = c->geom_policy;
-  struct Probe { double factor, ms, far_share; };
-  std::vector<Probe> probes;
-  // How long a timed launch has to be: long enough to rank grids that differ by 2 % (the device's launch-to-launch spread is
-  // ~0.5 %), no longer — pt_tune is part of a first frame.  The COLD launch (code load, tile order: never a measurement) is ONE
-  // pass and doubles as the yardstick: the timed launches get as many passes as make ~4 ms, at most four and at most n_passes
-  // (config 2: 2 passes, configs 3 and 5: 1; round 6's first version timed 4 passes whatever their length: 27 / 90 / 130 ms)
-  const uint32_t n_most = n_passes < 4u ? n_passes : 4u;
-  uint32_t n_timed = n_most;
-  auto measure = [&](double f, bool cold) -> int {
+  // one timed launch of n_timed passes through the grid walk on the grid built for `f`, after a cold one of one pass (the
+  // `yardstick` of timed_passes): kernel time from the launch's events, far share from its tallies.  `*probe` stays empty when no
+  // grid could be built for f.
+  const int policy_kept = c->geom.policy;
+  uint32_t n_timed = timed_passes(-1.0, n_passes);
+  auto measure = [&](double f, bool cold, bool yardstick, std::optional<ClassProbe>* probe) -> int {
     if (!at(f)) { int rc = rebuild_grid(c, f, false); if (rc != PT_OK) return rc; }
     if (!c->have_grid || !at(f)) return PT_OK;  // (no grid for that class: not a candidate)
-    c->geom_policy = PT_GEOM_GRID;
+    c->geom.policy = PT_GEOM_GRID;
     int rc = PT_OK;
     for (int k = cold ? 0 : 1; k < 2 && rc == PT_OK; k++) {
       unsigned long long before[PT_CTR_SCRATCH], after[PT_CTR_SCRATCH];
@@ -1829,50 +1707,32 @@ int tune_grid_to_view(pt_ctx* c, uint32_t n_passes, bool* launched) {
       if (rc != PT_OK) break;
       if (hipMemcpy(after, c->d_counters.get(), sizeof after, hipMemcpyDeviceToHost) != hipSuccess) { rc = PT_ERR_HIP; break; }
       const double ms = c->kernel_ms - ms0;
-      if (k == 0 && probes.empty()) {  // the yardstick (an over-estimate: it carries the code load — so the timed launches come out shorter, never longer)
-        const double want = ms > 0.0 ? std::ceil(4.0 / ms) : (double)n_most;
-        n_timed = want < 1.0 ? 1u : (want > (double)n_most ? n_most : (uint32_t)want);
+      if (k == 0 && yardstick) {
+        n_timed = timed_passes(ms, n_passes);
       } else if (k == 1) {
         const double seg = (double)(after[PT_CTR_SEGMENTS] - before[PT_CTR_SEGMENTS]);
-        probes.push_back({f, ms, seg > 0 ? (double)(after[PT_CTR_FAR_RAYS] - before[PT_CTR_FAR_RAYS]) / seg : 0.0});
+        *probe = ClassProbe{f, ms, seg > 0 ? (double)(after[PT_CTR_FAR_RAYS] - before[PT_CTR_FAR_RAYS]) / seg : 0.0};
       }
     }
-    c->geom_policy = policy_kept;
+    c->geom.policy = policy_kept;
     *launched = true;
     return rc == PT_ERR_HIP ? fail(c, PT_ERR_HIP, "pt_tune: a HIP call failed while timing a grid class") : rc;
   };
-  int rc = measure(need, true);
-  if (rc != PT_OK) return rc;
-  if (need < kDefaultNearFactor) { rc = measure(kDefaultNearFactor, false); if (rc != PT_OK) return rc; }
-  auto best = [&]() { size_t b = 0; for (size_t k = 1; k < probes.size(); k++) if (probes[k].ms < probes[b].ms) b = k; return b; };
-  for (int widened = 0; widened < 2 && !probes.empty(); widened++) {
-    const Probe& b = probes[best()];
-    if (b.far_share < 2e-5) break;  // (practically no ray takes the far path: a wider class only adds copies)
-    double next = 0.0;
-    for (double f : kNearFactors) {
-      bool seen = false;
-      for (const Probe& q : probes) seen = seen || std::fabs(q.factor - f) < 1e-6;
-      if (f > b.factor + 1e-6 && !seen) { next = f; break; }
-    }
-    if (next == 0.0) break;
-    const size_t n_before = probes.size();
-    rc = measure(next, false);
-    if (rc != PT_OK) return rc;
-    if (probes.size() == n_before || probes[best()].factor != next) break;  // (no grid for it, or not faster: stop widening)
+  GridClassSearch search(need);
+  for (GridClassSearch::Step step = search.next(); step.factor != 0.0; step = search.next()) {
+    std::optional<ClassProbe> probe;
+    if (int rc = measure(step.factor, step.cold, step.cold, &probe); rc != PT_OK) return rc;
+    search.report(probe);
   }
-  if (probes.empty()) return PT_OK;
-  const double keep = probes[best()].factor;
-  const double keep_ms = probes[best()].ms;
-  if (!at(keep)) { rc = rebuild_grid(c, keep, false); if (rc != PT_OK) return rc; }
-  // ... and WHICH BUILD walks it (grid_build_kind): where the staged entries take more than 16 KB of the LDS — fewer workgroups per
-  // CU — the build that gathers them from L2 is timed against the LDS-staged one, and kept when it is at least 2 % faster
+  if (!search.kept()) return PT_OK;
+  const double keep = search.keep();
+  if (!at(keep)) { int rc = rebuild_grid(c, keep, false); if (rc != PT_OK) return rc; }
   c->grid_cells_build = false;
-  if (c->have_grid && at(keep) && (size_t)c->grid.n_entries * 16 > (size_t)16384 && grid_build_kind(c, walk_lds_room()) == 1) {
+  if (c->have_grid && at(keep) && cells_build_worth_timing(c->grid.n_entries, grid_build(c).kind)) {
     c->grid_cells_build = true;
-    const size_t n_before = probes.size();
-    rc = measure(keep, true);  // (cold first: another kernel, its code object's first use)
-    if (rc != PT_OK) { c->grid_cells_build = false; return rc; }
-    if (probes.size() == n_before || probes.back().ms > 0.98 * keep_ms) c->grid_cells_build = false;
+    std::optional<ClassProbe> probe;
+    if (int rc = measure(keep, true, false, &probe); rc != PT_OK) { c->grid_cells_build = false; return rc; }
+    c->grid_cells_build = keep_cells_build(probe, search.keep_ms());
     c->epoch++;
   }
   return PT_OK;
@@ -1888,7 +1748,7 @@ PT_API int pt_refit_grid(pt_ctx* c, int only_if_stale) {
 
 PT_API int pt_grid_fit(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
-  return grid_fit_state(c);
+  return fit_state(c);
 }
 
 PT_API int pt_tune(pt_ctx* c, uint32_t n_passes) {
@@ -1898,11 +1758,10 @@ PT_API int pt_tune(pt_ctx* c, uint32_t n_passes) {
     int rc = tune_grid_to_view(c, n_passes, &launched);
     if (rc != PT_OK) return rc;
   }
-  if (c->geom_policy != PT_GEOM_AUTO || !c->have_spheres || c->n_trials < 2) // no path to decide
+  if (!c->have_spheres || !c->geom.has_path_to_decide())
     return launched ? pt_reset_accum(c) : PT_OK;
-  c->geom_tuned = 0;
-  c->trial_state = 0;
-  for (int k = 0; k < 1 + c->n_trials; k++) {
+  c->geom.reset();
+  for (int k = 0; k < 1 + c->geom.n_paths; k++) {
     int rc = pt_render_passes(c, n_passes);
     if (rc != PT_OK) return rc;
   }

@@ -1,7 +1,7 @@
 """GPU parity at the rim of every margin class of the grid walk (PT_GEOM_GRID).
 
 pt_tune and pt_refit_grid rebuild the grid for the margin class d_near / s0 in {2.5, 3, 4, 5.5, 8, 12, 16} that the camera
-needs (csrc/pt_api.hip kNearFactors, view_need_factor); the registration margin grows with d_near^2 (csrc/pt_grid.hpp).
+needs (csrc/pt_geom_plan.hpp kNearFactors, view_need_factor); the registration margin grows with d_near^2 (csrc/pt_grid.hpp).
 For each class and each of the three builds of the grid kernel (PtStats.grid_kernel_build: 1 cells and entries staged in
 the LDS, 2 entries gathered from L2, 3 nothing staged) three cameras render the same scene:
   A  where the class is the one the camera needs (tune(1), unmeasured: set_grid_fit(True)),
@@ -36,7 +36,7 @@ def assert_bit_equal(got, ref, what):
 
 
 def need_factor(rho, s0):
-    """view_need_factor (csrc/pt_api.hip) for a camera without a lens at distance rho from c0"""
+    """view_need_factor (csrc/pt_geom_plan.hpp) for a camera without a lens at distance rho from c0"""
     need = ((rho / 0.9999 + s0) / s0) * 1.01
     return next((f for f in CLASSES if f >= need), CLASSES[-1])
 
