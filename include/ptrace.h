@@ -234,7 +234,9 @@ typedef struct PtStats {
                                3 nothing staged (…_grid_gmem), 0 no grid.  What fits is staged — except while grid_fit_stale is 1
                                (the builds that gather hand a far ray to the whole wave: a stale view costs 4 x, not 16 x) and
                                where pt_tune timed the gathering build faster.  Scheduling only.                       */
-  uint32_t _pad2;
+  uint32_t grid_walk_flat;  /* 1: that launch is build 1 on a grid of ONE layer of cells along y (grid_cells[1] == 1) and runs the
+                               two-axis walk, pt_trace_kernel_grid; 0 with build 1: pt_trace_kernel_grid_layers, three axes.  (Took
+                               the place of a padding word: the struct's size and the other offsets are unchanged.)  */
 } PtStats;
 
 typedef struct pt_ctx pt_ctx;

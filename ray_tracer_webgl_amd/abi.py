@@ -150,7 +150,7 @@ class PtStats(C.Structure):
         ("grid_need_factor", C.c_float),
         ("far_rays", C.c_uint64),
         ("grid_kernel_build", C.c_uint32),  # 1 pt_trace_kernel_grid (all staged in the LDS) / 2 _grid_cells / 3 _grid_gmem / 0 no grid
-        ("_pad2", C.c_uint32),
+        ("grid_walk_flat", C.c_uint32),  # 1: build 1 on a one-layer grid, the two-axis walk (pt_trace_kernel_grid); 0 with build 1: _grid_layers
     ]
 
 

@@ -390,8 +390,10 @@ const void* extra_kernel(int device, int id) {
 // their kernels is first launched, so their handles are taken when an entry is chosen, not here.  Where a way to read the
 // list has no roulette build or no measuring twin, its column holds the plain build, which then runs.
 struct TraceKernel { const void* main; int extra, small, waves; };
-// ROW_SMALL + list length % 4; ROW_BVH / ROW_GRID + what is staged in the LDS (bind_hierarchy, bind_grid)
-enum TraceRow { ROW_LIST_LDS, ROW_SCALAR, ROW_SCALAR_NOLDS, ROW_SMALL, ROW_BVH = ROW_SMALL + 4, ROW_GRID = ROW_BVH + 3, ROW_COUNT = ROW_GRID + 3 };
+// ROW_SMALL + list length % 4; ROW_BVH / ROW_GRID + what is staged in the LDS (bind_hierarchy, bind_grid); ROW_GRID itself is
+// the LDS-staged build on a grid of one layer along y, ROW_GRID_LAYERS the same build on any other grid (grid_walk_flat)
+enum TraceRow { ROW_LIST_LDS, ROW_SCALAR, ROW_SCALAR_NOLDS, ROW_SMALL, ROW_BVH = ROW_SMALL + 4, ROW_GRID = ROW_BVH + 3, ROW_GRID_LAYERS = ROW_GRID + 3,
+                ROW_COUNT };
 enum TraceBuild { BUILD_PLAIN, BUILD_RR, BUILD_TWIN, BUILD_COUNT };
 
 template <class K>
@@ -414,6 +416,8 @@ const TraceKernel kTraceKernels[ROW_COUNT][BUILD_COUNT] = {
     {in_main(pt_trace_kernel_grid, PT_WAVES_WALK),          in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_COUNT)},
     {in_main(pt_trace_kernel_grid_cells, PT_WAVES_WALK),    in_extra(PT_X_GRID_CELLS_RR),                    in_extra(PT_X_GRID_CELLS_COUNT, PT_WAVES_TWIN_CELLS)},
     {in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),     in_extra(PT_X_GRID_GMEM_RR),                     in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK)},
+    // (the roulette build walks three axes on a one-layer grid too — right on any grid, and not measured: one build serves both rows)
+    {in_main(pt_trace_kernel_grid_layers, PT_WAVES_WALK),   in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_LAYERS_COUNT)},
 };
 
 inline uint32_t grid_for(uint32_t n, uint32_t block, uint32_t cap) {
@@ -1052,6 +1056,7 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
     const Staging st = path == PT_GEOM_BVH ? bind_hierarchy(c, A) : bind_grid(c, A);
     scene = st.bytes;
     row = path == PT_GEOM_BVH ? ROW_BVH + st.kind : ROW_GRID + st.kind - 1;
+    if (path == PT_GEOM_GRID && st.kind == 1 && !grid_walk_flat(st.kind, c->grid.n[1])) row = ROW_GRID_LAYERS;
     A.lds_scene_bytes = (uint32_t)scene;
   } else {
     // the LDS copy exists whenever the list fits; the scalar and small-list walks only change how the
@@ -1581,6 +1586,7 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
     out->grid_need_factor = (float)need_factor(c);
     out->grid_fit_stale = (uint32_t)fit_state(c);
     out->grid_kernel_build = (uint32_t)grid_build(c).kind;
+    out->grid_walk_flat = grid_walk_flat((int)out->grid_kernel_build, c->grid.n[1]) ? 1u : 0u;
   }
   if (c->have_bvh) {
     out->bvh_nodes = c->bvh_n_nodes;

@@ -198,6 +198,12 @@ inline Staging grid_staging(uint64_t n_cells, uint32_t n_entries, size_t lds_roo
   return need_cells <= lds_room ? Staging{2, need_cells} : Staging{3, 0};
 }
 
+// Which WALK the LDS-staged build runs: a grid of one layer of cells along y (pt_grid.hpp collapses a flat axis: a field on a
+// ground, configs 2 and 3) gets the two-axis walk of pt_grid_walk.hpp — pt_trace_kernel_grid —, a grid of several layers the
+// three-axis one — pt_trace_kernel_grid_layers; both are build 1.  The builds that gather (2, 3) walk three axes whatever the
+// grid: no flat scene large enough for them is measured.  The same cells' entries, the same tests, the same bits.
+inline bool grid_walk_flat(int build_kind, uint32_t n_layers_y) { return build_kind == 1 && n_layers_y == 1u; }
+
 // the hierarchy: 0 = nodes and slots staged, 1 = the nodes, 2 = nothing
 inline Staging hierarchy_staging(uint32_t n_nodes, uint32_t n_slots, size_t lds_room) {
   const size_t need_all = PT_BVH_LDS_BYTES32(n_nodes, n_slots);

@@ -18,6 +18,23 @@
 // (pt_kernels.hip).
 // Host-side check of the claim (registration invariant, the bound, a numpy emulation of this walk
 // against brute force): tests/test_grid.py.
+//
+// THE ONE-LAYER WALK (S::FLAT_Y: a grid with n[1] == 1, the LDS-staged build).  pt_grid.hpp collapses a flat axis to
+// one layer of cells (a field of spheres on a ground), and in one layer y is not an axis to step along: the first y
+// crossing of the three-axis walk leaves the grid.  The time of that crossing is a constant of the ray, so the walk is
+// a two-axis DDA over x and z that ends when that constant is the smallest of the three times — the same tie order (x
+// before y before z), the same `tmx` / `tmz` sequences (they never depended on y), hence the same cells in the same
+// order.  Which plane the constant is taken from: the box test's own far y plane, max(t1y, t2y), i.e. the slab
+// [grid_lo_n[1], grid_hi_n[1]] that the host has WIDENED (lo_n <= lo, hi_n >= hi >= fl(lo + h): pt_grid.hpp), not the
+// cell's far plane lo + (0 or 1) h of the three-axis walk.  It costs nothing (the box test has computed it; an entering
+// ray is a near ray, mm == 0, and tn <= tf <= max(t1y, t2y), so the clamp to the entry time is implied), and fma is
+// monotone in the plane, so this exit time is never EARLIER than the three-axis walk's: every `tmin` that was smaller
+// than the old y time is still chosen, bit for bit, and where the old walk ended on y the flat one ends there too or
+// goes on through further cells of the same layer with exit times >= the old one.  Later, never earlier: the argument
+// above only needs that every cell the ray passes through is looked at and that a walk stops no sooner than `closest <
+// t_exit` allows; cells looked at in addition change nothing (every entry looked at runs the literal test, acceptance
+// is order-free).  The images are the same bits.  tests/test_grid_flat.py emulates both walks: identical cells and exit
+// times with the unwidened planes, a prefix-and-later relation with the widened ones.
 #pragma once
 #include "pt_scene.hpp"
 
@@ -128,11 +145,17 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
   const float iy = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.y), -1e18f, 1e18f);
   const float iz = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d.z), -1e18f, 1e18f);
   const bool posx = ix > 0.0f, posy = iy > 0.0f, posz = iz > 0.0f;
-  const float tdx = K.grid_h[0] * __builtin_fabsf(ix), tdy = K.grid_h[1] * __builtin_fabsf(iy),
-              tdz = K.grid_h[2] * __builtin_fabsf(iz);
-  const int gnx = (int)K.grid_n[0], gny = (int)K.grid_n[1], gnz = (int)K.grid_n[2];
+  const float tdx = K.grid_h[0] * __builtin_fabsf(ix), tdz = K.grid_h[2] * __builtin_fabsf(iz);
+  const int gnx = (int)K.grid_n[0], gnz = (int)K.grid_n[2];
   const int sdx = posx ? 1 : -1;
-  const int sdy = posy ? gnx : -gnx;
+  // (one layer: no y step; its time is a constant of the ray and a z step is a row of gnx cells)
+  float tdy = 0.0f;
+  int gny = 1, sdy = 0;
+  if constexpr (!S::FLAT_Y) {
+    tdy = K.grid_h[1] * __builtin_fabsf(iy);
+    gny = (int)K.grid_n[1];
+    sdy = posy ? gnx : -gnx;
+  }
   const int sdz = posz ? gnx * gny : -(gnx * gny);
 
   // entry: where does the half-line meet the grid's box?
@@ -172,6 +195,29 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
       hit_pos = 0xffffffffu;
       enter = false;
     }
+    if constexpr (S::FLAT_Y) {
+      if (enter) {
+        tally.flag(PT_REG_WALK_ENTER_CELL);
+        // the x and z of the cell that holds the entry point, as below; the ray leaves the layer through the box test's
+        // own far y plane (file header): never before the entry time, and constant for the whole walk
+        const float glx = K.grid_lo[0], glz = K.grid_lo[2];
+        const float ghx = K.grid_h[0], ghz = K.grid_h[2];
+        const float fx = (fma_(d.x, tn, o.x) - glx) * K.grid_inv_h[0];
+        const float fz = (fma_(d.z, tn, o.z) - glz) * K.grid_inv_h[2];
+        const int nx1 = gnx - 1, nz1 = gnz - 1;
+        int cx = (int)__builtin_floorf(fx), cz = (int)__builtin_floorf(fz);
+        cx = cx < 0 ? 0 : (cx > nx1 ? nx1 : cx);
+        cz = cz < 0 ? 0 : (cz > nz1 ? nz1 : cz);
+        const float bx = fma_((float)(cx + (posx ? 1 : 0)), ghx, glx);
+        const float bz = fma_((float)(cz + (posz ? 1 : 0)), ghz, glz);
+        tmx = __builtin_fmaxf(fma_(bx, ix, -oix), tn);
+        tmy = __builtin_fmaxf(t1y, t2y);
+        tmz = __builtin_fmaxf(fma_(bz, iz, -oiz), tn);
+        // steps left before the walk leaves the grid, + 1: the x and z fields of the three-axis walk
+        rem = (uint32_t)((posx ? nx1 - cx : cx) + 1) | ((uint32_t)((posz ? nz1 - cz : cz) + 1) << 20);
+        cell = (uint32_t)cz * (uint32_t)gnx + (uint32_t)cx;
+      }
+    } else
     if (enter) {
       tally.flag(PT_REG_WALK_ENTER_CELL);
       // the cell that holds the entry point (clamped: rounding may put it a hair outside)
@@ -214,7 +260,26 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
     // branch is a ~30-tick bubble in its wave (tools/micro/valu_chain.hip) — the loop as the compiler lays it out takes
     // three (entry, back-edge, exit) for its one trip, this form none: config 2 -0.8 %, a band of eight -1.4 %, config 5
     // -1.2 % (profiles/r04_ab_runs.txt).
-#define PT_CELL_STEP \
+    // (one layer: x steps when its time is the smallest; otherwise z steps — unless the ray's exit from the layer is the
+    // smallest, which ends the walk exactly as running out of the y field does in the three-axis step)
+#define PT_CELL_STEP_FLAT \
+        tally.walk(m_mv); \
+        if (rem != 0u && pend < 0x1000000u) { \
+          const uint32_t rec = S::cell_at(A, cell); \
+          const float tmin = __builtin_fminf(__builtin_fminf(tmx, tmy), tmz); \
+          const bool isx = tmx == tmin; \
+          const bool endy = !isx && tmy == tmin; \
+          t_exit = tmin; \
+          pend = rec; \
+          tmx += isx ? tdx : 0.0f; \
+          tmz += isx ? 0.0f : tdz; \
+          const uint32_t dec = isx ? 1u : 1048576u; \
+          rem -= dec; \
+          const bool out = (rem & (dec * 1023u)) == 0u; \
+          cell += (uint32_t)(isx ? sdx : sdz); \
+          rem = (out || endy || ((rec >> 24) == 0u && closest < tmin)) ? 0u : rem; \
+        }
+#define PT_CELL_STEP_XYZ \
         tally.walk(m_mv); \
         if (rem != 0u && pend < 0x1000000u) { \
           const uint32_t rec = S::cell_at(A, cell); \
@@ -233,6 +298,8 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
           cell += (uint32_t)(isx ? sdx : (isy ? sdy : sdz)); \
           rem = (out || ((rec >> 24) == 0u && closest < tmin)) ? 0u : rem; \
         }
+#define PT_CELL_STEP \
+        if constexpr (S::FLAT_Y) { PT_CELL_STEP_FLAT } else { PT_CELL_STEP_XYZ }
     if (m_mv != 0ull) {
       tally.walk_first();
       PT_CELL_STEP
@@ -243,6 +310,8 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
       }
     }
 #undef PT_CELL_STEP
+#undef PT_CELL_STEP_FLAT
+#undef PT_CELL_STEP_XYZ
     tally.phase(4);
     const bool has = (pend >> 24) != 0u;
     const unsigned long long m_has = pt_ballot(has);

@@ -68,7 +68,13 @@ extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void p
   pt_trace_body<false, false, 3>(A);
 }
 // the grid walk (PT_GEOM_GRID): cells + entries staged in LDS, cells only, or nothing
+// (cells + entries staged: pt_trace_kernel_grid walks a grid of ONE layer along y with the two-axis walk of pt_grid_walk.hpp
+// — the common large scene, a field on a ground —, pt_trace_kernel_grid_layers any other with the three-axis walk; the host
+// chooses by grid_n[1], pt_geom_plan.hpp grid_walk_flat)
 extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_grid(const PtKernelArgs A) {
+  pt_trace_body<false, false, 4, false, false, -1, true>(A);
+}
+extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_grid_layers(const PtKernelArgs A) {
   pt_trace_body<false, false, 4>(A);
 }
 extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_grid_cells(const PtKernelArgs A) {

@@ -2,7 +2,7 @@
 // code object) of their own: the Russian-roulette kernels (PT_OPT_RUSSIAN_ROULETTE, pt_shade.hpp) and the
 // measuring twins (PT_OPT_COUNT_WORK: the same bodies with the executed-work tallies and the phase clock
 // live).  The HIP runtime loads a code object when one of its kernels is first asked for, so a context that
-// never turns these options on never pays for the sixteen kernels in here (round 3: one 557 KB code object
+// never turns these options on never pays for the seventeen kernels in here (round 3: one 557 KB code object
 // with 22 instantiations of the body, loaded by every context's first launch).  pt_api.hip reaches them
 // through pt_extra_kernel() only.
 #include "pt_trace_body.hpp"
@@ -12,7 +12,11 @@
 extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_bvh_count(const PtKernelArgs A) {
   pt_trace_body<false, false, 1, true>(A);
 }
+// (each the same walk as the kernel it measures: one layer / several layers, pt_kernels.hip)
 extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_grid_count(const PtKernelArgs A) {
+  pt_trace_body<false, false, 4, true, false, -1, true>(A);
+}
+extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_grid_layers_count(const PtKernelArgs A) {
   pt_trace_body<false, false, 4, true>(A);
 }
 extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_TWIN_CELLS) void pt_trace_kernel_grid_cells_count(const PtKernelArgs A) {
@@ -67,6 +71,7 @@ extern "C" const void* pt_extra_kernel(int id) {
   switch (id) {
     case PT_X_BVH_COUNT: return reinterpret_cast<const void*>(pt_trace_kernel_bvh_count);
     case PT_X_GRID_COUNT: return reinterpret_cast<const void*>(pt_trace_kernel_grid_count);
+    case PT_X_GRID_LAYERS_COUNT: return reinterpret_cast<const void*>(pt_trace_kernel_grid_layers_count);
     case PT_X_GRID_CELLS_COUNT: return reinterpret_cast<const void*>(pt_trace_kernel_grid_cells_count);
     case PT_X_SMALL_COUNT: return reinterpret_cast<const void*>(pt_trace_kernel_small_count);
     case PT_X_SMALL_RR + 0: return reinterpret_cast<const void*>(pt_trace_kernel_small_t0_rr);

@@ -109,12 +109,17 @@ struct GridWalk {  // boundary-crossing times, linear cell index, steps left per
 //                7     no structure, the LDS copy only for per-lane gathers: a list of at most 16 spheres (the reference's
 //                      u_sphere_list[15], static/shader.frag:103) tested group by group from SGPRs.
 //              List-order reads (tail mode, PHASE 3, shading) go to the global copy.
-template <bool SCAN_LDS_, bool HAVE_LDS_, int WALK_, int TAIL_ = -1>
+// FLAT_Y     : the LDS-staged grid walk (WALK 4) of a grid of ONE layer of cells along y (pt_grid.hpp collapses a flat
+//              axis: a field of spheres on a ground): y is not an axis to step along, the walk is a two-axis DDA over x and z
+//              that ends when the ray leaves the layer (pt_grid_walk.hpp).  The host launches it only on such a grid.
+template <bool SCAN_LDS_, bool HAVE_LDS_, int WALK_, int TAIL_ = -1, bool FLAT_Y_ = false>
 struct Scene {
   static constexpr bool SCAN_LDS = SCAN_LDS_, HAVE_LDS = HAVE_LDS_;
   static constexpr int WALK = WALK_;
   static constexpr bool BVH = WALK >= 1 && WALK <= 3;
   static constexpr bool GRID = WALK >= 4 && WALK <= 6;
+  static constexpr bool FLAT_Y = FLAT_Y_;
+  static_assert(!FLAT_Y_ || WALK_ == 4, "the one-layer walk exists for the LDS-staged grid build");
   static constexpr bool SMALL = WALK == 7;   // at most 16 spheres, tested straight from SGPRs (pt_list.hpp small_scan)
   // small-list builds: the list holds 4 q + SMALL_TAIL spheres (0 .. 3: the build for that remainder, pt_kernels_small.hip);
   // -1: any length, the last group's padding tested and masked (the opt-in builds of pt_kernels_extra.hip)

@@ -20,12 +20,13 @@ using namespace ptd;
 // --------------------------------------------------------------------------------------------
 // The path-tracing kernel body: one persistent wave working through (pixel, pass) items.
 // Template parameters: pt_scene.hpp `Scene`; COUNT = the measuring twin (tallies live); RR = the
-// opt-in Russian-roulette build (pt_shade.hpp); TAIL = the small-list builds' list remainder (pt_scene.hpp SMALL_TAIL).
+// opt-in Russian-roulette build (pt_shade.hpp); TAIL = the small-list builds' list remainder (pt_scene.hpp SMALL_TAIL);
+// FLAT_Y = the grid walk of a one-layer grid (pt_scene.hpp, pt_grid_walk.hpp).
 // --------------------------------------------------------------------------------------------
-template <bool SCAN_LDS, bool HAVE_LDS, int WALK = 0, bool COUNT = false, bool RR = false, int TAIL = -1>
+template <bool SCAN_LDS, bool HAVE_LDS, int WALK = 0, bool COUNT = false, bool RR = false, int TAIL = -1, bool FLAT_Y = false>
 __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
   using namespace ptk;
-  using S = Scene<SCAN_LDS, HAVE_LDS, WALK, TAIL>;
+  using S = Scene<SCAN_LDS, HAVE_LDS, WALK, TAIL, FLAT_Y>;
   S::stage(A);
 
   Path p;           // per lane

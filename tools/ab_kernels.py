@@ -40,6 +40,7 @@ def child():
              ("c2bvh", scenes.config2(1920, 1080, 16, 64, 50), 64, abi.PT_GEOM_BVH, 2),
              ("c2scalar", scenes.config2(1920, 1080, 16, 16, 50), 16, abi.PT_GEOM_SCALAR, 2),
              ("c2band8", scenes.config2(1920, 1080, 16, 8, 50), 8, abi.PT_GEOM_GRID, 3),
+             ("c3grid", scenes.config3(3840, 2160, 64, 16, 50), 16, abi.PT_GEOM_GRID, 3),  # (config 3's scene and size, 1024 spp in one launch)
              ("c4scalar", scenes.config4(1024, 1024, 64, 8, 50), 8, abi.PT_GEOM_SCALAR, 2),
              ("c4lds", scenes.config4(1024, 1024, 64, 8, 50), 8, abi.PT_GEOM_LDS, 2),
              ("c5grid", scenes.config5(1920, 1080, 64, 4, 50), 4, abi.PT_GEOM_GRID, 3),
