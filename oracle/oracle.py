@@ -66,6 +66,11 @@ def load():
     L.ora_render_pass.argtypes = [sp, C.c_uint32, pp, C.c_float, fp] + [C.c_uint32] * 5
     L.ora_render_passes.restype = C.c_uint64
     L.ora_render_passes.argtypes = [sp, C.c_uint32, pp, C.c_uint32, fp] + [C.c_uint32] * 5
+    L.ora_render_passes_rr.restype = C.c_uint64
+    L.ora_render_passes_rr.argtypes = [sp, C.c_uint32, pp, C.c_uint32, fp] + [C.c_uint32] * 5 + [C.c_int32]
+    L.ora_ray_color_rr.argtypes = [sp, C.c_uint32, pp, fp, fp, fp, fp, C.POINTER(C.c_uint64), C.c_int32]
+    L.ora_roulette_step.restype = C.c_int
+    L.ora_roulette_step.argtypes = [fp, fp]
     L.ora_resolve.argtypes = [fp, C.c_size_t, C.c_uint32, C.c_int, fp]
     L.ora_resolve_rgba8.argtypes = [fp, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p]
     L.ora_blend_rgba8.argtypes = [fp, C.c_size_t, C.c_uint32, pp, C.c_void_p, C.c_void_p]
@@ -81,10 +86,11 @@ def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
 
 
-def render(spheres, params, n_passes=1, window=None, nthreads=None, accum=None):
+def render(spheres, params, n_passes=1, window=None, nthreads=None, accum=None, roulette=0):
     """Render n_passes passes (u_time = params.time + k) of the owned rows on the CPU.
 
     window = (x0, x1, y0, y1) in global pixel coordinates restricts the computed pixels.
+    roulette = k > 0: with the Russian roulette of PT_OPT_RUSSIAN_ROULETTE after k bounces (0: the shader's loop).
     Returns (accum ndarray (local_rows, width, 4) float32, segments)."""
     L = load()
     ptr, n, keep = abi.spheres_as_ctypes(spheres)
@@ -95,8 +101,9 @@ def render(spheres, params, n_passes=1, window=None, nthreads=None, accum=None):
     x0, x1, y0, y1 = window if window is not None else (0, p.width, 0, p.height)
     if nthreads is None:
         nthreads = os.cpu_count() or 1
-    seg = L.ora_render_passes(ptr, n, C.byref(p), int(n_passes), accum.ctypes.data_as(C.POINTER(C.c_float)),
-                              int(x0), int(x1), int(y0), int(y1), int(nthreads))
+    args = (ptr, n, C.byref(p), int(n_passes), accum.ctypes.data_as(C.POINTER(C.c_float)),
+            int(x0), int(x1), int(y0), int(y1), int(nthreads))
+    seg = L.ora_render_passes_rr(*args, int(roulette)) if roulette else L.ora_render_passes(*args)
     return accum, int(seg)
 
 

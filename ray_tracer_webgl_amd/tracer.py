@@ -128,7 +128,8 @@ class PathTracer:
     def set_russian_roulette(self, min_depth):
         """Opt-in perf mode (0 = off, the default): after `min_depth` bounces a path survives each further
         bounce with probability min(max(throughput), 1) and is re-weighted.  Same expectation per pixel
-        as the reference's estimator, different samples: never bit-comparable with the oracle."""
+        as the reference's estimator, different samples: bit-comparable with oracle.render(..., roulette=min_depth),
+        not with the roulette-free oracle.  A context set to PT_GEOM_LDS renders through the scalar walk meanwhile."""
         self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_RUSSIAN_ROULETTE, int(min_depth)))
 
     def set_grid_fit(self, unmeasured):

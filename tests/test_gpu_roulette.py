@@ -1,7 +1,10 @@
-"""Russian roulette (PT_OPT_RUSSIAN_ROULETTE) — the ONE mode of the product that is not bit-exact
-against the oracle, by construction: the reference never ends a path early (static/shader.frag:297-339,
+"""Russian roulette (PT_OPT_RUSSIAN_ROULETTE) — the one mode of the product that is not the reference's
+estimator sample for sample: the reference never ends a path early (static/shader.frag:297-339,
 SURVEY.md §0 F3), so this opt-in mode draws different samples.  What it must keep is every pixel's
-EXPECTATION.  Checked the way tests/test_reference_pins.py checks the oracle itself:
+EXPECTATION — this file.  (That every roulette kernel computes the roulette estimator exactly, bit for bit
+against the oracle's restatement of the step, is tests/test_gpu_roulette_exact.py; bit parity cannot say
+whether that estimator is unbiased, these checks can.)  Checked the way tests/test_reference_pins.py checks
+the oracle itself:
 
   * against RNG-free float64 expectations (tests/analytic.py): the cosine-lobe closed form for the
     first diffuse bounce, and the exhaustive reflect/refract tree of the glass sphere;

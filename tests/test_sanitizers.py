@@ -68,6 +68,12 @@ def test_oracle_and_host_code_under_asan_ubsan(tmp_path):
         O.ora_render_passes.restype = C.c_uint64
         O.ora_render_passes.argtypes = [C.POINTER(abi.PtSphere), C.c_uint32, C.POINTER(abi.PtParams), C.c_uint32, fp] + [C.c_uint32] * 5
         seg = O.ora_render_passes(sp, n, C.byref(p), 2, acc.ctypes.data_as(fp), 3, p.width - 5, 0, p.height, 3)
+        # ... and the same render with the Russian roulette of PT_OPT_RUSSIAN_ROULETTE after two bounces: fewer segments
+        O.ora_render_passes_rr.restype = C.c_uint64
+        O.ora_render_passes_rr.argtypes = O.ora_render_passes.argtypes + [C.c_int32]
+        acc_rr = np.zeros_like(acc)
+        seg_rr = O.ora_render_passes_rr(sp, n, C.byref(p), 2, acc_rr.ctypes.data_as(fp), 3, p.width - 5, 0, p.height, 3, 2)
+        assert 0 < seg_rr < seg and np.isfinite(acc_rr).all() and not np.array_equal(acc_rr, acc)
         out = np.empty_like(acc)
         O.ora_resolve.argtypes = [fp, C.c_size_t, C.c_uint32, C.c_int, fp]
         O.ora_resolve(acc.ctypes.data_as(fp), acc.size // 4, 4, 1, out.ctypes.data_as(fp))
