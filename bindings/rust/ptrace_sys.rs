@@ -55,6 +55,9 @@ extern "C" {
     pub fn pt_set_stream(ctx: *mut PtCtx, hip_stream: *mut c_void) -> c_int;
     pub fn pt_set_option(ctx: *mut PtCtx, key: c_int, value: c_int) -> c_int;
     pub fn pt_tune(ctx: *mut PtCtx, n_passes: u32) -> c_int;
+    // the shader's debug overlay (static/shader.frag:307-318): the three uniforms of src/webgl.rs:554-587, copied
+    pub fn pt_set_debug_overlay(ctx: *mut PtCtx, enable: c_int, selected_object: i32, cursor_point: *const f32) -> c_int;
+    pub fn pt_last_trace_build(ctx: *mut PtCtx) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;

@@ -8,12 +8,16 @@
  * Without them every frame is still the same bits, several times slower (PtStats.far_rays counts why).
  *
  *   make -C examples fly
- *   examples/fly out.ppm scene.bin [width height ticks [refit]]        refit 0: never refit (to see the difference)
+ *   examples/fly out.ppm scene.bin [width height ticks [refit [debug]]]   refit 0: never refit (to see the difference)
+ *                                                                          debug 1: the shader's debug overlay (below)
  *
  * scene.bin: "PTSC", u32 n_spheres, u32 sizeof(PtSphere), u32 sizeof(PtParams), u32 n_passes, PtParams, PtSphere[n]
  * (tools/write_scene_bin.py; only the spheres are used here — the camera is the State's).  The camera starts inside the
  * scene, 's' is held (State moves it backwards along its view direction, MOVEMENT_SPEED * dt * fov per tick), one 1-spp
  * frame per tick is blended into the RGBA8 ping-pong textures on the device; out.ppm is the canvas after the last tick.
+ * With debug 1 the State's enable_debugging is set and the three overlay uniforms the reference uploads every frame
+ * (src/webgl.rs:554-587) go to the context before each frame: the sphere under the crosshair is outlined in red, the point
+ * the crosshair hits is a blue dot (static/shader.frag:307-318).
  */
 #include <math.h>
 #include <stdio.h>
@@ -32,12 +36,13 @@
   } while (0)
 
 int main(int argc, char** argv) {
-  if (argc < 3) { fprintf(stderr, "usage: fly out.ppm scene.bin [width height ticks [refit]]\n"); return 2; }
+  if (argc < 3) { fprintf(stderr, "usage: fly out.ppm scene.bin [width height ticks [refit [debug]]]\n"); return 2; }
   const char* out = argv[1];
   const char* scene_path = argv[2];
   const uint32_t w = argc > 3 ? (uint32_t)atoi(argv[3]) : 320, h = argc > 4 ? (uint32_t)atoi(argv[4]) : 180;
   const uint32_t ticks = argc > 5 ? (uint32_t)atoi(argv[5]) : 30;
   const int refit = argc > 6 ? atoi(argv[6]) : 1;
+  const int debug = argc > 7 ? atoi(argv[7]) : 0;
   const double dt = 11500.0; /* ms per tick (exact in fp32, and so are its multiples): ~12 units of flight per tick */
   pt_ctx* ctx = NULL;
   pt_state* st = NULL;
@@ -85,6 +90,7 @@ int main(int argc, char** argv) {
   pt_state_set_camera_origin(st, origin);
   pt_state_set_camera_angles(st, -132.0, -11.5);
   pt_state_set_keys(st, 4u);                          /* KeydownMap.s */
+  if (debug) pt_state_set_debugging(st, 1);
 
   uint32_t refits = 0;
   for (uint32_t k = 0; k < ticks; k++) {
@@ -100,6 +106,12 @@ int main(int argc, char** argv) {
     if (refit && pt_grid_fit(ctx) == 1) {                               /* the camera has left the region the grid serves */
       CHECK(pt_refit_grid(ctx, 0));
       refits++;
+    }
+    if (debug) {                                                        /* u_enable_debugging, u_selected_object, u_cursor_point */
+      int32_t enable, selected;
+      float cursor[3];
+      if (pt_state_debug_overlay(st, &enable, &selected, cursor) != PT_OK) return 1;
+      CHECK(pt_set_debug_overlay(ctx, enable, selected, cursor));
     }
     CHECK(pt_render_frame(ctx, v.even_odd_count));                      /* webgl::render */
   }

@@ -126,8 +126,8 @@ typedef struct PtSphere {
 /*
  * The per-frame uniform block: what Uniforms::run_setters uploads (src/webgl.rs:279-593,
  * :629-633; declarations static/shader.frag:79-102), minus the uniforms no code path reads
- * (u_aspect_ratio, u_viewport_*, u_focal_length, u_w) and the debug overlay (:100-102, dead:
- * enable_debugging is 0, src/state.rs:259).
+ * (u_aspect_ratio, u_viewport_*, u_focal_length, u_w) and the debug overlay (:100-102, opt-in:
+ * enable_debugging is 0 by default, src/state.rs:259; they go up through pt_set_debug_overlay).
  */
 typedef struct PtParams {
   uint32_t width;  /* u_width  */
@@ -344,6 +344,23 @@ int pt_write_texture(pt_ctx* ctx, int index, const uint8_t* rgba_in);
 /* ---- diagnostics ------------------------------------------------------------------------------ */
 int pt_get_stats(pt_ctx* ctx, PtStats* out);
 int pt_set_option(pt_ctx* ctx, int key, int value);
+/* The shader's DEBUG OVERLAY (static/shader.frag:307-318; uniforms u_enable_debugging, u_selected_object, u_cursor_point
+ * :100-102, uploaded every frame by src/webgl.rs:554-587).  With enable != 0 every hit is tested right after its hit record
+ * is complete — before the PT_EMISSIVE test and before any scatter draw:
+ *   cursor dot   sqrt(dot(v, v)) < 0.1 with v = hit_point - cursor_point  ->  the sample's value is (0, 0, 1)
+ *   outline      otherwise, PtSphere.uuid == selected_object && dot(normal, direction) > -0.05  ->  (1, 0, 0)
+ * (face-forward normal, unnormalised direction; the value is the shader's `return`: not multiplied by the path's
+ * throughput, also when the hit is seen through a mirror) and the path ends; the segment is counted in PtStats.segments.
+ * selected_object is compared as it is: the reference's "nothing selected" is 1000 (NO_SELECTED_OBJECT_ID, src/state.rs:12),
+ * and a sphere whose uuid is that value is outlined, as in the shader.  Copies its arguments (cursor_point may be NULL with
+ * enable == 0); takes effect from the next pt_render / pt_render_passes / pt_render_frame / pt_render_frames, whose graphs
+ * are captured again when the values change, as for any uniform.  enable == 0 restores the kernels and the bits of a context
+ * that never enabled it.  The overlay runs in builds of the trace kernels of its own (loaded at first use) and excludes
+ * PT_OPT_RUSSIAN_ROULETTE and PT_OPT_COUNT_WORK: turning one on while the other is on returns PT_ERR_INVALID.  A context
+ * set to PT_GEOM_LDS renders through the scalar walk meanwhile, as with roulette. */
+int pt_set_debug_overlay(pt_ctx* ctx, int enable, int32_t selected_object, const float cursor_point[3]);
+/* Which build of the trace kernel the most recent launch was: 0 plain, 1 Russian roulette, 2 measuring twin, 3 debug overlay. */
+int pt_last_trace_build(pt_ctx* ctx);
 /* Fits the context to scene AND uniforms.  (i) The uniform grid pt_set_spheres built for rays that start within twice the
  * scene's radius of its middle is rebuilt for the margin class that renders THIS view fastest: the smallest class that
  * covers the camera set by pt_set_params is a lower bound (a camera outside it sends every primary ray down the far path), and
@@ -495,6 +512,10 @@ int pt_state_set_quality(pt_state* s, uint32_t samples_per_pixel, uint32_t max_d
 int pt_state_set_flags(pt_state* s, int is_paused, int should_average, float last_frame_weight);
 /* KeydownMap :14-28 as a bit mask: 1 w, 2 a, 4 s, 8 d, 16 space, 32 shift */
 int pt_state_set_keys(pt_state* s, uint32_t key_mask);
+/* State.enable_debugging (src/state.rs:87), and the three overlay uniforms as run_setters uploads them (src/webgl.rs:554-587:
+ * the cursor narrowed like Vec3::to_array) — what a frame loop hands to pt_set_debug_overlay every tick.  Out pointers may be NULL. */
+int pt_state_set_debugging(pt_state* s, int enable);
+int pt_state_debug_overlay(const pt_state* s, int32_t* enable, int32_t* selected_object, float cursor_point[3]);
 int pt_state_update_position(pt_state* s, double dt_ms);      /* :411-441 (+ autofocus :453-471) */
 int pt_state_update_render_globals(pt_state* s);              /* :443-450 */
 int pt_state_resize(pt_state* s, uint32_t width, uint32_t height); /* :364-398, State half */

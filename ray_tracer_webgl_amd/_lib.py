@@ -46,6 +46,8 @@ SIGNATURES = {
     "pt_get_stats": (C.c_int, [_ctx, C.POINTER(abi.PtStats)]),
     "pt_set_option": (C.c_int, [_ctx, C.c_int, C.c_int]),
     "pt_tune": (C.c_int, [_ctx, C.c_uint32]),
+    "pt_set_debug_overlay": (C.c_int, [_ctx, C.c_int, C.c_int32, C.POINTER(C.c_float)]),
+    "pt_last_trace_build": (C.c_int, [_ctx]),
     "pt_refit_grid": (C.c_int, [_ctx, C.c_int]),
     "pt_grid_fit": (C.c_int, [_ctx]),
     "pt_build_bvh": (C.c_int, [C.POINTER(abi.PtSphere), C.c_uint32, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp,
@@ -75,6 +77,8 @@ SIGNATURES = {
     "pt_state_set_quality": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
     "pt_state_set_flags": (C.c_int, [_vp, C.c_int, C.c_int, C.c_float]),
     "pt_state_set_keys": (C.c_int, [_vp, C.c_uint32]),
+    "pt_state_set_debugging": (C.c_int, [_vp, C.c_int]),
+    "pt_state_debug_overlay": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "pt_state_update_position": (C.c_int, [_vp, C.c_double]),
     "pt_state_update_render_globals": (C.c_int, [_vp]),
     "pt_state_resize": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
@@ -88,6 +92,10 @@ SIGNATURES = {
         [C.POINTER(abi.PtHostSphere), C.c_uint32, C.POINTER(abi.PtCameraIn), C.POINTER(abi.PtCenterHit)],
     ),
 }
+
+
+# entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay
+ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_set_debugging", "pt_state_debug_overlay")
 
 
 def _elf_dynamic_strings(path, tags):
@@ -195,6 +203,8 @@ def load():
     _share_torch_hip_runtime(path)
     lib = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if name in ADDED_WITHIN_ABI_5 and "PT_LIB" in os.environ and not hasattr(lib, name):
+            continue  # (dev A/B against an older build of the same ABI, tools/ab_kernels.py: it simply lacks the newer entry points)
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

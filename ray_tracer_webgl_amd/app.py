@@ -25,10 +25,13 @@ class FrameLoop:
     # is refitted; a grid that is too SMALL (== 1: every primary ray tested against the whole list) is refitted at once
     LOOSE_FRAMES = 32
 
-    def __init__(self, width, height, device=0, mode="reference", host_spheres=None):
+    def __init__(self, width, height, device=0, mode="reference", host_spheres=None, debugging=False):
         assert mode in ("reference", "linear")
         self.mode = mode
+        self.debugging = bool(debugging)
         self.state = State(width, height)
+        if self.debugging:  # State.enable_debugging (src/state.rs:87): the shader's cursor dot and selected-object outline
+            self.state.set_debugging(True)
         if host_spheres is not None:  # another scene than State::default's nine spheres (abi.PtHostSphere records, f64 like src/glsl.rs:27-40)
             self.state.set_spheres(host_spheres)
         self.tracer = PathTracer(width, height, device=device)
@@ -73,6 +76,12 @@ class FrameLoop:
         else:
             self._loose = 0
 
+    def _upload_debug_overlay(self):
+        """u_enable_debugging / u_selected_object / u_cursor_point go up with every frame's uniforms (src/webgl.rs:554-587):
+        the State refreshes the last two whenever the camera moves (update_position -> get_center_hit)."""
+        if self.debugging:
+            self.tracer.set_debug_overlay(*self.state.debug_overlay())
+
     def frame(self, now_ms, should_save=False):
         """One rAF tick.  Returns True when a frame was rendered."""
         st = self.state
@@ -86,6 +95,7 @@ class FrameLoop:
         p = st.to_params(now_ms)                    # uniforms.run_setters, :96
         if self.mode == "reference":
             self.tracer.set_params(p)
+            self._upload_debug_overlay()
             self._keep_the_grid_fitted()
             # webgl::render: previous frame = textures[(even_odd + 1) % 2] (src/webgl.rs:186-190), draw
             # to the canvas (:193-194) and, when averaging, to the other texture (:197-204)
@@ -94,6 +104,7 @@ class FrameLoop:
             if v.render_count <= 1:  # accumulation restarts after any camera change
                 self.tracer.reset()
             self.tracer.set_params(p)
+            self._upload_debug_overlay()
             self._keep_the_grid_fitted()
             self.tracer.render()
             self._canvas = self.tracer.resolve_rgba8(True)
@@ -130,6 +141,7 @@ class FrameLoop:
         p.time_step = float(interval_ms)  # frame k: u_time = time + float(k) * interval (fp32, like the kernel's pass time)
         p.first_pass = 0
         self.tracer.set_params(p)
+        self._upload_debug_overlay()
         self._keep_the_grid_fitted()  # (before the series' graphs are captured: a refit re-captures them by itself)
         self.tracer.render_frames(v.even_odd_count, v.max_render_count, n)
         for _ in range(n - 1):                       # the host's copy of the counters follows

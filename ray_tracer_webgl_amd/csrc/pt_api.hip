@@ -32,8 +32,9 @@
 #define PT_API extern "C" __attribute__((visibility("default")))
 
 // the kernels every context uses are compiled into this object (no -fgpu-rdc needed); the opt-in builds
-// (Russian roulette, measuring twins) are the translation unit pt_kernels_extra.hip — a code object of their
-// own, which the HIP runtime loads when one of them is first asked for (extra_kernel below)
+// (Russian roulette, measuring twins) are the translation unit pt_kernels_extra.hip, the debug-overlay builds
+// pt_kernels_debug.hip — code objects of their own, which the HIP runtime loads when one of their kernels is first
+// asked for (extra_kernel, debug_kernel below)
 #include "pt_kernels.hip"
 
 static thread_local std::string g_create_error;
@@ -151,6 +152,18 @@ struct pt_ctx {
   uint32_t carry_lanes = 12;
   uint32_t refill_min = 4;
   int rr_min_depth = 0;  // PT_OPT_RUSSIAN_ROULETTE: 0 = off (the reference's estimator, bit-exact against the oracle)
+  // debug overlay (pt_set_debug_overlay): the shader's u_enable_debugging / u_selected_object / u_cursor_point, and the uuids
+  // its outline test compares — uploaded when the overlay is first turned on for a scene (upload_uuids), never before
+  bool dbg_enable = false;
+  int32_t dbg_selected = 0;
+  float dbg_cursor[3] = {0.f, 0.f, 0.f};
+  std::vector<int32_t> h_uuid;      // PtSphere.uuid in list order (host copy: the device arrays are made from it)
+  DevBuf<int32_t> d_uuid;           // n_spheres
+  DevBuf<int32_t> d_bvh_uuid;       // per hierarchy slot, like d_bvh_mat
+  DevBuf<int32_t> d_grid_uuid;      // per grid entry, like d_grid_mat
+  size_t bvh_index_n = 0;           // elements of d_bvh_index in use
+  bool uuid_valid = false;          // the three arrays match the scene and structures in place
+  int last_build = 0;               // which build the most recent trace launch was (pt_last_trace_build)
   // work-queue ordering feedback, one entry per tile
   DevBuf<uint32_t> d_tile_cost;
   DevBuf<uint32_t> d_tile_order;
@@ -384,40 +397,55 @@ const void* extra_kernel(int device, int id) {
   return k;
 }
 
+// a kernel of pt_kernels_debug.hip, likewise
+const void* debug_kernel(int device, int id) {
+  static std::once_flag once[64][PT_D_COUNT];
+  const void* k = pt_debug_kernel(id);
+  if (k)
+    std::call_once(once[device & 63][id], [k] {
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
+      (void)hipGetLastError();
+    });
+  return k;
+}
+
 // Every trace kernel, by how it reads the list (row) and which build runs (column), with the wave count it is built for
 // (its PT_BUILT_FOR).  A kernel of this object has `main`; one of pt_kernels_extra.hip a PT_X_* id (`extra`), one of
-// pt_kernels_small.hip the list length's remainder modulo four (`small`): those two objects are loaded only when one of
-// their kernels is first launched, so their handles are taken when an entry is chosen, not here.  Where a way to read the
-// list has no roulette build or no measuring twin, its column holds the plain build, which then runs.
-struct TraceKernel { const void* main; int extra, small, waves; };
+// pt_kernels_small.hip the list length's remainder modulo four (`small`), one of pt_kernels_debug.hip a PT_D_* id (`debug`):
+// those three objects are loaded only when one of their kernels is first launched, so their handles are taken when an entry
+// is chosen, not here.  Where a way to read the list has no roulette build, no measuring twin or no overlay build, its
+// column holds the plain build, which then runs (the LDS list walk: pt_geom_plan.hpp steers roulette and overlay launches
+// to the scalar row).
+struct TraceKernel { const void* main; int extra, small, waves; int debug = -1; };
 // ROW_SMALL + list length % 4; ROW_BVH / ROW_GRID + what is staged in the LDS (bind_hierarchy, bind_grid); ROW_GRID itself is
 // the LDS-staged build on a grid of one layer along y, ROW_GRID_LAYERS the same build on any other grid (grid_walk_flat)
 enum TraceRow { ROW_LIST_LDS, ROW_SCALAR, ROW_SCALAR_NOLDS, ROW_SMALL, ROW_BVH = ROW_SMALL + 4, ROW_GRID = ROW_BVH + 3, ROW_GRID_LAYERS = ROW_GRID + 3,
                 ROW_COUNT };
-enum TraceBuild { BUILD_PLAIN, BUILD_RR, BUILD_TWIN, BUILD_COUNT };
+enum TraceBuild { BUILD_PLAIN, BUILD_RR, BUILD_TWIN, BUILD_DBG, BUILD_COUNT };
 
 template <class K>
 TraceKernel in_main(K* k, int waves) { return {reinterpret_cast<const void*>(k), -1, -1, waves}; }
 TraceKernel in_extra(int id, int waves = PT_WAVES_WALK) { return {nullptr, id, -1, waves}; }
 TraceKernel in_small(int rem) { return {nullptr, -1, rem, PT_WAVES_SMALL}; }
+TraceKernel in_debug(int id, int waves = PT_WAVES_WALK) { return {nullptr, -1, -1, waves, id}; }
 
 const TraceKernel kTraceKernels[ROW_COUNT][BUILD_COUNT] = {
-    // plain                                                roulette                                         measuring twin
-    {in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),           in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),     in_main(pt_trace_kernel, PT_WAVES_LIST_LDS)},
-    {in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),        in_extra(PT_X_SCALAR_RR, PT_WAVES_LIST),         in_main(pt_trace_kernel_scalar, PT_WAVES_LIST)},
-    {in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_extra(PT_X_SCALAR_NOLDS_RR, PT_WAVES_LIST),   in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST)},
-    {in_small(0),                                           in_extra(PT_X_SMALL_RR + 0, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL)},
-    {in_small(1),                                           in_extra(PT_X_SMALL_RR + 1, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL)},
-    {in_small(2),                                           in_extra(PT_X_SMALL_RR + 2, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL)},
-    {in_small(3),                                           in_extra(PT_X_SMALL_RR + 3, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL)},
-    {in_main(pt_trace_kernel_bvh, PT_WAVES_WALK),           in_extra(PT_X_BVH_RR),                           in_extra(PT_X_BVH_COUNT)},
-    {in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),     in_extra(PT_X_BVH_NODES_RR),                     in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK)},
-    {in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),      in_extra(PT_X_BVH_GMEM_RR),                      in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK)},
-    {in_main(pt_trace_kernel_grid, PT_WAVES_WALK),          in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_COUNT)},
-    {in_main(pt_trace_kernel_grid_cells, PT_WAVES_WALK),    in_extra(PT_X_GRID_CELLS_RR),                    in_extra(PT_X_GRID_CELLS_COUNT, PT_WAVES_TWIN_CELLS)},
-    {in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),     in_extra(PT_X_GRID_GMEM_RR),                     in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK)},
-    // (the roulette build walks three axes on a one-layer grid too — right on any grid, and not measured: one build serves both rows)
-    {in_main(pt_trace_kernel_grid_layers, PT_WAVES_WALK),   in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_LAYERS_COUNT)},
+    // plain                                                roulette                                         measuring twin                                    debug overlay
+    {in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),           in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),     in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),  in_main(pt_trace_kernel, PT_WAVES_LIST_LDS)},
+    {in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),        in_extra(PT_X_SCALAR_RR, PT_WAVES_LIST),         in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),  in_debug(PT_D_SCALAR, PT_WAVES_LIST)},
+    {in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_extra(PT_X_SCALAR_NOLDS_RR, PT_WAVES_LIST),   in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_debug(PT_D_SCALAR_NOLDS, PT_WAVES_LIST)},
+    {in_small(0),                                           in_extra(PT_X_SMALL_RR + 0, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 0, PT_WAVES_SMALL)},
+    {in_small(1),                                           in_extra(PT_X_SMALL_RR + 1, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 1, PT_WAVES_SMALL)},
+    {in_small(2),                                           in_extra(PT_X_SMALL_RR + 2, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 2, PT_WAVES_SMALL)},
+    {in_small(3),                                           in_extra(PT_X_SMALL_RR + 3, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 3, PT_WAVES_SMALL)},
+    {in_main(pt_trace_kernel_bvh, PT_WAVES_WALK),           in_extra(PT_X_BVH_RR),                           in_extra(PT_X_BVH_COUNT),  in_debug(PT_D_BVH)},
+    {in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),     in_extra(PT_X_BVH_NODES_RR),                     in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),  in_debug(PT_D_BVH_NODES)},
+    {in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),      in_extra(PT_X_BVH_GMEM_RR),                      in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),  in_debug(PT_D_BVH_GMEM)},
+    {in_main(pt_trace_kernel_grid, PT_WAVES_WALK),          in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_COUNT),  in_debug(PT_D_GRID)},
+    {in_main(pt_trace_kernel_grid_cells, PT_WAVES_WALK),    in_extra(PT_X_GRID_CELLS_RR),                    in_extra(PT_X_GRID_CELLS_COUNT, PT_WAVES_TWIN_CELLS),  in_debug(PT_D_GRID_CELLS)},
+    {in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),     in_extra(PT_X_GRID_GMEM_RR),                     in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),  in_debug(PT_D_GRID_GMEM)},
+    // (the roulette and overlay builds walk three axes on a one-layer grid too — right on any grid, and not measured: one build each serves both rows)
+    {in_main(pt_trace_kernel_grid_layers, PT_WAVES_WALK),   in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_LAYERS_COUNT),  in_debug(PT_D_GRID)},
 };
 
 inline uint32_t grid_for(uint32_t n, uint32_t block, uint32_t cap) {
@@ -556,6 +584,7 @@ bool build_grid(const float* geom, const float* radii, uint32_t n, double near_f
 // upload a grid (the caller has made sure that nothing in flight reads the previous one); empties the host arrays of `grid`
 int install_grid(pt_ctx* c, ptgrid::Grid& grid, const PtMatRec* mat, uint32_t n) {
   c->have_grid = false;  // (until everything below has succeeded: a failed allocation must not leave a grid that points nowhere)
+  c->uuid_valid = false;  // (the entries move: their uuids follow when the overlay is on — upload_uuids)
   const size_t n_cells_pad = (grid.cells.size() + 3u) & ~(size_t)3u;  // the kernels stage 16 B at a time
   if (c->d_grid_cells.capacity() < n_cells_pad) PT_HIP(c, c->d_grid_cells.reserve(n_cells_pad));
   // + four entries of slack: a leaf round reads four consecutive entries whatever the cell's
@@ -580,6 +609,32 @@ int install_grid(pt_ctx* c, ptgrid::Grid& grid, const PtMatRec* mat, uint32_t n)
   grid.entry_index.clear(); grid.entry_index.shrink_to_fit();
   c->grid = grid;
   c->have_grid = true;
+  return PT_OK;
+}
+
+// The debug overlay's uuid arrays: PtSphere.uuid in list order and per slot of the structures in place (the walk kernels
+// shade from a slot, like slot_mat).  Made when the overlay is turned on and again whenever the scene or the grid changes while
+// it is on; a context that never enables the overlay never allocates them.  Synchronises: a set-up call's work.
+int upload_uuids(pt_ctx* c) {
+  PT_HIP(c, hipSetDevice(c->device));
+  PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight may read the arrays in place
+  const uint32_t n = c->n_spheres;
+  auto per_slot = [&](const DevBuf<uint32_t>& d_index, size_t n_index, DevBuf<int32_t>& d_out) -> int {
+    std::vector<uint32_t> index(n_index);
+    PT_HIP(c, hipMemcpy(index.data(), d_index.get(), n_index * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::vector<int32_t> u(n_index);
+    for (size_t k = 0; k < n_index; k++) u[k] = index[k] < n ? c->h_uuid[index[k]] : 0;  // (padding slots are never hit)
+    if (d_out.capacity() < n_index) PT_HIP(c, d_out.reserve(n_index));
+    PT_HIP(c, hipMemcpy(d_out.get(), u.data(), n_index * sizeof(int32_t), hipMemcpyHostToDevice));
+    return PT_OK;
+  };
+  if (c->d_uuid.capacity() < (n ? n : 1u)) PT_HIP(c, c->d_uuid.reserve(n ? n : 1u));
+  if (n) PT_HIP(c, hipMemcpy(c->d_uuid.get(), c->h_uuid.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (c->have_bvh && c->bvh_index_n)
+    if (int rc = per_slot(c->d_bvh_index, c->bvh_index_n, c->d_bvh_uuid); rc != PT_OK) return rc;
+  if (c->have_grid)
+    if (int rc = per_slot(c->d_grid_index, (size_t)c->grid.n_entries + 4u, c->d_grid_uuid); rc != PT_OK) return rc;
+  c->uuid_valid = true;
   return PT_OK;
 }
 
@@ -628,6 +683,9 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
     mat[i].inv_ri = 1.0f / s[i].refraction_index;  // (IEEE division, -ffp-contract=off: what `1.0 / ri` is in the shader's arithmetic contract)
     radii[i] = s[i].radius;
   }
+  c->h_uuid.resize(n);
+  for (uint32_t i = 0; i < n; i++) c->h_uuid[i] = s[i].uuid;
+  c->uuid_valid = false;
   const double t_split = host_ms();
   // the culling hierarchy of PT_GEOM_BVH (regular scenes of at least 16 spheres)
   ptbvh::Bvh bvh;
@@ -679,6 +737,7 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
       for (size_t k = 0; k < sm.size(); k++) sm[k] = bvh.slot_index[k] < n ? mat[bvh.slot_index[k]] : PtMatRec{};
       PT_HIP(c, hipMemcpy(c->d_bvh_mat.get(), sm.data(), sm.size() * sizeof(PtMatRec), hipMemcpyHostToDevice));
     }
+    c->bvh_index_n = bvh.slot_index.size();
     c->bvh_n_nodes = bvh.n_nodes; c->bvh_n_slots = bvh.n_slots; c->bvh_n_tree_slots = bvh.n_tree_slots;
     c->bvh_n_outliers = bvh.n_outliers; c->bvh_depth = bvh.depth;
     for (int k = 0; k < 3; k++) c->bvh_c0[k] = bvh.c0[k];
@@ -703,6 +762,10 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
   c->scene_regular = regular;
   c->have_spheres = true;
   c->geom.list_paths(path_scene(c));
+  if (c->dbg_enable) {
+    int rc = upload_uuids(c);
+    if (rc != PT_OK) return rc;
+  }
   {
     const double t_end = host_ms();
     c->setup_ms[PT_SETUP_SPHERES_UPLOAD] = t_end - t_grid;
@@ -940,6 +1003,11 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   A.carry_lanes = c->carry_lanes;
   A.refill_min = c->refill_min;
   A.frame_ctr = c->d_frame_ctr.get() + 1;  // the cell that stays 0 (pt_render_frames points at [0])
+  if (c->dbg_enable) {  // (zero otherwise: an overlay-off launch's argument block is what it was before the overlay existed)
+    A.uuid = c->d_uuid.get();
+    A.dbg_selected = c->dbg_selected;
+    for (int k = 0; k < 3; k++) A.dbg_cursor[k] = c->dbg_cursor[k];
+  }
   return PT_OK;
 }
 
@@ -950,6 +1018,7 @@ static Staging bind_hierarchy(pt_ctx* c, PtKernelArgs& A) {
   A.bvh_slots = c->d_bvh_slots.get();
   A.bvh_slot_index = c->d_bvh_index.get();
   A.slot_mat = c->d_bvh_mat.get();
+  if (c->dbg_enable) A.slot_uuid = c->d_bvh_uuid.get();
   A.n_nodes = c->bvh_n_nodes;
   A.n_tree_slots = c->bvh_n_tree_slots;
   A.n_slots = c->bvh_n_slots;
@@ -966,6 +1035,7 @@ static Staging bind_grid(pt_ctx* c, PtKernelArgs& A) {
   A.bvh_slots = c->d_grid_entries.get();
   A.bvh_slot_index = c->d_grid_index.get();
   A.slot_mat = c->d_grid_mat.get();
+  if (c->dbg_enable) A.slot_uuid = c->d_grid_uuid.get();
   A.grid_cells = c->d_grid_cells.get();
   A.n_cells = g.n[0] * g.n[1] * g.n[2];
   A.n_tree_slots = g.n_cell_entries;
@@ -1041,10 +1111,13 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
   const LaunchKnobs knobs = read_launch_knobs();
   if (knobs.carry_lanes) A.carry_lanes = *knobs.carry_lanes;
   if (c->geom.policy == PT_GEOM_AUTO) try_finish_tuning(c);
-  const bool rr = c->rr_min_depth > 0;
-  const PathChoice choice = c->geom.choose(path_scene(c), allow_trials, rr);
-  const int path = choice.path;
+  const bool rr = c->rr_min_depth > 0, dbg = c->dbg_enable;
   if (rr && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and PT_OPT_RUSSIAN_ROULETTE exclude each other");
+  if (dbg && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and the debug overlay exclude each other");
+  if (dbg && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "debug overlay: the uuid arrays are not in place (pt_set_debug_overlay after a failed upload?)");
+  // (the overlay builds exist for the ways to read the list that have a roulette build: the same steering away from the LDS walk)
+  const PathChoice choice = c->geom.choose(path_scene(c), allow_trials, rr || dbg);
+  const int path = choice.path;
   c->geom.last = path;
 
   // the kernel, its workgroup size and its dynamic LDS (staged scene + the parked path state of every
@@ -1066,8 +1139,12 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
     row = path == PT_GEOM_SMALL ? ROW_SMALL + (int)(c->n_spheres & 3u)
                                 : (path == PT_GEOM_LDS ? ROW_LIST_LDS : (have_lds ? ROW_SCALAR : ROW_SCALAR_NOLDS));
   }
-  const TraceKernel& tk = kTraceKernels[row][rr ? BUILD_RR : (c->count_work ? BUILD_TWIN : BUILD_PLAIN)];
-  const void* kfn = tk.main ? tk.main : (tk.extra >= 0 ? extra_kernel(c->device, tk.extra) : pt_small_kernel((unsigned)tk.small));
+  const int build = dbg ? BUILD_DBG : (rr ? BUILD_RR : (c->count_work ? BUILD_TWIN : BUILD_PLAIN));
+  const TraceKernel& tk = kTraceKernels[row][build];
+  const void* kfn = tk.main ? tk.main
+                            : (tk.debug >= 0 ? debug_kernel(c->device, tk.debug)
+                                             : (tk.extra >= 0 ? extra_kernel(c->device, tk.extra) : pt_small_kernel((unsigned)tk.small)));
+  c->last_build = build;
   const uint32_t block = walk ? walk_block_threads(kfn, tk.waves, scene, kWalkLdsMax, knobs.bvh_block) : list_block_threads(scene);
   const size_t lds = walk ? scene + (size_t)PT_PARK_STRIDE * 4 * block : scene;
   A.block_threads = block;
@@ -1618,6 +1695,9 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
   }
   if (key == PT_OPT_RUSSIAN_ROULETTE) { // changes sample values (not expectations): off unless asked for
     if (value < 0 || value > 1000000) return fail(c, PT_ERR_INVALID, "pt_set_option: roulette depth %d", value);
+    if (value > 0 && c->dbg_enable)
+      return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_RUSSIAN_ROULETTE and the debug overlay exclude each other (turn the overlay off first: "
+                                     "pt_set_debug_overlay(ctx, 0, ...))");
     c->rr_min_depth = value;
     return PT_OK;
   }
@@ -1632,6 +1712,36 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     return PT_OK;
   }
   return fail(c, PT_ERR_INVALID, "pt_set_option: unknown key %d", key);
+}
+
+// u_enable_debugging / u_selected_object / u_cursor_point (static/shader.frag:100-102; the reference uploads them every frame,
+// src/webgl.rs:554-587).  Copies; takes effect from the next render call (a captured frame bakes the values in: the plans of
+// pt_render_frames differ and their graphs are captured again).
+PT_API int pt_set_debug_overlay(pt_ctx* c, int enable, int32_t selected_object, const float cursor_point[3]) {
+  if (!c) return PT_ERR_INVALID;
+  if (enable && !cursor_point) return fail(c, PT_ERR_INVALID, "pt_set_debug_overlay: cursor_point is NULL");
+  if (enable && c->rr_min_depth > 0)
+    return fail(c, PT_ERR_INVALID, "pt_set_debug_overlay: the debug overlay and PT_OPT_RUSSIAN_ROULETTE exclude each other (turn roulette off first: "
+                                   "pt_set_option(ctx, PT_OPT_RUSSIAN_ROULETTE, 0))");
+  c->epoch++;
+  if (!enable) {
+    c->dbg_enable = false;
+    return PT_OK;
+  }
+  if (!c->uuid_valid && c->have_spheres) {
+    int rc = upload_uuids(c);
+    if (rc != PT_OK) return rc;
+  }
+  c->dbg_enable = true;
+  c->dbg_selected = selected_object;
+  for (int k = 0; k < 3; k++) c->dbg_cursor[k] = cursor_point[k];
+  return PT_OK;
+}
+
+// which build of the trace kernel the most recent launch was: 0 plain, 1 Russian roulette, 2 measuring twin, 3 debug overlay
+PT_API int pt_last_trace_build(pt_ctx* c) {
+  if (!c) return PT_ERR_INVALID;
+  return c->last_build;
 }
 
 namespace {
@@ -1668,6 +1778,7 @@ int rebuild_grid(pt_ctx* c, double factor, bool keep_tuned) {
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight read the grid in place
   const int tuned = c->geom.tuned;
   int rc = install_grid(c, grid, c->h_mat.data(), n);
+  if (rc == PT_OK && c->dbg_enable) rc = upload_uuids(c);
   c->epoch++;
   c->geom.list_paths(path_scene(c));  // (which kernels the grid can feed, and whether PT_GEOM_AUTO has anything to measure, follow its size — or its absence, had the upload failed)
   if (keep_tuned && rc == PT_OK && tuned == PT_GEOM_GRID && c->have_grid) c->geom.tuned = tuned;  // a refit keeps the settled choice

@@ -9,3 +9,10 @@ enum {
 extern "C" const void* pt_extra_kernel(int id);
 // pt_kernels_small.hip (a code object of its own): the small-list kernel built for this list length's remainder modulo four
 extern "C" const void* pt_small_kernel(unsigned n_spheres);
+// pt_kernels_debug.hip (a code object of its own): the debug-overlay builds (pt_set_debug_overlay), one per launch that has a
+// roulette build
+enum {
+  PT_D_SMALL = 0 /* + list length % 4: four builds */, PT_D_SCALAR = PT_D_SMALL + 4, PT_D_SCALAR_NOLDS, PT_D_BVH, PT_D_BVH_NODES, PT_D_BVH_GMEM,
+  PT_D_GRID, PT_D_GRID_CELLS, PT_D_GRID_GMEM, PT_D_COUNT
+};
+extern "C" const void* pt_debug_kernel(int id);

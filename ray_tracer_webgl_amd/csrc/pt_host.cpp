@@ -372,6 +372,27 @@ PT_API int pt_state_set_flags(pt_state* h, int is_paused, int should_average, fl
   return PT_OK;
 }
 
+// State.enable_debugging (src/state.rs:87; the reference's author flips the constant of :259): a change of the State, so the
+// accumulation restarts like after any other (update_pipeline's whole-struct compare, :343-346)
+PT_API int pt_state_set_debugging(pt_state* h, int enable) {
+  if (!h) return PT_ERR_INVALID;
+  const int32_t v = enable ? 1 : 0;
+  if (v != h->s.enable_debugging) h->s.dirty = true;
+  h->s.enable_debugging = v;
+  h->s.update_pipeline();
+  return PT_OK;
+}
+
+// the three overlay uniforms as Uniforms::run_setters uploads them (src/webgl.rs:554-587): the ints as they are, the
+// cursor narrowed like Vec3::to_array (src/math.rs:107-109)
+PT_API int pt_state_debug_overlay(const pt_state* h, int32_t* enable, int32_t* selected_object, float cursor_point[3]) {
+  if (!h) return PT_ERR_INVALID;
+  if (enable) *enable = h->s.enable_debugging;
+  if (selected_object) *selected_object = h->s.selected_object;
+  if (cursor_point) pt::put3(cursor_point, h->s.cursor_point);
+  return PT_OK;
+}
+
 PT_API int pt_state_set_keys(pt_state* h, uint32_t m) {
   if (!h) return PT_ERR_INVALID;
   pt::KeydownMap& k = h->s.keydown_map;

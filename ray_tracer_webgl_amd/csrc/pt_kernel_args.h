@@ -97,6 +97,12 @@ struct PtKernelArgs {
                                    // hipGraph advance it on the device); points at a zero cell otherwise.  Never NULL.
   const float* mat_r0;             // n_spheres x {r0 of reflectance() for the ratio 1 / ri, for the ratio ri}: ((1 - ratio) / (1 + ratio))^2 made on the host (small-list kernels)
                                    // (last: the other kernels' argument offsets — and with them their scalar loads and spills — stay as they were)
+  // debug overlay (pt_set_debug_overlay; read by the overlay builds of pt_kernels_debug.hip only, at the point of use: pt_shade.hpp).
+  // Behind everything else for the same reason as mat_r0.
+  const int32_t* uuid;             // n_spheres: PtSphere.uuid in list order (the caller's values, not indices)
+  const int32_t* slot_uuid;        // n_slots: the slot's sphere's uuid (walk kernels, like slot_mat)
+  float dbg_cursor[3];             // u_cursor_point, static/shader.frag:102
+  int32_t dbg_selected;            // u_selected_object, :101
 };
 
 // ---- waves per SIMD each trace kernel is BUILT FOR -------------------------------------------------------------

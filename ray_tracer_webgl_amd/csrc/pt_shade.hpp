@@ -18,7 +18,8 @@ namespace ptk {
 // material record are read instead of going through the list index
 // RR: the opt-in Russian-roulette build of a kernel (PT_OPT_RUSSIAN_ROULETTE); the kernels without it
 // carry none of its code or registers
-template <typename S, bool RR, bool COUNT>
+// DBG: the opt-in debug-overlay build (pt_set_debug_overlay; pt_kernels_debug.hip), carried the same way
+template <typename S, bool RR, bool COUNT, bool DBG = false>
 __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, const Hit& h, const Carry& cw, Tally<COUNT>& tally) {
   tally.flag(PT_REG_SHADE_ANY);
   // local copies, written back at the end (see pt_grid_walk.hpp: references would be memory to the
@@ -72,6 +73,26 @@ __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, co
     front = dot3(d, on) < 0.0f; // :137
     n = front ? on : mk(-on.x, -on.y, -on.z);
     alb = mk(m0.x, m0.y, m0.z);
+    if constexpr (DBG) {
+      // DEBUG OVERLAY — opt-in (pt_set_debug_overlay), static/shader.frag:307-318, on the complete hit record: before the
+      // PT_EMISSIVE test and before any scatter draw.  The cursor dot: |hit point - cursor| < 0.1 -> the sample is (0, 0, 1);
+      // otherwise the outline of the selected sphere: uuid == selected && dot(normal, direction) > -0.05 -> (1, 0, 0).  Either
+      // is the `return` of the shader: not multiplied by the throughput, and the path ends without a draw — it is
+      // handed on as a material nothing recognises (:284-285: no seed step, no contribution).  Its four uniforms and the
+      // uuid arrays are read from the kernarg segment HERE (pt_scene.hpp kargs): they hold no SGPR across the walk.
+      karg_t* K = kargs();
+      const V3 v = mk(hp.x - K->dbg_cursor[0], hp.y - K->dbg_cursor[1], hp.z - K->dbg_cursor[2]);
+      const bool on_cursor = sqrt_rn(dot3(v, v)) < 0.1f;
+      const int32_t* up = K->uuid + hit;  // the caller's value (PtSphere.uuid), not the list index
+      if constexpr (S::TREE) {
+        if (hit_pos != 0xffffffffu) up = K->slot_uuid + hit_pos;
+      }
+      const bool on_outline = *up == K->dbg_selected && dot3(n, d) > -0.05f;
+      if (on_cursor || on_outline) {
+        sum.x += on_cursor ? 0.0f : 1.0f; sum.y += 0.0f; sum.z += on_cursor ? 1.0f : 0.0f;
+        mtype = 4;
+      }
+    }
   }
   const bool sky = hit < 0 && A.background_mode == 0;
   const float inv = inv_sqrt_rn(a); // background() :290, GLASS :253

@@ -1,7 +1,8 @@
-// pt_trace_body.hpp — the path-tracing kernel body shared by the three device translation units (each a gfx950
+// pt_trace_body.hpp — the path-tracing kernel body shared by the four device translation units (each a gfx950
 // code object of its own, loaded when one of its kernels is first asked for): pt_kernels.hip (list and walk
-// kernels), pt_kernels_small.hip (the small-list kernels, one per list length modulo four) and
-// pt_kernels_extra.hip (the opt-in builds: the Russian-roulette kernels and the measuring twins).
+// kernels), pt_kernels_small.hip (the small-list kernels, one per list length modulo four),
+// pt_kernels_extra.hip (the opt-in builds: the Russian-roulette kernels and the measuring twins) and
+// pt_kernels_debug.hip (the opt-in debug-overlay builds).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,9 +22,10 @@ using namespace ptd;
 // The path-tracing kernel body: one persistent wave working through (pixel, pass) items.
 // Template parameters: pt_scene.hpp `Scene`; COUNT = the measuring twin (tallies live); RR = the
 // opt-in Russian-roulette build (pt_shade.hpp); TAIL = the small-list builds' list remainder (pt_scene.hpp SMALL_TAIL);
-// FLAT_Y = the grid walk of a one-layer grid (pt_scene.hpp, pt_grid_walk.hpp).
+// FLAT_Y = the grid walk of a one-layer grid (pt_scene.hpp, pt_grid_walk.hpp); DBG = the opt-in debug-overlay build
+// (pt_shade.hpp).
 // --------------------------------------------------------------------------------------------
-template <bool SCAN_LDS, bool HAVE_LDS, int WALK = 0, bool COUNT = false, bool RR = false, int TAIL = -1, bool FLAT_Y = false>
+template <bool SCAN_LDS, bool HAVE_LDS, int WALK = 0, bool COUNT = false, bool RR = false, int TAIL = -1, bool FLAT_Y = false, bool DBG = false>
 __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
   using namespace ptk;
   using S = Scene<SCAN_LDS, HAVE_LDS, WALK, TAIL, FLAT_Y>;
@@ -109,7 +111,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
     const bool shade = p.alive && !cw.carried;
     seg_count += (uint32_t)__popcll(pt_ballot(shade));
     tally.timebin(A, shade);
-    if (shade) shade_segment<S, RR>(A, p, h, cw, tally);
+    if (shade) shade_segment<S, RR, COUNT, DBG>(A, p, h, cw, tally);
     tally.collect();
     tally.phase(7);
   }

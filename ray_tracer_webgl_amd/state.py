@@ -64,6 +64,27 @@ class State:
         self._ok(self.lib.pt_state_set_keys(self._h, int(mask)))
         self.keys = int(mask)
 
+    def set_debugging(self, enable):
+        """State.enable_debugging (src/state.rs:87): the shader's debug overlay."""
+        self._ok(self.lib.pt_state_set_debugging(self._h, 1 if enable else 0))
+
+    def debug_overlay(self):
+        """(enable, selected_object, cursor_point) as run_setters uploads them (src/webgl.rs:554-587): the cursor narrowed to
+        three float32 — the arguments of PathTracer.set_debug_overlay."""
+        en, sel = C.c_int32(), C.c_int32()
+        cur = (C.c_float * 3)()
+        self._ok(self.lib.pt_state_debug_overlay(self._h, C.byref(en), C.byref(sel), cur))
+        return bool(en.value), int(sel.value), (float(cur[0]), float(cur[1]), float(cur[2]))
+
+    def pick(self):
+        """Refresh cursor_point / selected_object for the camera as it stands (State::update_cursor_position_in_world,
+        src/state.rs:453-471, which the reference reaches through update_position while a key is held): 'w' held for a tick
+        of zero length moves nothing and runs the pick ray."""
+        keys = self.keys
+        self.set_keys(keys | abi.KEY_W)
+        self.update_position(0.0)
+        self.set_keys(keys)
+
     # src/state.rs:411-450
     def update_position(self, dt_ms):
         self._ok(self.lib.pt_state_update_position(self._h, float(dt_ms)))

@@ -132,6 +132,20 @@ class PathTracer:
         not with the roulette-free oracle.  A context set to PT_GEOM_LDS renders through the scalar walk meanwhile."""
         self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_RUSSIAN_ROULETTE, int(min_depth)))
 
+    def set_debug_overlay(self, enable, selected_object=abi.NO_SELECTED_OBJECT_ID, cursor_point=(0.0, 0.0, 0.0)):
+        """The shader's debug overlay (static/shader.frag:307-318; pt_set_debug_overlay): hits within 0.1 of `cursor_point`
+        are blue, the silhouette band of the sphere whose uuid is `selected_object` is red, and such a path ends there.
+        Off by default; enable=False restores the plain kernels and their bits.  Excludes Russian roulette."""
+        cur = (C.c_float * 3)(*[float(x) for x in cursor_point])
+        self._check(self.lib.pt_set_debug_overlay(self._ctx, 1 if enable else 0, int(selected_object), cur))
+
+    def last_trace_build(self):
+        """abi.BUILD_*: which build of the trace kernel the most recent launch was."""
+        rc = self.lib.pt_last_trace_build(self._ctx)
+        if rc < 0:
+            raise PtError(rc, "pt_last_trace_build failed")
+        return rc
+
     def set_grid_fit(self, unmeasured):
         """How tune() chooses the grid's margin class: False (default) it times the candidates, True it takes the smallest
         class that covers the camera without launching anything (PT_OPT_GRID_FIT).  Speed only."""
@@ -274,10 +288,11 @@ class PathTracer:
         return out
 
 
-def render_scene(scene, device=0, use_torch=False, passes_per_launch=None, band=None, geometry_path=None, tune=None):
+def render_scene(scene, device=0, use_torch=False, passes_per_launch=None, band=None, geometry_path=None, tune=None, overlay=None):
     """Render a scenes.Scene completely; returns (PathTracer, accum ndarray).  `tune` = n: pt_tune(n) after scene and
     uniforms are up, as bench.py does before it times anything — the grid is refitted to the camera and PT_GEOM_AUTO
-    settled with n-pass launches (the as-benchmarked path: tests that pin what the bench line times pass it)."""
+    settled with n-pass launches (the as-benchmarked path: tests that pin what the bench line times pass it).
+    `overlay` = (selected_object, cursor_point): with the debug overlay on (set_debug_overlay)."""
     p = scene.params.copy()
     if band is not None:
         p.band_rows, p.band_index, p.band_count = band
@@ -285,6 +300,8 @@ def render_scene(scene, device=0, use_torch=False, passes_per_launch=None, band=
     if geometry_path is not None:
         pt.set_geometry_path(geometry_path)
     pt.set_spheres(scene.spheres)
+    if overlay is not None:
+        pt.set_debug_overlay(True, overlay[0], overlay[1])
     pt.set_params(p)
     per = passes_per_launch or scene.n_passes
     pt.reserve_passes(max(per, int(tune or 0)))
