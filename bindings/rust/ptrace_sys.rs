@@ -29,6 +29,13 @@ pub struct PtParams {            // == uniform block, static/shader.frag:79-99
     pub time_step: f32, pub first_pass: u32,
 }
 
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtErrorStats {        // the frame's noise figures, summed from the error estimate's tile records
+    pub sum_e2: f64, pub sum_m2: f64, pub rel_error: f64, pub rms_error: f64,
+    pub pixels: u64, pub pixels_counted: u64, pub pixels_short: u64, pub pixels_nonfinite: u64,
+    pub passes_min: u32, pub passes_max: u32, pub passes_rendered: u32, pub reached: u32,
+}
+
 #[repr(C)] pub struct PtCtx { _private: [u8; 0] }
 
 #[link(name = "ptrace")]
@@ -58,6 +65,13 @@ extern "C" {
     // the shader's debug overlay (static/shader.frag:307-318): the three uniforms of src/webgl.rs:554-587, copied
     pub fn pt_set_debug_overlay(ctx: *mut PtCtx, enable: c_int, selected_object: i32, cursor_point: *const f32) -> c_int;
     pub fn pt_last_trace_build(ctx: *mut PtCtx) -> c_int;
+    // the per-pixel error estimate (pt_set_option PT_OPT_ERROR_ESTIMATE 1): raw state, standard-error image, 8x8-tile
+    // records {sum se^2, sum mean^2, counted pixels, min passes}, the frame's figures, and rendering to a noise target
+    pub fn pt_error_ptr(ctx: *mut PtCtx, dev_ptr: *mut *mut c_void, bytes: *mut usize) -> c_int;
+    pub fn pt_resolve_error(ctx: *mut PtCtx, rgba_out: *mut f32) -> c_int;
+    pub fn pt_error_tiles(ctx: *mut PtCtx, tiles_out: *mut f32, tiles_x: *mut u32, tiles_y: *mut u32) -> c_int;
+    pub fn pt_error_stats(ctx: *mut PtCtx, out: *mut PtErrorStats) -> c_int;
+    pub fn pt_render_until(ctx: *mut PtCtx, target_rel_error: f32, passes_per_launch: u32, max_passes: u32, out: *mut PtErrorStats) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;
@@ -78,6 +92,7 @@ extern "C" {
 }
 
 pub const PT_OPT_GEOMETRY_PATH: c_int = 1;      // PT_GEOM_AUTO 0 / LDS 1 / SCALAR 2 / BVH 3 / GRID 4 / SMALL 5
+pub const PT_OPT_ERROR_ESTIMATE: c_int = 7;     // opt-in, 0 = off; the image bits do not depend on it
 pub const PT_OPT_RUSSIAN_ROULETTE: c_int = 5;   // opt-in, 0 = off: the reference's estimator has none (shader.frag:297-339)
 
 // The rAF closure of src/lib.rs:65-104 with webgl::render replaced (one tick):

@@ -7,6 +7,8 @@
  *   gcc -O2 -Iinclude examples/render.c -o examples/render -Lray_tracer_webgl_amd -lptrace \
  *       -Wl,-rpath,'$ORIGIN/../ray_tracer_webgl_amd'
  *   examples/render out.ppm 640 351 16
+ *   examples/render out.ppm 640 351 16 0.02     render to a noise target: launches of 16 passes until the frame's
+ *                                               relative error is at most 0.02 (at most 64 launches)
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +29,7 @@ int main(int argc, char** argv) {
   const char* out = argc > 1 ? argv[1] : "render.ppm";
   uint32_t w = argc > 2 ? (uint32_t)atoi(argv[2]) : 640, h = argc > 3 ? (uint32_t)atoi(argv[3]) : 351;
   uint32_t frames = argc > 4 ? (uint32_t)atoi(argv[4]) : 16;
+  float noise_target = argc > 5 ? (float)atof(argv[5]) : 0.0f;   /* 0: render `frames` passes and stop */
   pt_ctx* ctx = NULL;
   pt_state* st = NULL;
 
@@ -43,8 +46,17 @@ int main(int argc, char** argv) {
   CHECK(pt_state_to_params(st, 0.0, &p));             /* Uniforms::run_setters: paused -> 25 spp */
   p.background_mode = PT_BG_SKY;
   p.band_rows = 8; p.band_index = 0; p.band_count = 1;
+  if (noise_target > 0.0f) p.time_step = PT_TIME_STEP_DECORRELATED;   /* the estimate assumes independent passes */
   CHECK(pt_set_params(ctx, &p));
-  CHECK(pt_render_passes(ctx, frames));               /* `frames` passes, u_time = 0, 1, 2, ... */
+  if (noise_target > 0.0f) {
+    PtErrorStats es;
+    CHECK(pt_set_option(ctx, PT_OPT_ERROR_ESTIMATE, 1));
+    CHECK(pt_render_until(ctx, noise_target, frames, 64 * frames, &es));
+    printf("noise target %g: %u passes, relative error %.5f, %s\n", noise_target, es.passes_rendered, es.rel_error,
+           es.reached ? "reached" : "not reached");
+  } else {
+    CHECK(pt_render_passes(ctx, frames));             /* `frames` passes, u_time = 0, 1, 2, ... */
+  }
 
   unsigned char* rgba = (unsigned char*)malloc((size_t)w * h * 4);
   CHECK(pt_resolve_rgba8(ctx, rgba, 1));

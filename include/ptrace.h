@@ -98,6 +98,9 @@ enum {
                              length 40 segments).  0 = off (default): bit-exact against the oracle. */
   PT_OPT_GRID_FIT = 6,    /* how pt_tune chooses the grid's margin class.  0 (default): it measures the candidates (see
                              pt_tune).  1: the smallest class that covers the camera, no launches.  Speed only. */
+  PT_OPT_ERROR_ESTIMATE = 7, /* 1: keep a per-pixel error estimate beside the accumulation (see pt_error_ptr below); allocates
+                             and zeroes two float4 per local pixel.  0 (default): off, releases them.  The image bits of a
+                             context are the same either way. */
 };
 
 /* ---- background modes ----------------------------------------------------------------------- */
@@ -300,6 +303,70 @@ int pt_bind_accum(pt_ctx* ctx, void* dev_ptr, size_t bytes);
  * device's default stream IS the NULL handle: name it as hipStreamLegacy, PT_STREAM_LEGACY. */
 int pt_set_stream(pt_ctx* ctx, void* hip_stream);
 #define PT_STREAM_LEGACY ((void*)1) /* = hipStreamLegacy */
+
+/* ---- per-pixel error estimate: how noisy is the frame still? (build extension, opt-in: PT_OPT_ERROR_ESTIMATE) ----------
+ * pt_render_passes writes every pass into a slab of its own and then folds the slabs into the accumulation in pass order.
+ * While the estimate is on, the fold also keeps, per local pixel i, the running mean and sum of squared deviations of the
+ * PASS SUMS (batch means; Welford's update) in two float4:
+ *     A = {mean.r, mean.g, mean.b, n}      B = {M2.r, M2.g, M2.b, k}          n passes folded, k = their samples
+ * For each pass p in order, with s = slab[p][i] = {sum r, sum g, sum b, spp}, in fp32, ONE IEEE operation per statement,
+ * nothing fused, `/` correctly rounded:
+ *     accum.c = accum.c + s.c  (c = r, g, b, w: the adds of a context without the estimate, in their order)
+ *     n = n + 1.0f;   k = k + s.w;
+ *     per channel c:  d = s.c - mean.c;  mean.c = mean.c + d / n;  e = s.c - mean.c;  M2.c = M2.c + d * e;
+ * s.c is the pass SUM, not its mean, so all passes of an estimate must have the same samples_per_pixel: the first fold
+ * after a clear decides, and pt_render / pt_render_passes with another value return PT_ERR_INVALID (clear first).  n and k
+ * live in the buffer, like accum.w: the estimate stays right when a captured pt_render_passes is replayed from a hipGraph.
+ * THE ESTIMATE SPEAKS FOR THE PASSES FOLDED SINCE ITS LAST CLEAR.  It is cleared wherever the accumulation is cleared or
+ * replaced: pt_reset_accum, pt_tune when it launched anything, pt_resize, a pt_set_params that changes the row partition,
+ * pt_load_accum, pt_bind_accum — after pt_load_accum the image holds more passes than the estimate knows of.
+ * pt_render_frame(s) are not involved.
+ * ASSUMPTION: the passes are independent, i.e. time_step is a step such as PT_TIME_STEP_DECORRELATED.  With whole-number
+ * steps consecutive passes share random numbers (PtParams.time_step: the +27 % finding) and the estimate reads low.
+ *
+ * pt_error_ptr: the raw state, device pointer to local_rows*width pairs A, B (32 bytes per pixel, row 0 = lowest owned
+ * row); PT_ERR_NOT_READY while the estimate is off — like the three read-outs below.
+ * pt_resolve_error: the standard error of each pixel's mean as linear radiance, local_rows*width RGBA fp32 texels to a host
+ * or device pointer; synchronises like pt_resolve.  Per pixel:
+ *     if (!(n >= 2.0f) || !(k > 0.0f))  se = {0, 0, 0};
+ *     else { q = n / k;  v.c = M2.c / (n * (n - 1.0f));  se.c = sqrtf(v.c) * q; }
+ *     out = {se.r, se.g, se.b, n}                      and the estimate's own mean is  m.c = mean.c * q
+ * pt_error_tiles: one record of four floats per 8x8 tile of the LOCAL rows (the work queue's tiles), ceil(width / 8) x
+ * ceil(local_rows / 8) of them in row-major order; tiles_out (host or device) may be NULL to query the sizes only.  One
+ * wave64 handles a tile, lane l owns local pixel (8 tx + l % 8, 8 ty + l / 8).  A lane is COUNTED when its pixel lies inside
+ * the image, has n >= 2, k > 0 and finite se and m; it contributes e = (se.r*se.r + se.g*se.g) + se.b*se.b and
+ * m2 = (m.r*m.r + m.g*m.g) + m.b*m.b, every other lane +0 to both, and the wave adds them with the fixed tree
+ *     for off in 32, 16, 8, 4, 2, 1:  v[l] = v[l] + v[l + off]   (l < off)
+ * record = {sum e, sum m2, counted lanes, min n over counted lanes (0 if none)}.  The same state gives the same bits on every
+ * run and launch shape.
+ * pt_error_stats: runs the tile kernel, copies the records (and a second float4 of tallies per tile: 1 MB in all at
+ * 1920x1080) to the host and adds them in tile index order in double. */
+typedef struct PtErrorStats {
+  double sum_e2;    /* E: sum of the records' sum e  (squared standard errors over counted pixels and channels) */
+  double sum_m2;    /* M: sum of the records' sum m2 (squared means, likewise)                                  */
+  double rel_error; /* M > 0 ? sqrt(E / M) : 0     the frame's noise relative to its signal                   */
+  double rms_error; /* counted ? sqrt(E / (3 counted)) : 0                                                    */
+  uint64_t pixels;           /* local_rows * width                                                             */
+  uint64_t pixels_counted;   /* the counted lanes of all tiles                                                 */
+  uint64_t pixels_short;     /* pixels with !(n >= 2): too few passes for a variance                           */
+  uint64_t pixels_nonfinite; /* pixels with n >= 2 that are not counted: se or m not finite (NaN / inf radiance), or !(k > 0) */
+  uint32_t passes_min, passes_max; /* min / max n over the counted pixels (0 if none)                            */
+  uint32_t passes_rendered;  /* pt_render_until: passes this call rendered (0 from pt_error_stats)             */
+  uint32_t reached;          /* pt_render_until: 1 when it stopped because the target was met                  */
+} PtErrorStats;
+/* Multi-GPU: sum_e2, sum_m2 and the pixel counts of the ranks' row bands ADD (passes_min / passes_max: min / max), so the frame
+ * figure of an N-rank render is the ranks' sums combined: rel_error = sqrt(sum of sum_e2 / sum of sum_m2). */
+int pt_error_ptr(pt_ctx* ctx, void** dev_ptr, size_t* bytes);
+int pt_resolve_error(pt_ctx* ctx, float* rgba_out);
+int pt_error_tiles(pt_ctx* ctx, float* tiles_out, uint32_t* tiles_x, uint32_t* tiles_y);
+int pt_error_stats(pt_ctx* ctx, PtErrorStats* out);
+/* Render to a noise target.  Synchronous, a set-up-style call (not inside a stream capture): needs the estimate on
+ * (PT_ERR_INVALID otherwise), passes_per_launch <= the reserved passes (PT_ERR_CAPACITY) and a finite positive target.  Loop:
+ * render min(passes_per_launch, max_passes - done) passes, advance the context's params.first_pass by that many (so the frame
+ * is the frame one uninterrupted pt_render_passes would give), take pt_error_stats; stop with reached = 1 when
+ * rel_error <= target and pixels_short == 0, with reached = 0 (still PT_OK) when max_passes are spent.  first_pass stays
+ * advanced: a second call continues the same frame.  Relies on the ASSUMPTION above (independent passes). */
+int pt_render_until(pt_ctx* ctx, float target_rel_error, uint32_t passes_per_launch, uint32_t max_passes, PtErrorStats* out);
 
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)

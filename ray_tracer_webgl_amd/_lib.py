@@ -48,6 +48,11 @@ SIGNATURES = {
     "pt_tune": (C.c_int, [_ctx, C.c_uint32]),
     "pt_set_debug_overlay": (C.c_int, [_ctx, C.c_int, C.c_int32, C.POINTER(C.c_float)]),
     "pt_last_trace_build": (C.c_int, [_ctx]),
+    "pt_error_ptr": (C.c_int, [_ctx, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "pt_resolve_error": (C.c_int, [_ctx, _vp]),
+    "pt_error_tiles": (C.c_int, [_ctx, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "pt_error_stats": (C.c_int, [_ctx, C.POINTER(abi.PtErrorStats)]),
+    "pt_render_until": (C.c_int, [_ctx, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(abi.PtErrorStats)]),
     "pt_refit_grid": (C.c_int, [_ctx, C.c_int]),
     "pt_grid_fit": (C.c_int, [_ctx]),
     "pt_build_bvh": (C.c_int, [C.POINTER(abi.PtSphere), C.c_uint32, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp,
@@ -94,8 +99,9 @@ SIGNATURES = {
 }
 
 
-# entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay
-ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_set_debugging", "pt_state_debug_overlay")
+# entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay, the error estimate
+ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_set_debugging", "pt_state_debug_overlay",
+                      "pt_error_ptr", "pt_resolve_error", "pt_error_tiles", "pt_error_stats", "pt_render_until")
 
 
 def _elf_dynamic_strings(path, tags):

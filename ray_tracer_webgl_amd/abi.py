@@ -30,6 +30,7 @@ PT_BG_BLACK = 1
 
 PT_GEOM_AUTO, PT_GEOM_LDS, PT_GEOM_SCALAR, PT_GEOM_BVH, PT_GEOM_GRID, PT_GEOM_SMALL = 0, 1, 2, 3, 4, 5
 PT_OPT_GEOMETRY_PATH, PT_OPT_COUNT_WORK, PT_OPT_CARRY_LANES, PT_OPT_REFILL_MIN, PT_OPT_RUSSIAN_ROULETTE, PT_OPT_GRID_FIT = 1, 2, 3, 4, 5, 6
+PT_OPT_ERROR_ESTIMATE = 7  # the per-pixel error estimate (pt_error_ptr, pt_resolve_error, pt_error_tiles, pt_error_stats, pt_render_until)
 PT_TIME_STEP_DECORRELATED = 0.3618034  # include/ptrace.h
 NO_SELECTED_OBJECT_ID = 1000  # src/state.rs:12: State.selected_object while the crosshair is on nothing
 BUILD_PLAIN, BUILD_ROULETTE, BUILD_TWIN, BUILD_DEBUG_OVERLAY = 0, 1, 2, 3  # pt_last_trace_build
@@ -153,6 +154,25 @@ class PtStats(C.Structure):
         ("far_rays", C.c_uint64),
         ("grid_kernel_build", C.c_uint32),  # 1 pt_trace_kernel_grid (all staged in the LDS) / 2 _grid_cells / 3 _grid_gmem / 0 no grid
         ("grid_walk_flat", C.c_uint32),  # 1: build 1 on a one-layer grid, the two-axis walk (pt_trace_kernel_grid); 0 with build 1: _grid_layers
+    ]
+
+
+class PtErrorStats(C.Structure):
+    """include/ptrace.h PtErrorStats: the frame's noise figures, summed from the error estimate's tile records."""
+
+    _fields_ = [
+        ("sum_e2", C.c_double),
+        ("sum_m2", C.c_double),
+        ("rel_error", C.c_double),
+        ("rms_error", C.c_double),
+        ("pixels", C.c_uint64),
+        ("pixels_counted", C.c_uint64),
+        ("pixels_short", C.c_uint64),
+        ("pixels_nonfinite", C.c_uint64),
+        ("passes_min", C.c_uint32),
+        ("passes_max", C.c_uint32),
+        ("passes_rendered", C.c_uint32),
+        ("reached", C.c_uint32),
     ]
 
 

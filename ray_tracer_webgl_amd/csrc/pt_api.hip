@@ -120,6 +120,13 @@ struct pt_ctx {
   uint32_t reserved_passes = 1;
   // read-out staging
   DevBuf<float4> d_resolve;
+  // per-pixel error estimate (PT_OPT_ERROR_ESTIMATE; pt_kernels_error.hip): two float4 per local pixel, A = {mean.rgb, n} and
+  // B = {M2.rgb, k}, folded by pt_fold_error_kernel in pt_accumulate_kernel's place; the tile records and their tallies
+  bool err_on = false;
+  bool err_paused = false;          // pt_tune's measuring launches fold the plain way (it clears everything afterwards)
+  int err_spp = 0;                  // samples_per_pixel of the passes folded since the last clear (0 = none yet)
+  DevBuf<float4> d_err;
+  DevBuf<float4> d_err_tiles;       // tiles records, then tiles tallies (pt_error_tiles_kernel)
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   PathTuner geom;
   hipEvent_t trial_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // begin/end per trial
@@ -302,6 +309,23 @@ int ensure_buffers(pt_ctx* c) {
     PT_HIP(c, hipMemsetAsync(c->d_canvas.get(), 0, pix * sizeof(uint32_t), c->stream));
   }
   if (c->d_resolve.capacity() < pix) PT_HIP(c, c->d_resolve.reserve(pix));
+  if (c->err_on) {
+    if (c->d_err.capacity() < 2 * pix) {
+      PT_HIP(c, c->d_err.reserve(2 * pix));
+      PT_HIP(c, hipMemsetAsync(c->d_err.get(), 0, 2 * pix * sizeof(float4), c->stream));
+      c->err_spp = 0;
+    }
+    if (c->d_err_tiles.capacity() < 2 * tiles) PT_HIP(c, c->d_err_tiles.reserve(2 * tiles));
+  }
+  return PT_OK;
+}
+
+// the error estimate speaks for the passes folded since its last clear: cleared wherever the accumulation is cleared or replaced
+int clear_error(pt_ctx* c) {
+  if (!c->err_on) return PT_OK;
+  const size_t pix = (size_t)c->local_rows * c->width;
+  if (pix) PT_HIP(c, hipMemsetAsync(c->d_err.get(), 0, 2 * pix * sizeof(float4), c->stream));
+  c->err_spp = 0;
   return PT_OK;
 }
 
@@ -813,6 +837,7 @@ PT_API int pt_set_params(pt_ctx* c, const PtParams* p) {
     c->captured = false;  // whatever a replayed graph accumulated is gone with the old partition
     // a different set of rows: the accumulated image no longer applies, and neither do the frame textures
     PT_HIP(c, hipMemsetAsync(c->accum, 0, (size_t)c->local_rows * c->width * sizeof(float4), c->stream));
+    if (int rc = clear_error(c); rc != PT_OK) return rc;
     return pt_clear_textures(c);
   }
   c->params = *p;
@@ -861,6 +886,7 @@ PT_API int pt_reset_accum(pt_ctx* c) {
   if (c->accum)
     PT_HIP(c, hipMemsetAsync(c->accum, 0, (size_t)c->local_rows * c->width * sizeof(float4), c->stream));
   PT_HIP(c, hipMemsetAsync(c->d_counters.get(), 0, PT_CTR_COUNT * sizeof(unsigned long long), c->stream));
+  if (int rc = clear_error(c); rc != PT_OK) return rc;
   PT_HIP(c, hipStreamSynchronize(c->stream));
   c->events_used = 0;
   c->kernel_ms = 0.0;
@@ -880,7 +906,7 @@ PT_API int pt_bind_accum(pt_ctx* c, void* dev_ptr, size_t bytes) {
     c->accum = nullptr;
     int rc = ensure_buffers(c);
     c->total_spp = 0;
-    return rc;
+    return rc != PT_OK ? rc : clear_error(c);
   }
   size_t need = (size_t)c->local_rows * c->width * sizeof(float4);
   if (bytes < need) return fail(c, PT_ERR_CAPACITY, "pt_bind_accum: %zu bytes < %zu needed", bytes, need);
@@ -889,7 +915,7 @@ PT_API int pt_bind_accum(pt_ctx* c, void* dev_ptr, size_t bytes) {
   c->accum_pixels = bytes / sizeof(float4);
   c->accum_bound = true;
   c->total_spp = 0; // the caller owns the contents; spp counting restarts
-  return PT_OK;
+  return clear_error(c);  // (and so does the estimate: it knows nothing of what the caller's buffer holds)
 }
 
 PT_API int pt_accum_ptr(pt_ctx* c, void** dev_ptr, size_t* bytes) {
@@ -936,6 +962,7 @@ PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
     return fail(c, PT_ERR_INVALID, "pt_load_accum: sample counts differ across the buffer (%g ... %g): not an accumulation of whole passes",
                 (double)w, (double)ends[1].w);
   PT_HIP(c, hipMemcpyAsync(c->accum, c->d_resolve.get(), need, hipMemcpyDeviceToDevice, c->stream));
+  if (int rc = clear_error(c); rc != PT_OK) return rc;  // (a checkpoint carries sums, not the passes they came from)
   PT_HIP(c, hipStreamSynchronize(c->stream));
   // the host-side mirrors follow the loaded state
   c->total_spp = (uint32_t)w;
@@ -1175,6 +1202,11 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
     return fail(c, PT_ERR_CAPACITY, "pt_render_passes: %u passes > %u reserved (pt_reserve_passes)",
                 n_passes, c->reserved_passes);
   if (c->local_rows == 0) return PT_OK; // this band owns no rows
+  const bool estimate = c->err_on && !c->err_paused;
+  // the estimate folds pass SUMS: every pass since its last clear must hold the same number of samples
+  if (estimate && c->err_spp != 0 && c->err_spp != c->params.samples_per_pixel)
+    return fail(c, PT_ERR_INVALID, "pt_render_passes: %d samples per pixel while the error estimate holds passes of %d: clear first "
+                                   "(pt_reset_accum)", c->params.samples_per_pixel, c->err_spp);
   PT_HIP(c, hipSetDevice(c->device));
 
   Launch L;
@@ -1238,9 +1270,19 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
   }
 
   uint32_t n_pix = c->local_rows * c->width;
-  hipLaunchKernelGGL(pt_accumulate_kernel, dim3(grid_for(n_pix, 256, 2048)), dim3(256), 0, c->stream,
-                     c->accum, c->d_slab.get(), n_pix, n_passes);
-  PT_HIP(c, hipGetLastError());
+  if (estimate) {  // the same adds into accum, and the estimate's update beside them (pt_kernels_error.hip)
+    float4* accum = c->accum;
+    float4* est = c->d_err.get();
+    const float4* slab = c->d_slab.get();
+    uint32_t passes = n_passes;
+    void* kargs[] = {&accum, &est, &slab, &n_pix, &passes};
+    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD), dim3(grid_for(n_pix, 256, 2048)), dim3(256), kargs, 0, c->stream));
+    c->err_spp = p.samples_per_pixel;
+  } else {
+    hipLaunchKernelGGL(pt_accumulate_kernel, dim3(grid_for(n_pix, 256, 2048)), dim3(256), 0, c->stream,
+                       c->accum, c->d_slab.get(), n_pix, n_passes);
+    PT_HIP(c, hipGetLastError());
+  }
 
   // Host-side tallies describe work enqueued directly.  A captured launch runs as often as its
   // graph is replayed, which the host cannot see: read-out takes its divisor from the device
@@ -1628,6 +1670,126 @@ PT_API int pt_blend_rgba8(pt_ctx* c, const uint8_t* prev, uint8_t* out) {
   return resolve_common(c, out, 1, 2, prev);
 }
 
+// ---- the error estimate's read-out (include/ptrace.h; kernels: pt_kernels_error.hip) ------------------------------------
+PT_API int pt_error_ptr(pt_ctx* c, void** dev_ptr, size_t* bytes) {
+  if (!c || !dev_ptr) return fail(c, PT_ERR_INVALID, "pt_error_ptr: NULL argument");
+  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_ptr: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+  *dev_ptr = c->d_err.get();
+  if (bytes) *bytes = (size_t)c->local_rows * c->width * 2 * sizeof(float4);
+  return PT_OK;
+}
+
+PT_API int pt_resolve_error(pt_ctx* c, float* rgba_out) {
+  if (!c || !rgba_out) return fail(c, PT_ERR_INVALID, "pt_resolve_error: NULL argument");
+  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_resolve_error: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+  PT_HIP(c, hipSetDevice(c->device));
+  uint32_t n_pix = c->local_rows * c->width;
+  if (n_pix == 0) return PT_OK;
+  const float4* est = c->d_err.get();
+  float4* out = c->d_resolve.get();
+  void* kargs[] = {&est, &out, &n_pix};
+  PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_RESOLVE), dim3(grid_for(n_pix, 256, 2048)), dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, hipMemcpyAsync(rgba_out, c->d_resolve.get(), (size_t)n_pix * sizeof(float4), hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+// the tile kernel over the current state: records into d_err_tiles[0, n), tallies into [n, 2 n); enqueued, not awaited
+static int launch_error_tiles(pt_ctx* c, uint32_t* tx, uint32_t* ty) {
+  *tx = (c->width + 7) / 8;
+  *ty = (c->local_rows + 7) / 8;
+  uint32_t n_tiles = *tx * *ty;
+  if (n_tiles == 0) return PT_OK;
+  const float4* est = c->d_err.get();
+  float4* tiles = c->d_err_tiles.get();
+  float4* aux = tiles + n_tiles;
+  uint32_t width = c->width, rows = c->local_rows, tiles_x = *tx;
+  void* kargs[] = {&est, &tiles, &aux, &width, &rows, &tiles_x, &n_tiles};
+  // four waves, hence four tiles, per workgroup
+  PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_TILES), dim3(grid_for(n_tiles, 4, 4096)), dim3(256), kargs, 0, c->stream));
+  return PT_OK;
+}
+
+PT_API int pt_error_tiles(pt_ctx* c, float* tiles_out, uint32_t* tiles_x, uint32_t* tiles_y) {
+  if (!c) return PT_ERR_INVALID;
+  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_tiles: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+  uint32_t tx = (c->width + 7) / 8, ty = (c->local_rows + 7) / 8;
+  if (tiles_x) *tiles_x = tx;
+  if (tiles_y) *tiles_y = ty;
+  if (!tiles_out || tx * ty == 0) return PT_OK;
+  PT_HIP(c, hipSetDevice(c->device));
+  if (int rc = launch_error_tiles(c, &tx, &ty); rc != PT_OK) return rc;
+  PT_HIP(c, hipMemcpyAsync(tiles_out, c->d_err_tiles.get(), (size_t)tx * ty * sizeof(float4), hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+PT_API int pt_error_stats(pt_ctx* c, PtErrorStats* out) {
+  if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_error_stats: NULL argument");
+  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_stats: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+  memset(out, 0, sizeof *out);
+  out->pixels = (uint64_t)c->local_rows * c->width;
+  PT_HIP(c, hipSetDevice(c->device));
+  uint32_t tx = 0, ty = 0;
+  if (int rc = launch_error_tiles(c, &tx, &ty); rc != PT_OK) return rc;
+  const size_t n_tiles = (size_t)tx * ty;
+  if (n_tiles == 0) return PT_OK;
+  std::vector<float4> h(2 * n_tiles);
+  PT_HIP(c, hipMemcpyAsync(h.data(), c->d_err_tiles.get(), 2 * n_tiles * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  // in tile index order, in double
+  double E = 0.0, M = 0.0;
+  uint64_t counted = 0, n_short = 0, n_bad = 0;
+  float nmin = 0.f, nmax = 0.f;
+  for (size_t t = 0; t < n_tiles; t++) {
+    const float4 r = h[t], a = h[n_tiles + t];
+    E += (double)r.x;
+    M += (double)r.y;
+    if (r.z > 0.0f) {
+      nmin = counted ? std::fmin(nmin, r.w) : r.w;
+      nmax = std::fmax(nmax, a.z);
+    }
+    counted += (uint64_t)r.z;
+    n_short += (uint64_t)a.x;
+    n_bad += (uint64_t)a.y;
+  }
+  out->sum_e2 = E;
+  out->sum_m2 = M;
+  out->rel_error = M > 0.0 ? std::sqrt(E / M) : 0.0;
+  out->rms_error = counted ? std::sqrt(E / (3.0 * (double)counted)) : 0.0;
+  out->pixels_counted = counted;
+  out->pixels_short = n_short;
+  out->pixels_nonfinite = n_bad;
+  out->passes_min = nmin < 4294967040.0f ? (uint32_t)nmin : 0xffffffffu;
+  out->passes_max = nmax < 4294967040.0f ? (uint32_t)nmax : 0xffffffffu;
+  return PT_OK;
+}
+
+PT_API int pt_render_until(pt_ctx* c, float target_rel_error, uint32_t passes_per_launch, uint32_t max_passes, PtErrorStats* out) {
+  if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_render_until: NULL argument");
+  if (!c->err_on) return fail(c, PT_ERR_INVALID, "pt_render_until: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+  if (!(target_rel_error > 0.0f) || !std::isfinite(target_rel_error))
+    return fail(c, PT_ERR_INVALID, "pt_render_until: the target must be finite and positive");
+  if (passes_per_launch == 0 || max_passes == 0) return fail(c, PT_ERR_INVALID, "pt_render_until: no passes to render");
+  if (passes_per_launch > c->reserved_passes)
+    return fail(c, PT_ERR_CAPACITY, "pt_render_until: %u passes per launch > %u reserved (pt_reserve_passes)", passes_per_launch,
+                c->reserved_passes);
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_render_until: synchronises; not inside a stream capture");
+  uint32_t done = 0;
+  for (;;) {
+    const uint32_t k = passes_per_launch < max_passes - done ? passes_per_launch : max_passes - done;
+    if (int rc = pt_render_passes(c, k); rc != PT_OK) return rc;
+    // the frame is the frame one uninterrupted call would give: the next launch goes on where this one ended
+    c->params.first_pass += k;
+    c->epoch++;
+    done += k;
+    if (int rc = pt_error_stats(c, out); rc != PT_OK) return rc;
+    out->passes_rendered = done;
+    out->reached = (out->rel_error <= (double)target_rel_error && out->pixels_short == 0) ? 1u : 0u;
+    if (out->reached || done >= max_passes) return PT_OK;
+  }
+}
+
 PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
   if (!c || !out) return PT_ERR_INVALID;
   PT_HIP(c, hipSetDevice(c->device));
@@ -1710,6 +1872,27 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: grid fit mode %d", value);
     c->grid_fit_mode = value;
     return PT_OK;
+  }
+  if (key == PT_OPT_ERROR_ESTIMATE) { // the image does not depend on it; the state is allocated and zeroed here, released when turned off
+    if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: error estimate %d", value);
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipStreamSynchronize(c->stream));  // (a fold in flight reads the state)
+    if (!value) {
+      c->err_on = false;
+      c->err_spp = 0;
+      c->d_err = DevBuf<float4>();
+      c->d_err_tiles = DevBuf<float4>();
+      return PT_OK;
+    }
+    if (c->err_on) return PT_OK;
+    // (asking for a kernel's attributes loads the estimate's code object now: a set-up call's work, not a captured launch's)
+    hipFuncAttributes attr;
+    PT_HIP(c, hipFuncGetAttributes(&attr, pt_error_kernel(PT_E_FOLD)));
+    c->err_on = true;
+    int rc = ensure_buffers(c);
+    if (rc == PT_OK) rc = clear_error(c);
+    if (rc != PT_OK) { c->err_on = false; c->d_err = DevBuf<float4>(); c->d_err_tiles = DevBuf<float4>(); }
+    return rc;
   }
   return fail(c, PT_ERR_INVALID, "pt_set_option: unknown key %d", key);
 }
@@ -1870,6 +2053,9 @@ PT_API int pt_grid_fit(pt_ctx* c) {
 
 PT_API int pt_tune(pt_ctx* c, uint32_t n_passes) {
   if (!c || n_passes == 0) return fail(c, PT_ERR_INVALID, "pt_tune: bad argument");
+  // measuring launches are not part of any frame: they fold the plain way, and whatever they launched is cleared below
+  struct Pause { pt_ctx* c; ~Pause() { c->err_paused = false; } } pause{c};
+  c->err_paused = true;
   bool launched = false;
   if (c->have_spheres) {
     int rc = tune_grid_to_view(c, n_passes, &launched);

@@ -1,0 +1,139 @@
+// pt_kernels_error.hip — the PER-PIXEL ERROR ESTIMATE (pt_set_option PT_OPT_ERROR_ESTIMATE; include/ptrace.h, DESIGN.md
+// §error estimate), a translation unit and gfx950 code object of its own: the HIP runtime loads it when the estimate is
+// first turned on, so a context that never asks for it pays nothing.  Three kernels, none of them a trace kernel:
+//   pt_fold_error_kernel     takes pt_accumulate_kernel's place: the same four fp32 adds per pass in the same order (accum
+//                            keeps its bits) and, beside them, Welford's update of the pass sums' mean and M2 per channel
+//   pt_resolve_error_kernel  the standard error of each pixel's mean as linear radiance
+//   pt_error_tiles_kernel    per 8x8 tile of the local rows, one wave64: sums of se^2 and mean^2 over the counted pixels
+// The arithmetic is a contract (tests/error_ref.py restates it statement by statement): ONE IEEE fp32 operation per
+// statement, nothing fused (-ffp-contract=off), `/` and sqrtf correctly rounded.  pt_api.hip reaches the kernels through
+// pt_error_kernel() only.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "pt_extra.h"
+
+// state per pixel i: est[2 i] = A = {mean.r, mean.g, mean.b, n}, est[2 i + 1] = B = {M2.r, M2.g, M2.b, k}
+// (n passes folded, k their samples: both live in the buffer, like accum.w, so a hipGraph replay keeps them right)
+__device__ __forceinline__ void welford(float x, float n, float& mean, float& m2) {
+  const float d = x - mean;
+  const float q = d / n;
+  mean = mean + q;
+  const float e = x - mean;
+  const float t = d * e;
+  m2 = m2 + t;
+}
+
+extern "C" __global__ __launch_bounds__(256) void pt_fold_error_kernel(float4* accum, float4* est, const float4* slab,
+                                                                       uint32_t n_pix, uint32_t n_passes) {
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += stride) {
+    float4 acc = accum[i];
+    float4 a = est[2 * (size_t)i], b = est[2 * (size_t)i + 1];
+    for (uint32_t p = 0; p < n_passes; p++) {
+      const float4 s = slab[(size_t)p * n_pix + i];
+      acc.x += s.x; acc.y += s.y; acc.z += s.z; acc.w += s.w;
+      a.w = a.w + 1.0f;
+      b.w = b.w + s.w;
+      welford(s.x, a.w, a.x, b.x);
+      welford(s.y, a.w, a.y, b.y);
+      welford(s.z, a.w, a.z, b.z);
+    }
+    accum[i] = acc;
+    est[2 * (size_t)i] = a;
+    est[2 * (size_t)i + 1] = b;
+  }
+}
+
+// what a pixel's state reads as: se = sqrt(M2 / (n (n - 1))) n / k, the estimate's own mean m = mean n / k
+struct PixelError { float se[3], m[3]; bool known; };
+__device__ __forceinline__ PixelError pixel_error(const float4 a, const float4 b) {
+  PixelError r;
+  const float n = a.w, k = b.w;
+  r.known = (n >= 2.0f) && (k > 0.0f);
+  const float q = n / k;
+  const float n1 = n - 1.0f;
+  const float nn = n * n1;
+  const float mean[3] = {a.x, a.y, a.z}, m2[3] = {b.x, b.y, b.z};
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const float v = m2[c] / nn;
+    const float s = __builtin_sqrtf(v);
+    r.se[c] = r.known ? s * q : 0.0f;
+    r.m[c] = r.known ? mean[c] * q : 0.0f;
+  }
+  return r;
+}
+
+extern "C" __global__ __launch_bounds__(256) void pt_resolve_error_kernel(const float4* est, float4* out, uint32_t n_pix) {
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += stride) {
+    const float4 a = est[2 * (size_t)i], b = est[2 * (size_t)i + 1];
+    const PixelError r = pixel_error(a, b);
+    out[i] = make_float4(r.se[0], r.se[1], r.se[2], a.w);
+  }
+}
+
+__device__ __forceinline__ bool finite3(const float v[3]) {
+  return __builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) && __builtin_isfinite(v[2]);
+}
+
+// One wave64 per 8x8 tile (the work queue's tiles, of the context's LOCAL rows); lane l owns pixel (8 tx + l % 8, 8 ty + l / 8).
+// The wave reduces with the fixed tree  for off in 32, 16, 8, 4, 2, 1: v[l] = v[l] + v[l + off] (l < off)  through cross-lane
+// moves (__shfl_down: a lane at or above `off` computes something nobody reads), so a tile's record depends on the state
+// alone — not on the launch shape, which only decides which wave takes which tile.
+//   tiles[t] = {sum e, sum m2, counted lanes, min n over counted lanes (0 if none)}
+//   aux[t]   = {lanes with !(n >= 2), lanes with n >= 2 that are not counted (k <= 0 or NaN, se or m not finite),
+//               max n over counted lanes (0 if none), 0}                                   (what pt_error_stats adds up)
+extern "C" __global__ __launch_bounds__(256) void pt_error_tiles_kernel(const float4* est, float4* tiles, float4* aux,
+                                                                        uint32_t width, uint32_t rows, uint32_t tiles_x,
+                                                                        uint32_t n_tiles) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+  for (uint32_t t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); t < n_tiles; t += waves) {
+    const uint32_t x = 8u * (t % tiles_x) + (lane & 7u), y = 8u * (t / tiles_x) + (lane >> 3);
+    const bool inside = x < width && y < rows;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+    if (inside) {
+      const size_t i = (size_t)y * width + x;
+      a = est[2 * i];
+      b = est[2 * i + 1];
+    }
+    const PixelError r = pixel_error(a, b);
+    const bool counted = inside && r.known && finite3(r.se) && finite3(r.m);
+    const float e01 = r.se[0] * r.se[0], e1 = r.se[1] * r.se[1], e2 = r.se[2] * r.se[2];
+    const float m01 = r.m[0] * r.m[0], m1 = r.m[1] * r.m[1], m2 = r.m[2] * r.m[2];
+    const float es = e01 + e1, ms = m01 + m1;
+    float e = counted ? es + e2 : 0.0f;
+    float m = counted ? ms + m2 : 0.0f;
+    float cnt = counted ? 1.0f : 0.0f;
+    float nmin = counted ? a.w : __builtin_inff();
+    float nmax = counted ? a.w : 0.0f;
+    const bool is_short = inside && !(a.w >= 2.0f);
+    float n_short = is_short ? 1.0f : 0.0f;
+    float n_bad = (inside && !is_short && !counted) ? 1.0f : 0.0f;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      e = e + __shfl_down(e, off, 64);
+      m = m + __shfl_down(m, off, 64);
+      cnt = cnt + __shfl_down(cnt, off, 64);
+      n_short = n_short + __shfl_down(n_short, off, 64);
+      n_bad = n_bad + __shfl_down(n_bad, off, 64);
+      nmin = fminf(nmin, __shfl_down(nmin, off, 64));
+      nmax = fmaxf(nmax, __shfl_down(nmax, off, 64));
+    }
+    if (lane == 0u) {
+      tiles[t] = make_float4(e, m, cnt, cnt > 0.0f ? nmin : 0.0f);
+      aux[t] = make_float4(n_short, n_bad, nmax, 0.0f);
+    }
+  }
+}
+
+extern "C" const void* pt_error_kernel(int id) {
+  switch (id) {
+    case PT_E_FOLD: return reinterpret_cast<const void*>(pt_fold_error_kernel);
+    case PT_E_RESOLVE: return reinterpret_cast<const void*>(pt_resolve_error_kernel);
+    case PT_E_TILES: return reinterpret_cast<const void*>(pt_error_tiles_kernel);
+    default: return nullptr;
+  }
+}

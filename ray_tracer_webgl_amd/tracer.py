@@ -273,6 +273,68 @@ class PathTracer:
                              % (a.shape, (self.local_rows, self.width, 4)))
         self._check(self.lib.pt_load_accum(self._ctx, a.ctypes.data_as(C.c_void_p), a.nbytes))
 
+    # -- the per-pixel error estimate (include/ptrace.h PT_OPT_ERROR_ESTIMATE) --------------------
+    def error_estimate(self, on=True):
+        """Keep a per-pixel error estimate beside the accumulation: mean and M2 of the pass sums (batch means), folded
+        by the kernel that folds the slabs.  Off by default; the image bits are the same either way.  The estimate
+        speaks for the passes folded since its last clear (reset, tune, resize, repartition, load_accum, bind), all of
+        which must have the same samples_per_pixel, and assumes independent passes (time_step such as
+        abi.PT_TIME_STEP_DECORRELATED)."""
+        self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_ERROR_ESTIMATE, 1 if on else 0))
+
+    def error_state(self):
+        """The raw state (local_rows, width, 2, 4) fp32: [..., 0, :] = {mean.rgb, n}, [..., 1, :] = {M2.rgb, k}."""
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        self._check(self.lib.pt_error_ptr(self._ctx, C.byref(ptr), C.byref(nbytes)))
+        self.synchronize()
+        out = np.empty((self.local_rows, self.width, 2, 4), dtype=np.float32)
+        assert out.nbytes == nbytes.value
+        if out.size:
+            _memcpy(out.ctypes.data_as(C.c_void_p), ptr, out.nbytes, _D2H)
+        return out
+
+    def load_error_state(self, state):
+        """Overwrite the raw state (tests and checkpoints): the inverse of error_state()."""
+        a = np.ascontiguousarray(state, dtype=np.float32)
+        if a.shape != (self.local_rows, self.width, 2, 4):
+            raise ValueError("error state is %s, this context holds %s" % (a.shape, (self.local_rows, self.width, 2, 4)))
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        self._check(self.lib.pt_error_ptr(self._ctx, C.byref(ptr), C.byref(nbytes)))
+        self.synchronize()
+        if a.size:
+            _memcpy(ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, _H2D)
+
+    def error_image(self):
+        """(local_rows, width, 4) fp32: the standard error of each pixel's mean as linear radiance, a = passes folded."""
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
+        if out.size:
+            self._check(self.lib.pt_resolve_error(self._ctx, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def error_tiles(self):
+        """(tiles_y, tiles_x, 4) fp32 per 8x8 tile of the local rows: {sum se^2, sum mean^2, counted pixels, min passes}."""
+        tx, ty = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.pt_error_tiles(self._ctx, None, C.byref(tx), C.byref(ty)))
+        out = np.empty((ty.value, tx.value, 4), dtype=np.float32)
+        if out.size:
+            self._check(self.lib.pt_error_tiles(self._ctx, out.ctypes.data_as(C.c_void_p), C.byref(tx), C.byref(ty)))
+        return out
+
+    def error_stats(self):
+        st = abi.PtErrorStats()
+        self._check(self.lib.pt_error_stats(self._ctx, C.byref(st)))
+        return st
+
+    def render_until(self, target, passes_per_launch, max_passes):
+        """Render until the frame's relative error (error_stats().rel_error) is at most `target`, passes_per_launch
+        passes at a time, at most max_passes; returns the PtErrorStats of the last look (passes_rendered, reached).
+        The context's first_pass advances by the passes rendered: a second call continues the same frame."""
+        st = abi.PtErrorStats()
+        self._check(self.lib.pt_render_until(self._ctx, float(target), int(passes_per_launch), int(max_passes), C.byref(st)))
+        if self.params is not None:
+            self.params.first_pass += st.passes_rendered
+        return st
+
     def stats(self):
         st = abi.PtStats()
         self._check(self.lib.pt_get_stats(self._ctx, C.byref(st)))
@@ -286,6 +348,22 @@ class PathTracer:
                               out.ctypes.data_as(C.c_void_p), out.size, int(n))
         )
         return out
+
+
+_D2H, _H2D = 2, 1  # hipMemcpyDeviceToHost, hipMemcpyHostToDevice
+
+
+def _memcpy(dst, src, nbytes, kind):
+    """hipMemcpy of the HIP runtime this process already holds (the one serving libptrace.so, _lib.py): the raw error
+    state is reached through its device pointer, like pt_accum_ptr's buffer."""
+    hip = getattr(_memcpy, "hip", None)
+    if hip is None:
+        mapped = [ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln]
+        hip = _memcpy.hip = C.CDLL(mapped[0] if mapped else "libamdhip64.so")
+        hip.hipMemcpy.restype, hip.hipMemcpy.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    rc = hip.hipMemcpy(dst, src, nbytes, kind)
+    if rc != 0:
+        raise PtError(abi.PT_ERR_HIP, "hipMemcpy failed with %d" % rc)
 
 
 def render_scene(scene, device=0, use_torch=False, passes_per_launch=None, band=None, geometry_path=None, tune=None, overlay=None):
