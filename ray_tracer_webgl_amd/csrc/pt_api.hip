@@ -24,6 +24,7 @@
 #include "../../include/ptrace_dev.h"
 #include "pt_bvh.hpp"
 #include "pt_grid.hpp"
+#include "pt_grid_records.hpp"
 #include "pt_extra.h"
 #include "pt_kernel_args.h"
 #include "pt_geom_plan.hpp"
@@ -145,6 +146,7 @@ struct pt_ctx {
   std::vector<float> h_geom, h_radii;
   std::vector<PtMatRec> h_mat;
   DevBuf<uint32_t> d_grid_cells;
+  DevBuf<uint32_t> d_grid_ring;  // a one-layer grid's records once more, in the ring layout the two-axis walk reads (pt_grid_records.hpp)
   DevBuf<float> d_grid_entries;  // 16 B per entry
   DevBuf<uint32_t> d_grid_index;
   DevBuf<PtMatRec> d_grid_mat;
@@ -403,10 +405,16 @@ int fit_state(const pt_ctx* c) {
   return grid_fit_state(c->geom.grid_in_use(c->have_grid), need_factor(c), (double)c->grid.near_factor);
 }
 
+// cell records a build that stages them copies into the LDS: a one-layer grid's in the ring layout (pt_grid_records.hpp; the
+// builds that walk such a grid along three axes stage the plain array into the same room)
+uint64_t staged_cells(const ptgrid::Grid& g) {
+  return g.n[1] == 1u ? ptrec::ring_cells(g.n[0], g.n[2]) : (uint64_t)g.n[0] * g.n[1] * g.n[2];
+}
+
 // the build of the grid kernel the next launch gets and the bytes it stages (with a grid)
 Staging grid_build(const pt_ctx* c) {
   const ptgrid::Grid& g = c->grid;
-  return grid_staging((uint64_t)g.n[0] * g.n[1] * g.n[2], g.n_entries, walk_lds_room(), c->grid_cells_build, fit_state(c));
+  return grid_staging(staged_cells(g), g.n_entries, walk_lds_room(), c->grid_cells_build, fit_state(c));
 }
 
 // a kernel of pt_kernels_extra.hip; its first use loads that code object and lifts its dynamic-LDS limit
@@ -595,14 +603,16 @@ namespace {
 bool build_grid(const float* geom, const float* radii, uint32_t n, double near_factor, ptgrid::Grid* grid) {
   if (!ptgrid::build(geom, radii, n, grid, near_factor)) return false;
   // entries that will not be staged in the LDS (bind_grid) are gathered from L2: their runs in Morton order of the cells
-  if (PT_GRID_LDS_CELLS(grid->cells.size()) + (size_t)grid->n_entries * 16 > walk_lds_room()) {
+  if (PT_GRID_LDS_CELLS(staged_cells(*grid)) + (size_t)grid->n_entries * 16 > walk_lds_room()) {
     int mode = 2;
 #ifdef PT_DEV_KNOBS  // A/B only: PT_PAD_RUNS = 0 plain layout, 1 padded runs in Morton order, 2 Morton order (default), 3 padded runs
     if (getenv("PT_PAD_RUNS")) mode = atoi(getenv("PT_PAD_RUNS"));
 #endif
     if (mode) (void)ptgrid::morton_runs(grid, mode != 2, mode != 3);
   }
-  return true;
+  // the device record's entry field (pt_grid_records.hpp), checked on the layout that is uploaded (padded runs are longer):
+  // no grid, as when the host format overflows
+  return ptrec::fits(grid->n_entries);
 }
 
 // upload a grid (the caller has made sure that nothing in flight reads the previous one); empties the host arrays of `grid`
@@ -618,7 +628,19 @@ int install_grid(pt_ctx* c, ptgrid::Grid& grid, const PtMatRec* mat, uint32_t n)
   if (c->d_grid_index.capacity() < n_ent_pad) PT_HIP(c, c->d_grid_index.reserve(n_ent_pad));
   if (c->d_grid_mat.capacity() < n_ent_pad) PT_HIP(c, c->d_grid_mat.reserve(n_ent_pad));
   PT_HIP(c, hipMemset(c->d_grid_cells.get(), 0, n_cells_pad * sizeof(uint32_t)));
-  PT_HIP(c, hipMemcpy(c->d_grid_cells.get(), grid.cells.data(), grid.cells.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  {
+    // the device reads derived records (pt_grid_records.hpp): what a leaf round would decode from `first | count << 24`, made once
+    std::vector<uint32_t> recs(grid.cells.size());
+    for (size_t k = 0; k < recs.size(); k++) recs[k] = ptrec::from_host(grid.cells[k]);
+    PT_HIP(c, hipMemcpy(c->d_grid_cells.get(), recs.data(), recs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (grid.n[1] == 1u) {  // ... and in the ring layout, for the two-axis walk
+      const size_t n_ring = (size_t)ptrec::ring_cells(grid.n[0], grid.n[2]), n_ring_pad = (n_ring + 3u) & ~(size_t)3u;
+      recs.assign(n_ring_pad, ptrec::kOutside);
+      ptrec::ring_layout(grid.cells.data(), grid.n[0], grid.n[2], recs.data());
+      if (c->d_grid_ring.capacity() < n_ring_pad) PT_HIP(c, c->d_grid_ring.reserve(n_ring_pad));
+      PT_HIP(c, hipMemcpy(c->d_grid_ring.get(), recs.data(), n_ring_pad * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+  }
   PT_HIP(c, hipMemset(c->d_grid_entries.get(), 0, n_ent_pad * 16));
   PT_HIP(c, hipMemcpy(c->d_grid_entries.get(), grid.entries.data(), (size_t)grid.n_entries * 16, hipMemcpyHostToDevice));
   PT_HIP(c, hipMemset(c->d_grid_index.get(), 0xff, n_ent_pad * sizeof(uint32_t)));
@@ -1167,6 +1189,12 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
                                 : (path == PT_GEOM_LDS ? ROW_LIST_LDS : (have_lds ? ROW_SCALAR : ROW_SCALAR_NOLDS));
   }
   const int build = dbg ? BUILD_DBG : (rr ? BUILD_RR : (c->count_work ? BUILD_TWIN : BUILD_PLAIN));
+  // the two-axis walk (pt_trace_kernel_grid and its twin; the roulette and overlay builds of that row walk three axes) reads
+  // the ring layout; it is what `scene` was sized for (staged_cells)
+  if (walk && path == PT_GEOM_GRID && row == ROW_GRID && (build == BUILD_PLAIN || build == BUILD_TWIN)) {
+    A.grid_cells = c->d_grid_ring.get();
+    A.n_cells = (uint32_t)ptrec::ring_cells(c->grid.n[0], c->grid.n[2]);
+  }
   const TraceKernel& tk = kTraceKernels[row][build];
   const void* kfn = tk.main ? tk.main
                             : (tk.debug >= 0 ? debug_kernel(c->device, tk.debug)

@@ -16,6 +16,8 @@
 // inflated by its own delta(D); if it enters, the ray is handed over whole: to the literal loop over the
 // list, or (kernels whose entries do not fit the LDS: long lists) to the wave, 64 spheres at a time
 // (pt_kernels.hip).
+// The cell records the kernels read are the host's `first | count << 24` re-encoded at upload (pt_grid_records.hpp): the set
+// and the order of the entries looked at are unchanged, so the argument stands as written.
 // Host-side check of the claim (registration invariant, the bound, a numpy emulation of this walk
 // against brute force): tests/test_grid.py.
 //
@@ -36,6 +38,7 @@
 // is order-free).  The images are the same bits.  tests/test_grid_flat.py emulates both walks: identical cells and exit
 // times with the unwidened planes, a prefix-and-later relation with the widened ones.
 #pragma once
+#include "pt_grid_records.hpp"
 #include "pt_scene.hpp"
 
 namespace ptk {
@@ -148,7 +151,7 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
   const float tdx = K.grid_h[0] * __builtin_fabsf(ix), tdz = K.grid_h[2] * __builtin_fabsf(iz);
   const int gnx = (int)K.grid_n[0], gnz = (int)K.grid_n[2];
   const int sdx = posx ? 1 : -1;
-  // (one layer: no y step; its time is a constant of the ray and a z step is a row of gnx cells)
+  // (one layer: no y step; its time is a constant of the ray and a z step is a row of the ring layout: gnx + 2 records)
   float tdy = 0.0f;
   int gny = 1, sdy = 0;
   if constexpr (!S::FLAT_Y) {
@@ -156,10 +159,12 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
     gny = (int)K.grid_n[1];
     sdy = posy ? gnx : -gnx;
   }
-  const int sdz = posz ? gnx * gny : -(gnx * gny);
+  const int row = S::FLAT_Y ? gnx + (int)ptrec::kRing2 : gnx;
+  const int sdz = posz ? row * gny : -(row * gny);
 
   // entry: where does the half-line meet the grid's box?
   if (!carried) { rem = 0u; pend = 0u; }
+  if constexpr (S::FLAT_Y) { if (!carried) cell = 0u; }  // (one layer: `cell` is the walking flag, see the cell step)
   if (pt_ballot(fresh) != 0ull) {
     if (fresh) tally.flag(PT_REG_WALK_ENTRY);
     // near rays (|o - c0| + s0 <= d_near, tested on squares: grid_r2_near = (0.9999 d_near - s0)^2):
@@ -213,9 +218,8 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
         tmx = __builtin_fmaxf(fma_(bx, ix, -oix), tn);
         tmy = __builtin_fmaxf(t1y, t2y);
         tmz = __builtin_fmaxf(fma_(bz, iz, -oiz), tn);
-        // steps left before the walk leaves the grid, + 1: the x and z fields of the three-axis walk
-        rem = (uint32_t)((posx ? nx1 - cx : cx) + 1) | ((uint32_t)((posz ? nz1 - cz : cz) + 1) << 20);
-        cell = (uint32_t)cz * (uint32_t)gnx + (uint32_t)cx;
+        // the cell's index in the ring layout; no step counters: the walk ends on the ring's record
+        cell = (uint32_t)(cz + 1) * (uint32_t)row + (uint32_t)(cx + 1);
       }
     } else
     if (enter) {
@@ -248,6 +252,8 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
   }
 
   tally.phase(3);
+  // is this lane's walk still on?  Three axes: step counters left.  One layer: it stands on a record (index 0 is the ring's corner)
+  auto on = [&]() -> bool { if constexpr (S::FLAT_Y) return cell != 0u; else return rem != 0u; };
   uint32_t walk_iters = 0;
   const uint32_t carry_base = A.carry_lanes, carry_slope = A.carry_lanes != 0u ? 4u : 0u; // (0: nobody is left behind)
   const uint32_t half_live = ((uint32_t)n_live + 1u) >> 1;
@@ -255,16 +261,21 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
     // advance: a lane without a cell under test looks at the cell it stands in, notes its
     // exit time, and steps on; it leaves this loop with a non-empty cell or with its walk over
     // (ballots of single compares, joined as masks: a ballot of `a && b` goes through a VGPR)
-    unsigned long long m_mv = pt_ballot(rem != 0u) & pt_ballot(pend < 0x1000000u);
+    unsigned long long m_mv = pt_ballot(on()) & pt_ballot(pend < ptrec::kNone);
     // The FIRST cell step is written out in front of the loop: one step per leaf round is the common case, and a TAKEN
     // branch is a ~30-tick bubble in its wave (tools/micro/valu_chain.hip) — the loop as the compiler lays it out takes
     // three (entry, back-edge, exit) for its one trip, this form none: config 2 -0.8 %, a band of eight -1.4 %, config 5
     // -1.2 % (profiles/r04_ab_runs.txt).
     // (one layer: x steps when its time is the smallest; otherwise z steps — unless the ray's exit from the layer is the
     // smallest, which ends the walk exactly as running out of the y field does in the three-axis step)
+    // THE RING.  The one-layer walk reads its records from the ring layout of pt_grid_records.hpp: the nx x nz real cells inside
+    // a border of "outside" records (0: no entries — so nothing is tested and nothing is pending — and unlike any real cell's
+    // record).  A step that leaves the grid sideways lands on the ring, and the NEXT step reads that record and ends the walk:
+    // no step counters to fill, decrement and test, and `cell` itself is the walking flag (a real cell's index is never 0).
+    // Real cells are visited in the same order with the same tmin / t_exit; a lane that leaves sideways pays one more step.
 #define PT_CELL_STEP_FLAT \
         tally.walk(m_mv); \
-        if (rem != 0u && pend < 0x1000000u) { \
+        if (cell != 0u && pend < ptrec::kNone) { \
           const uint32_t rec = S::cell_at(A, cell); \
           const float tmin = __builtin_fminf(__builtin_fminf(tmx, tmy), tmz); \
           const bool isx = tmx == tmin; \
@@ -273,15 +284,12 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
           pend = rec; \
           tmx += isx ? tdx : 0.0f; \
           tmz += isx ? 0.0f : tdz; \
-          const uint32_t dec = isx ? 1u : 1048576u; \
-          rem -= dec; \
-          const bool out = (rem & (dec * 1023u)) == 0u; \
           cell += (uint32_t)(isx ? sdx : sdz); \
-          rem = (out || endy || ((rec >> 24) == 0u && closest < tmin)) ? 0u : rem; \
+          cell = (rec == ptrec::kOutside || endy || (rec < ptrec::kNone && closest < tmin)) ? 0u : cell; \
         }
 #define PT_CELL_STEP_XYZ \
         tally.walk(m_mv); \
-        if (rem != 0u && pend < 0x1000000u) { \
+        if (rem != 0u && pend < ptrec::kNone) { \
           const uint32_t rec = S::cell_at(A, cell); \
           const float tmin = __builtin_fminf(__builtin_fminf(tmx, tmy), tmz); \
           const bool isx = tmx == tmin; \
@@ -296,24 +304,24 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
           rem -= dec; \
           const bool out = (rem & (dec * 1023u)) == 0u; \
           cell += (uint32_t)(isx ? sdx : (isy ? sdy : sdz)); \
-          rem = (out || ((rec >> 24) == 0u && closest < tmin)) ? 0u : rem; \
+          rem = (out || (rec < ptrec::kNone && closest < tmin)) ? 0u : rem; \
         }
 #define PT_CELL_STEP \
         if constexpr (S::FLAT_Y) { PT_CELL_STEP_FLAT } else { PT_CELL_STEP_XYZ }
     if (m_mv != 0ull) {
       tally.walk_first();
       PT_CELL_STEP
-      m_mv = pt_ballot(rem != 0u) & pt_ballot(pend < 0x1000000u);
+      m_mv = pt_ballot(on()) & pt_ballot(pend < ptrec::kNone);
       while (__builtin_expect(m_mv != 0ull, 0)) {
         PT_CELL_STEP
-        m_mv = pt_ballot(rem != 0u) & pt_ballot(pend < 0x1000000u);
+        m_mv = pt_ballot(on()) & pt_ballot(pend < ptrec::kNone);
       }
     }
 #undef PT_CELL_STEP
 #undef PT_CELL_STEP_FLAT
 #undef PT_CELL_STEP_XYZ
     tally.phase(4);
-    const bool has = (pend >> 24) != 0u;
+    const bool has = pend >= ptrec::kNone;
     const unsigned long long m_has = pt_ballot(has);
     if (m_has == 0ull) break; // no cell under test and nobody can move: every walk is over
     tally.leaf(m_has);
@@ -327,8 +335,7 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
       // gathers they cost in trips of this loop, each a dependent round trip to the L1.  Four it stays.
       constexpr uint32_t G = S::WALK == 4 ? 4u : (uint32_t)PT_LEAF_GROUP_GMEM;
       static_assert(G >= 2u && G <= 4u, "a leaf round tests two, three or four entries");
-      const uint32_t base = pend & 0xffffffu;
-      const uint32_t left = pend >> 24;
+      const uint32_t base = pend & ptrec::kFirstMask;
       tally.leaf_cells(A, has, base, A.n_slots);
       float4 g[4];
 #pragma unroll
@@ -338,20 +345,36 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
       for (uint32_t k = 0; k < G; k++) sphere_test(o, d, a, g[k], hb[k], cc[k], ds[k]);
 #pragma unroll
       for (uint32_t k = G; k < 4u; k++) { hb[k] = hb[G - 1u]; ds[k] = ds[G - 1u]; }  // (never selected: the mask has G bits)
-      // (no `if (has)` around this: a lane without a cell under test has left == 0, so its mask is empty and
-      // its pend becomes 0 — which is all that `pend < 2^24` meant for it)
-      uint32_t mask = 0u;
+      // (no `if (has)` around this: a lane without a cell under test has an empty field, so its mask is empty and
+      // its pend becomes 0 — which is all that `pend < kNone` meant for it)
+      uint32_t cand = 0u;
 #pragma unroll
-      for (uint32_t k = 0; k < G; k++) mask |= pass_bit(hb[k], cc[k], ds[k]) << k;
-      mask &= left >= G ? ((1u << G) - 1u) : ((1u << left) - 1u);
-      pend = left > G ? (base + G) | ((left - G) << 24) : 0u;
+      for (uint32_t k = 0; k < G; k++) cand |= pass_bit(hb[k], cc[k], ds[k]) << k;
+      // The record carries the valid mask of a cell's only round (pt_grid_records.hpp): nothing is decoded and nothing is
+      // pending.  Lanes in a LONG cell (more than four entries: the record's sign bit) accept every candidate of this round
+      // and compute the record of the rest, in a branch taken only when a ballot finds one.  The entries looked at, and
+      // their order, are those of `first | count << 24`.
+      uint32_t mask;
+      if constexpr (G == 4u) {
+        mask = ptrec::short_mask4(pend, cand);
+        const bool lng = ptrec::is_long(pend);
+        const uint32_t rec = pend;
+        pend = 0u;
+        if (pt_ballot(lng) != 0ull) {
+          if (lng) { mask = cand; pend = ptrec::next_long4(rec); }
+        }
+      } else {
+        mask = cand & ptrec::round_mask(pend, G);
+        pend = ptrec::next(pend, G);
+      }
       exact_group(base, mask, hb[0], hb[1], hb[2], hb[3], ds[0], ds[1], ds[2], ds[3]);
       // the cell is done: can anything registered only in later cells still win?
-      rem = (has && pend < 0x1000000u && closest < t_exit) ? 0u : rem;
+      if constexpr (S::FLAT_Y) cell = (has && pend < ptrec::kNone && closest < t_exit) ? 0u : cell;
+      else rem = (has && pend < ptrec::kNone && closest < t_exit) ? 0u : rem;
     }
     tally.phase(5);
     walk_iters++;
-    const uint32_t n_on = (uint32_t)__popcll(pt_ballot(rem != 0u) | pt_ballot(pend >= 0x1000000u));
+    const uint32_t n_on = (uint32_t)__popcll(pt_ballot(on()) | pt_ballot(pend >= ptrec::kNone));
     // The loop ends when nobody walks any more — or with a few stragglers left, which are carried: the
     // longer this step's walk has run, the more lanes may be left behind (a long walk means a scene of
     // long walks, where waiting for the last quarter of the lanes costs more than shading at three
@@ -363,7 +386,7 @@ __device__ __forceinline__ void grid_walk(const PtKernelArgs& A, const Path& p, 
     const uint32_t lim = thr < half_live ? thr : half_live;
     if (n_on < (lim > 1u ? lim : 1u)) break;
   }
-  carried = rem != 0u || pend >= 0x1000000u;
+  carried = on() || pend >= ptrec::kNone;
   tally.carried(carried);
   if (hit_pos != 0xffffffffu) hit = 0; // a hit; shading reads the slot's own copies (index not needed)
   h.closest = closest; h.hit = hit; h.lit_from = lit_from;

@@ -86,7 +86,8 @@ struct BvhWalk {  // cursor, queued leaves (8 x 16 bit), queued candidates (8 x 
   uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0, q_cnt = 0;
 };
 struct GridWalk {  // boundary-crossing times, linear cell index, steps left per axis (3 x 10 bit, each + 1),
-                   // the cell being tested (first untested entry | entries left << 24), its exit time
+                   // the cell being tested (a device cell record, pt_grid_records.hpp: first untested entry | valid mask or
+                   // 256 | entries left, << 23), its exit time
   float tmx = 0.f, tmy = 0.f, tmz = 0.f, t_exit = 0.f;
   uint32_t cell = 0, rem = 0, pend = 0;
 };
