@@ -36,6 +36,12 @@ pub struct PtErrorStats {        // the frame's noise figures, summed from the e
     pub passes_min: u32, pub passes_max: u32, pub passes_rendered: u32, pub reached: u32,
 }
 
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtAdaptiveStats {     // what one pt_render_adaptive call did
+    pub rounds: u32, pub partial_rounds: u32, pub tiles: u32, pub tiles_active: u32,
+    pub tile_passes: u64, pub samples: u64,
+}
+
 #[repr(C)] pub struct PtCtx { _private: [u8; 0] }
 
 #[link(name = "ptrace")]
@@ -72,6 +78,8 @@ extern "C" {
     pub fn pt_error_tiles(ctx: *mut PtCtx, tiles_out: *mut f32, tiles_x: *mut u32, tiles_y: *mut u32) -> c_int;
     pub fn pt_error_stats(ctx: *mut PtCtx, out: *mut PtErrorStats) -> c_int;
     pub fn pt_render_until(ctx: *mut PtCtx, target_rel_error: f32, passes_per_launch: u32, max_passes: u32, out: *mut PtErrorStats) -> c_int;
+    pub fn pt_render_adaptive(ctx: *mut PtCtx, target_rel_error: f32, passes_per_round: u32, max_passes: u32, out: *mut PtErrorStats, adaptive_out: *mut PtAdaptiveStats) -> c_int;
+    pub fn pt_adaptive_tiles(ctx: *mut PtCtx, base_out: *mut u32, order_out: *mut u32, n_tiles: *mut u32, n_active: *mut u32) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;

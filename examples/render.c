@@ -9,6 +9,8 @@
  *   examples/render out.ppm 640 351 16
  *   examples/render out.ppm 640 351 16 0.02     render to a noise target: launches of 16 passes until the frame's
  *                                               relative error is at most 0.02 (at most 64 launches)
+ *   examples/render out.ppm 640 351 16 0.02 1   the same adaptively: after every look only the 8x8 tiles that still miss
+ *                                               their share of the target are traced (pt_render_adaptive)
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,6 +32,7 @@ int main(int argc, char** argv) {
   uint32_t w = argc > 2 ? (uint32_t)atoi(argv[2]) : 640, h = argc > 3 ? (uint32_t)atoi(argv[3]) : 351;
   uint32_t frames = argc > 4 ? (uint32_t)atoi(argv[4]) : 16;
   float noise_target = argc > 5 ? (float)atof(argv[5]) : 0.0f;   /* 0: render `frames` passes and stop */
+  int adaptive = argc > 6 ? atoi(argv[6]) : 0;
   pt_ctx* ctx = NULL;
   pt_state* st = NULL;
 
@@ -51,7 +54,14 @@ int main(int argc, char** argv) {
   if (noise_target > 0.0f) {
     PtErrorStats es;
     CHECK(pt_set_option(ctx, PT_OPT_ERROR_ESTIMATE, 1));
-    CHECK(pt_render_until(ctx, noise_target, frames, 64 * frames, &es));
+    if (adaptive) {
+      PtAdaptiveStats ad;
+      CHECK(pt_render_adaptive(ctx, noise_target, frames, 64 * frames, &es, &ad));
+      printf("adaptive: %u rounds, %u of them partial, %u of %u tiles still active, %llu camera paths\n", ad.rounds, ad.partial_rounds,
+             ad.tiles_active, ad.tiles, (unsigned long long)ad.samples);
+    } else {
+      CHECK(pt_render_until(ctx, noise_target, frames, 64 * frames, &es));
+    }
     printf("noise target %g: %u passes, relative error %.5f, %s\n", noise_target, es.passes_rendered, es.rel_error,
            es.reached ? "reached" : "not reached");
   } else {

@@ -368,6 +368,51 @@ int pt_error_stats(pt_ctx* ctx, PtErrorStats* out);
  * advanced: a second call continues the same frame.  Relies on the ASSUMPTION above (independent passes). */
 int pt_render_until(pt_ctx* ctx, float target_rel_error, uint32_t passes_per_launch, uint32_t max_passes, PtErrorStats* out);
 
+/* ---- adaptive sampling: render only the tiles that still miss the noise target (build extension, opt-in) ----------------
+ * pt_render_adaptive is pt_render_until with a choice of tiles between the launches.  Preconditions and error codes are
+ * pt_render_until's (estimate on, finite positive target, passes_per_round <= the reserved passes, not inside a stream
+ * capture, one samples_per_pixel per estimate); PT_OPT_COUNT_WORK must be off (PT_ERR_INVALID).  The tiles are the 8x8 tiles
+ * of pt_error_tiles: the work queue's.  `act` starts from a look (steps 4 to 6 with done = 0) at the state the call finds: in
+ * a fresh estimate every pixel is short, so `act` starts as "all tiles"; in a frame under way it is the selection that state
+ * gives, so two calls are exactly the rounds of one call of their passes together — and a call that finds the target met, or
+ * no tile active, renders nothing.  Each round:
+ *   1. k = min(passes_per_round, max_passes - done).
+ *   2. Every tile active: the round IS pt_render_passes(k).  Otherwise a PARTIAL round: the trace launch runs over the work
+ *      items of the active tiles only (the same kernel, reading a tile table that is a stable partition of the queue's cost
+ *      order, active tiles first, and n_active x 64 x k items; it reports no costs), and the fold runs over their pixels only,
+ *      statement for statement the fold above.  Pixels of idle tiles are neither read nor written.
+ *   3. params.first_pass += k, done += k — k does not depend on how many tiles ran, so a pass index is frame-wide: A PIXEL HOLDS
+ *      EXACTLY THOSE PASSES OF THE UNINTERRUPTED FRAME DURING WHICH ITS TILE WAS ACTIVE, FOLDED IN ORDER.
+ *   4. pt_error_stats -> out; passes_rendered = done; reached = rel_error <= target && pixels_short == 0.
+ *   5. `act` for the next round, THE SELECTION RULE, on the host in double, one IEEE operation per statement, from the records
+ *      and tallies pt_error_stats has just copied — E, M, C = sum_e2, sum_m2, pixels_counted; per tile t: e_t = the record's
+ *      sum e, c_t its counted lanes, short_t its pixels with !(n >= 2):
+ *          tau = (double)target;  t2 = tau * tau;  b = t2 * M;  Cd = (double)C;
+ *          per tile t:  lhs = (double)e_t * Cd;  rhs = b * (double)c_t;  active_t = short_t > 0 || lhs > rhs;
+ *      A tile is active while its mean squared standard error per counted pixel is above the per-pixel share that meets the
+ *      frame target, if every tile meets it.  A tile with no counted and no short pixel is never active: sampling cannot help
+ *      it (it lies outside the image or holds non-finite radiance).
+ *   6. Stop when the target is reached, when done >= max_passes, when no tile is active.
+ * first_pass stays advanced: a second call continues the frame.  After a partial
+ * round the pixels of one frame hold different numbers of passes; every read-out divides by the pixel's own count,
+ * PtErrorStats.passes_min / passes_max show the spread, and PtStats.total_spp is pixel (0, 0)'s count.  PtStats.samples,
+ * render_launches and render_kernel_ms count a partial round like any launch (samples: the camera paths really started).
+ * Multi-GPU: a band context selects on its own band's E, M and C; the ranks' choices are then not the single-GPU frame's. */
+typedef struct PtAdaptiveStats {
+  uint32_t rounds;         /* launches this call made                                              */
+  uint32_t partial_rounds; /* of them, launches over fewer than all tiles                          */
+  uint32_t tiles;          /* 8x8 tiles of the local rows                                          */
+  uint32_t tiles_active;   /* tiles the rule selects after the last look                           */
+  uint64_t tile_passes;    /* sum over the rounds of (active tiles x passes of the round)          */
+  uint64_t samples;        /* camera paths this call started: in-image pixels of active tiles x passes x spp */
+} PtAdaptiveStats;
+int pt_render_adaptive(pt_ctx* ctx, float target_rel_error, uint32_t passes_per_round, uint32_t max_passes, PtErrorStats* out,
+                       PtAdaptiveStats* adaptive_out /* may be NULL */);
+/* The tables of the most recent partial round.  base = the cost order it partitioned.  order = the table the trace launch read.
+ * n_tiles entries each (host pointers; capacity: the tile count of pt_error_tiles).  Pointers may be NULL (sizes only).
+ * PT_ERR_NOT_READY before the first partial round, and again after pt_set_spheres, pt_resize and any repartition. */
+int pt_adaptive_tiles(pt_ctx* ctx, uint32_t* base_out, uint32_t* order_out, uint32_t* n_tiles, uint32_t* n_active);
+
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)
  * using params.render_count / should_average / last_frame_weight, writes RGBA8 to `out_rgba8`.

@@ -53,6 +53,10 @@ SIGNATURES = {
     "pt_error_tiles": (C.c_int, [_ctx, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "pt_error_stats": (C.c_int, [_ctx, C.POINTER(abi.PtErrorStats)]),
     "pt_render_until": (C.c_int, [_ctx, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(abi.PtErrorStats)]),
+    "pt_render_adaptive": (C.c_int, [_ctx, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(abi.PtErrorStats),
+                                     C.POINTER(abi.PtAdaptiveStats)]),
+    "pt_adaptive_tiles": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint32)]),
     "pt_refit_grid": (C.c_int, [_ctx, C.c_int]),
     "pt_grid_fit": (C.c_int, [_ctx]),
     "pt_build_bvh": (C.c_int, [C.POINTER(abi.PtSphere), C.c_uint32, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp,
@@ -99,9 +103,11 @@ SIGNATURES = {
 }
 
 
-# entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay, the error estimate
+# entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay, the error
+# estimate, adaptive sampling
 ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_set_debugging", "pt_state_debug_overlay",
-                      "pt_error_ptr", "pt_resolve_error", "pt_error_tiles", "pt_error_stats", "pt_render_until")
+                      "pt_error_ptr", "pt_resolve_error", "pt_error_tiles", "pt_error_stats", "pt_render_until",
+                      "pt_render_adaptive", "pt_adaptive_tiles")
 
 
 def _elf_dynamic_strings(path, tags):

@@ -176,6 +176,19 @@ class PtErrorStats(C.Structure):
     ]
 
 
+class PtAdaptiveStats(C.Structure):
+    """include/ptrace.h PtAdaptiveStats: what one pt_render_adaptive call did."""
+
+    _fields_ = [
+        ("rounds", C.c_uint32),
+        ("partial_rounds", C.c_uint32),
+        ("tiles", C.c_uint32),
+        ("tiles_active", C.c_uint32),
+        ("tile_passes", C.c_uint64),
+        ("samples", C.c_uint64),
+    ]
+
+
 class PtHostSphere(C.Structure):
     """src/glsl.rs:27-40: f64 centre/radius/albedo, f32 fuzz/refraction_index."""
 

@@ -177,6 +177,13 @@ struct pt_ctx {
   DevBuf<uint32_t> d_tile_cost;
   DevBuf<uint32_t> d_tile_order;
   bool tile_order_valid = false;  // d_tile_order holds an order for the current tile count
+  bool costs_pending = false;     // a direct launch has reported costs that no order kernel has consumed yet
+  // adaptive sampling (pt_render_adaptive): a partial round's tables — 3 x tiles words: the flags as uploaded, the partition the
+  // trace launch and the masked fold read, the cost order it was made from — and the host's copy of the flags
+  DevBuf<uint32_t> d_adapt;
+  std::vector<uint32_t> h_adapt_flags;
+  bool adapt_valid = false;       // the tables are those of a partial round of the scene and partition in place (pt_adaptive_tiles)
+  uint32_t adapt_tiles = 0, adapt_active = 0;
   // the frames' cost-sorted tile order (ensure_cost_order): which view and scene it was probed for, frames drawn since
   bool order_probed = false;
   PtParams order_view;
@@ -301,6 +308,8 @@ int ensure_buffers(pt_ctx* c) {
     }
     c->tile_order_valid = false;
     c->order_probed = false;
+    c->costs_pending = false;
+    c->adapt_valid = false;
   }
   if (c->d_canvas.capacity() < pix) {  // create_texture x2 (src/webgl.rs:82-123), cleared: alpha 0 = "no data" (shader.frag:391)
     for (int k = 0; k < 2; k++) {
@@ -804,6 +813,7 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
   c->grid_cells_build = false;  // (a measurement of the previous scene)
   c->epoch++;
   c->scene_gen++;
+  c->adapt_valid = false;
   c->geom.reset();  // a new scene: PT_GEOM_AUTO measures again
   c->scene_regular = regular;
   c->have_spheres = true;
@@ -857,6 +867,7 @@ PT_API int pt_set_params(pt_ctx* c, const PtParams* p) {
     c->epoch++;
     c->total_spp = 0;
     c->captured = false;  // whatever a replayed graph accumulated is gone with the old partition
+    c->adapt_valid = false;
     // a different set of rows: the accumulated image no longer applies, and neither do the frame textures
     PT_HIP(c, hipMemsetAsync(c->accum, 0, (size_t)c->local_rows * c->width * sizeof(float4), c->stream));
     if (int rc = clear_error(c); rc != PT_OK) return rc;
@@ -876,6 +887,7 @@ PT_API int pt_resize(pt_ctx* c, uint32_t width, uint32_t height) {
   c->height = height;
   c->epoch++;
   c->have_params = false; // uniforms must be re-uploaded for the new size
+  c->adapt_valid = false;
   c->params.band_count = 0;
   c->local_rows = height;
   if (c->accum_bound) { c->accum_bound = false; c->accum = nullptr; }
@@ -1151,11 +1163,18 @@ static LaunchKnobs read_launch_knobs() {
   return k;
 }
 
-static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launch* L) {
+// (`n_first_tiles` > 0: a partial round of pt_render_adaptive — the launch covers the first n_first_tiles positions of `table`, a
+// full permutation of the tiles, and is planned for that many items; tiles_x, tiles_y and div_per_tile stay the frame's)
+static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launch* L, uint32_t n_first_tiles = 0,
+                          const uint32_t* table = nullptr) {
   PtKernelArgs& A = L->A;
   {
     int rc = fill_uniforms(c, n_passes, A);
     if (rc != PT_OK) return rc;
+  }
+  if (n_first_tiles) {
+    A.n_items = n_first_tiles * 64u * n_passes;  // (below the frame's count, which fill_uniforms has checked)
+    A.tile_order = table;
   }
   const LaunchKnobs knobs = read_launch_knobs();
   if (knobs.carry_lanes) A.carry_lanes = *knobs.carry_lanes;
@@ -1281,7 +1300,7 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
   if (A.cost_feedback || !c->tile_order_valid) {
     int rc = launch_tile_order(c);
     if (rc != PT_OK) return rc;
-    if (!capturing) c->tile_order_valid = true;  // (a captured order kernel has not run: the next direct launch runs its own)
+    if (!capturing) { c->tile_order_valid = true; c->costs_pending = false; }  // (a captured order kernel has not run: the next direct launch runs its own)
   }
   if (capturing) trial = -1;
   if (trial >= 0) {
@@ -1291,6 +1310,7 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
   }
   if (ev) PT_HIP(c, hipEventRecord(ev->first, c->stream));
   if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
+  if (A.cost_feedback && !capturing) c->costs_pending = true;
   if (ev) PT_HIP(c, hipEventRecord(ev->second, c->stream));
   if (trial >= 0) {
     PT_HIP(c, hipEventRecord(c->trial_ev[2 * trial + 1], c->stream));
@@ -1389,6 +1409,7 @@ int ensure_tile_order(pt_ctx* c) {
   int rc = launch_tile_order(c);
   if (rc != PT_OK) return rc;
   c->tile_order_valid = true;
+  c->costs_pending = false;
   return PT_OK;
 }
 
@@ -1417,6 +1438,7 @@ int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
                             // zero, a pt_render_passes with cost feedback since then does not: cleared here)
       c->order_probed = false;
       c->tile_order_valid = false;
+      c->costs_pending = false;
       PT_HIP(c, hipMemsetAsync(c->d_tile_cost.get(), 0, c->d_tile_cost.capacity() * sizeof(uint32_t), c->stream));
     }
     return ensure_tile_order(c);
@@ -1444,6 +1466,7 @@ int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
   if (rc != PT_OK) return rc;
   PT_HIP(c, hipMemcpyAsync(seg, c->d_counters.get() + PT_CTR_SCRATCH, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
   c->order_probed = true;
+  c->costs_pending = false;
   c->order_view = c->params;
   c->order_scene_gen = c->scene_gen;
   c->frames_since_probe = 0;
@@ -1752,7 +1775,9 @@ PT_API int pt_error_tiles(pt_ctx* c, float* tiles_out, uint32_t* tiles_x, uint32
   return PT_OK;
 }
 
-PT_API int pt_error_stats(pt_ctx* c, PtErrorStats* out) {
+// (`h`: the records [0, tiles) and tallies [tiles, 2 tiles) as copied, for a caller that goes on with them)
+static int error_stats(pt_ctx* c, PtErrorStats* out, std::vector<float4>& h) {
+  h.clear();
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_error_stats: NULL argument");
   if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_stats: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
   memset(out, 0, sizeof *out);
@@ -1762,7 +1787,7 @@ PT_API int pt_error_stats(pt_ctx* c, PtErrorStats* out) {
   if (int rc = launch_error_tiles(c, &tx, &ty); rc != PT_OK) return rc;
   const size_t n_tiles = (size_t)tx * ty;
   if (n_tiles == 0) return PT_OK;
-  std::vector<float4> h(2 * n_tiles);
+  h.resize(2 * n_tiles);
   PT_HIP(c, hipMemcpyAsync(h.data(), c->d_err_tiles.get(), 2 * n_tiles * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   // in tile index order, in double
@@ -1793,6 +1818,11 @@ PT_API int pt_error_stats(pt_ctx* c, PtErrorStats* out) {
   return PT_OK;
 }
 
+PT_API int pt_error_stats(pt_ctx* c, PtErrorStats* out) {
+  std::vector<float4> h;
+  return error_stats(c, out, h);
+}
+
 PT_API int pt_render_until(pt_ctx* c, float target_rel_error, uint32_t passes_per_launch, uint32_t max_passes, PtErrorStats* out) {
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_render_until: NULL argument");
   if (!c->err_on) return fail(c, PT_ERR_INVALID, "pt_render_until: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
@@ -1816,6 +1846,173 @@ PT_API int pt_render_until(pt_ctx* c, float target_rel_error, uint32_t passes_pe
     out->reached = (out->rel_error <= (double)target_rel_error && out->pixels_short == 0) ? 1u : 0u;
     if (out->reached || done >= max_passes) return PT_OK;
   }
+}
+
+// ---- adaptive sampling (include/ptrace.h pt_render_adaptive; kernels: pt_kernels_error.hip) -----------------------------------
+namespace {
+
+// in-image pixels of tile t of the local rows
+inline uint32_t tile_pixels(const pt_ctx* c, uint32_t tiles_x, uint32_t t) {
+  const uint32_t x0 = 8u * (t % tiles_x), y0 = 8u * (t / tiles_x);
+  const uint32_t w = c->width > x0 ? (c->width - x0 < 8u ? c->width - x0 : 8u) : 0u;
+  const uint32_t h = c->local_rows > y0 ? (c->local_rows - y0 < 8u ? c->local_rows - y0 : 8u) : 0u;
+  return w * h;
+}
+
+// THE SELECTION RULE (include/ptrace.h), on the records and tallies error_stats has just copied; returns the active count
+uint32_t select_tiles(const PtErrorStats& st, float target, const std::vector<float4>& h, std::vector<uint32_t>& flags) {
+  const size_t n_tiles = h.size() / 2;
+  flags.assign(n_tiles, 0u);
+  const double tau = (double)target;
+  const double t2 = tau * tau;
+  const double b = t2 * st.sum_m2;
+  const double Cd = (double)st.pixels_counted;
+  uint32_t n_active = 0;
+  for (size_t t = 0; t < n_tiles; t++) {
+    const double lhs = (double)h[t].x * Cd;
+    const double rhs = b * (double)h[t].z;
+    const bool active = h[n_tiles + t].x > 0.0f || lhs > rhs;
+    flags[t] = active ? 1u : 0u;
+    n_active += active ? 1u : 0u;
+  }
+  return n_active;
+}
+
+// One partial round: k passes over the tiles flagged in c->h_adapt_flags (n_active of n_tiles, 0 < n_active < n_tiles).
+int partial_round(pt_ctx* c, uint32_t k, uint32_t n_tiles, uint32_t n_active, uint64_t pixels_active) {
+  const PtParams& p = c->params;
+  if (!c->have_spheres || !c->have_params)
+    return fail(c, PT_ERR_NOT_READY, "pt_render_adaptive: pt_set_spheres and pt_set_params must come first");
+  PT_HIP(c, hipSetDevice(c->device));
+  if (c->d_adapt.capacity() != 3 * (size_t)n_tiles) {
+    PT_HIP(c, hipStreamSynchronize(c->stream));
+    PT_HIP(c, c->d_adapt.reserve(3 * (size_t)n_tiles));
+  }
+  uint32_t* flags = c->d_adapt.get();
+  uint32_t* part = flags + n_tiles;
+  uint32_t* base = part + n_tiles;
+  c->adapt_valid = false;
+  // the cost order up to date, as the next pt_render_passes would bring it — and never from costs that are all zero: the order
+  // kernel would write the identity over a sorted order
+  if (c->costs_pending || !c->tile_order_valid) {
+    if (int rc = launch_tile_order(c); rc != PT_OK) return rc;
+    c->tile_order_valid = true;
+    c->costs_pending = false;
+  }
+  PT_HIP(c, hipMemcpyAsync(flags, c->h_adapt_flags.data(), (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  {
+    const uint32_t* order = c->d_tile_order.get();
+    const uint32_t* fl = flags;
+    uint32_t n = n_tiles;
+    void* kargs[] = {&order, &fl, &part, &base, &n};
+    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_PARTITION), dim3(1), dim3(1024), kargs, 0, c->stream));
+  }
+  Launch L;
+  if (int rc = prepare_launch(c, k, false, &L, n_active, part); rc != PT_OK) return rc;
+  L.A.cost_feedback = 0;  // a partial launch keeps the order it finds, as a frame does
+  L.A.wave_log = nullptr;
+  L.A.cell_hist = nullptr;
+  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+  if (int rc = next_events(c, &ev); rc != PT_OK) return rc;
+  PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
+  PT_HIP(c, hipEventRecord(ev->first, c->stream));
+  if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
+  PT_HIP(c, hipEventRecord(ev->second, c->stream));
+  {
+    float4* accum = c->accum;
+    float4* est = c->d_err.get();
+    const float4* slab = c->d_slab.get();
+    const uint32_t* order = part;
+    uint32_t na = n_active, width = c->width, rows = c->local_rows, tiles_x = (c->width + 7) / 8, passes = k;
+    void* kargs[] = {&accum, &est, &slab, &order, &na, &width, &rows, &tiles_x, &passes};
+    // four waves, hence four tiles, per workgroup
+    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD_TILES), dim3(grid_for(n_active, 4, 4096)), dim3(256), kargs, 0, c->stream));
+  }
+  c->err_spp = p.samples_per_pixel;
+  c->adapt_valid = true;
+  c->adapt_tiles = n_tiles;
+  c->adapt_active = n_active;
+  c->launches++;
+  c->samples += pixels_active * k * (uint64_t)p.samples_per_pixel;
+  return PT_OK;
+}
+
+} // namespace
+
+PT_API int pt_render_adaptive(pt_ctx* c, float target_rel_error, uint32_t passes_per_round, uint32_t max_passes, PtErrorStats* out,
+                              PtAdaptiveStats* adaptive_out) {
+  if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: NULL argument");
+  if (!c->err_on) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+  if (!(target_rel_error > 0.0f) || !std::isfinite(target_rel_error))
+    return fail(c, PT_ERR_INVALID, "pt_render_adaptive: the target must be finite and positive");
+  if (passes_per_round == 0 || max_passes == 0) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: no passes to render");
+  if (passes_per_round > c->reserved_passes)
+    return fail(c, PT_ERR_CAPACITY, "pt_render_adaptive: %u passes per round > %u reserved (pt_reserve_passes)", passes_per_round,
+                c->reserved_passes);
+  if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: not with PT_OPT_COUNT_WORK (the measuring twins log whole launches)");
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: synchronises; not inside a stream capture");
+  // (refused before the first look: a call must not answer for an estimate it could not continue)
+  if (c->have_params && c->err_spp != 0 && c->err_spp != c->params.samples_per_pixel)
+    return fail(c, PT_ERR_INVALID, "pt_render_adaptive: %d samples per pixel while the error estimate holds passes of %d: clear first "
+                                   "(pt_reset_accum)", c->params.samples_per_pixel, c->err_spp);
+  const uint32_t tiles_x = (c->width + 7) / 8;
+  const uint32_t n_tiles = tiles_x * ((c->local_rows + 7) / 8);
+  PtAdaptiveStats ad;
+  memset(&ad, 0, sizeof ad);
+  ad.tiles = n_tiles;
+  uint32_t n_active = 0;
+  uint64_t pixels_active = 0;
+  std::vector<float4> h;
+  uint32_t done = 0;
+  // `act` starts from a look at the state the call finds.  A fresh estimate has every pixel short: all tiles.  A frame under way
+  // goes on with the selection its state gives, so two calls are the rounds of one call of their passes together.
+  auto look = [&]() -> int {
+    if (int rc = error_stats(c, out, h); rc != PT_OK) return rc;
+    out->passes_rendered = done;
+    out->reached = (out->rel_error <= (double)target_rel_error && out->pixels_short == 0) ? 1u : 0u;
+    n_active = select_tiles(*out, target_rel_error, h, c->h_adapt_flags);
+    pixels_active = 0;
+    for (uint32_t t = 0; t < n_tiles; t++)
+      if (c->h_adapt_flags[t]) pixels_active += tile_pixels(c, tiles_x, t);
+    ad.tiles_active = n_active;
+    return PT_OK;
+  };
+  int rc = look();
+  while (rc == PT_OK && !out->reached && done < max_passes && n_active != 0) {
+    const uint32_t k = passes_per_round < max_passes - done ? passes_per_round : max_passes - done;
+    if (n_active == n_tiles) {
+      rc = pt_render_passes(c, k);
+    } else {
+      rc = partial_round(c, k, n_tiles, n_active, pixels_active);
+    }
+    if (rc != PT_OK) break;
+    ad.rounds++;
+    ad.partial_rounds += n_active != n_tiles ? 1u : 0u;
+    ad.tile_passes += (uint64_t)n_active * k;
+    ad.samples += pixels_active * k * (uint64_t)c->params.samples_per_pixel;
+    // pass indices are frame-wide: the step does not depend on how many tiles ran
+    c->params.first_pass += k;
+    c->epoch++;
+    done += k;
+    rc = look();
+  }
+  if (adaptive_out) *adaptive_out = ad;
+  return rc;
+}
+
+PT_API int pt_adaptive_tiles(pt_ctx* c, uint32_t* base_out, uint32_t* order_out, uint32_t* n_tiles, uint32_t* n_active) {
+  if (!c) return PT_ERR_INVALID;
+  if (!c->adapt_valid) return fail(c, PT_ERR_NOT_READY, "pt_adaptive_tiles: no partial round yet (pt_render_adaptive)");
+  if (n_tiles) *n_tiles = c->adapt_tiles;
+  if (n_active) *n_active = c->adapt_active;
+  if (!base_out && !order_out) return PT_OK;
+  PT_HIP(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)c->adapt_tiles * sizeof(uint32_t);
+  const uint32_t* part = c->d_adapt.get() + c->adapt_tiles;
+  if (order_out) PT_HIP(c, hipMemcpyAsync(order_out, part, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (base_out) PT_HIP(c, hipMemcpyAsync(base_out, part + c->adapt_tiles, bytes, hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
 }
 
 PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {

@@ -1,10 +1,12 @@
 // pt_kernels_error.hip — the PER-PIXEL ERROR ESTIMATE (pt_set_option PT_OPT_ERROR_ESTIMATE; include/ptrace.h, DESIGN.md
 // §error estimate), a translation unit and gfx950 code object of its own: the HIP runtime loads it when the estimate is
-// first turned on, so a context that never asks for it pays nothing.  Three kernels, none of them a trace kernel:
+// first turned on, so a context that never asks for it pays nothing.  Five kernels, none of them a trace kernel:
 //   pt_fold_error_kernel     takes pt_accumulate_kernel's place: the same four fp32 adds per pass in the same order (accum
 //                            keeps its bits) and, beside them, Welford's update of the pass sums' mean and M2 per channel
 //   pt_resolve_error_kernel  the standard error of each pixel's mean as linear radiance
 //   pt_error_tiles_kernel    per 8x8 tile of the local rows, one wave64: sums of se^2 and mean^2 over the counted pixels
+//   pt_partition_order_kernel, pt_fold_error_tiles_kernel   a partial round of pt_render_adaptive: the queue's tile table with
+//                            the active tiles first, and the fold over those tiles' pixels only
 // The arithmetic is a contract (tests/error_ref.py restates it statement by statement): ONE IEEE fp32 operation per
 // statement, nothing fused (-ffp-contract=off), `/` and sqrtf correctly rounded.  pt_api.hip reaches the kernels through
 // pt_error_kernel() only.
@@ -24,24 +26,77 @@ __device__ __forceinline__ void welford(float x, float n, float& mean, float& m2
   m2 = m2 + t;
 }
 
+// one pixel's fold over the launch's slabs: the statements of the contract, shared by the two fold kernels below
+__device__ __forceinline__ void fold_pixel(float4* accum, float4* est, const float4* slab, size_t i, size_t n_pix, uint32_t n_passes) {
+  float4 acc = accum[i];
+  float4 a = est[2 * i], b = est[2 * i + 1];
+  for (uint32_t p = 0; p < n_passes; p++) {
+    const float4 s = slab[(size_t)p * n_pix + i];
+    acc.x += s.x; acc.y += s.y; acc.z += s.z; acc.w += s.w;
+    a.w = a.w + 1.0f;
+    b.w = b.w + s.w;
+    welford(s.x, a.w, a.x, b.x);
+    welford(s.y, a.w, a.y, b.y);
+    welford(s.z, a.w, a.z, b.z);
+  }
+  accum[i] = acc;
+  est[2 * i] = a;
+  est[2 * i + 1] = b;
+}
+
 extern "C" __global__ __launch_bounds__(256) void pt_fold_error_kernel(float4* accum, float4* est, const float4* slab,
                                                                        uint32_t n_pix, uint32_t n_passes) {
   const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += stride) {
-    float4 acc = accum[i];
-    float4 a = est[2 * (size_t)i], b = est[2 * (size_t)i + 1];
-    for (uint32_t p = 0; p < n_passes; p++) {
-      const float4 s = slab[(size_t)p * n_pix + i];
-      acc.x += s.x; acc.y += s.y; acc.z += s.z; acc.w += s.w;
-      a.w = a.w + 1.0f;
-      b.w = b.w + s.w;
-      welford(s.x, a.w, a.x, b.x);
-      welford(s.y, a.w, a.y, b.y);
-      welford(s.z, a.w, a.z, b.z);
-    }
-    accum[i] = acc;
-    est[2 * (size_t)i] = a;
-    est[2 * (size_t)i + 1] = b;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += stride) fold_pixel(accum, est, slab, i, n_pix, n_passes);
+}
+
+// The fold of a PARTIAL round (pt_render_adaptive): one wave64 per table position j < n_active, its tile order[j], lane l owns
+// local pixel (8 tx + l % 8, 8 ty + l / 8) as in the tile kernel below; a lane inside the image folds its pixel exactly as
+// pt_fold_error_kernel does.  Pixels of the other tiles are neither read nor written (their slab slots are stale).
+extern "C" __global__ __launch_bounds__(256) void pt_fold_error_tiles_kernel(float4* accum, float4* est, const float4* slab,
+                                                                             const uint32_t* order, uint32_t n_active,
+                                                                             uint32_t width, uint32_t rows, uint32_t tiles_x,
+                                                                             uint32_t n_passes) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+  const size_t n_pix = (size_t)width * rows;
+  for (uint32_t j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); j < n_active; j += waves) {
+    const uint32_t t = order[j];
+    const uint32_t x = 8u * (t % tiles_x) + (lane & 7u), y = 8u * (t / tiles_x) + (lane >> 3);
+    if (x < width && y < rows) fold_pixel(accum, est, slab, (size_t)y * width + x, n_pix, n_passes);
+  }
+}
+
+// The tile table of a partial round: a STABLE PARTITION of the queue's current order by flags[tile] — the flagged tiles first in
+// their present relative order, then the rest, a full permutation again (every tile_order[...] read of the refill stays valid);
+// `base` receives the order as it was found.  One 1024-thread workgroup: thread t owns a run of ceil(n / 1024) positions,
+// counts its flagged ones, an inclusive scan of the counts in the LDS gives every run its two starts.
+extern "C" __global__ __launch_bounds__(1024) void pt_partition_order_kernel(const uint32_t* order, const uint32_t* flags,
+                                                                             uint32_t* part, uint32_t* base, uint32_t n_tiles) {
+  __shared__ uint32_t s_scan[1024];
+  const uint32_t t = threadIdx.x;
+  const uint32_t per = (n_tiles + 1023u) / 1024u;
+  const uint32_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
+  uint32_t cnt = 0;
+  for (uint32_t i = lo; i < hi; i++) {
+    const uint32_t tile = order[i];
+    cnt += (tile < n_tiles && flags[tile] != 0u) ? 1u : 0u;
+  }
+  s_scan[t] = cnt;
+  __syncthreads();
+  for (uint32_t off = 1; off < 1024; off <<= 1) {
+    const uint32_t v = t >= off ? s_scan[t - off] : 0u;
+    __syncthreads();
+    s_scan[t] += v;
+    __syncthreads();
+  }
+  const uint32_t total = s_scan[1023];
+  uint32_t a = s_scan[t] - cnt;      // flagged tiles before this run
+  uint32_t r = total + (lo - a);     // the rest start behind all flagged ones
+  for (uint32_t i = lo; i < hi; i++) {
+    const uint32_t tile = order[i];
+    base[i] = tile;
+    if (tile < n_tiles && flags[tile] != 0u) part[a++] = tile; else part[r++] = tile;
   }
 }
 
@@ -134,6 +189,8 @@ extern "C" const void* pt_error_kernel(int id) {
     case PT_E_FOLD: return reinterpret_cast<const void*>(pt_fold_error_kernel);
     case PT_E_RESOLVE: return reinterpret_cast<const void*>(pt_resolve_error_kernel);
     case PT_E_TILES: return reinterpret_cast<const void*>(pt_error_tiles_kernel);
+    case PT_E_FOLD_TILES: return reinterpret_cast<const void*>(pt_fold_error_tiles_kernel);
+    case PT_E_PARTITION: return reinterpret_cast<const void*>(pt_partition_order_kernel);
     default: return nullptr;
   }
 }

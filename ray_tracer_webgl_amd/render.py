@@ -4,6 +4,7 @@ src/dom.rs:126-143, without a browser).
     python -m ray_tracer_webgl_amd.render --config config2 --width 1920 --height 1080 --out cover.png
     python -m ray_tracer_webgl_amd.render --config default --debug-overlay --out overlay.png
     python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.02 --max-spp 4096 --error-out cover_error.png
+    python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.02 --adaptive --samples-out cover_samples.png
 """
 import argparse
 import time
@@ -33,7 +34,12 @@ def main(argv=None):
                          "errors over the summed squared means) is at most X, instead of a fixed number of passes; prints spp "
                          "rendered, rel_error and reached.  Passes get the decorrelated time step: the estimate assumes independent passes")
     ap.add_argument("--max-spp", type=int, metavar="N", help="with --noise-target: stop after N samples per pixel (default: the config's spp)")
+    ap.add_argument("--adaptive", action="store_true",
+                    help="with --noise-target: after every look trace only the 8x8 tiles that still miss their share of the target "
+                         "(pt_render_adaptive); prints rounds, partial rounds and the share of the uniform samples traced")
     ap.add_argument("--error-out", metavar="FILE", help="also write the per-pixel standard error (linear radiance, shown x 8) as an image")
+    ap.add_argument("--samples-out", metavar="FILE",
+                    help="also write the per-pixel sample counts (white = the frame's largest count) as an image")
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--checkpoint", help="also save the fp32 accumulation buffer (.npz)")
     args = ap.parse_args(argv)
@@ -65,6 +71,8 @@ def main(argv=None):
     geom = {"auto": abi.PT_GEOM_AUTO, "lds": abi.PT_GEOM_LDS, "scalar": abi.PT_GEOM_SCALAR, "bvh": abi.PT_GEOM_BVH,
             "grid": abi.PT_GEOM_GRID, "small": abi.PT_GEOM_SMALL}[args.geometry]
     per = min(sc.n_passes, 16)
+    if args.adaptive and args.noise_target is None:
+        ap.error("--adaptive chooses tiles by the noise target: only with --noise-target")
     if args.noise_target is not None or args.error_out:
         if overlay is not None:
             ap.error("--noise-target / --error-out measure the frame's noise: not with --debug-overlay")
@@ -81,6 +89,11 @@ def main(argv=None):
         err[..., :3] *= 8.0
         err[..., 3] = 1.0
         image_io.write_png(args.error_out, err)
+    if args.samples_out:
+        n = pt.sample_counts()
+        img = np.ones(n.shape + (4,), np.float32)
+        img[..., :3] = (n / max(float(n.max()), 1.0))[..., None]
+        image_io.write_png(args.samples_out, img)
     if args.checkpoint:
         image_io.save_accum(args.checkpoint, acc, st.total_spp)
     print("%s: %dx%d, %d spheres, %d spp, depth %d: %.2f s, %.0f Mray/s -> %s" % (
@@ -102,7 +115,13 @@ def render_to_target(sc, args, geom, per):
     pt.error_estimate(True)
     max_passes = sc.n_passes if not args.max_spp else max(1, args.max_spp // p.samples_per_pixel)
     # (without a target: one that cannot be met, so the fixed number of passes is rendered)
-    es = pt.render_until(args.noise_target if args.noise_target is not None else 1e-30, per, max_passes)
+    if args.adaptive:
+        es, ad = pt.render_adaptive(args.noise_target, per, max_passes)
+        uniform = es.pixels * es.passes_rendered * p.samples_per_pixel
+        print("adaptive: %d rounds, %d of them partial, %d of %d tiles still active, %.1f %% of the uniform samples traced" % (
+            ad.rounds, ad.partial_rounds, ad.tiles_active, ad.tiles, 100.0 * ad.samples / max(uniform, 1)))
+    else:
+        es = pt.render_until(args.noise_target if args.noise_target is not None else 1e-30, per, max_passes)
     print("%d spp rendered (%d passes of %d), rel_error %.5f, rms_error %.5g, reached %d" % (
         es.passes_rendered * p.samples_per_pixel, es.passes_rendered, p.samples_per_pixel, es.rel_error, es.rms_error, es.reached))
     return pt, pt.accum()

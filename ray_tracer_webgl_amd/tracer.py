@@ -335,6 +335,31 @@ class PathTracer:
             self.params.first_pass += st.passes_rendered
         return st
 
+    def render_adaptive(self, target, passes_per_round, max_passes):
+        """render_until with a choice of tiles between the launches (include/ptrace.h pt_render_adaptive): after every look
+        only the 8x8 tiles that still miss their share of the target are traced and folded.  Returns (PtErrorStats,
+        PtAdaptiveStats); the context's first_pass advances by the passes rendered, whatever share of the tiles ran."""
+        st, ad = abi.PtErrorStats(), abi.PtAdaptiveStats()
+        rc = self.lib.pt_render_adaptive(self._ctx, float(target), int(passes_per_round), int(max_passes), C.byref(st), C.byref(ad))
+        if self.params is not None:
+            self.params.first_pass += st.passes_rendered   # (rounds that ran before a failing one have advanced it too)
+        self._check(rc)
+        return st, ad
+
+    def adaptive_tiles(self):
+        """The tables of the most recent partial round: (base, order, n_active) — the cost order it partitioned and the table
+        the trace launch read, uint32 arrays of one entry per tile; the first n_active entries of `order` are the active tiles."""
+        n, na = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.pt_adaptive_tiles(self._ctx, None, None, C.byref(n), C.byref(na)))
+        base, order = np.empty(n.value, np.uint32), np.empty(n.value, np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self.lib.pt_adaptive_tiles(self._ctx, base.ctypes.data_as(u32p), order.ctypes.data_as(u32p), C.byref(n), C.byref(na)))
+        return base, order, int(na.value)
+
+    def sample_counts(self):
+        """(local_rows, width) fp32: the samples each pixel holds (accum's fourth channel)."""
+        return self.accum()[..., 3]
+
     def stats(self):
         st = abi.PtStats()
         self._check(self.lib.pt_get_stats(self._ctx, C.byref(st)))
