@@ -29,6 +29,8 @@
 #include "pt_kernel_args.h"
 #include "pt_geom_plan.hpp"
 #include "pt_launch_plan.hpp"
+#include "pt_tile_order.hpp"
+#include "pt_error_plan.hpp"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -176,19 +178,14 @@ struct pt_ctx {
   // work-queue ordering feedback, one entry per tile
   DevBuf<uint32_t> d_tile_cost;
   DevBuf<uint32_t> d_tile_order;
-  bool tile_order_valid = false;  // d_tile_order holds an order for the current tile count
-  bool costs_pending = false;     // a direct launch has reported costs that no order kernel has consumed yet
+  TileOrder order;  // what the host knows of the two (pt_tile_order.hpp): when the order kernel runs, when the frames' order is probed
   // adaptive sampling (pt_render_adaptive): a partial round's tables — 3 x tiles words: the flags as uploaded, the partition the
   // trace launch and the masked fold read, the cost order it was made from — and the host's copy of the flags
   DevBuf<uint32_t> d_adapt;
   std::vector<uint32_t> h_adapt_flags;
   bool adapt_valid = false;       // the tables are those of a partial round of the scene and partition in place (pt_adaptive_tiles)
   uint32_t adapt_tiles = 0, adapt_active = 0;
-  // the frames' cost-sorted tile order (ensure_cost_order): which view and scene it was probed for, frames drawn since
-  bool order_probed = false;
-  PtParams order_view;
-  uint64_t order_scene_gen = 0, scene_gen = 0;
-  uint32_t frames_since_probe = 0;
+  uint64_t scene_gen = 0;  // counts pt_set_spheres: the frames' cost-sorted tile order is probed per scene (ensure_cost_order)
   // the reference's frame (pt_render_frame / pt_render_frames): two RGBA8 textures + canvas, the
   // device-side frame counter ([0] frames replayed since the series began, [1] a cell that stays 0)
   DevBuf<uint32_t> d_tex[2];
@@ -199,7 +196,6 @@ struct pt_ctx {
   hipGraphExec_t frame_exec[4] = {nullptr, nullptr, nullptr, nullptr};
   FramePlan frame_plan[4];               // the plan each cached graph was captured from (copied and compared bytewise)
   DevBuf<float4> d_frame_slab;           // a group's slabs (up to 16 passes), allocated by the first pt_render_frames that needs them
-  uint64_t epoch = 0;                    // bumped by everything a captured frame bakes in
   // counters + timing
   DevBuf<unsigned long long> d_counters;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events; // pool
@@ -209,7 +205,6 @@ struct pt_ctx {
   uint64_t samples = 0;
   // device properties
   int num_cus = 256;
-  int max_lds = 65536;
   // host-clock durations of the set-up calls, ms (include/ptrace_dev.h pt_debug_setup_times: where a first frame's time goes)
   double setup_ms[PT_SETUP_COUNT] = {0};
   std::string error;
@@ -224,6 +219,22 @@ struct pt_ctx {
 };
 
 namespace {
+
+// the pixels a context owns (its local rows) and the work queue's 8x8 tiles over them
+inline size_t n_pixels(const pt_ctx* c) { return (size_t)c->local_rows * c->width; }
+inline uint32_t tiles_x(const pt_ctx* c) { return (c->width + 7) / 8; }
+inline uint32_t tiles_y(const pt_ctx* c) { return (c->local_rows + 7) / 8; }
+inline uint32_t n_tiles(const pt_ctx* c) { return tiles_x(c) * tiles_y(c); }
+
+inline uint32_t grid_for(uint32_t n, uint32_t block, uint32_t cap) {
+  uint32_t g = (n + block - 1) / block;
+  if (g < 1) g = 1;
+  return g > cap ? cap : g;
+}
+// the grid of a kernel that strides 256-thread workgroups over the pixels
+inline uint32_t pixel_grid(uint32_t n_pix) { return grid_for(n_pix, 256, 2048); }
+// ... and of one whose wave64s take a tile each: four waves, hence four tiles, per 256-thread workgroup
+inline uint32_t tile_grid(uint32_t n) { return grid_for(n, 4, 4096); }
 
 // the work queue's heads start a launch at zero: the shared head, or the grouped queue's (pt_refill.hpp)
 inline hipError_t zero_queue_heads(pt_ctx* c, uint32_t queue_static) {
@@ -278,7 +289,7 @@ uint32_t count_local_rows(uint32_t height, const PtParams& p) {
 }
 
 int ensure_buffers(pt_ctx* c) {
-  size_t pix = (size_t)c->local_rows * c->width;
+  size_t pix = n_pixels(c);
   if (pix == 0) pix = 1;
   if (!c->accum_bound) {
     if (c->own_accum.capacity() < pix) {
@@ -291,7 +302,7 @@ int ensure_buffers(pt_ctx* c) {
   }
   const size_t need = pix * (size_t)c->reserved_passes;
   if (c->d_slab.capacity() < need) PT_HIP(c, c->d_slab.reserve(need));
-  size_t tiles = (size_t)((c->width + 7) / 8) * ((c->local_rows + 7) / 8);
+  size_t tiles = (size_t)tiles_x(c) * tiles_y(c);
   if (tiles == 0) tiles = 1;
   // reallocated and re-seeded whenever the tile count CHANGES, not only when it grows: an order left from another count would
   // name tiles that do not exist, or miss some
@@ -306,9 +317,7 @@ int ensure_buffers(pt_ctx* c) {
       for (size_t i = 0; i < tiles; i++) ident[i] = (uint32_t)i;
       PT_HIP(c, hipMemcpy(c->d_tile_order.get(), ident.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    c->tile_order_valid = false;
-    c->order_probed = false;
-    c->costs_pending = false;
+    c->order.reseeded();
     c->adapt_valid = false;
   }
   if (c->d_canvas.capacity() < pix) {  // create_texture x2 (src/webgl.rs:82-123), cleared: alpha 0 = "no data" (shader.frag:391)
@@ -334,7 +343,7 @@ int ensure_buffers(pt_ctx* c) {
 // the error estimate speaks for the passes folded since its last clear: cleared wherever the accumulation is cleared or replaced
 int clear_error(pt_ctx* c) {
   if (!c->err_on) return PT_OK;
-  const size_t pix = (size_t)c->local_rows * c->width;
+  const size_t pix = n_pixels(c);
   if (pix) PT_HIP(c, hipMemsetAsync(c->d_err.get(), 0, 2 * pix * sizeof(float4), c->stream));
   c->err_spp = 0;
   return PT_OK;
@@ -370,6 +379,21 @@ int next_events(pt_ctx* c, std::pair<hipEvent_t, hipEvent_t>** ev) {
   return PT_OK;
 }
 
+// A timed span of stream work: the next pair of the pool, recorded before and after it.  take() comes before anything of the
+// span is enqueued (it may drain the pool); a span that never took a pair — a launch being captured — records nothing.
+struct TimedSpan {
+  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+  int take(pt_ctx* c) { return next_events(c, &ev); }
+  int begin(pt_ctx* c) const {
+    if (ev) PT_HIP(c, hipEventRecord(ev->first, c->stream));
+    return PT_OK;
+  }
+  int end(pt_ctx* c) const {
+    if (ev) PT_HIP(c, hipEventRecord(ev->second, c->stream));
+    return PT_OK;
+  }
+};
+
 // is the context's stream being captured into a hipGraph (its own or a caller's)?
 bool is_capturing(const pt_ctx* c) {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -380,7 +404,7 @@ bool is_capturing(const pt_ctx* c) {
 // the queue order of the tiles from their costs (the identity while every cost is zero)
 int launch_tile_order(pt_ctx* c) {
   hipLaunchKernelGGL(pt_tile_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tile_cost.get(), c->d_tile_order.get(),
-                     ((c->width + 7) / 8) * ((c->local_rows + 7) / 8));
+                     n_tiles(c));
   PT_HIP(c, hipGetLastError());
   return PT_OK;
 }
@@ -489,12 +513,6 @@ const TraceKernel kTraceKernels[ROW_COUNT][BUILD_COUNT] = {
     {in_main(pt_trace_kernel_grid_layers, PT_WAVES_WALK),   in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_LAYERS_COUNT),  in_debug(PT_D_GRID)},
 };
 
-inline uint32_t grid_for(uint32_t n, uint32_t block, uint32_t cap) {
-  uint32_t g = (n + block - 1) / block;
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
-}
-
 } // namespace
 
 PT_API int pt_device_count(void) {
@@ -537,7 +555,6 @@ static int create_common(pt_ctx** out, int device, uint32_t width, uint32_t heig
   hipDeviceProp_t prop;
   if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return bail(e, "hipGetDeviceProperties");
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  c->max_lds = (int)prop.sharedMemPerBlock;
   const double t_device = host_ms();
   if (caller_stream) {
     c->stream = (hipStream_t)caller_stream;
@@ -602,7 +619,6 @@ PT_API int pt_set_stream(pt_ctx* c, void* hip_stream) {
   if (!hip_stream && !c->own_stream)  // a context made by pt_create_on_stream that now wants a stream of its own
     PT_HIP(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-  c->epoch++;
   return PT_OK;
 }
 
@@ -811,7 +827,6 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
   }
   c->n_spheres = n;
   c->grid_cells_build = false;  // (a measurement of the previous scene)
-  c->epoch++;
   c->scene_gen++;
   c->adapt_valid = false;
   c->geom.reset();  // a new scene: PT_GEOM_AUTO measures again
@@ -864,18 +879,16 @@ PT_API int pt_set_params(pt_ctx* c, const PtParams* p) {
     // (a refused clear leaves a self-consistent context whose old image is gone, never a new partition with old uniforms).
     c->params = *p;
     c->have_params = true;
-    c->epoch++;
     c->total_spp = 0;
     c->captured = false;  // whatever a replayed graph accumulated is gone with the old partition
     c->adapt_valid = false;
     // a different set of rows: the accumulated image no longer applies, and neither do the frame textures
-    PT_HIP(c, hipMemsetAsync(c->accum, 0, (size_t)c->local_rows * c->width * sizeof(float4), c->stream));
+    PT_HIP(c, hipMemsetAsync(c->accum, 0, n_pixels(c) * sizeof(float4), c->stream));
     if (int rc = clear_error(c); rc != PT_OK) return rc;
     return pt_clear_textures(c);
   }
   c->params = *p;
   c->have_params = true;
-  c->epoch++;
   return PT_OK;
 }
 
@@ -885,7 +898,6 @@ PT_API int pt_resize(pt_ctx* c, uint32_t width, uint32_t height) {
   PT_HIP(c, hipStreamSynchronize(c->stream));
   c->width = width;
   c->height = height;
-  c->epoch++;
   c->have_params = false; // uniforms must be re-uploaded for the new size
   c->adapt_valid = false;
   c->params.band_count = 0;
@@ -907,7 +919,6 @@ PT_API int pt_reserve_passes(pt_ctx* c, uint32_t max_passes) {
   if (max_passes > c->reserved_passes) {
     PT_HIP(c, hipStreamSynchronize(c->stream));
     c->reserved_passes = max_passes;
-    c->epoch++;  // the slab may move
   }
   const int rc = ensure_buffers(c);
   c->setup_ms[PT_SETUP_RESERVE_TOTAL] = host_ms() - t_begin;
@@ -918,7 +929,7 @@ PT_API int pt_reset_accum(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   PT_HIP(c, hipSetDevice(c->device));
   if (c->accum)
-    PT_HIP(c, hipMemsetAsync(c->accum, 0, (size_t)c->local_rows * c->width * sizeof(float4), c->stream));
+    PT_HIP(c, hipMemsetAsync(c->accum, 0, n_pixels(c) * sizeof(float4), c->stream));
   PT_HIP(c, hipMemsetAsync(c->d_counters.get(), 0, PT_CTR_COUNT * sizeof(unsigned long long), c->stream));
   if (int rc = clear_error(c); rc != PT_OK) return rc;
   PT_HIP(c, hipStreamSynchronize(c->stream));
@@ -942,7 +953,7 @@ PT_API int pt_bind_accum(pt_ctx* c, void* dev_ptr, size_t bytes) {
     c->total_spp = 0;
     return rc != PT_OK ? rc : clear_error(c);
   }
-  size_t need = (size_t)c->local_rows * c->width * sizeof(float4);
+  size_t need = n_pixels(c) * sizeof(float4);
   if (bytes < need) return fail(c, PT_ERR_CAPACITY, "pt_bind_accum: %zu bytes < %zu needed", bytes, need);
   if (((uintptr_t)dev_ptr & 15u) != 0) return fail(c, PT_ERR_INVALID, "pt_bind_accum: pointer not 16-byte aligned");
   c->accum = (float4*)dev_ptr;
@@ -955,7 +966,7 @@ PT_API int pt_bind_accum(pt_ctx* c, void* dev_ptr, size_t bytes) {
 PT_API int pt_accum_ptr(pt_ctx* c, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr) return PT_ERR_INVALID;
   *dev_ptr = c->accum;
-  if (bytes) *bytes = (size_t)c->local_rows * c->width * sizeof(float4);
+  if (bytes) *bytes = n_pixels(c) * sizeof(float4);
   return PT_OK;
 }
 
@@ -964,7 +975,7 @@ PT_API int pt_accum_ptr(pt_ctx* c, void** dev_ptr, size_t* bytes) {
 // {sum r, sum g, sum b, spp}).  `dst` / `src` may be host or device pointers.
 PT_API int pt_read_accum(pt_ctx* c, float* dst, size_t bytes) {
   if (!c || !dst) return fail(c, PT_ERR_INVALID, "pt_read_accum: NULL argument");
-  const size_t need = (size_t)c->local_rows * c->width * sizeof(float4);
+  const size_t need = n_pixels(c) * sizeof(float4);
   if (bytes < need) return fail(c, PT_ERR_CAPACITY, "pt_read_accum: %zu bytes < %zu needed", bytes, need);
   PT_HIP(c, hipSetDevice(c->device));
   if (need) PT_HIP(c, hipMemcpyAsync(dst, c->accum, need, hipMemcpyDefault, c->stream));
@@ -974,7 +985,7 @@ PT_API int pt_read_accum(pt_ctx* c, float* dst, size_t bytes) {
 
 PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
   if (!c || !src) return fail(c, PT_ERR_INVALID, "pt_load_accum: NULL argument");
-  const size_t need = (size_t)c->local_rows * c->width * sizeof(float4);
+  const size_t need = n_pixels(c) * sizeof(float4);
   if (bytes != need)
     return fail(c, PT_ERR_INVALID, "pt_load_accum: %zu bytes, the current row partition holds %zu", bytes, need);
   PT_HIP(c, hipSetDevice(c->device));
@@ -983,7 +994,7 @@ PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
   // buffer, its sample count — the .w every pixel carries; a pass adds the same spp to all of them, so
   // the first and the last pixel must agree — is checked there, and only then does it replace the
   // accumulation.  A refused checkpoint leaves the context as it was.
-  const size_t n_pix = (size_t)c->local_rows * c->width;
+  const size_t n_pix = n_pixels(c);
   PT_HIP(c, hipMemcpyAsync(c->d_resolve.get(), src, need, hipMemcpyDefault, c->stream));
   float4 ends[2];
   PT_HIP(c, hipMemcpyAsync(&ends[0], c->d_resolve.get(), sizeof(float4), hipMemcpyDeviceToHost, c->stream));
@@ -1043,8 +1054,8 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   A.n_passes = n_passes;
   A.n_spheres = c->n_spheres;
   A.scene_regular = c->scene_regular ? 1u : 0u;
-  A.tiles_x = (c->width + 7) / 8;
-  A.tiles_y = (c->local_rows + 7) / 8;
+  A.tiles_x = tiles_x(c);
+  A.tiles_y = tiles_y(c);
   unsigned long long items = (unsigned long long)A.tiles_x * A.tiles_y * n_passes * 64ull;
   if (items > 0xfffffff0ull)
     return fail(c, PT_ERR_CAPACITY, "pt_render_passes: %llu work items exceed 2^32; render fewer passes per call", items);
@@ -1163,18 +1174,27 @@ static LaunchKnobs read_launch_knobs() {
   return k;
 }
 
-// (`n_first_tiles` > 0: a partial round of pt_render_adaptive — the launch covers the first n_first_tiles positions of `table`, a
-// full permutation of the tiles, and is planned for that many items; tiles_x, tiles_y and div_per_tile stay the frame's)
-static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launch* L, uint32_t n_first_tiles = 0,
-                          const uint32_t* table = nullptr) {
+// What a launch is for, as far as prepare_launch bakes it in.
+struct LaunchUse {
+  bool allow_trials = false;  // may be the autotune measurement of a geometry path (PT_GEOM_AUTO)
+  // does the launch report per-tile costs: as plan_launch decides, or overridden AFTER the plan (the plan itself is the same)
+  enum Feedback { PLANNED, OFF, ON } feedback = PLANNED;
+  // n_first_tiles > 0: a partial round of pt_render_adaptive — the launch covers the first n_first_tiles positions of `table`, a
+  // full permutation of the tiles, and is planned for that many items; tiles_x, tiles_y and div_per_tile stay the frame's
+  uint32_t n_first_tiles = 0;
+  const uint32_t* table = nullptr;
+};
+
+// (what fill_uniforms zeroed and nothing here sets stays zero: wave_log and cell_hist, which only a measuring twin gets)
+static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, Launch* L) {
   PtKernelArgs& A = L->A;
   {
     int rc = fill_uniforms(c, n_passes, A);
     if (rc != PT_OK) return rc;
   }
-  if (n_first_tiles) {
-    A.n_items = n_first_tiles * 64u * n_passes;  // (below the frame's count, which fill_uniforms has checked)
-    A.tile_order = table;
+  if (use.n_first_tiles) {
+    A.n_items = use.n_first_tiles * 64u * n_passes;  // (below the frame's count, which fill_uniforms has checked)
+    A.tile_order = use.table;
   }
   const LaunchKnobs knobs = read_launch_knobs();
   if (knobs.carry_lanes) A.carry_lanes = *knobs.carry_lanes;
@@ -1184,7 +1204,7 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
   if (dbg && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and the debug overlay exclude each other");
   if (dbg && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "debug overlay: the uuid arrays are not in place (pt_set_debug_overlay after a failed upload?)");
   // (the overlay builds exist for the ways to read the list that have a roulette build: the same steering away from the LDS walk)
-  const PathChoice choice = c->geom.choose(path_scene(c), allow_trials, rr || dbg);
+  const PathChoice choice = c->geom.choose(path_scene(c), use.allow_trials, rr || dbg);
   const int path = choice.path;
   c->geom.last = path;
 
@@ -1228,7 +1248,8 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, bool allow_trials, Launc
   const LaunchPlan P = plan_launch({A.n_items, c->params.samples_per_pixel, n_passes, block, per_cu, (uint32_t)c->num_cus, walk,
                                     c->n_spheres, knobs});
   A.queue_chunk = P.queue_chunk; A.queue_static = (uint32_t)P.deal; A.queue_groups = P.queue_groups;
-  A.n_waves = P.n_waves; A.cost_feedback = P.cost_feedback; A.coop_max_live = P.coop_max_live;
+  A.n_waves = P.n_waves; A.coop_max_live = P.coop_max_live;
+  A.cost_feedback = use.feedback == LaunchUse::PLANNED ? P.cost_feedback : (use.feedback == LaunchUse::ON ? 1u : 0u);
   L->kfn = kfn; L->grid = P.grid; L->block = block; L->lds = lds; L->path = path; L->trial = choice.trial;
   return PT_OK;
 }
@@ -1258,7 +1279,9 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
 
   Launch L;
   {
-    int rc = prepare_launch(c, n_passes, true, &L);
+    LaunchUse use;
+    use.allow_trials = true;
+    int rc = prepare_launch(c, n_passes, use, &L);
     if (rc != PT_OK) return rc;
   }
   PtKernelArgs& A = L.A;
@@ -1272,8 +1295,6 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
   const bool capturing = is_capturing(c);
   if (capturing && c->count_work)
     return fail(c, PT_ERR_INVALID, "pt_render_passes: PT_OPT_COUNT_WORK (measuring twin: allocates its wave log) cannot be captured into a hipGraph");
-  A.wave_log = nullptr;
-  A.cell_hist = nullptr;
   if (c->count_work && (path == PT_GEOM_BVH || path == PT_GEOM_GRID || path == PT_GEOM_SMALL)) { // measuring twin: not a product launch, may allocate
     const size_t n_waves = (size_t)grid * (block / 64);
     if (c->d_wave_log.capacity() < n_waves * PT_WAVE_LOG_WORDS) PT_HIP(c, c->d_wave_log.reserve(n_waves * PT_WAVE_LOG_WORDS));
@@ -1288,19 +1309,17 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
       A.cell_hist = c->d_cell_hist.get();
     }
   }
-  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;  // (capturing: no timing event pair)
-  if (!capturing) {
-    int rc = next_events(c, &ev);
-    if (rc != PT_OK) return rc;
-  }
+  TimedSpan span;  // (capturing: no timing event pair)
+  if (!capturing)
+    if (int rc = span.take(c); rc != PT_OK) return rc;
 
   PT_HIP(c, zero_queue_heads(c, A.queue_static));  // (a statically dealt launch takes no reservations from any head)
   // queue order from the previous launch's per-tile cost (identity when there is none yet); launches
   // that report no cost keep the order they find
-  if (A.cost_feedback || !c->tile_order_valid) {
+  if (c->order.uniform_wants_order_kernel(A.cost_feedback != 0u)) {
     int rc = launch_tile_order(c);
     if (rc != PT_OK) return rc;
-    if (!capturing) { c->tile_order_valid = true; c->costs_pending = false; }  // (a captured order kernel has not run: the next direct launch runs its own)
+    c->order.uniform_order_kernel_enqueued(capturing);  // (a captured order kernel has not run: the next direct launch runs its own)
   }
   if (capturing) trial = -1;
   if (trial >= 0) {
@@ -1308,26 +1327,26 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
       if (!c->trial_ev[2 * trial + k]) PT_HIP(c, hipEventCreate(&c->trial_ev[2 * trial + k]));
     PT_HIP(c, hipEventRecord(c->trial_ev[2 * trial], c->stream));
   }
-  if (ev) PT_HIP(c, hipEventRecord(ev->first, c->stream));
+  if (int rc = span.begin(c); rc != PT_OK) return rc;
   if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
-  if (A.cost_feedback && !capturing) c->costs_pending = true;
-  if (ev) PT_HIP(c, hipEventRecord(ev->second, c->stream));
+  c->order.uniform_traced(A.cost_feedback != 0u, capturing);
+  if (int rc = span.end(c); rc != PT_OK) return rc;
   if (trial >= 0) {
     PT_HIP(c, hipEventRecord(c->trial_ev[2 * trial + 1], c->stream));
-    c->geom.enqueued(trial, (double)c->local_rows * c->width * n_passes * (double)p.samples_per_pixel);
+    c->geom.enqueued(trial, (double)n_pixels(c) * n_passes * (double)p.samples_per_pixel);
   }
 
-  uint32_t n_pix = c->local_rows * c->width;
+  uint32_t n_pix = (uint32_t)n_pixels(c);
   if (estimate) {  // the same adds into accum, and the estimate's update beside them (pt_kernels_error.hip)
     float4* accum = c->accum;
     float4* est = c->d_err.get();
     const float4* slab = c->d_slab.get();
     uint32_t passes = n_passes;
     void* kargs[] = {&accum, &est, &slab, &n_pix, &passes};
-    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD), dim3(grid_for(n_pix, 256, 2048)), dim3(256), kargs, 0, c->stream));
+    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
     c->err_spp = p.samples_per_pixel;
   } else {
-    hipLaunchKernelGGL(pt_accumulate_kernel, dim3(grid_for(n_pix, 256, 2048)), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(pt_accumulate_kernel, dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream,
                        c->accum, c->d_slab.get(), n_pix, n_passes);
     PT_HIP(c, hipGetLastError());
   }
@@ -1362,12 +1381,11 @@ int plan_frame(pt_ctx* c, const uint32_t* ctr, uint32_t even_odd0, int max_rende
   // items, as the reference's frames are, through the shared queue from there on.  Round 4 dealt every group statically
   // "whatever its size"; measured in round 5 on the reference's scene and size: groups of 4- / 8- / 25-sample frames 0.126 /
   // 0.238 / 0.727 ms per frame dealt statically, 0.126 / 0.211 / 0.561 through the queue; profiles/r05_ab_runs.txt)
-  int rc = prepare_launch(c, n_frames, false, &F->L);
+  LaunchUse use;
+  use.feedback = LaunchUse::OFF;  // a frame is one short launch: it keeps the tile order it finds
+  int rc = prepare_launch(c, n_frames, use, &F->L);
   if (rc != PT_OK) return rc;
   F->L.A.frame_ctr = ctr;
-  F->L.A.cost_feedback = 0;  // a frame is one short launch: it keeps the tile order it finds
-  F->L.A.wave_log = nullptr;
-  F->L.A.cell_hist = nullptr;
   F->ctr = ctr; F->even_odd0 = even_odd0; F->max_render_count = max_render_count;
   F->render_count0 = c->params.render_count; F->should_average = c->params.should_average;
   F->last_frame_weight = c->params.last_frame_weight;
@@ -1383,15 +1401,15 @@ int enqueue_frame(pt_ctx* c, FramePlan& F, bool advance) {
   if (int rc = launch_trace(c, F.L); rc != PT_OK) return rc;
   // a frame's one pass sits in its slab ({sum r, g, b, spp} per pixel): blend straight from there, frame after frame
   // (each blend reads the texture the one before it wrote)
-  const uint32_t n_pix = c->local_rows * c->width;
+  const uint32_t n_pix = (uint32_t)n_pixels(c);
   if (F.n_frames > 1u) {  // a group: its blends as one pass over the pixels
-    hipLaunchKernelGGL(pt_frames_blend_kernel, dim3(grid_for(n_pix, 256, 2048)), dim3(256), 0, c->stream, F.slab, F.n_frames,
+    hipLaunchKernelGGL(pt_frames_blend_kernel, dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream, F.slab, F.n_frames,
                        c->d_tex[0].get(), c->d_tex[1].get(), c->d_canvas.get(), n_pix, F.ctr, F.render_count0, F.even_odd0, F.max_render_count,
                        F.should_average, F.last_frame_weight);
     PT_HIP(c, hipGetLastError());
   }
   for (uint32_t f = 0; f < (F.n_frames > 1u ? 0u : 1u); f++) {
-    hipLaunchKernelGGL(pt_frame_blend_kernel, dim3(grid_for(n_pix, 256, 2048)), dim3(256), 0, c->stream, F.slab + (size_t)f * n_pix,
+    hipLaunchKernelGGL(pt_frame_blend_kernel, dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream, F.slab + (size_t)f * n_pix,
                        c->d_tex[0].get(), c->d_tex[1].get(), c->d_canvas.get(), n_pix, F.ctr, f, F.render_count0, F.even_odd0, F.max_render_count,
                        F.should_average, F.last_frame_weight);
     PT_HIP(c, hipGetLastError());
@@ -1403,16 +1421,7 @@ int enqueue_frame(pt_ctx* c, FramePlan& F, bool advance) {
   return PT_OK;
 }
 
-// the tile order a frame finds must exist (frames report no costs and never run the order kernel themselves)
-int ensure_tile_order(pt_ctx* c) {
-  if (c->tile_order_valid) return PT_OK;
-  int rc = launch_tile_order(c);
-  if (rc != PT_OK) return rc;
-  c->tile_order_valid = true;
-  c->costs_pending = false;
-  return PT_OK;
-}
-
+// The tile order a frame finds must exist (frames report no costs and never run the order kernel themselves)
 // ... and for frames of four samples or more it should be a COST-SORTED one.  A frame (group) is a statically dealt launch:
 // wave w takes the reservations w, w + n_waves, ... of the tile-major item list, a fixed sample of the tiles.  In the IDENTITY
 // order of a fresh context that sample is a few places of the image, and a wave's load follows what lies there (sky: one
@@ -1427,35 +1436,22 @@ int ensure_tile_order(pt_ctx* c) {
 // order.  (Dealing the rounds in serpentine order, the textbook companion of a sorted list, measured +2 ... +10 % on every
 // statically dealt shape and is not used.)  Scheduling only: the probe's slab is scratch, its segment tally is taken back out
 // of the statistics.
-bool same_view(const PtParams& a, const PtParams& b) {
-  return memcmp(a.camera_origin, b.camera_origin, sizeof a.camera_origin) == 0 && memcmp(a.horizontal, b.horizontal, sizeof a.horizontal) == 0 &&
-         memcmp(a.vertical, b.vertical, sizeof a.vertical) == 0 && memcmp(a.lower_left_corner, b.lower_left_corner, sizeof a.lower_left_corner) == 0 &&
-         a.lens_radius == b.lens_radius && a.max_depth == b.max_depth;
-}
+// (When which of it happens: TileOrder::frames, pt_tile_order.hpp.)
 int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
-  if (c->params.samples_per_pixel < 4) {
-    if (c->order_probed) {  // back to the identity order: what the order kernel writes when every cost is zero (a probe leaves them
-                            // zero, a pt_render_passes with cost feedback since then does not: cleared here)
-      c->order_probed = false;
-      c->tile_order_valid = false;
-      c->costs_pending = false;
-      PT_HIP(c, hipMemsetAsync(c->d_tile_cost.get(), 0, c->d_tile_cost.capacity() * sizeof(uint32_t), c->stream));
-    }
-    return ensure_tile_order(c);
+  const TileOrder::FrameStep step = c->order.frames(c->params.samples_per_pixel, c->params, c->scene_gen, n_frames, [c] { return is_capturing(c); });
+  if (step.zero_costs)  // back to the identity order: what the order kernel writes when every cost is zero
+    PT_HIP(c, hipMemsetAsync(c->d_tile_cost.get(), 0, c->d_tile_cost.capacity() * sizeof(uint32_t), c->stream));
+  if (step.order_kernel) {
+    int rc = launch_tile_order(c);
+    if (rc != PT_OK) return rc;
+    c->order.order_kernel_ran();
   }
-  const bool fresh = c->order_probed && c->tile_order_valid && c->order_scene_gen == c->scene_gen &&
-                     (same_view(c->order_view, c->params) || c->frames_since_probe < 64u);
-  c->frames_since_probe += n_frames;
-  if (fresh) return PT_OK;
-  int rc = ensure_tile_order(c);
-  if (rc != PT_OK) return rc;
-  if (is_capturing(c)) return PT_OK;  // (a caller capturing single frames: no probe inside its graph)
+  if (!step.probe) return PT_OK;
   Launch L;
-  rc = prepare_launch(c, 1, false, &L);
+  LaunchUse use;
+  use.feedback = LaunchUse::ON;
+  int rc = prepare_launch(c, 1, use, &L);
   if (rc != PT_OK) return rc;
-  L.A.cost_feedback = 1u;
-  L.A.wave_log = nullptr;
-  L.A.cell_hist = nullptr;
   L.A.slab = reinterpret_cast<float*>(c->d_slab.get());  // scratch: a frame's own slab is written before it is read
   unsigned long long* seg = c->d_counters.get() + PT_CTR_SEGMENTS;
   PT_HIP(c, hipMemcpyAsync(c->d_counters.get() + PT_CTR_SCRATCH, seg, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
@@ -1465,11 +1461,7 @@ int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
   rc = launch_tile_order(c);
   if (rc != PT_OK) return rc;
   PT_HIP(c, hipMemcpyAsync(seg, c->d_counters.get() + PT_CTR_SCRATCH, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
-  c->order_probed = true;
-  c->costs_pending = false;
-  c->order_view = c->params;
-  c->order_scene_gen = c->scene_gen;
-  c->frames_since_probe = 0;
+  c->order.probed_for(c->params, c->scene_gen);
   return PT_OK;
 }
 
@@ -1486,7 +1478,7 @@ int frame_ready(pt_ctx* c, const char* who) {
 PT_API int pt_clear_textures(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   PT_HIP(c, hipSetDevice(c->device));
-  const size_t bytes = (size_t)c->local_rows * c->width * sizeof(uint32_t);
+  const size_t bytes = n_pixels(c) * sizeof(uint32_t);
   if (bytes == 0) return PT_OK;
   for (int k = 0; k < 2; k++) PT_HIP(c, hipMemsetAsync(c->d_tex[k].get(), 0, bytes, c->stream));
   PT_HIP(c, hipMemsetAsync(c->d_canvas.get(), 0, bytes, c->stream));
@@ -1507,7 +1499,7 @@ PT_API int pt_render_frame(pt_ctx* c, uint32_t even_odd_count) {
   rc = enqueue_frame(c, F, false);
   if (rc != PT_OK) return rc;
   c->launches++;
-  c->samples += (uint64_t)c->local_rows * c->width * (uint64_t)c->params.samples_per_pixel;
+  c->samples += (uint64_t)n_pixels(c) * (uint64_t)c->params.samples_per_pixel;
   return PT_OK;
 }
 
@@ -1533,7 +1525,7 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
   {
     uint32_t left = n_frames;
     for (int g = 0; g < kFrameLevels; g++) {
-      if (kFrameGroups[g] > 16u && (size_t)c->local_rows * c->width * kFrameGroups[g] * sizeof(float4) > kFrameSlabCap) continue;  // (too big a slab)
+      if (kFrameGroups[g] > 16u && n_pixels(c) * kFrameGroups[g] * sizeof(float4) > kFrameSlabCap) continue;  // (too big a slab)
       counts[g] = left / kFrameGroups[g];
       left -= counts[g] * kFrameGroups[g];
     }
@@ -1544,7 +1536,7 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
   // single frames out of the slab every context owns — slower, never a failed call.
   for (int g = 0; g < kFrameLevels - 1; g++) {
     if (!counts[g]) continue;
-    const size_t need = (size_t)c->local_rows * c->width * kFrameGroups[g];
+    const size_t need = n_pixels(c) * kFrameGroups[g];
     if (c->d_frame_slab.capacity() >= need) break;
     PT_HIP(c, hipStreamSynchronize(c->stream));
     if (c->d_frame_slab.reserve(need) == hipSuccess) break;
@@ -1583,22 +1575,21 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
   PT_HIP(c, hipMemsetAsync(c->d_frame_ctr.get(), 0, sizeof(uint32_t), c->stream));
   PT_HIP(c, hipMemsetAsync(c->d_counters.get() + PT_CTR_HEAD, 0, sizeof(unsigned long long), c->stream));
   PT_HIP(c, zero_queue_heads(c, 2u));
-  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-  rc = next_events(c, &ev);
-  if (rc != PT_OK) return rc;
-  PT_HIP(c, hipEventRecord(ev->first, c->stream));
+  TimedSpan span;
+  if (rc = span.take(c); rc != PT_OK) return rc;
+  if (rc = span.begin(c); rc != PT_OK) return rc;
   for (int g = 0; g < kFrameLevels; g++)
     for (uint32_t k = 0; k < counts[g]; k++) PT_HIP(c, hipGraphLaunch(c->frame_exec[g], c->stream));
-  PT_HIP(c, hipEventRecord(ev->second, c->stream));
+  if (rc = span.end(c); rc != PT_OK) return rc;
   c->launches += n_frames;
-  c->samples += (uint64_t)n_frames * c->local_rows * c->width * (uint64_t)c->params.samples_per_pixel;
+  c->samples += (uint64_t)n_frames * n_pixels(c) * (uint64_t)c->params.samples_per_pixel;
   return PT_OK;
 }
 
 static int read_rgba8(pt_ctx* c, const uint32_t* src, uint8_t* out, const char* who) {
   if (!c || !out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
   PT_HIP(c, hipSetDevice(c->device));
-  const size_t bytes = (size_t)c->local_rows * c->width * 4;
+  const size_t bytes = n_pixels(c) * 4;
   if (bytes) PT_HIP(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
@@ -1612,7 +1603,7 @@ PT_API int pt_write_texture(pt_ctx* c, int index, const uint8_t* rgba_in) {
   if (!c || !rgba_in) return fail(c, PT_ERR_INVALID, "pt_write_texture: NULL argument");
   if (index < 0 || index > 1) return fail(c, PT_ERR_INVALID, "pt_write_texture: index %d", index);
   PT_HIP(c, hipSetDevice(c->device));
-  const size_t bytes = (size_t)c->local_rows * c->width * 4;
+  const size_t bytes = n_pixels(c) * 4;
   if (bytes) PT_HIP(c, hipMemcpyAsync(c->d_tex[index].get(), rgba_in, bytes, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
@@ -1685,10 +1676,10 @@ static int resolve_common(pt_ctx* c, void* out, int gamma, int mode, const uint8
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_resolve: NULL argument");
   if (c->total_spp == 0 && !c->captured) return fail(c, PT_ERR_NOT_READY, "pt_resolve: nothing rendered yet");
   PT_HIP(c, hipSetDevice(c->device));
-  uint32_t n_pix = c->local_rows * c->width;
+  uint32_t n_pix = (uint32_t)n_pixels(c);
   if (n_pix == 0) return PT_OK;
   // the 1/spp of static/shader.frag:376 is taken per pixel from accum.w on the device
-  uint32_t grid = grid_for(n_pix, 256, 2048);
+  uint32_t grid = pixel_grid(n_pix);
   size_t bytes;
   if (mode == 0) {
     hipLaunchKernelGGL(pt_resolve_kernel, dim3(grid), dim3(256), 0, c->stream, c->accum, c->d_resolve.get(),
@@ -1726,7 +1717,7 @@ PT_API int pt_error_ptr(pt_ctx* c, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr) return fail(c, PT_ERR_INVALID, "pt_error_ptr: NULL argument");
   if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_ptr: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
   *dev_ptr = c->d_err.get();
-  if (bytes) *bytes = (size_t)c->local_rows * c->width * 2 * sizeof(float4);
+  if (bytes) *bytes = n_pixels(c) * 2 * sizeof(float4);
   return PT_OK;
 }
 
@@ -1734,116 +1725,107 @@ PT_API int pt_resolve_error(pt_ctx* c, float* rgba_out) {
   if (!c || !rgba_out) return fail(c, PT_ERR_INVALID, "pt_resolve_error: NULL argument");
   if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_resolve_error: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
   PT_HIP(c, hipSetDevice(c->device));
-  uint32_t n_pix = c->local_rows * c->width;
+  uint32_t n_pix = (uint32_t)n_pixels(c);
   if (n_pix == 0) return PT_OK;
   const float4* est = c->d_err.get();
   float4* out = c->d_resolve.get();
   void* kargs[] = {&est, &out, &n_pix};
-  PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_RESOLVE), dim3(grid_for(n_pix, 256, 2048)), dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_RESOLVE), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
   PT_HIP(c, hipMemcpyAsync(rgba_out, c->d_resolve.get(), (size_t)n_pix * sizeof(float4), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
 
 // the tile kernel over the current state: records into d_err_tiles[0, n), tallies into [n, 2 n); enqueued, not awaited
-static int launch_error_tiles(pt_ctx* c, uint32_t* tx, uint32_t* ty) {
-  *tx = (c->width + 7) / 8;
-  *ty = (c->local_rows + 7) / 8;
-  uint32_t n_tiles = *tx * *ty;
-  if (n_tiles == 0) return PT_OK;
+static int launch_error_tiles(pt_ctx* c) {
+  uint32_t tiles_n = n_tiles(c);
+  if (tiles_n == 0) return PT_OK;
   const float4* est = c->d_err.get();
   float4* tiles = c->d_err_tiles.get();
-  float4* aux = tiles + n_tiles;
-  uint32_t width = c->width, rows = c->local_rows, tiles_x = *tx;
-  void* kargs[] = {&est, &tiles, &aux, &width, &rows, &tiles_x, &n_tiles};
-  // four waves, hence four tiles, per workgroup
-  PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_TILES), dim3(grid_for(n_tiles, 4, 4096)), dim3(256), kargs, 0, c->stream));
+  float4* aux = tiles + tiles_n;
+  uint32_t width = c->width, rows = c->local_rows, tx = tiles_x(c);
+  void* kargs[] = {&est, &tiles, &aux, &width, &rows, &tx, &tiles_n};
+  PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_TILES), dim3(tile_grid(tiles_n)), dim3(256), kargs, 0, c->stream));
   return PT_OK;
 }
 
-PT_API int pt_error_tiles(pt_ctx* c, float* tiles_out, uint32_t* tiles_x, uint32_t* tiles_y) {
+PT_API int pt_error_tiles(pt_ctx* c, float* tiles_out, uint32_t* tx_out, uint32_t* ty_out) {
   if (!c) return PT_ERR_INVALID;
   if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_tiles: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
-  uint32_t tx = (c->width + 7) / 8, ty = (c->local_rows + 7) / 8;
-  if (tiles_x) *tiles_x = tx;
-  if (tiles_y) *tiles_y = ty;
-  if (!tiles_out || tx * ty == 0) return PT_OK;
+  if (tx_out) *tx_out = tiles_x(c);
+  if (ty_out) *ty_out = tiles_y(c);
+  if (!tiles_out || n_tiles(c) == 0) return PT_OK;
   PT_HIP(c, hipSetDevice(c->device));
-  if (int rc = launch_error_tiles(c, &tx, &ty); rc != PT_OK) return rc;
-  PT_HIP(c, hipMemcpyAsync(tiles_out, c->d_err_tiles.get(), (size_t)tx * ty * sizeof(float4), hipMemcpyDefault, c->stream));
+  if (int rc = launch_error_tiles(c); rc != PT_OK) return rc;
+  PT_HIP(c, hipMemcpyAsync(tiles_out, c->d_err_tiles.get(), (size_t)tiles_x(c) * tiles_y(c) * sizeof(float4), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
 
-// (`h`: the records [0, tiles) and tallies [tiles, 2 tiles) as copied, for a caller that goes on with them)
-static int error_stats(pt_ctx* c, PtErrorStats* out, std::vector<float4>& h) {
+// (`h`: the records [0, tiles) and tallies [tiles, 2 tiles) as copied, four floats each, for a caller that goes on with them; the
+// arithmetic on them: pt_error_plan.hpp)
+static int error_stats(pt_ctx* c, PtErrorStats* out, std::vector<float>& h) {
   h.clear();
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_error_stats: NULL argument");
   if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_stats: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
   memset(out, 0, sizeof *out);
-  out->pixels = (uint64_t)c->local_rows * c->width;
+  out->pixels = (uint64_t)n_pixels(c);
   PT_HIP(c, hipSetDevice(c->device));
-  uint32_t tx = 0, ty = 0;
-  if (int rc = launch_error_tiles(c, &tx, &ty); rc != PT_OK) return rc;
-  const size_t n_tiles = (size_t)tx * ty;
-  if (n_tiles == 0) return PT_OK;
-  h.resize(2 * n_tiles);
-  PT_HIP(c, hipMemcpyAsync(h.data(), c->d_err_tiles.get(), 2 * n_tiles * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = launch_error_tiles(c); rc != PT_OK) return rc;
+  const size_t tiles = (size_t)tiles_x(c) * tiles_y(c);
+  if (tiles == 0) return PT_OK;
+  h.resize(8 * tiles);
+  PT_HIP(c, hipMemcpyAsync(h.data(), c->d_err_tiles.get(), 2 * tiles * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
-  // in tile index order, in double
-  double E = 0.0, M = 0.0;
-  uint64_t counted = 0, n_short = 0, n_bad = 0;
-  float nmin = 0.f, nmax = 0.f;
-  for (size_t t = 0; t < n_tiles; t++) {
-    const float4 r = h[t], a = h[n_tiles + t];
-    E += (double)r.x;
-    M += (double)r.y;
-    if (r.z > 0.0f) {
-      nmin = counted ? std::fmin(nmin, r.w) : r.w;
-      nmax = std::fmax(nmax, a.z);
-    }
-    counted += (uint64_t)r.z;
-    n_short += (uint64_t)a.x;
-    n_bad += (uint64_t)a.y;
-  }
-  out->sum_e2 = E;
-  out->sum_m2 = M;
-  out->rel_error = M > 0.0 ? std::sqrt(E / M) : 0.0;
-  out->rms_error = counted ? std::sqrt(E / (3.0 * (double)counted)) : 0.0;
-  out->pixels_counted = counted;
-  out->pixels_short = n_short;
-  out->pixels_nonfinite = n_bad;
-  out->passes_min = nmin < 4294967040.0f ? (uint32_t)nmin : 0xffffffffu;
-  out->passes_max = nmax < 4294967040.0f ? (uint32_t)nmax : 0xffffffffu;
+  pterr::sum_tiles(h.data(), tiles, out->pixels, out);
   return PT_OK;
 }
 
 PT_API int pt_error_stats(pt_ctx* c, PtErrorStats* out) {
-  std::vector<float4> h;
+  std::vector<float> h;
   return error_stats(c, out, h);
 }
 
+// ---- rendering to a noise target: pt_render_until and, choosing tiles between the launches, pt_render_adaptive -------------------
+namespace {
+
+// what both entry points ask of their arguments (`who`: the entry point; `per`: what it calls the passes of one launch)
+int noise_target_args(pt_ctx* c, const char* who, const char* per, float target, uint32_t passes_per, uint32_t max_passes, const PtErrorStats* out) {
+  if (!c || !out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
+  if (!c->err_on) return fail(c, PT_ERR_INVALID, "%s: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", who);
+  if (!(target > 0.0f) || !std::isfinite(target)) return fail(c, PT_ERR_INVALID, "%s: the target must be finite and positive", who);
+  if (passes_per == 0 || max_passes == 0) return fail(c, PT_ERR_INVALID, "%s: no passes to render", who);
+  if (passes_per > c->reserved_passes)
+    return fail(c, PT_ERR_CAPACITY, "%s: %u passes per %s > %u reserved (pt_reserve_passes)", who, passes_per, per, c->reserved_passes);
+  return PT_OK;
+}
+int not_capturing(pt_ctx* c, const char* who) {
+  return is_capturing(c) ? fail(c, PT_ERR_INVALID, "%s: synchronises; not inside a stream capture", who) : PT_OK;
+}
+
+// the frame is the frame one uninterrupted call would give: the next launch goes on where this one ended (pass indices are
+// frame-wide: the step does not depend on how many tiles ran)
+void advance_first_pass(pt_ctx* c, uint32_t k) { c->params.first_pass += k; }
+
+// what a look at the estimate adds to its stats
+void mark_look(PtErrorStats* out, uint32_t done, float target) {
+  out->passes_rendered = done;
+  out->reached = pterr::target_reached(*out, target) ? 1u : 0u;
+}
+
+} // namespace
+
 PT_API int pt_render_until(pt_ctx* c, float target_rel_error, uint32_t passes_per_launch, uint32_t max_passes, PtErrorStats* out) {
-  if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_render_until: NULL argument");
-  if (!c->err_on) return fail(c, PT_ERR_INVALID, "pt_render_until: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
-  if (!(target_rel_error > 0.0f) || !std::isfinite(target_rel_error))
-    return fail(c, PT_ERR_INVALID, "pt_render_until: the target must be finite and positive");
-  if (passes_per_launch == 0 || max_passes == 0) return fail(c, PT_ERR_INVALID, "pt_render_until: no passes to render");
-  if (passes_per_launch > c->reserved_passes)
-    return fail(c, PT_ERR_CAPACITY, "pt_render_until: %u passes per launch > %u reserved (pt_reserve_passes)", passes_per_launch,
-                c->reserved_passes);
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_render_until: synchronises; not inside a stream capture");
+  if (int rc = noise_target_args(c, "pt_render_until", "launch", target_rel_error, passes_per_launch, max_passes, out); rc != PT_OK) return rc;
+  if (int rc = not_capturing(c, "pt_render_until"); rc != PT_OK) return rc;
   uint32_t done = 0;
   for (;;) {
     const uint32_t k = passes_per_launch < max_passes - done ? passes_per_launch : max_passes - done;
     if (int rc = pt_render_passes(c, k); rc != PT_OK) return rc;
-    // the frame is the frame one uninterrupted call would give: the next launch goes on where this one ended
-    c->params.first_pass += k;
-    c->epoch++;
+    advance_first_pass(c, k);
     done += k;
     if (int rc = pt_error_stats(c, out); rc != PT_OK) return rc;
-    out->passes_rendered = done;
-    out->reached = (out->rel_error <= (double)target_rel_error && out->pixels_short == 0) ? 1u : 0u;
+    mark_look(out, done, target_rel_error);
     if (out->reached || done >= max_passes) return PT_OK;
   }
 }
@@ -1851,86 +1833,58 @@ PT_API int pt_render_until(pt_ctx* c, float target_rel_error, uint32_t passes_pe
 // ---- adaptive sampling (include/ptrace.h pt_render_adaptive; kernels: pt_kernels_error.hip) -----------------------------------
 namespace {
 
-// in-image pixels of tile t of the local rows
-inline uint32_t tile_pixels(const pt_ctx* c, uint32_t tiles_x, uint32_t t) {
-  const uint32_t x0 = 8u * (t % tiles_x), y0 = 8u * (t / tiles_x);
-  const uint32_t w = c->width > x0 ? (c->width - x0 < 8u ? c->width - x0 : 8u) : 0u;
-  const uint32_t h = c->local_rows > y0 ? (c->local_rows - y0 < 8u ? c->local_rows - y0 : 8u) : 0u;
-  return w * h;
-}
-
-// THE SELECTION RULE (include/ptrace.h), on the records and tallies error_stats has just copied; returns the active count
-uint32_t select_tiles(const PtErrorStats& st, float target, const std::vector<float4>& h, std::vector<uint32_t>& flags) {
-  const size_t n_tiles = h.size() / 2;
-  flags.assign(n_tiles, 0u);
-  const double tau = (double)target;
-  const double t2 = tau * tau;
-  const double b = t2 * st.sum_m2;
-  const double Cd = (double)st.pixels_counted;
-  uint32_t n_active = 0;
-  for (size_t t = 0; t < n_tiles; t++) {
-    const double lhs = (double)h[t].x * Cd;
-    const double rhs = b * (double)h[t].z;
-    const bool active = h[n_tiles + t].x > 0.0f || lhs > rhs;
-    flags[t] = active ? 1u : 0u;
-    n_active += active ? 1u : 0u;
-  }
-  return n_active;
-}
-
-// One partial round: k passes over the tiles flagged in c->h_adapt_flags (n_active of n_tiles, 0 < n_active < n_tiles).
-int partial_round(pt_ctx* c, uint32_t k, uint32_t n_tiles, uint32_t n_active, uint64_t pixels_active) {
+// One partial round: k passes over the tiles flagged in c->h_adapt_flags (n_active of `tiles`, 0 < n_active < tiles).
+int partial_round(pt_ctx* c, uint32_t k, uint32_t tiles, uint32_t n_active, uint64_t pixels_active) {
   const PtParams& p = c->params;
   if (!c->have_spheres || !c->have_params)
     return fail(c, PT_ERR_NOT_READY, "pt_render_adaptive: pt_set_spheres and pt_set_params must come first");
   PT_HIP(c, hipSetDevice(c->device));
-  if (c->d_adapt.capacity() != 3 * (size_t)n_tiles) {
+  if (c->d_adapt.capacity() != 3 * (size_t)tiles) {
     PT_HIP(c, hipStreamSynchronize(c->stream));
-    PT_HIP(c, c->d_adapt.reserve(3 * (size_t)n_tiles));
+    PT_HIP(c, c->d_adapt.reserve(3 * (size_t)tiles));
   }
   uint32_t* flags = c->d_adapt.get();
-  uint32_t* part = flags + n_tiles;
-  uint32_t* base = part + n_tiles;
+  uint32_t* part = flags + tiles;
+  uint32_t* base = part + tiles;
   c->adapt_valid = false;
   // the cost order up to date, as the next pt_render_passes would bring it — and never from costs that are all zero: the order
   // kernel would write the identity over a sorted order
-  if (c->costs_pending || !c->tile_order_valid) {
+  if (c->order.partial_wants_order_kernel()) {
     if (int rc = launch_tile_order(c); rc != PT_OK) return rc;
-    c->tile_order_valid = true;
-    c->costs_pending = false;
+    c->order.order_kernel_ran();
   }
-  PT_HIP(c, hipMemcpyAsync(flags, c->h_adapt_flags.data(), (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  PT_HIP(c, hipMemcpyAsync(flags, c->h_adapt_flags.data(), (size_t)tiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   {
     const uint32_t* order = c->d_tile_order.get();
     const uint32_t* fl = flags;
-    uint32_t n = n_tiles;
+    uint32_t n = tiles;
     void* kargs[] = {&order, &fl, &part, &base, &n};
     PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_PARTITION), dim3(1), dim3(1024), kargs, 0, c->stream));
   }
   Launch L;
-  if (int rc = prepare_launch(c, k, false, &L, n_active, part); rc != PT_OK) return rc;
-  L.A.cost_feedback = 0;  // a partial launch keeps the order it finds, as a frame does
-  L.A.wave_log = nullptr;
-  L.A.cell_hist = nullptr;
-  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-  if (int rc = next_events(c, &ev); rc != PT_OK) return rc;
+  LaunchUse use;
+  use.feedback = LaunchUse::OFF;  // a partial launch keeps the order it finds, as a frame does
+  use.n_first_tiles = n_active;
+  use.table = part;
+  if (int rc = prepare_launch(c, k, use, &L); rc != PT_OK) return rc;
+  TimedSpan span;
+  if (int rc = span.take(c); rc != PT_OK) return rc;
   PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
-  PT_HIP(c, hipEventRecord(ev->first, c->stream));
+  if (int rc = span.begin(c); rc != PT_OK) return rc;
   if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
-  PT_HIP(c, hipEventRecord(ev->second, c->stream));
+  if (int rc = span.end(c); rc != PT_OK) return rc;
   {
     float4* accum = c->accum;
     float4* est = c->d_err.get();
     const float4* slab = c->d_slab.get();
     const uint32_t* order = part;
-    uint32_t na = n_active, width = c->width, rows = c->local_rows, tiles_x = (c->width + 7) / 8, passes = k;
-    void* kargs[] = {&accum, &est, &slab, &order, &na, &width, &rows, &tiles_x, &passes};
-    // four waves, hence four tiles, per workgroup
-    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD_TILES), dim3(grid_for(n_active, 4, 4096)), dim3(256), kargs, 0, c->stream));
+    uint32_t na = n_active, width = c->width, rows = c->local_rows, tx = tiles_x(c), passes = k;
+    void* kargs[] = {&accum, &est, &slab, &order, &na, &width, &rows, &tx, &passes};
+    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD_TILES), dim3(tile_grid(n_active)), dim3(256), kargs, 0, c->stream));
   }
   c->err_spp = p.samples_per_pixel;
   c->adapt_valid = true;
-  c->adapt_tiles = n_tiles;
+  c->adapt_tiles = tiles;
   c->adapt_active = n_active;
   c->launches++;
   c->samples += pixels_active * k * (uint64_t)p.samples_per_pixel;
@@ -1941,58 +1895,48 @@ int partial_round(pt_ctx* c, uint32_t k, uint32_t n_tiles, uint32_t n_active, ui
 
 PT_API int pt_render_adaptive(pt_ctx* c, float target_rel_error, uint32_t passes_per_round, uint32_t max_passes, PtErrorStats* out,
                               PtAdaptiveStats* adaptive_out) {
-  if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: NULL argument");
-  if (!c->err_on) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
-  if (!(target_rel_error > 0.0f) || !std::isfinite(target_rel_error))
-    return fail(c, PT_ERR_INVALID, "pt_render_adaptive: the target must be finite and positive");
-  if (passes_per_round == 0 || max_passes == 0) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: no passes to render");
-  if (passes_per_round > c->reserved_passes)
-    return fail(c, PT_ERR_CAPACITY, "pt_render_adaptive: %u passes per round > %u reserved (pt_reserve_passes)", passes_per_round,
-                c->reserved_passes);
+  if (int rc = noise_target_args(c, "pt_render_adaptive", "round", target_rel_error, passes_per_round, max_passes, out); rc != PT_OK) return rc;
   if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: not with PT_OPT_COUNT_WORK (the measuring twins log whole launches)");
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: synchronises; not inside a stream capture");
+  if (int rc = not_capturing(c, "pt_render_adaptive"); rc != PT_OK) return rc;
   // (refused before the first look: a call must not answer for an estimate it could not continue)
   if (c->have_params && c->err_spp != 0 && c->err_spp != c->params.samples_per_pixel)
     return fail(c, PT_ERR_INVALID, "pt_render_adaptive: %d samples per pixel while the error estimate holds passes of %d: clear first "
                                    "(pt_reset_accum)", c->params.samples_per_pixel, c->err_spp);
-  const uint32_t tiles_x = (c->width + 7) / 8;
-  const uint32_t n_tiles = tiles_x * ((c->local_rows + 7) / 8);
+  const uint32_t tiles = n_tiles(c);
   PtAdaptiveStats ad;
   memset(&ad, 0, sizeof ad);
-  ad.tiles = n_tiles;
+  ad.tiles = tiles;
   uint32_t n_active = 0;
   uint64_t pixels_active = 0;
-  std::vector<float4> h;
+  std::vector<float> h;
   uint32_t done = 0;
   // `act` starts from a look at the state the call finds.  A fresh estimate has every pixel short: all tiles.  A frame under way
   // goes on with the selection its state gives, so two calls are the rounds of one call of their passes together.
   auto look = [&]() -> int {
     if (int rc = error_stats(c, out, h); rc != PT_OK) return rc;
-    out->passes_rendered = done;
-    out->reached = (out->rel_error <= (double)target_rel_error && out->pixels_short == 0) ? 1u : 0u;
-    n_active = select_tiles(*out, target_rel_error, h, c->h_adapt_flags);
+    mark_look(out, done, target_rel_error);
+    c->h_adapt_flags.assign(h.size() / 8, 0u);  // (a flag per tile record)
+    n_active = pterr::select_tiles(*out, target_rel_error, h.data(), c->h_adapt_flags.size(), c->h_adapt_flags.data());
     pixels_active = 0;
-    for (uint32_t t = 0; t < n_tiles; t++)
-      if (c->h_adapt_flags[t]) pixels_active += tile_pixels(c, tiles_x, t);
+    for (uint32_t t = 0; t < tiles; t++)
+      if (c->h_adapt_flags[t]) pixels_active += pterr::tile_pixels(c->width, c->local_rows, tiles_x(c), t);
     ad.tiles_active = n_active;
     return PT_OK;
   };
   int rc = look();
   while (rc == PT_OK && !out->reached && done < max_passes && n_active != 0) {
     const uint32_t k = passes_per_round < max_passes - done ? passes_per_round : max_passes - done;
-    if (n_active == n_tiles) {
+    if (n_active == tiles) {
       rc = pt_render_passes(c, k);
     } else {
-      rc = partial_round(c, k, n_tiles, n_active, pixels_active);
+      rc = partial_round(c, k, tiles, n_active, pixels_active);
     }
     if (rc != PT_OK) break;
     ad.rounds++;
-    ad.partial_rounds += n_active != n_tiles ? 1u : 0u;
+    ad.partial_rounds += n_active != tiles ? 1u : 0u;
     ad.tile_passes += (uint64_t)n_active * k;
     ad.samples += pixels_active * k * (uint64_t)c->params.samples_per_pixel;
-    // pass indices are frame-wide: the step does not depend on how many tiles ran
-    c->params.first_pass += k;
-    c->epoch++;
+    advance_first_pass(c, k);
     done += k;
     rc = look();
   }
@@ -2063,7 +2007,6 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
 
 PT_API int pt_set_option(pt_ctx* c, int key, int value) {
   if (!c) return PT_ERR_INVALID;
-  c->epoch++;
   if (key == PT_OPT_GEOMETRY_PATH) {
     if (value != PT_GEOM_AUTO && value != PT_GEOM_LDS && value != PT_GEOM_SCALAR && value != PT_GEOM_BVH &&
         value != PT_GEOM_GRID && value != PT_GEOM_SMALL)
@@ -2131,7 +2074,6 @@ PT_API int pt_set_debug_overlay(pt_ctx* c, int enable, int32_t selected_object, 
   if (enable && c->rr_min_depth > 0)
     return fail(c, PT_ERR_INVALID, "pt_set_debug_overlay: the debug overlay and PT_OPT_RUSSIAN_ROULETTE exclude each other (turn roulette off first: "
                                    "pt_set_option(ctx, PT_OPT_RUSSIAN_ROULETTE, 0))");
-  c->epoch++;
   if (!enable) {
     c->dbg_enable = false;
     return PT_OK;
@@ -2187,7 +2129,6 @@ int rebuild_grid(pt_ctx* c, double factor, bool keep_tuned) {
   const int tuned = c->geom.tuned;
   int rc = install_grid(c, grid, c->h_mat.data(), n);
   if (rc == PT_OK && c->dbg_enable) rc = upload_uuids(c);
-  c->epoch++;
   c->geom.list_paths(path_scene(c));  // (which kernels the grid can feed, and whether PT_GEOM_AUTO has anything to measure, follow its size — or its absence, had the upload failed)
   if (keep_tuned && rc == PT_OK && tuned == PT_GEOM_GRID && c->have_grid) c->geom.tuned = tuned;  // a refit keeps the settled choice
   return rc;
@@ -2258,7 +2199,6 @@ int tune_grid_to_view(pt_ctx* c, uint32_t n_passes, bool* launched) {
     std::optional<ClassProbe> probe;
     if (int rc = measure(keep, true, false, &probe); rc != PT_OK) { c->grid_cells_build = false; return rc; }
     c->grid_cells_build = keep_cells_build(probe, search.keep_ms());
-    c->epoch++;
   }
   return PT_OK;
 }
@@ -2296,7 +2236,6 @@ PT_API int pt_tune(pt_ctx* c, uint32_t n_passes) {
   PT_HIP(c, hipSetDevice(c->device));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   try_finish_tuning(c);
-  c->epoch++;
   return pt_reset_accum(c);
 }
 

@@ -304,6 +304,83 @@ def test_a_partial_round_leaves_the_cost_order_as_it_found_it(ora):
     t.close()
 
 
+def _snapshot(t):
+    return {"accum": t.accum(), "state": t.error_state(), "canvas": t.read_canvas(), "tex0": t.read_texture(0), "tex1": t.read_texture(1)}
+
+
+def _load_accum_raw(t, accum):
+    """The accumulation as bytes, through its device pointer: pt_load_accum takes whole-pass checkpoints only, and after a partial
+    round the pixels' sample counts differ."""
+    from ray_tracer_webgl_amd.tracer import _H2D, _memcpy
+    ptr, nbytes = C.c_void_p(), C.c_size_t()
+    assert t.lib.pt_accum_ptr(t._ctx, C.byref(ptr), C.byref(nbytes)) == abi.PT_OK and nbytes.value == accum.nbytes
+    t.synchronize()
+    _memcpy(ptr, np.ascontiguousarray(accum).ctypes.data_as(C.c_void_p), accum.nbytes, _H2D)
+
+
+def test_every_launch_kind_in_one_context(ora):
+    """The five kinds of trace launch — uniform, single frame (with its cost-order probe), captured frame groups, partial round,
+    a frame below four samples (which takes the probed order back) — one after the other in ONE context, whose tile-order state
+    and cached plans each step hands to the next.  After every step the context holds, bit for bit, what a fresh context gives
+    that starts from the same accumulation, estimate and textures and runs that step alone (a fresh context writes its canvas
+    only in a frame step: elsewhere the one context's canvas must be the one it had).  Segment tallies add up: the probes'
+    are taken back out.  After the partial round `base` is a permutation of the tiles and `order` its stable partition."""
+    spheres, p, _ = _default(ora, 61, 37)
+    even = np.arange(40) % 2 == 0
+    loaded = E.empty_state(37, 61)          # the state of test_a_partial_round_leaves_the_cost_order_as_it_found_it
+    loaded[..., 0, :3] = 1.0
+    loaded[..., 0, 3] = 2.0
+    loaded[..., 1, 3] = 8.0
+    loaded[A.pixel_mask(even, 37, 61), 1, :3] = 100.0
+    assert A.select(loaded, TARGET).tolist() == even.tolist()
+    one_spp = p.copy()
+    one_spp.samples_per_pixel = 1
+
+    def adaptive(t):
+        st, ad = t.render_adaptive(TARGET, PER_ROUND, 2)
+        assert (ad.rounds, ad.partial_rounds, ad.tile_passes) == (1, 1, 40)
+        base, order, n_active = t.adaptive_tiles()
+        assert sorted(base.tolist()) == list(range(40)) and n_active == 20
+        assert order.tolist() == A.partition(base, even).tolist()
+
+    def frame_at_one_spp(t):
+        back = t.params.copy()
+        t.set_params(one_spp)
+        t.render_frame(0)
+        t.set_params(back)
+
+    steps = [("render_passes(2)", lambda t: t.render_passes(2), False),
+             ("a frame, which probes", lambda t: t.render_frame(0), True),
+             ("a series of 5 frames", lambda t: t.render_frames(1, 100000, 5), True),
+             ("load_error_state", lambda t: t.load_error_state(loaded), False),
+             ("an adaptive call with a partial round", adaptive, False),
+             ("a frame at 1 spp", frame_at_one_spp, True),
+             ("render_passes(2) again", lambda t: t.render_passes(2), False)]
+    t = _context(spheres, p)
+    segments = 0
+    for name, step, draws in steps:
+        before, params = _snapshot(t), t.params.copy()
+        step(t)
+        after = _snapshot(t)
+        u = _context(spheres, params)
+        _load_accum_raw(u, before["accum"])
+        u.load_error_state(before["state"])
+        u.write_texture(0, before["tex0"])
+        u.write_texture(1, before["tex1"])
+        step(u)
+        alone = _snapshot(u)
+        for k in after:
+            want = alone[k] if draws or k != "canvas" else before[k]
+            assert after[k].tobytes() == want.tobytes(), "%s: %s differs from a fresh context's" % (name, k)
+        assert t.params.first_pass == u.params.first_pass, name
+        segments += u.stats().segments
+        assert t.stats().segments == segments, name
+        u.close()
+    n = t.error_state()[..., 0, 3]
+    assert np.all(n[A.pixel_mask(even, 37, 61)] == 6.0) and np.all(n[A.pixel_mask(~even, 37, 61)] == 4.0)
+    t.close()
+
+
 def test_nothing_to_skip(ora):
     """A target so loose that it is reached at the first look: one uniform round, the bytes of pt_render_until."""
     spheres, p, solo = _default(ora, 61, 37)
