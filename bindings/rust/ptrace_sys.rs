@@ -80,6 +80,9 @@ extern "C" {
     pub fn pt_render_until(ctx: *mut PtCtx, target_rel_error: f32, passes_per_launch: u32, max_passes: u32, out: *mut PtErrorStats) -> c_int;
     pub fn pt_render_adaptive(ctx: *mut PtCtx, target_rel_error: f32, passes_per_round: u32, max_passes: u32, out: *mut PtErrorStats, adaptive_out: *mut PtAdaptiveStats) -> c_int;
     pub fn pt_adaptive_tiles(ctx: *mut PtCtx, base_out: *mut u32, order_out: *mut u32, n_tiles: *mut u32, n_active: *mut u32) -> c_int;
+    // the variance-guided filtered read-out of the estimate: each pixel's mean averaged with the neighbours within `radius` whose
+    // means differ by no more than kappa standard errors of the difference; out.a = accepted taps
+    pub fn pt_resolve_filtered(ctx: *mut PtCtx, rgba_out: *mut f32, radius: u32, kappa: f32, gamma: c_int) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;
@@ -101,6 +104,8 @@ extern "C" {
 
 pub const PT_OPT_GEOMETRY_PATH: c_int = 1;      // PT_GEOM_AUTO 0 / LDS 1 / SCALAR 2 / BVH 3 / GRID 4 / SMALL 5
 pub const PT_OPT_ERROR_ESTIMATE: c_int = 7;     // opt-in, 0 = off; the image bits do not depend on it
+pub const PT_FILTER_MAX_RADIUS: u32 = 4;        // pt_resolve_filtered: the largest radius
+pub const PT_FILTER_KAPPA_DEFAULT: f32 = 2.0;   // ... and the kappa its callers start from
 pub const PT_OPT_RUSSIAN_ROULETTE: c_int = 5;   // opt-in, 0 = off: the reference's estimator has none (shader.frag:297-339)
 
 // The rAF closure of src/lib.rs:65-104 with webgl::render replaced (one tick):

@@ -413,6 +413,55 @@ int pt_render_adaptive(pt_ctx* ctx, float target_rel_error, uint32_t passes_per_
  * PT_ERR_NOT_READY before the first partial round, and again after pt_set_spheres, pt_resize and any repartition. */
 int pt_adaptive_tiles(pt_ctx* ctx, uint32_t* base_out, uint32_t* order_out, uint32_t* n_tiles, uint32_t* n_active);
 
+/* ---- variance-guided filtered read-out of the estimate (build extension, opt-in: PT_OPT_ERROR_ESTIMATE) ------------------
+ * pt_resolve_filtered: the estimate's own mean of each pixel, averaged with those neighbours within `radius` whose means differ
+ * from it by no more than their standard errors explain (kappa standard errors of the difference, all three channels
+ * together).  rgba_out: host or device pointer to local_rows*width RGBA fp32 texels, row 0 = lowest owned row.  Synchronises
+ * like pt_resolve: a read-out, not for use inside a stream capture.
+ * PT_ERR_INVALID for a NULL ctx or rgba_out, for radius > PT_FILTER_MAX_RADIUS, for a kappa that is not finite or is below 0;
+ * PT_ERR_NOT_READY while the estimate is off, like pt_resolve_error.
+ * THE CALL READS THE ESTIMATE'S STATE ONLY.  It never reads accum: it speaks for the passes the estimate knows of.
+ * fp32, ONE IEEE operation per statement, nothing fused, `/` and sqrtf correctly rounded (the error kernels' discipline):
+ *     (the read-out of DESIGN.md §4.8b is pt_resolve_error's above: se, and m.c = mean.c * q; both 0 where !known)
+ *     per pixel: (se, m, known) = the read-out of §4.8b (pixel_error)
+ *                counted = known && finite se && finite m     (the tile kernel's "counted")
+ *                v.c = se.c * se.c
+ *     once:      k2 = kappa * kappa
+ *     rows p may look at: band_count <= 1: all local rows
+ *                         otherwise: the local rows ly with ly / band_rows == y_p / band_rows
+ *                         (p's own chunk of consecutive image rows; local rows of different chunks
+ *                         are not neighbours in the image)
+ *     centre p = (x, y) not counted:
+ *         f = m                                   (0 where unknown, non-finite stays non-finite)
+ *         cnt = 0
+ *     centre p counted:
+ *         sum = {+0, +0, +0}
+ *         cnt = +0
+ *         for dy = -R .. R ascending, for dx = -R .. R ascending:
+ *             q = (x + dx, y + dy)
+ *             skip unless 0 <= q.x < width, q.y is a row p may look at, and q is counted
+ *             if (dx, dy) != (0, 0):
+ *                 d.c = m_p.c - m_q.c
+ *                 d2.c = d.c * d.c
+ *                 t = (d2.r + d2.g) + d2.b
+ *                 s.c = v_p.c + v_q.c
+ *                 u = (s.r + s.g) + s.b
+ *                 rhs = k2 * u
+ *                 skip unless t <= rhs            (a NaN on either side skips)
+ *             sum.c = sum.c + m_q.c
+ *             cnt = cnt + 1.0f
+ *         f.c = sum.c / cnt
+ *     gamma != 0: f.c = sqrtf(f.c)                (every pixel)
+ *     out = {f.r, f.g, f.b, cnt}                  (.a = accepted taps, 0 for an uncounted centre)
+ * Radius 0 is the estimate's own mean with cnt 1: the centre is always accepted.  The test is symmetric in p and q.
+ * Multi-GPU: a band context filters inside its own row chunks, so its gathered frame differs from the single-GPU filtered
+ * frame near chunk borders.  A host that wants exactly that frame gathers the ranks' raw states (pt_error_ptr), loads them
+ * into one full-height context and filters there: the state is the only input, so this works.
+ * There is no standard error of the filtered frame (the propagated variance reads far too low). */
+#define PT_FILTER_MAX_RADIUS 4
+#define PT_FILTER_KAPPA_DEFAULT 2.0f
+int pt_resolve_filtered(pt_ctx* ctx, float* rgba_out, uint32_t radius, float kappa, int gamma);
+
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)
  * using params.render_count / should_average / last_frame_weight, writes RGBA8 to `out_rgba8`.

@@ -57,6 +57,7 @@ SIGNATURES = {
                                      C.POINTER(abi.PtAdaptiveStats)]),
     "pt_adaptive_tiles": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                     C.POINTER(C.c_uint32)]),
+    "pt_resolve_filtered": (C.c_int, [_ctx, _vp, C.c_uint32, C.c_float, C.c_int]),
     "pt_refit_grid": (C.c_int, [_ctx, C.c_int]),
     "pt_grid_fit": (C.c_int, [_ctx]),
     "pt_build_bvh": (C.c_int, [C.POINTER(abi.PtSphere), C.c_uint32, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp,
@@ -104,10 +105,10 @@ SIGNATURES = {
 
 
 # entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay, the error
-# estimate, adaptive sampling
+# estimate, adaptive sampling, the filtered read-out
 ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_set_debugging", "pt_state_debug_overlay",
                       "pt_error_ptr", "pt_resolve_error", "pt_error_tiles", "pt_error_stats", "pt_render_until",
-                      "pt_render_adaptive", "pt_adaptive_tiles")
+                      "pt_render_adaptive", "pt_adaptive_tiles", "pt_resolve_filtered")
 
 
 def _elf_dynamic_strings(path, tags):

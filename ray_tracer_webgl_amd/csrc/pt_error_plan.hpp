@@ -74,4 +74,15 @@ inline uint32_t tile_pixels(uint32_t width, uint32_t rows, uint32_t tiles_x, uin
   return w * h;
 }
 
+// pt_resolve_filtered: the rows a pixel of local row ly may look at — its own chunk of band_rows consecutive
+// image rows, as first and last LOCAL row (the last chunk of a band may be partial).  band_rows == 0: the context is no band,
+// every local row.  ly < local_rows.  (constexpr: pt_filter_kernel computes its row range with this very function.)
+struct ChunkRows { uint32_t first, last; };
+constexpr ChunkRows chunk_rows(uint32_t ly, uint32_t band_rows, uint32_t local_rows) {
+  if (band_rows == 0u) return ChunkRows{0u, local_rows - 1u};
+  const uint32_t first = ly / band_rows * band_rows;
+  const uint32_t left = local_rows - first;            // rows from `first` to the end: at least 1
+  return ChunkRows{first, first + (left < band_rows ? left : band_rows) - 1u};
+}
+
 }  // namespace pterr

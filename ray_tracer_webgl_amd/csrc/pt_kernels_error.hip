@@ -1,18 +1,21 @@
 // pt_kernels_error.hip — the PER-PIXEL ERROR ESTIMATE (pt_set_option PT_OPT_ERROR_ESTIMATE; include/ptrace.h, DESIGN.md
 // §error estimate), a translation unit and gfx950 code object of its own: the HIP runtime loads it when the estimate is
-// first turned on, so a context that never asks for it pays nothing.  Five kernels, none of them a trace kernel:
+// first turned on, so a context that never asks for it pays nothing.  Six kernels, none of them a trace kernel:
 //   pt_fold_error_kernel     takes pt_accumulate_kernel's place: the same four fp32 adds per pass in the same order (accum
 //                            keeps its bits) and, beside them, Welford's update of the pass sums' mean and M2 per channel
 //   pt_resolve_error_kernel  the standard error of each pixel's mean as linear radiance
 //   pt_error_tiles_kernel    per 8x8 tile of the local rows, one wave64: sums of se^2 and mean^2 over the counted pixels
 //   pt_partition_order_kernel, pt_fold_error_tiles_kernel   a partial round of pt_render_adaptive: the queue's tile table with
 //                            the active tiles first, and the fold over those tiles' pixels only
+//   pt_filter_kernel         the variance-guided filtered read-out (pt_resolve_filtered): each pixel's mean averaged with the
+//                            neighbours whose means differ by no more than the standard errors explain
 // The arithmetic is a contract (tests/error_ref.py restates it statement by statement): ONE IEEE fp32 operation per
 // statement, nothing fused (-ffp-contract=off), `/` and sqrtf correctly rounded.  pt_api.hip reaches the kernels through
 // pt_error_kernel() only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pt_error_plan.hpp"
 #include "pt_extra.h"
 
 // state per pixel i: est[2 i] = A = {mean.r, mean.g, mean.b, n}, est[2 i + 1] = B = {M2.r, M2.g, M2.b, k}
@@ -184,8 +187,105 @@ extern "C" __global__ __launch_bounds__(256) void pt_error_tiles_kernel(const fl
   }
 }
 
+// THE FILTERED READ-OUT (pt_resolve_filtered; the statements: include/ptrace.h, DESIGN.md §4.8d, tests/filter_ref.py).  A
+// 256-thread workgroup owns a 32x8 tile of output pixels, thread t the pixel (t % 32, t / 32) of it.  It stages the tile and a halo
+// of PT_FILTER_MAX_RADIUS texels into the LDS as seven planes — m.rgb, v.rgb = se.rgb^2 and the counted flag — so the read-out
+// (three divisions, three square roots, the finiteness tests) is evaluated once per staged texel, not per tap; texels outside
+// the image are staged as not counted.  After one barrier every pixel runs the tap loop from the LDS in the contract's order
+// (dy ascending, then dx ascending); a tap row outside the pixel's chunk of band rows is rejected by comparing it with the
+// chunk's first and last local row, computed once per pixel.
+// Row stride 40 = the staged width, no padding: every LDS access here is a ds_read_b32 / ds_write_b32, which the LDS serves in
+// two groups of 32 lanes with 32 banks.  A group is one 32-pixel row of the tile: 32 consecutive dwords, conflict-free whatever
+// the stride; and the staging stores of 32 consecutive texels are 32 consecutive dwords only without padding.
+#define FILTER_TW 32
+#define FILTER_TH 8
+#define FILTER_SW (FILTER_TW + 2 * PT_FILTER_MAX_RADIUS)
+#define FILTER_SH (FILTER_TH + 2 * PT_FILTER_MAX_RADIUS)
+struct FilterTile {
+  float m[3][FILTER_SH * FILTER_SW], v[3][FILTER_SH * FILTER_SW];
+  uint32_t counted[FILTER_SH * FILTER_SW];
+};
+
+// one pixel's taps, the loops over the launch-uniform radius at run time: a tap is seven LDS reads and some twenty VALU
+// operations, beside which its address arithmetic does not count; one instantiation per radius with both loops unrolled made
+// the scheduler hoist the 567 reads of radius 4 (512 registers, spills, one wave per SIMD)
+__device__ __forceinline__ float4 filter_taps(const FilterTile& s, int centre, int y, int first_row, int last_row, int R, float k2) {
+  const float mp[3] = {s.m[0][centre], s.m[1][centre], s.m[2][centre]};
+  const float vp[3] = {s.v[0][centre], s.v[1][centre], s.v[2][centre]};
+  float sum[3] = {0.0f, 0.0f, 0.0f};
+  float cnt = 0.0f;
+  for (int dy = -R; dy <= R; dy++) {
+    if (y + dy < first_row || y + dy > last_row) continue;   // (uniform over a row of the tile: half a wave)
+    for (int dx = -R; dx <= R; dx++) {
+      const int q = centre + dy * FILTER_SW + dx;
+      const float mq[3] = {s.m[0][q], s.m[1][q], s.m[2][q]};
+      const float vq[3] = {s.v[0][q], s.v[1][q], s.v[2][q]};
+      const float d0 = mp[0] - mq[0], d1 = mp[1] - mq[1], d2 = mp[2] - mq[2];
+      const float e0 = d0 * d0, e1 = d1 * d1, e2 = d2 * d2;
+      const float t01 = e0 + e1;
+      const float t = t01 + e2;
+      const float s0 = vp[0] + vq[0], s1 = vp[1] + vq[1], s2 = vp[2] + vq[2];
+      const float u01 = s0 + s1;
+      const float u = u01 + s2;
+      const float rhs = k2 * u;
+      const bool ok = s.counted[q] != 0u && ((dx == 0 && dy == 0) || t <= rhs);   // the centre is accepted untested
+      const float a0 = sum[0] + mq[0], a1 = sum[1] + mq[1], a2 = sum[2] + mq[2];
+      const float c1 = cnt + 1.0f;
+      sum[0] = ok ? a0 : sum[0];
+      sum[1] = ok ? a1 : sum[1];
+      sum[2] = ok ? a2 : sum[2];
+      cnt = ok ? c1 : cnt;
+    }
+  }
+  return make_float4(sum[0] / cnt, sum[1] / cnt, sum[2] / cnt, cnt);
+}
+
+// grid: ceil(width / 32) x ceil(rows / 8) workgroups.  band_rows: the chunk height of a band context, 0 for a context that is no
+// band (pt_error_plan.hpp chunk_rows).
+extern "C" __global__ __launch_bounds__(256) void pt_filter_kernel(const float4* est, float4* out, uint32_t width, uint32_t rows,
+                                                                   uint32_t band_rows, uint32_t radius, float kappa, int gamma) {
+  __shared__ FilterTile s;
+  const int x0 = (int)(blockIdx.x * FILTER_TW), y0 = (int)(blockIdx.y * FILTER_TH);
+  for (int i = (int)threadIdx.x; i < FILTER_SH * FILTER_SW; i += 256) {
+    const int gx = x0 + i % FILTER_SW - PT_FILTER_MAX_RADIUS, gy = y0 + i / FILTER_SW - PT_FILTER_MAX_RADIUS;
+    const bool inside = gx >= 0 && gx < (int)width && gy >= 0 && gy < (int)rows;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+    if (inside) {
+      const size_t j = (size_t)gy * width + (size_t)gx;
+      a = est[2 * j];
+      b = est[2 * j + 1];
+    }
+    const PixelError r = pixel_error(a, b);
+    s.counted[i] = (inside && r.known && finite3(r.se) && finite3(r.m)) ? 1u : 0u;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      s.m[c][i] = r.m[c];
+      s.v[c][i] = r.se[c] * r.se[c];
+    }
+  }
+  __syncthreads();
+  const int tx = (int)(threadIdx.x % FILTER_TW), ty = (int)(threadIdx.x / FILTER_TW);
+  const int x = x0 + tx, y = y0 + ty;
+  if (x >= (int)width || y >= (int)rows) return;
+  const int centre = (ty + PT_FILTER_MAX_RADIUS) * FILTER_SW + tx + PT_FILTER_MAX_RADIUS;
+  float4 f = make_float4(s.m[0][centre], s.m[1][centre], s.m[2][centre], 0.0f);   // an uncounted centre passes through
+  if (s.counted[centre] != 0u) {
+    const pterr::ChunkRows ch = pterr::chunk_rows((uint32_t)y, band_rows, rows);
+    const int first_row = (int)ch.first, last_row = (int)ch.last;
+    const float k2 = kappa * kappa;
+    f = filter_taps(s, centre, y, first_row, last_row, (int)radius, k2);
+  }
+  if (gamma != 0) {
+    f.x = __builtin_sqrtf(f.x);
+    f.y = __builtin_sqrtf(f.y);
+    f.z = __builtin_sqrtf(f.z);
+  }
+  out[(size_t)y * width + (size_t)x] = f;
+}
+
 extern "C" const void* pt_error_kernel(int id) {
   switch (id) {
+    case PT_E_FILTER: return reinterpret_cast<const void*>(pt_filter_kernel);
     case PT_E_FOLD: return reinterpret_cast<const void*>(pt_fold_error_kernel);
     case PT_E_RESOLVE: return reinterpret_cast<const void*>(pt_resolve_error_kernel);
     case PT_E_TILES: return reinterpret_cast<const void*>(pt_error_tiles_kernel);

@@ -5,9 +5,13 @@ src/dom.rs:126-143, without a browser).
     python -m ray_tracer_webgl_amd.render --config default --debug-overlay --out overlay.png
     python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.02 --max-spp 4096 --error-out cover_error.png
     python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.02 --adaptive --samples-out cover_samples.png
+    python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.05 --denoise --out cover_filtered.png
 """
 import argparse
+import math
 import time
+
+import numpy as np
 
 from . import image_io, scenes
 from . import abi
@@ -40,6 +44,11 @@ def main(argv=None):
     ap.add_argument("--error-out", metavar="FILE", help="also write the per-pixel standard error (linear radiance, shown x 8) as an image")
     ap.add_argument("--samples-out", metavar="FILE",
                     help="also write the per-pixel sample counts (white = the frame's largest count) as an image")
+    ap.add_argument("--denoise", nargs="?", const="2", metavar="R[,KAPPA]",
+                    help="with --noise-target or --error-out: write the main image from the variance-guided filtered read-out "
+                         "(pt_resolve_filtered: a pixel is averaged with the neighbours within R whose means differ by no more than "
+                         "KAPPA standard errors; default 2,%g; R at most %d); prints the mean accepted taps"
+                         % (abi.PT_FILTER_KAPPA_DEFAULT, abi.PT_FILTER_MAX_RADIUS))
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--checkpoint", help="also save the fp32 accumulation buffer (.npz)")
     args = ap.parse_args(argv)
@@ -73,6 +82,14 @@ def main(argv=None):
     per = min(sc.n_passes, 16)
     if args.adaptive and args.noise_target is None:
         ap.error("--adaptive chooses tiles by the noise target: only with --noise-target")
+    denoise = None
+    if args.denoise is not None:
+        if args.noise_target is None and not args.error_out:
+            ap.error("--denoise filters by the error estimate: only with --noise-target or --error-out")
+        try:
+            denoise = parse_denoise(args.denoise)
+        except ValueError as e:
+            ap.error("--denoise: %s" % e)
     if args.noise_target is not None or args.error_out:
         if overlay is not None:
             ap.error("--noise-target / --error-out measure the frame's noise: not with --debug-overlay")
@@ -82,7 +99,12 @@ def main(argv=None):
         pt, acc = render_scene(sc, device=args.device, passes_per_launch=per, geometry_path=geom, tune=min(per, 8), overlay=overlay)
     dt = time.perf_counter() - t0
     st = pt.stats()
-    frame = pt.resolve(gamma=True)
+    if denoise is not None:
+        frame = pt.filtered_image(denoise[0], denoise[1], gamma=True)
+        print("denoise: radius %d, kappa %g, %.2f accepted taps per pixel" % (denoise[0], denoise[1], float(frame[..., 3].mean())))
+        frame[..., 3] = 1.0   # (the taps are no alpha)
+    else:
+        frame = pt.resolve(gamma=True)
     image_io.write_png(args.out, frame)
     if args.error_out:
         err = pt.error_image()
@@ -99,6 +121,20 @@ def main(argv=None):
     print("%s: %dx%d, %d spheres, %d spp, depth %d: %.2f s, %.0f Mray/s -> %s" % (
         sc.name, p.width, p.height, len(sc.spheres), st.total_spp, p.max_depth, dt, st.segments / dt / 1e6, args.out))
     pt.close()
+
+
+def parse_denoise(text):
+    """--denoise's value "R" or "R,KAPPA" -> (radius, kappa); ValueError says what is wrong with it."""
+    parts = text.split(",")
+    if len(parts) > 2:
+        raise ValueError("R or R,KAPPA, not %r" % text)
+    radius = int(parts[0])
+    kappa = float(parts[1]) if len(parts) == 2 else abi.PT_FILTER_KAPPA_DEFAULT
+    if not 0 <= radius <= abi.PT_FILTER_MAX_RADIUS:
+        raise ValueError("the radius is 0 to %d" % abi.PT_FILTER_MAX_RADIUS)
+    if not math.isfinite(kappa) or kappa < 0.0:
+        raise ValueError("kappa is finite and not negative")
+    return radius, kappa
 
 
 def render_to_target(sc, args, geom, per):

@@ -311,6 +311,17 @@ class PathTracer:
             self._check(self.lib.pt_resolve_error(self._ctx, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def filtered_image(self, radius=2, kappa=abi.PT_FILTER_KAPPA_DEFAULT, gamma=True):
+        """(local_rows, width, 4) fp32: the estimate's own mean of each pixel averaged with the neighbours within `radius`
+        (at most abi.PT_FILTER_MAX_RADIUS) whose means differ from it by no more than `kappa` standard errors of the
+        difference (include/ptrace.h pt_resolve_filtered); a = the accepted taps, 0 where the estimate has nothing to say.
+        Reads the estimate's state only: it speaks for the passes the estimate knows of.  A band context filters inside its
+        own row chunks."""
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
+        if out.size:
+            self._check(self.lib.pt_resolve_filtered(self._ctx, out.ctypes.data_as(C.c_void_p), int(radius), float(kappa), 1 if gamma else 0))
+        return out
+
     def error_tiles(self):
         """(tiles_y, tiles_x, 4) fp32 per 8x8 tile of the local rows: {sum se^2, sum mean^2, counted pixels, min passes}."""
         tx, ty = C.c_uint32(), C.c_uint32()
