@@ -260,7 +260,8 @@ int pt_resize(pt_ctx* ctx, uint32_t width, uint32_t height);
 /* ---- scene + uniforms ------------------------------------------------------------------------
  * pt_set_spheres replaces webgl::set_geometry (src/webgl.rs:225-274); n is not capped at 15:
  * up to 10 232 spheres are walked from LDS, up to 65 528 from global memory (PT_ERR_CAPACITY beyond).
- * pt_set_params replaces Uniforms::run_setters (src/webgl.rs:629-633). Both copy. */
+ * pt_set_params replaces Uniforms::run_setters (src/webgl.rs:629-633). Both copy.  A pt_set_spheres that fails after its
+ * first device write leaves the context without a scene: the render calls return PT_ERR_NOT_READY until a call succeeds. */
 int pt_set_spheres(pt_ctx* ctx, const PtSphere* spheres, uint32_t n);
 int pt_set_params(pt_ctx* ctx, const PtParams* params);
 

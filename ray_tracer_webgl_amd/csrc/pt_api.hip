@@ -25,6 +25,7 @@
 #include "pt_bvh.hpp"
 #include "pt_grid.hpp"
 #include "pt_grid_records.hpp"
+#include "pt_scene_image.hpp"
 #include "pt_extra.h"
 #include "pt_kernel_args.h"
 #include "pt_geom_plan.hpp"
@@ -98,17 +99,38 @@ struct FramePlan {
   uint32_t n_frames = 1;  // frames traced by the one launch (as its passes), blended one after the other
 };
 
+// The scene on the device (pt_set_spheres installs it; pt_scene_image.hpp makes what is uploaded): the sphere list and the two
+// culling structures, which tiny and irregular scenes do not get.  Each owns its buffers and keeps its host head.
+struct SceneList {
+  DevBuf<float> geom, r0;  // r0: PtKernelArgs::mat_r0
+  DevBuf<PtMatRec> mat;
+  DevBuf<int32_t> uuid;    // n: PtSphere.uuid in list order (debug overlay: upload_uuids)
+  uint32_t n = 0;
+  ptscene::Split host;     // what was uploaded: pt_tune rebuilds the grid from it (fit_grid_to_view), the uuid arrays are made from it
+};
+// what the walk kernels read per slot of a structure (index_n slots in use), and whether the structure is in place
+struct SceneSlots {
+  bool present = false;
+  DevBuf<uint32_t> index;  // the slot's sphere
+  DevBuf<PtMatRec> mat;    // ... its material
+  DevBuf<int32_t> uuid;    // ... its uuid (debug overlay)
+  size_t index_n = 0;
+};
+// (the heads: host copies of the scalars, the arrays released after upload)
+struct SceneBvh : SceneSlots { ptbvh::Bvh head; DevBuf<uint32_t> nodes; DevBuf<float> nodes32, slots; };
+// ring: a one-layer grid's records once more, in the ring layout the two-axis walk reads (pt_grid_records.hpp); entries: 16 B each
+struct SceneGrid : SceneSlots { ptgrid::Grid head; DevBuf<uint32_t> cells, ring; DevBuf<float> entries; };
+
 struct pt_ctx {
   int device = 0;
   uint32_t width = 0, height = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr; // own_stream or the caller's
   // scene
-  DevBuf<float> d_geom;
-  DevBuf<char> d_mat;  // sphere_cap shading records, then their r0 pairs (PtKernelArgs::mat_r0)
-  uint32_t n_spheres = 0, sphere_cap = 0;
-  bool scene_regular = true;
-  bool have_spheres = false, have_params = false;
+  SceneList list;
+  SceneBvh bvh;
+  SceneGrid grid;
+  bool have_spheres = false, have_params = false;  // have_spheres: list, bvh and grid are one scene's, wholly installed
   PtParams params{};
   uint32_t local_rows = 0;
   // accumulation
@@ -133,26 +155,6 @@ struct pt_ctx {
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   PathTuner geom;
   hipEvent_t trial_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // begin/end per trial
-  // culling hierarchy (PT_GEOM_BVH), rebuilt by pt_set_spheres; absent for tiny / irregular scenes
-  bool have_bvh = false;
-  DevBuf<uint32_t> d_bvh_nodes;
-  DevBuf<float> d_bvh_nodes32;
-  DevBuf<float> d_bvh_slots;
-  DevBuf<uint32_t> d_bvh_index;
-  DevBuf<PtMatRec> d_bvh_mat;   // per slot: the material of the slot's sphere
-  uint32_t bvh_n_nodes = 0, bvh_n_slots = 0, bvh_n_tree_slots = 0, bvh_n_outliers = 0, bvh_depth = 0;
-  float bvh_c0[3] = {0, 0, 0}, bvh_s0 = 0, bvh_kinv = 1;
-  // uniform grid (PT_GEOM_GRID), rebuilt by pt_set_spheres; absent for tiny / irregular scenes
-  bool have_grid = false;
-  // host copies of what the grid is built from: pt_tune rebuilds it for the view (fit_grid_to_view)
-  std::vector<float> h_geom, h_radii;
-  std::vector<PtMatRec> h_mat;
-  DevBuf<uint32_t> d_grid_cells;
-  DevBuf<uint32_t> d_grid_ring;  // a one-layer grid's records once more, in the ring layout the two-axis walk reads (pt_grid_records.hpp)
-  DevBuf<float> d_grid_entries;  // 16 B per entry
-  DevBuf<uint32_t> d_grid_index;
-  DevBuf<PtMatRec> d_grid_mat;
-  ptgrid::Grid grid;  // host copy of the scalars (the arrays are released after upload)
   bool grid_cells_build = false;  // pt_tune measured the build that gathers its entries from L2 faster than the LDS-staged one on this scene and view (grid_staging)
   int grid_fit_mode = 0;  // PT_OPT_GRID_FIT: 0 pt_tune measures the margin classes, 1 it takes the one the camera needs unmeasured
   int count_work = 0; // PT_OPT_COUNT_WORK: launch the measuring twin of the walk kernel
@@ -168,12 +170,7 @@ struct pt_ctx {
   bool dbg_enable = false;
   int32_t dbg_selected = 0;
   float dbg_cursor[3] = {0.f, 0.f, 0.f};
-  std::vector<int32_t> h_uuid;      // PtSphere.uuid in list order (host copy: the device arrays are made from it)
-  DevBuf<int32_t> d_uuid;           // n_spheres
-  DevBuf<int32_t> d_bvh_uuid;       // per hierarchy slot, like d_bvh_mat
-  DevBuf<int32_t> d_grid_uuid;      // per grid entry, like d_grid_mat
-  size_t bvh_index_n = 0;           // elements of d_bvh_index in use
-  bool uuid_valid = false;          // the three arrays match the scene and structures in place
+  bool uuid_valid = false;          // the three uuid arrays match the scene and structures in place
   int last_build = 0;               // which build the most recent trace launch was (pt_last_trace_build)
   // work-queue ordering feedback, one entry per tile
   DevBuf<uint32_t> d_tile_cost;
@@ -425,29 +422,23 @@ void try_finish_tuning(pt_ctx* c) {
 }
 
 PathScene path_scene(const pt_ctx* c) {
-  return {c->n_spheres, c->have_bvh, c->have_grid, c->grid.max_cell_entries, c->grid.n_always};
+  return {c->list.n, c->bvh.present, c->grid.present, c->grid.head.max_cell_entries, c->grid.head.n_always};
 }
 
 // the margin class the current uniforms need of the grid (pt_geom_plan.hpp); 0 = no grid / no uniforms / a camera that is not finite
 double need_factor(const pt_ctx* c) {
-  return c->have_grid && c->have_params ? view_need_factor(c->params, c->grid.c0, c->grid.s0) : 0.0;
+  return c->grid.present && c->have_params ? view_need_factor(c->params, c->grid.head.c0, c->grid.head.s0) : 0.0;
 }
 
 // does the grid in place fit the view (PtStats.grid_fit_stale, pt_grid_fit)?
 int fit_state(const pt_ctx* c) {
-  return grid_fit_state(c->geom.grid_in_use(c->have_grid), need_factor(c), (double)c->grid.near_factor);
-}
-
-// cell records a build that stages them copies into the LDS: a one-layer grid's in the ring layout (pt_grid_records.hpp; the
-// builds that walk such a grid along three axes stage the plain array into the same room)
-uint64_t staged_cells(const ptgrid::Grid& g) {
-  return g.n[1] == 1u ? ptrec::ring_cells(g.n[0], g.n[2]) : (uint64_t)g.n[0] * g.n[1] * g.n[2];
+  return grid_fit_state(c->geom.grid_in_use(c->grid.present), need_factor(c), (double)c->grid.head.near_factor);
 }
 
 // the build of the grid kernel the next launch gets and the bytes it stages (with a grid)
 Staging grid_build(const pt_ctx* c) {
-  const ptgrid::Grid& g = c->grid;
-  return grid_staging(staged_cells(g), g.n_entries, walk_lds_room(), c->grid_cells_build, fit_state(c));
+  const ptgrid::Grid& g = c->grid.head;
+  return grid_staging(ptscene::staged_cells(g), g.n_entries, walk_lds_room(), c->grid_cells_build, fit_state(c));
 }
 
 // a kernel of pt_kernels_extra.hip; its first use loads that code object and lifts its dynamic-LDS limit
@@ -624,89 +615,96 @@ PT_API int pt_set_stream(pt_ctx* c, void* hip_stream) {
 
 namespace {
 
-// the uniform grid of PT_GEOM_GRID for a scene, laid out for the kernel that will read it
-bool build_grid(const float* geom, const float* radii, uint32_t n, double near_factor, ptgrid::Grid* grid) {
-  if (!ptgrid::build(geom, radii, n, grid, near_factor)) return false;
-  // entries that will not be staged in the LDS (bind_grid) are gathered from L2: their runs in Morton order of the cells
-  if (PT_GRID_LDS_CELLS(staged_cells(*grid)) + (size_t)grid->n_entries * 16 > walk_lds_room()) {
-    int mode = 2;
-#ifdef PT_DEV_KNOBS  // A/B only: PT_PAD_RUNS = 0 plain layout, 1 padded runs in Morton order, 2 Morton order (default), 3 padded runs
-    if (getenv("PT_PAD_RUNS")) mode = atoi(getenv("PT_PAD_RUNS"));
-#endif
-    if (mode) (void)ptgrid::morton_runs(grid, mode != 2, mode != 3);
-  }
-  // the device record's entry field (pt_grid_records.hpp), checked on the layout that is uploaded (padded runs are longer):
-  // no grid, as when the host format overflows
-  return ptrec::fits(grid->n_entries);
+#define PT_TRY(call) do { if (int rc_ = (call); rc_ != PT_OK) return rc_; } while (0)
+
+// `n` elements of `src` into `buf`, in front of padding up to `n_pad` elements of `pad_byte`: the buffer grows only when it is
+// smaller, the padding is written, then the payload (the caller has made sure that nothing in flight reads the buffer)
+template <class T>
+int upload(pt_ctx* c, DevBuf<T>& buf, const T* src, size_t n, size_t n_pad, int pad_byte) {
+  if (buf.capacity() < n_pad) PT_HIP(c, buf.reserve(n_pad));
+  if (n_pad > n) PT_HIP(c, hipMemset(buf.get() + n, pad_byte, (n_pad - n) * sizeof(T)));
+  if (n) PT_HIP(c, hipMemcpy(buf.get(), src, n * sizeof(T), hipMemcpyHostToDevice));
+  return PT_OK;
+}
+template <class T>
+int upload(pt_ctx* c, DevBuf<T>& buf, const std::vector<T>& src) { return upload(c, buf, src.data(), src.size(), src.size(), 0); }
+template <class T>
+void release(std::vector<T>& v) { std::vector<T>().swap(v); }
+
+// no scene is in place (until an install has wholly succeeded: the render calls answer PT_ERR_NOT_READY meanwhile)
+void drop_scene(pt_ctx* c) { c->have_spheres = c->bvh.present = c->grid.present = c->uuid_valid = false; }
+
+// (list.n and list.host follow when the whole scene is in place: pt_set_spheres)
+int install_list(pt_ctx* c, const ptscene::Split& sp, size_t n) {
+  PT_TRY(upload(c, c->list.geom, sp.geom));
+  PT_TRY(upload(c, c->list.mat, sp.mat.data(), n, n ? n : 1u, 0));
+  return upload(c, c->list.r0, sp.r0.data(), 2 * n, n ? 2 * n : 2u, 0);
 }
 
-// upload a grid (the caller has made sure that nothing in flight reads the previous one); empties the host arrays of `grid`
-int install_grid(pt_ctx* c, ptgrid::Grid& grid, const PtMatRec* mat, uint32_t n) {
-  c->have_grid = false;  // (until everything below has succeeded: a failed allocation must not leave a grid that points nowhere)
-  c->uuid_valid = false;  // (the entries move: their uuids follow when the overlay is on — upload_uuids)
-  const size_t n_cells_pad = (grid.cells.size() + 3u) & ~(size_t)3u;  // the kernels stage 16 B at a time
-  if (c->d_grid_cells.capacity() < n_cells_pad) PT_HIP(c, c->d_grid_cells.reserve(n_cells_pad));
+// a structure's index (padding: 0xff, no sphere) and per-slot materials (padding: 0); its uuids follow when the overlay is on
+int install_slots(pt_ctx* c, SceneSlots& s, const std::vector<uint32_t>& index, size_t n, size_t n_pad, const ptscene::Split& sp) {
+  s.present = false;  // (until the caller's install has succeeded: a failed allocation must not leave a structure that points nowhere)
+  c->uuid_valid = false;
+  PT_TRY(upload(c, s.index, index.data(), n, n_pad, 0xff));
+  s.index_n = n_pad;
+  return upload(c, s.mat, ptscene::per_slot(index.data(), n, sp.mat.data(), sp.mat.size()).data(), n, n_pad, 0);
+}
+
+// upload a hierarchy / a grid (the caller has made sure that nothing in flight reads the previous one); empties the host arrays
+int install_bvh(pt_ctx* c, ptbvh::Bvh& bvh, const ptscene::Split& sp) {
+  PT_TRY(install_slots(c, c->bvh, bvh.slot_index, bvh.slot_index.size(), bvh.slot_index.size(), sp));
+  PT_TRY(upload(c, c->bvh.nodes, bvh.nodes16));
+  PT_TRY(upload(c, c->bvh.nodes32, bvh.nodes32));
+  PT_TRY(upload(c, c->bvh.slots, bvh.slots));
+  release(bvh.nodes); release(bvh.nodes16); release(bvh.nodes32); release(bvh.slots); release(bvh.slot_index);
+  c->bvh.head = std::move(bvh);
+  c->bvh.present = true;
+  return PT_OK;
+}
+int install_grid(pt_ctx* c, ptgrid::Grid& grid, const ptscene::Split& sp) {
   // + four entries of slack: a leaf round reads four consecutive entries whatever the cell's
   // count (and lanes without a cell under test read, and discard, wherever their stale record points)
-  const size_t n_ent_pad = (size_t)grid.n_entries + 4u;
-  if (c->d_grid_entries.capacity() < n_ent_pad * 4) PT_HIP(c, c->d_grid_entries.reserve(n_ent_pad * 4));
-  if (c->d_grid_index.capacity() < n_ent_pad) PT_HIP(c, c->d_grid_index.reserve(n_ent_pad));
-  if (c->d_grid_mat.capacity() < n_ent_pad) PT_HIP(c, c->d_grid_mat.reserve(n_ent_pad));
-  PT_HIP(c, hipMemset(c->d_grid_cells.get(), 0, n_cells_pad * sizeof(uint32_t)));
-  {
-    // the device reads derived records (pt_grid_records.hpp): what a leaf round would decode from `first | count << 24`, made once
-    std::vector<uint32_t> recs(grid.cells.size());
-    for (size_t k = 0; k < recs.size(); k++) recs[k] = ptrec::from_host(grid.cells[k]);
-    PT_HIP(c, hipMemcpy(c->d_grid_cells.get(), recs.data(), recs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (grid.n[1] == 1u) {  // ... and in the ring layout, for the two-axis walk
-      const size_t n_ring = (size_t)ptrec::ring_cells(grid.n[0], grid.n[2]), n_ring_pad = (n_ring + 3u) & ~(size_t)3u;
-      recs.assign(n_ring_pad, ptrec::kOutside);
-      ptrec::ring_layout(grid.cells.data(), grid.n[0], grid.n[2], recs.data());
-      if (c->d_grid_ring.capacity() < n_ring_pad) PT_HIP(c, c->d_grid_ring.reserve(n_ring_pad));
-      PT_HIP(c, hipMemcpy(c->d_grid_ring.get(), recs.data(), n_ring_pad * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+  const size_t n_ent = grid.n_entries, n_ent_pad = n_ent + 4u;
+  PT_TRY(install_slots(c, c->grid, grid.entry_index, n_ent, n_ent_pad, sp));
+  PT_TRY(upload(c, c->grid.entries, grid.entries.data(), n_ent * 4, n_ent_pad * 4, 0));
+  // the device reads derived records (pt_grid_records.hpp): what a leaf round would decode from `first | count << 24`, made once
+  std::vector<uint32_t> recs(grid.cells.size());
+  for (size_t k = 0; k < recs.size(); k++) recs[k] = ptrec::from_host(grid.cells[k]);
+  PT_TRY(upload(c, c->grid.cells, recs.data(), recs.size(), (recs.size() + 3u) & ~(size_t)3u, 0));  // (the kernels stage 16 B at a time)
+  if (grid.n[1] == 1u) {  // ... and in the ring layout, for the two-axis walk
+    recs.assign(((size_t)ptrec::ring_cells(grid.n[0], grid.n[2]) + 3u) & ~(size_t)3u, ptrec::kOutside);
+    ptrec::ring_layout(grid.cells.data(), grid.n[0], grid.n[2], recs.data());
+    PT_TRY(upload(c, c->grid.ring, recs));
   }
-  PT_HIP(c, hipMemset(c->d_grid_entries.get(), 0, n_ent_pad * 16));
-  PT_HIP(c, hipMemcpy(c->d_grid_entries.get(), grid.entries.data(), (size_t)grid.n_entries * 16, hipMemcpyHostToDevice));
-  PT_HIP(c, hipMemset(c->d_grid_index.get(), 0xff, n_ent_pad * sizeof(uint32_t)));
-  PT_HIP(c, hipMemcpy(c->d_grid_index.get(), grid.entry_index.data(), (size_t)grid.n_entries * sizeof(uint32_t), hipMemcpyHostToDevice));
-  {
-    std::vector<PtMatRec> sm(n_ent_pad);
-    for (size_t k = 0; k < (size_t)grid.n_entries; k++) sm[k] = grid.entry_index[k] < n ? mat[grid.entry_index[k]] : PtMatRec{};
-    PT_HIP(c, hipMemcpy(c->d_grid_mat.get(), sm.data(), sm.size() * sizeof(PtMatRec), hipMemcpyHostToDevice));
-  }
-  grid.cells.clear(); grid.cells.shrink_to_fit();
-  grid.entries.clear(); grid.entries.shrink_to_fit();
-  grid.entry_index.clear(); grid.entry_index.shrink_to_fit();
-  c->grid = grid;
-  c->have_grid = true;
+  release(grid.cells); release(grid.entries); release(grid.entry_index);
+  c->grid.head = std::move(grid);
+  c->grid.present = true;
   return PT_OK;
 }
 
 // The debug overlay's uuid arrays: PtSphere.uuid in list order and per slot of the structures in place (the walk kernels
 // shade from a slot, like slot_mat).  Made when the overlay is turned on and again whenever the scene or the grid changes while
 // it is on; a context that never enables the overlay never allocates them.  Synchronises: a set-up call's work.
-int upload_uuids(pt_ctx* c) {
+int upload_uuids(pt_ctx* c, const std::vector<int32_t>& uuid) {
   PT_HIP(c, hipSetDevice(c->device));
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight may read the arrays in place
-  const uint32_t n = c->n_spheres;
-  auto per_slot = [&](const DevBuf<uint32_t>& d_index, size_t n_index, DevBuf<int32_t>& d_out) -> int {
-    std::vector<uint32_t> index(n_index);
-    PT_HIP(c, hipMemcpy(index.data(), d_index.get(), n_index * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::vector<int32_t> u(n_index);
-    for (size_t k = 0; k < n_index; k++) u[k] = index[k] < n ? c->h_uuid[index[k]] : 0;  // (padding slots are never hit)
-    if (d_out.capacity() < n_index) PT_HIP(c, d_out.reserve(n_index));
-    PT_HIP(c, hipMemcpy(d_out.get(), u.data(), n_index * sizeof(int32_t), hipMemcpyHostToDevice));
-    return PT_OK;
-  };
-  if (c->d_uuid.capacity() < (n ? n : 1u)) PT_HIP(c, c->d_uuid.reserve(n ? n : 1u));
-  if (n) PT_HIP(c, hipMemcpy(c->d_uuid.get(), c->h_uuid.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (c->have_bvh && c->bvh_index_n)
-    if (int rc = per_slot(c->d_bvh_index, c->bvh_index_n, c->d_bvh_uuid); rc != PT_OK) return rc;
-  if (c->have_grid)
-    if (int rc = per_slot(c->d_grid_index, (size_t)c->grid.n_entries + 4u, c->d_grid_uuid); rc != PT_OK) return rc;
+  PT_TRY(upload(c, c->list.uuid, uuid.data(), uuid.size(), uuid.empty() ? 1u : uuid.size(), 0));
+  for (SceneSlots* s : std::initializer_list<SceneSlots*>{&c->bvh, &c->grid}) {
+    if (!s->present || !s->index_n) continue;
+    std::vector<uint32_t> index(s->index_n);  // (read back from the device: the structure's host arrays are gone by now)
+    PT_HIP(c, hipMemcpy(index.data(), s->index.get(), index.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    PT_TRY(upload(c, s->uuid, ptscene::per_slot(index.data(), index.size(), uuid.data(), uuid.size())));  // (padding slots are never hit)
+  }
   c->uuid_valid = true;
   return PT_OK;
+}
+
+// the device half of pt_set_spheres: list, hierarchy, grid, and the uuid arrays when the overlay is on
+int install_scene(pt_ctx* c, const ptscene::Split& sp, uint32_t n, ptbvh::Bvh* bvh, ptgrid::Grid* grid) {
+  PT_TRY(install_list(c, sp, n));
+  if (bvh) PT_TRY(install_bvh(c, *bvh, sp));
+  if (grid) PT_TRY(install_grid(c, *grid, sp));
+  return c->dbg_enable ? upload_uuids(c, sp.uuid) : PT_OK;
 }
 
 } // namespace
@@ -718,130 +716,35 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
                 n, PT_MAX_SPHERES);
   PT_HIP(c, hipSetDevice(c->device));
   const double t_begin = host_ms();
-  if (n > c->sphere_cap || !c->d_geom.get() || !c->d_mat.get()) {
-    c->sphere_cap = 0;
-    PT_HIP(c, c->d_geom.reserve((size_t)PT_LDS_ENTRIES(n) * 4));
-    PT_HIP(c, c->d_mat.reserve((size_t)(n ? n : 1) * (sizeof(PtMatRec) + 2 * sizeof(float))));  // (+ the r0 pairs behind the records)
-    c->sphere_cap = n;
-  }
-  // split into the 16-byte geometry record the intersection loop stages into LDS and the 32-byte
-  // shading record read once per closest hit
-  // geometry is uploaded already padded (multiple of 8 + one prefetch group, unreachable
-  // spheres beyond MAX_T) and with r*r precomputed: the fp32 multiply `pow(radius, 2.)` of
-  // static/shader.frag:149, performed here under -ffp-contract=off
-  const uint32_t n_pad = PT_LDS_ENTRIES(n);
-  std::vector<float> geom((size_t)n_pad * 4);
-  for (uint32_t i = n; i < n_pad; i++) {
-    geom[4 * i + 0] = 1e15f; geom[4 * i + 1] = 1e15f; geom[4 * i + 2] = 1e15f; geom[4 * i + 3] = 0.0f;
-  }
-  std::vector<PtMatRec> mat(n);
-  std::vector<float> radii(n);
-  bool regular = true;
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < 3; k++) regular = regular && (std::fabs(s[i].center[k]) < 1e15f);
-    regular = regular && (std::fabs(s[i].radius) < 1e15f); // NaN fails both
-    geom[4 * i + 0] = s[i].center[0];
-    geom[4 * i + 1] = s[i].center[1];
-    geom[4 * i + 2] = s[i].center[2];
-    geom[4 * i + 3] = s[i].radius * s[i].radius;
-    mat[i].albedo[0] = s[i].albedo[0];
-    mat[i].albedo[1] = s[i].albedo[1];
-    mat[i].albedo[2] = s[i].albedo[2];
-    mat[i].fuzz = s[i].fuzz;
-    mat[i].refraction_index = s[i].refraction_index;
-    mat[i].type = s[i].type;
-    mat[i].radius = s[i].radius;
-    mat[i].inv_ri = 1.0f / s[i].refraction_index;  // (IEEE division, -ffp-contract=off: what `1.0 / ri` is in the shader's arithmetic contract)
-    radii[i] = s[i].radius;
-  }
-  c->h_uuid.resize(n);
-  for (uint32_t i = 0; i < n; i++) c->h_uuid[i] = s[i].uuid;
-  c->uuid_valid = false;
+  ptscene::Split sp = ptscene::split(s, n);
   const double t_split = host_ms();
   // the culling hierarchy of PT_GEOM_BVH (regular scenes of at least 16 spheres)
   ptbvh::Bvh bvh;
-  const bool have_bvh = regular && ptbvh::build(geom.data(), radii.data(), n, &bvh);
+  const bool have_bvh = sp.regular && ptbvh::build(sp.geom.data(), sp.radii.data(), n, &bvh);
   const double t_bvh = host_ms();
   // ... and the uniform grid of PT_GEOM_GRID (same precondition)
   ptgrid::Grid grid;
-  const bool have_grid = regular && build_grid(geom.data(), radii.data(), n, 3.0, &grid);
+  const bool have_grid = sp.regular && ptscene::build_grid(sp.geom.data(), sp.radii.data(), n, 3.0, &grid);
   const double t_grid = host_ms();
-  c->setup_ms[PT_SETUP_SPHERES_SPLIT] = t_split - t_begin;
-  c->setup_ms[PT_SETUP_SPHERES_BVH_BUILD] = t_bvh - t_split;
-  c->setup_ms[PT_SETUP_SPHERES_GRID_BUILD] = t_grid - t_bvh;
-  {
-    // the stream may still be reading the previous scene
-    PT_HIP(c, hipStreamSynchronize(c->stream));
-    PT_HIP(c, hipMemcpy(c->d_geom.get(), geom.data(), (size_t)n_pad * 16, hipMemcpyHostToDevice));
-  }
-  if (n) {
-    PT_HIP(c, hipMemcpy(c->d_mat.get(), mat.data(), (size_t)n * sizeof(PtMatRec), hipMemcpyHostToDevice));
-    // reflectance()'s r0 = ((1 - ratio) / (1 + ratio))^2 (static/shader.frag:205) for both ratios a GLASS sphere is entered
-    // with, 1 / ri (front face) and ri: a subtraction, an addition, an IEEE division and a product in fp32 under
-    // -ffp-contract=off give the same bits here as in the kernel.  Read by the small-list kernels only (pt_shade.hpp): in
-    // the closed room (config 4) the GLASS branch runs in 95 % of the wave steps for 3.6 lanes, and a division is a dozen
-    // instructions for the whole wave (config 4 -0.7 %, State::default within the boxes' spread; the kernels of the large scenes
-    // sit at their register limits and measured +1 % with it: they keep the division; profiles/r05_ab_runs.txt)
-    std::vector<float> r0(2 * (size_t)n);
-    for (uint32_t i = 0; i < n; i++) {
-      const float front = mat[i].inv_ri, back = mat[i].refraction_index;
-      const float qf = (1.0f - front) / (1.0f + front), qb = (1.0f - back) / (1.0f + back);
-      r0[2 * i] = qf * qf;
-      r0[2 * i + 1] = qb * qb;
-    }
-    PT_HIP(c, hipMemcpy(c->d_mat.get() + (size_t)c->sphere_cap * sizeof(PtMatRec), r0.data(), r0.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  c->have_bvh = false;
-  if (have_bvh) {
-    if (c->d_bvh_nodes.capacity() < bvh.nodes16.size()) PT_HIP(c, c->d_bvh_nodes.reserve(bvh.nodes16.size()));
-    if (c->d_bvh_nodes32.capacity() < bvh.nodes32.size()) PT_HIP(c, c->d_bvh_nodes32.reserve(bvh.nodes32.size()));
-    if (c->d_bvh_slots.capacity() < bvh.slots.size()) PT_HIP(c, c->d_bvh_slots.reserve(bvh.slots.size()));
-    if (c->d_bvh_index.capacity() < bvh.slot_index.size()) PT_HIP(c, c->d_bvh_index.reserve(bvh.slot_index.size()));
-    if (c->d_bvh_mat.capacity() < bvh.slot_index.size()) PT_HIP(c, c->d_bvh_mat.reserve(bvh.slot_index.size()));
-    PT_HIP(c, hipMemcpy(c->d_bvh_nodes.get(), bvh.nodes16.data(), bvh.nodes16.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->d_bvh_nodes32.get(), bvh.nodes32.data(), bvh.nodes32.size() * sizeof(float), hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->d_bvh_slots.get(), bvh.slots.data(), bvh.slots.size() * sizeof(float), hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->d_bvh_index.get(), bvh.slot_index.data(), bvh.slot_index.size() * sizeof(uint32_t),
-                        hipMemcpyHostToDevice));
-    {
-      std::vector<PtMatRec> sm(bvh.slot_index.size());
-      for (size_t k = 0; k < sm.size(); k++) sm[k] = bvh.slot_index[k] < n ? mat[bvh.slot_index[k]] : PtMatRec{};
-      PT_HIP(c, hipMemcpy(c->d_bvh_mat.get(), sm.data(), sm.size() * sizeof(PtMatRec), hipMemcpyHostToDevice));
-    }
-    c->bvh_index_n = bvh.slot_index.size();
-    c->bvh_n_nodes = bvh.n_nodes; c->bvh_n_slots = bvh.n_slots; c->bvh_n_tree_slots = bvh.n_tree_slots;
-    c->bvh_n_outliers = bvh.n_outliers; c->bvh_depth = bvh.depth;
-    for (int k = 0; k < 3; k++) c->bvh_c0[k] = bvh.c0[k];
-    c->bvh_s0 = bvh.s0;
-    c->bvh_kinv = bvh.kinv;
-    c->have_bvh = true;
-  }
-  c->have_grid = false;
-  c->h_geom.clear(); c->h_radii.clear(); c->h_mat.clear();
-  if (have_grid) {
-    int rc = install_grid(c, grid, mat.data(), n);
-    if (rc != PT_OK) return rc;
-    c->h_geom.assign(geom.begin(), geom.begin() + 4 * (size_t)n);
-    c->h_radii = radii;
-    c->h_mat = mat;
-  }
-  c->n_spheres = n;
+  // the stream may still be reading the previous scene
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  // validate first, commit afterwards: from the first device write until everything is in place the context has no scene
+  drop_scene(c);
+  if (int rc = install_scene(c, sp, n, have_bvh ? &bvh : nullptr, have_grid ? &grid : nullptr); rc != PT_OK) return drop_scene(c), rc;
+  c->list.n = n;
+  c->list.host = std::move(sp);
   c->grid_cells_build = false;  // (a measurement of the previous scene)
   c->scene_gen++;
   c->adapt_valid = false;
   c->geom.reset();  // a new scene: PT_GEOM_AUTO measures again
-  c->scene_regular = regular;
   c->have_spheres = true;
   c->geom.list_paths(path_scene(c));
-  if (c->dbg_enable) {
-    int rc = upload_uuids(c);
-    if (rc != PT_OK) return rc;
-  }
-  {
-    const double t_end = host_ms();
-    c->setup_ms[PT_SETUP_SPHERES_UPLOAD] = t_end - t_grid;
-    c->setup_ms[PT_SETUP_SPHERES_TOTAL] = t_end - t_begin;
-  }
+  const double t_end = host_ms();
+  c->setup_ms[PT_SETUP_SPHERES_SPLIT] = t_split - t_begin;
+  c->setup_ms[PT_SETUP_SPHERES_BVH_BUILD] = t_bvh - t_split;
+  c->setup_ms[PT_SETUP_SPHERES_GRID_BUILD] = t_grid - t_bvh;
+  c->setup_ms[PT_SETUP_SPHERES_UPLOAD] = t_end - t_grid;
+  c->setup_ms[PT_SETUP_SPHERES_TOTAL] = t_end - t_begin;
   return PT_OK;
 }
 
@@ -1052,8 +955,8 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   A.band_index = p.band_index;
   A.band_count = p.band_count;
   A.n_passes = n_passes;
-  A.n_spheres = c->n_spheres;
-  A.scene_regular = c->scene_regular ? 1u : 0u;
+  A.n_spheres = c->list.n;
+  A.scene_regular = c->list.host.regular ? 1u : 0u;
   A.tiles_x = tiles_x(c);
   A.tiles_y = tiles_y(c);
   unsigned long long items = (unsigned long long)A.tiles_x * A.tiles_y * n_passes * 64ull;
@@ -1065,9 +968,9 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   A.div_per_tile = pt_div_make(64u * n_passes);
   A.div_tiles_x = pt_div_make(A.tiles_x);
   A.div_band_rows = pt_div_make(A.band_rows);
-  A.geom = c->d_geom.get();
-  A.mat = reinterpret_cast<const PtMatRec*>(c->d_mat.get());
-  A.mat_r0 = reinterpret_cast<const float*>(c->d_mat.get() + (size_t)c->sphere_cap * sizeof(PtMatRec));
+  A.geom = c->list.geom.get();
+  A.mat = c->list.mat.get();
+  A.mat_r0 = c->list.r0.get();
   A.slab = reinterpret_cast<float*>(c->d_slab.get());
   A.counters = c->d_counters.get();
   A.tile_order = c->d_tile_order.get();
@@ -1076,7 +979,7 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   A.refill_min = c->refill_min;
   A.frame_ctr = c->d_frame_ctr.get() + 1;  // the cell that stays 0 (pt_render_frames points at [0])
   if (c->dbg_enable) {  // (zero otherwise: an overlay-off launch's argument block is what it was before the overlay existed)
-    A.uuid = c->d_uuid.get();
+    A.uuid = c->list.uuid.get();
     A.dbg_selected = c->dbg_selected;
     for (int k = 0; k < 3; k++) A.dbg_cursor[k] = c->dbg_cursor[k];
   }
@@ -1085,30 +988,31 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
 
 // hierarchy walk: the tree's arrays and constants; returns what is staged in the LDS (hierarchy_staging)
 static Staging bind_hierarchy(pt_ctx* c, PtKernelArgs& A) {
-  A.bvh_nodes = c->d_bvh_nodes.get();
-  A.bvh_nodes32 = c->d_bvh_nodes32.get();
-  A.bvh_slots = c->d_bvh_slots.get();
-  A.bvh_slot_index = c->d_bvh_index.get();
-  A.slot_mat = c->d_bvh_mat.get();
-  if (c->dbg_enable) A.slot_uuid = c->d_bvh_uuid.get();
-  A.n_nodes = c->bvh_n_nodes;
-  A.n_tree_slots = c->bvh_n_tree_slots;
-  A.n_slots = c->bvh_n_slots;
-  A.n_outliers = c->bvh_n_outliers;
-  for (int k = 0; k < 3; k++) A.bvh_c0[k] = c->bvh_c0[k];
-  A.bvh_s0 = c->bvh_s0;
-  A.bvh_kinv = c->bvh_kinv;
-  return hierarchy_staging(c->bvh_n_nodes, c->bvh_n_slots, walk_lds_room());
+  const SceneBvh& b = c->bvh;
+  A.bvh_nodes = b.nodes.get();
+  A.bvh_nodes32 = b.nodes32.get();
+  A.bvh_slots = b.slots.get();
+  A.bvh_slot_index = b.index.get();
+  A.slot_mat = b.mat.get();
+  if (c->dbg_enable) A.slot_uuid = b.uuid.get();
+  A.n_nodes = b.head.n_nodes;
+  A.n_tree_slots = b.head.n_tree_slots;
+  A.n_slots = b.head.n_slots;
+  A.n_outliers = b.head.n_outliers;
+  for (int k = 0; k < 3; k++) A.bvh_c0[k] = b.head.c0[k];
+  A.bvh_s0 = b.head.s0;
+  A.bvh_kinv = b.head.kinv;
+  return hierarchy_staging(b.head.n_nodes, b.head.n_slots, walk_lds_room());
 }
 
 // grid walk: likewise (grid_staging)
 static Staging bind_grid(pt_ctx* c, PtKernelArgs& A) {
-  const ptgrid::Grid& g = c->grid;
-  A.bvh_slots = c->d_grid_entries.get();
-  A.bvh_slot_index = c->d_grid_index.get();
-  A.slot_mat = c->d_grid_mat.get();
-  if (c->dbg_enable) A.slot_uuid = c->d_grid_uuid.get();
-  A.grid_cells = c->d_grid_cells.get();
+  const ptgrid::Grid& g = c->grid.head;
+  A.bvh_slots = c->grid.entries.get();
+  A.bvh_slot_index = c->grid.index.get();
+  A.slot_mat = c->grid.mat.get();
+  if (c->dbg_enable) A.slot_uuid = c->grid.uuid.get();
+  A.grid_cells = c->grid.cells.get();
   A.n_cells = g.n[0] * g.n[1] * g.n[2];
   A.n_tree_slots = g.n_cell_entries;
   A.n_slots = g.n_entries;
@@ -1217,22 +1121,22 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
     const Staging st = path == PT_GEOM_BVH ? bind_hierarchy(c, A) : bind_grid(c, A);
     scene = st.bytes;
     row = path == PT_GEOM_BVH ? ROW_BVH + st.kind : ROW_GRID + st.kind - 1;
-    if (path == PT_GEOM_GRID && st.kind == 1 && !grid_walk_flat(st.kind, c->grid.n[1])) row = ROW_GRID_LAYERS;
+    if (path == PT_GEOM_GRID && st.kind == 1 && !grid_walk_flat(st.kind, c->grid.head.n[1])) row = ROW_GRID_LAYERS;
     A.lds_scene_bytes = (uint32_t)scene;
   } else {
     // the LDS copy exists whenever the list fits; the scalar and small-list walks only change how the
     // SCAN reads (their per-lane gathers — shading, tail mode — still come from the copy)
-    const bool have_lds = c->n_spheres <= PT_MAX_SPHERES_LDS;
-    scene = have_lds ? (size_t)PT_LDS_ENTRIES(c->n_spheres) * 16 : 0;
-    row = path == PT_GEOM_SMALL ? ROW_SMALL + (int)(c->n_spheres & 3u)
+    const bool have_lds = c->list.n <= PT_MAX_SPHERES_LDS;
+    scene = have_lds ? (size_t)PT_LDS_ENTRIES(c->list.n) * 16 : 0;
+    row = path == PT_GEOM_SMALL ? ROW_SMALL + (int)(c->list.n & 3u)
                                 : (path == PT_GEOM_LDS ? ROW_LIST_LDS : (have_lds ? ROW_SCALAR : ROW_SCALAR_NOLDS));
   }
   const int build = dbg ? BUILD_DBG : (rr ? BUILD_RR : (c->count_work ? BUILD_TWIN : BUILD_PLAIN));
   // the two-axis walk (pt_trace_kernel_grid and its twin; the roulette and overlay builds of that row walk three axes) reads
   // the ring layout; it is what `scene` was sized for (staged_cells)
   if (walk && path == PT_GEOM_GRID && row == ROW_GRID && (build == BUILD_PLAIN || build == BUILD_TWIN)) {
-    A.grid_cells = c->d_grid_ring.get();
-    A.n_cells = (uint32_t)ptrec::ring_cells(c->grid.n[0], c->grid.n[2]);
+    A.grid_cells = c->grid.ring.get();
+    A.n_cells = (uint32_t)ptrec::ring_cells(c->grid.head.n[0], c->grid.head.n[2]);
   }
   const TraceKernel& tk = kTraceKernels[row][build];
   const void* kfn = tk.main ? tk.main
@@ -1246,7 +1150,7 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   PT_HIP(c, resident_blocks(kfn, block, lds, tk.waves, &per_cu));
 
   const LaunchPlan P = plan_launch({A.n_items, c->params.samples_per_pixel, n_passes, block, per_cu, (uint32_t)c->num_cus, walk,
-                                    c->n_spheres, knobs});
+                                    c->list.n, knobs});
   A.queue_chunk = P.queue_chunk; A.queue_static = (uint32_t)P.deal; A.queue_groups = P.queue_groups;
   A.n_waves = P.n_waves; A.coop_max_live = P.coop_max_live;
   A.cost_feedback = use.feedback == LaunchUse::PLANNED ? P.cost_feedback : (use.feedback == LaunchUse::ON ? 1u : 0u);
@@ -1990,7 +1894,7 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
   memset(out, 0, sizeof *out);
   out->segments = ctr[PT_CTR_SEGMENTS];
   out->samples = c->samples;
-  out->sphere_tests = ctr[PT_CTR_SEGMENTS] * (uint64_t)c->n_spheres;
+  out->sphere_tests = ctr[PT_CTR_SEGMENTS] * (uint64_t)c->list.n;
   out->render_kernel_ms = c->kernel_ms;
   out->render_launches = c->launches;
   out->total_spp = c->total_spp;
@@ -1999,28 +1903,28 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
     PT_HIP(c, hipMemcpy(&px0, c->accum, sizeof px0, hipMemcpyDeviceToHost));
     if (px0.w >= 0.0f && px0.w < 4294967040.0f) out->total_spp = (uint32_t)px0.w;
   }
-  out->n_spheres = c->n_spheres;
+  out->n_spheres = c->list.n;
   try_finish_tuning(c);
   out->local_rows = c->local_rows;
   out->geometry_path = (uint32_t)c->geom.last;
   out->geometry_tuned = c->geom.tuned ? 1u : 0u;
   for (int k = 0; k < 8; k++) out->work[k] = ctr[PT_CTR_WORK + k];
   out->far_rays = ctr[PT_CTR_FAR_RAYS];
-  if (c->have_grid) {
-    for (int k = 0; k < 3; k++) out->grid_cells[k] = c->grid.n[k];
-    out->grid_entries = c->grid.n_entries;
-    out->grid_always = c->grid.n_always;
-    out->grid_near_factor = c->grid.near_factor;
+  if (c->grid.present) {
+    for (int k = 0; k < 3; k++) out->grid_cells[k] = c->grid.head.n[k];
+    out->grid_entries = c->grid.head.n_entries;
+    out->grid_always = c->grid.head.n_always;
+    out->grid_near_factor = c->grid.head.near_factor;
     out->grid_need_factor = (float)need_factor(c);
     out->grid_fit_stale = (uint32_t)fit_state(c);
     out->grid_kernel_build = (uint32_t)grid_build(c).kind;
-    out->grid_walk_flat = grid_walk_flat((int)out->grid_kernel_build, c->grid.n[1]) ? 1u : 0u;
+    out->grid_walk_flat = grid_walk_flat((int)out->grid_kernel_build, c->grid.head.n[1]) ? 1u : 0u;
   }
-  if (c->have_bvh) {
-    out->bvh_nodes = c->bvh_n_nodes;
-    out->bvh_slots = c->bvh_n_slots;
-    out->bvh_outliers = c->bvh_n_outliers;
-    out->bvh_depth = c->bvh_depth;
+  if (c->bvh.present) {
+    out->bvh_nodes = c->bvh.head.n_nodes;
+    out->bvh_slots = c->bvh.head.n_slots;
+    out->bvh_outliers = c->bvh.head.n_outliers;
+    out->bvh_depth = c->bvh.head.depth;
   }
   return PT_OK;
 }
@@ -2099,7 +2003,7 @@ PT_API int pt_set_debug_overlay(pt_ctx* c, int enable, int32_t selected_object, 
     return PT_OK;
   }
   if (!c->uuid_valid && c->have_spheres) {
-    int rc = upload_uuids(c);
+    int rc = upload_uuids(c, c->list.host.uuid);
     if (rc != PT_OK) return rc;
   }
   c->dbg_enable = true;
@@ -2128,11 +2032,11 @@ namespace {
 // uniforms (grid_fit_state: PtStats.grid_fit_stale, pt_grid_fit): pt_set_params never rebuilds — a rebuild synchronises the
 // stream and moves device buffers.
 // (the decisions: pt_geom_plan.hpp)
-// May the grid be rebuilt for the view at all: there is one, with uniforms and the host copies it is built from, no launch
+// May the grid be rebuilt for the view at all: there is one (and with it the host copies it is built from), with uniforms, no launch
 // captured into a caller's hipGraph holds its numbers, and no A/B build fixes its factor (PT_GRID_DNEAR, PT_DEV_KNOBS builds only:
 // pt_grid.hpp builds every grid for it)?
 bool grid_refittable(const pt_ctx* c) {
-  if (!c->have_grid || !c->have_params || c->captured || c->h_geom.empty()) return false;
+  if (!c->grid.present || !c->have_params || c->captured) return false;
 #ifdef PT_DEV_KNOBS
   if (getenv("PT_GRID_DNEAR")) return false;  // (the A/B build's own factor stands)
 #endif
@@ -2142,15 +2046,15 @@ bool grid_refittable(const pt_ctx* c) {
 // replace the grid in place by one built for d_near = factor * s0 (the caller has decided that it should be)
 int rebuild_grid(pt_ctx* c, double factor, bool keep_tuned) {
   ptgrid::Grid grid;
-  const uint32_t n = (uint32_t)c->h_radii.size();
-  if (!build_grid(c->h_geom.data(), c->h_radii.data(), n, factor, &grid)) return PT_OK;  // (no grid for that factor: the one in place stays)
+  const ptscene::Split& sp = c->list.host;
+  if (!ptscene::build_grid(sp.geom.data(), sp.radii.data(), c->list.n, factor, &grid)) return PT_OK;  // (no grid for that factor: the one in place stays)
   PT_HIP(c, hipSetDevice(c->device));
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight read the grid in place
   const int tuned = c->geom.tuned;
-  int rc = install_grid(c, grid, c->h_mat.data(), n);
-  if (rc == PT_OK && c->dbg_enable) rc = upload_uuids(c);
+  int rc = install_grid(c, grid, sp);
+  if (rc == PT_OK && c->dbg_enable) rc = upload_uuids(c, sp.uuid);
   c->geom.list_paths(path_scene(c));  // (which kernels the grid can feed, and whether PT_GEOM_AUTO has anything to measure, follow its size — or its absence, had the upload failed)
-  if (keep_tuned && rc == PT_OK && tuned == PT_GEOM_GRID && c->have_grid) c->geom.tuned = tuned;  // a refit keeps the settled choice
+  if (keep_tuned && rc == PT_OK && tuned == PT_GEOM_GRID && c->grid.present) c->geom.tuned = tuned;  // a refit keeps the settled choice
   return rc;
 }
 
@@ -2167,7 +2071,7 @@ int tune_grid_to_view(pt_ctx* c, uint32_t n_passes, bool* launched) {
   if (!grid_refittable(c) || !c->geom.grid_tried()) return PT_OK;
   const double need = need_factor(c);
   if (need <= 0.0) return PT_OK;
-  auto at = [&](double f) { return same_class(f, (double)c->grid.near_factor); };
+  auto at = [&](double f) { return same_class(f, (double)c->grid.head.near_factor); };
   if (grid_class_unmeasured(c->grid_fit_mode, n_passes, c->reserved_passes)) {  // the class the camera needs
     return at(need) ? PT_OK : rebuild_grid(c, need, false);
   }
@@ -2178,7 +2082,7 @@ int tune_grid_to_view(pt_ctx* c, uint32_t n_passes, bool* launched) {
   uint32_t n_timed = timed_passes(-1.0, n_passes);
   auto measure = [&](double f, bool cold, bool yardstick, std::optional<ClassProbe>* probe) -> int {
     if (!at(f)) { int rc = rebuild_grid(c, f, false); if (rc != PT_OK) return rc; }
-    if (!c->have_grid || !at(f)) return PT_OK;  // (no grid for that class: not a candidate)
+    if (!c->grid.present || !at(f)) return PT_OK;  // (no grid for that class: not a candidate)
     c->geom.policy = PT_GEOM_GRID;
     int rc = PT_OK;
     for (int k = cold ? 0 : 1; k < 2 && rc == PT_OK; k++) {
@@ -2214,7 +2118,7 @@ int tune_grid_to_view(pt_ctx* c, uint32_t n_passes, bool* launched) {
   const double keep = search.keep();
   if (!at(keep)) { int rc = rebuild_grid(c, keep, false); if (rc != PT_OK) return rc; }
   c->grid_cells_build = false;
-  if (c->have_grid && at(keep) && cells_build_worth_timing(c->grid.n_entries, grid_build(c).kind)) {
+  if (c->grid.present && at(keep) && cells_build_worth_timing(c->grid.head.n_entries, grid_build(c).kind)) {
     c->grid_cells_build = true;
     std::optional<ClassProbe> probe;
     if (int rc = measure(keep, true, false, &probe); rc != PT_OK) { c->grid_cells_build = false; return rc; }

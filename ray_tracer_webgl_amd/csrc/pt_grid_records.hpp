@@ -13,7 +13,7 @@
 // A leaf round ANDs its candidate mask with the field and has nothing pending; lanes in a long cell (a ballot of the
 // sign bit, rarely set) take every candidate of the round and compute the record of the rest — `next` below, in this
 // same format, so the next round decodes it the same way.  The record is exact for every count the host format can
-// express (0 .. 255); `first` loses one bit, which the host checks when it builds a grid for the device (`fits`, pt_api.hip build_grid:
+// express (0 .. 255); `first` loses one bit, which the host checks when it builds a grid for the device (`fits`, pt_scene_image.hpp build_grid:
 // a grid of 2^23 entries or more is not walked — 128 MiB of entry copies for at most 65 528 spheres).
 //
 // The one-layer walk reads the same records from the ring layout at the end of this file.

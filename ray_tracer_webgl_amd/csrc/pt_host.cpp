@@ -3,7 +3,7 @@
 #include "pt_host.hpp"
 
 #include "pt_bvh.hpp"
-#include "pt_grid.hpp"
+#include "pt_scene_image.hpp"
 
 #include <new>
 
@@ -126,24 +126,14 @@ static pt::Sphere from_host(const PtHostSphere& h) {
   return s;
 }
 
-// the hierarchy of PT_GEOM_BVH exactly as pt_set_spheres (pt_api.hip) builds and uploads it
+// the grid of PT_GEOM_GRID from the split pt_set_spheres (pt_api.hip) builds it from (pt_scene_image.hpp), in either layout
 static int build_grid_export(bool runs, const PtSphere* s, uint32_t n, uint32_t* counts8, float* geom12, float* margin4,
                          float* delta_g, uint32_t* cells, size_t n_cells, float* entries, size_t entry_floats,
                          uint32_t* entry_index, size_t n_index) {
   if (!s && n) return PT_ERR_INVALID;
-  std::vector<float> geom((size_t)n * 4), radii(n);
-  bool regular = true;
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < 3; k++) {
-      regular = regular && (std::fabs(s[i].center[k]) < 1e15f);
-      geom[4 * (size_t)i + k] = s[i].center[k];
-    }
-    regular = regular && (std::fabs(s[i].radius) < 1e15f);
-    geom[4 * (size_t)i + 3] = s[i].radius * s[i].radius;
-    radii[i] = s[i].radius;
-  }
+  const ptscene::Split sp = ptscene::split(s, n);
   ptgrid::Grid g;
-  if (!regular || !ptgrid::build(geom.data(), radii.data(), n, &g)) return PT_ERR_NOT_READY;
+  if (!sp.regular || !ptgrid::build(sp.geom.data(), sp.radii.data(), n, &g)) return PT_ERR_NOT_READY;
   if (runs && !ptgrid::morton_runs(&g)) return PT_ERR_CAPACITY;
   if (counts8) {
     counts8[0] = g.n[0]; counts8[1] = g.n[1]; counts8[2] = g.n[2]; counts8[3] = g.n_cell_entries;
@@ -180,19 +170,9 @@ PT_API int pt_build_grid_runs(const PtSphere* s, uint32_t n, uint32_t* counts8, 
 // out10 = {r2_near, lo_n.xyz, hi_n.xyz, inv_h.xyz}.
 PT_API int pt_grid_walk_constants(const PtSphere* s, uint32_t n, float* out10) {
   if ((!s && n) || !out10) return PT_ERR_INVALID;
-  std::vector<float> geom((size_t)n * 4), radii(n);
-  bool regular = true;
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < 3; k++) {
-      regular = regular && (std::fabs(s[i].center[k]) < 1e15f);
-      geom[4 * (size_t)i + k] = s[i].center[k];
-    }
-    regular = regular && (std::fabs(s[i].radius) < 1e15f);
-    geom[4 * (size_t)i + 3] = s[i].radius * s[i].radius;
-    radii[i] = s[i].radius;
-  }
+  const ptscene::Split sp = ptscene::split(s, n);
   ptgrid::Grid g;
-  if (!regular || !ptgrid::build(geom.data(), radii.data(), n, &g)) return PT_ERR_NOT_READY;
+  if (!sp.regular || !ptgrid::build(sp.geom.data(), sp.radii.data(), n, &g)) return PT_ERR_NOT_READY;
   out10[0] = g.r2_near;
   for (int k = 0; k < 3; k++) { out10[1 + k] = g.lo_n[k]; out10[4 + k] = g.hi_n[k]; out10[7 + k] = g.inv_h[k]; }
   return PT_OK;
@@ -203,19 +183,9 @@ PT_API int pt_build_bvh(const PtSphere* s, uint32_t n, float* nodes, size_t node
                         uint32_t* counts5, uint32_t* nodes16, size_t n_words16, float* kscale,
                         float* nodes32, size_t n_floats32) {
   if (!s && n) return PT_ERR_INVALID;
-  std::vector<float> geom((size_t)n * 4), radii(n);
-  bool regular = true;
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < 3; k++) {
-      regular = regular && (std::fabs(s[i].center[k]) < 1e15f);
-      geom[4 * (size_t)i + k] = s[i].center[k];
-    }
-    regular = regular && (std::fabs(s[i].radius) < 1e15f);
-    geom[4 * (size_t)i + 3] = s[i].radius * s[i].radius;
-    radii[i] = s[i].radius;
-  }
+  const ptscene::Split sp = ptscene::split(s, n);
   ptbvh::Bvh b;
-  if (!regular || !ptbvh::build(geom.data(), radii.data(), n, &b)) return PT_ERR_NOT_READY;
+  if (!sp.regular || !ptbvh::build(sp.geom.data(), sp.radii.data(), n, &b)) return PT_ERR_NOT_READY;
   if (counts5) {
     counts5[0] = b.n_nodes; counts5[1] = b.n_slots; counts5[2] = b.n_tree_slots;
     counts5[3] = b.n_outliers; counts5[4] = b.depth;

@@ -5,7 +5,7 @@
 // shim calls that builder with a class of the caller's choice, in either layout, and returns what pt_build_grid and
 // pt_grid_walk_constants return for it.  It is compiled by the tests (g++, -ffp-contract=off like the library); that it
 // builds the library's grid is checked against pt_build_grid / pt_build_grid_runs / pt_grid_walk_constants at class 3.
-#include "../ray_tracer_webgl_amd/csrc/pt_grid.hpp"
+#include "../ray_tracer_webgl_amd/csrc/pt_scene_image.hpp"
 #include "../include/ptrace.h"
 
 #include <algorithm>
@@ -21,19 +21,9 @@ extern "C" __attribute__((visibility("default"))) int grid_class_build(
     size_t n_index) {
   if (!std::isfinite(near_factor) || near_factor < 2.0 || near_factor > 16.0 || (layout != 0 && layout != 1)) return PT_ERR_INVALID;
   if (!s && n) return PT_ERR_INVALID;
-  std::vector<float> geom((size_t)n * 4), radii(n);
-  bool regular = true;
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < 3; k++) {
-      regular = regular && (std::fabs(s[i].center[k]) < 1e15f);
-      geom[4 * (size_t)i + k] = s[i].center[k];
-    }
-    regular = regular && (std::fabs(s[i].radius) < 1e15f);
-    geom[4 * (size_t)i + 3] = s[i].radius * s[i].radius;
-    radii[i] = s[i].radius;
-  }
+  const ptscene::Split sp = ptscene::split(s, n);
   ptgrid::Grid g;
-  if (!regular || !ptgrid::build(geom.data(), radii.data(), n, &g, near_factor)) return PT_ERR_NOT_READY;
+  if (!sp.regular || !ptgrid::build(sp.geom.data(), sp.radii.data(), n, &g, near_factor)) return PT_ERR_NOT_READY;
   if (layout == 1 && !ptgrid::morton_runs(&g)) return PT_ERR_CAPACITY;
   if (counts8) {
     counts8[0] = g.n[0]; counts8[1] = g.n[1]; counts8[2] = g.n[2]; counts8[3] = g.n_cell_entries;

@@ -2,8 +2,7 @@
 // layout of a one-layer grid) for tests/test_grid_records.py; host only, no HIP runtime.  Built by the test with
 // -DPT_DEV_KNOBS: ptgrid::build then reads its cell-edge scale from PT_GRID_EDGE, which is how the test gets the library's own
 // builder to make grids of 1 x 1 x 1 and 2 x 1 x 3 cells.
-#include "../ray_tracer_webgl_amd/csrc/pt_grid.hpp"
-#include "../ray_tracer_webgl_amd/csrc/pt_grid_records.hpp"
+#include "../ray_tracer_webgl_amd/csrc/pt_scene_image.hpp"
 #include "../include/ptrace.h"
 
 #include <cstdio>
@@ -48,12 +47,7 @@ SHIM void ring_layout(const uint32_t* host_cells, uint32_t nx, uint32_t nz, uint
 // ptgrid::build on a sphere list with the cell edge scaled by edge_scale (<= 0: as the library builds it): n3 = cells per
 // axis, cells = the host records (cap of them at most)
 SHIM int records_build_grid(const PtSphere* s, uint32_t n, double edge_scale, uint32_t* n3, uint32_t* cells, size_t cap) {
-  std::vector<float> geom((size_t)n * 4), radii(n);
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < 3; k++) geom[4 * (size_t)i + k] = s[i].center[k];
-    geom[4 * (size_t)i + 3] = s[i].radius * s[i].radius;
-    radii[i] = s[i].radius;
-  }
+  const ptscene::Split sp = ptscene::split(s, n);
   if (edge_scale > 0.0) {
     char buf[64];
     std::snprintf(buf, sizeof buf, "%.17g", edge_scale);
@@ -62,7 +56,7 @@ SHIM int records_build_grid(const PtSphere* s, uint32_t n, double edge_scale, ui
     unsetenv("PT_GRID_EDGE");
   }
   ptgrid::Grid g;
-  const bool ok = ptgrid::build(geom.data(), radii.data(), n, &g);
+  const bool ok = ptgrid::build(sp.geom.data(), sp.radii.data(), n, &g);
   unsetenv("PT_GRID_EDGE");
   if (!ok) return PT_ERR_NOT_READY;
   for (int k = 0; k < 3; k++) n3[k] = g.n[k];
