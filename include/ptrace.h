@@ -254,13 +254,23 @@ int pt_create(pt_ctx** out, int device, uint32_t width, uint32_t height);
  * pt_set_stream(ctx, NULL) on such a context creates the own stream then. */
 int pt_create_on_stream(pt_ctx** out, int device, uint32_t width, uint32_t height, void* hip_stream);
 int pt_destroy(pt_ctx* ctx);
-/* resize path, src/state.rs:364-398: reallocates buffers and clears the accumulation */
+/* resize path, src/state.rs:364-398: reallocates buffers and clears the accumulation.  Everything that belongs to the old size goes
+ * with it: accumulation, sample count, error estimate, both textures, the canvas and the statistics are cleared, the row partition
+ * is dropped ("all rows"), a caller-bound accumulation buffer is given back (as pt_bind_accum(ctx, NULL) does), and the uniforms are
+ * forgotten: the render calls return PT_ERR_NOT_READY until pt_set_params has brought uniforms of the new size. */
 int pt_resize(pt_ctx* ctx, uint32_t width, uint32_t height);
 
 /* ---- scene + uniforms ------------------------------------------------------------------------
  * pt_set_spheres replaces webgl::set_geometry (src/webgl.rs:225-274); n is not capped at 15:
  * up to 10 232 spheres are walked from LDS, up to 65 528 from global memory (PT_ERR_CAPACITY beyond).
- * pt_set_params replaces Uniforms::run_setters (src/webgl.rs:629-633). Both copy.  A pt_set_spheres that fails after its
+ * pt_set_params replaces Uniforms::run_setters (src/webgl.rs:629-633). Both copy.  pt_set_spheres replaces the scene and nothing
+ * else: accumulation, error estimate, textures and statistics stay, passes of the new scene add to what is there.  pt_set_params
+ * replaces ALL uniforms, first_pass included (it overwrites what pt_render_until / pt_render_adaptive have advanced).  A
+ * pt_set_params that CHANGES THE ROW PARTITION — band_* name another set of rows; band_count <= 1 is "all rows" whatever band_rows
+ * and band_index hold — clears the accumulation, its sample count, the error estimate, both textures and the canvas (they held
+ * other rows) and ends the validity of pt_adaptive_tiles; the statistics (PtStats.segments, samples, render_launches) keep counting.
+ * It is refused with PT_ERR_CAPACITY, nothing changed, when a caller-bound accumulation buffer cannot hold the new rows.  A
+ * pt_set_spheres that fails after its
  * first device write leaves the context without a scene: the render calls return PT_ERR_NOT_READY until a call succeeds. */
 int pt_set_spheres(pt_ctx* ctx, const PtSphere* spheres, uint32_t n);
 int pt_set_params(pt_ctx* ctx, const PtParams* params);
@@ -273,7 +283,9 @@ int pt_set_params(pt_ctx* ctx, const PtParams* params);
  * result is bit-identical to n_passes pt_render calls with those times. */
 int pt_render(pt_ctx* ctx);
 int pt_render_passes(pt_ctx* ctx, uint32_t n_passes);
-/* Pre-sizes the per-pass workspace so pt_render_passes(n <= max_passes) never allocates. */
+/* Pre-sizes the per-pass workspace so pt_render_passes(n <= max_passes) never allocates.  The reservation only grows: a smaller
+ * max_passes leaves it as it is.  pt_render_passes with more passes than the largest reservation so far returns PT_ERR_CAPACITY
+ * and enqueues nothing. */
 int pt_reserve_passes(pt_ctx* ctx, uint32_t max_passes);
 /* render_count = 0 (src/state.rs:343-346): clears accumulation, spp counter and statistics */
 int pt_reset_accum(pt_ctx* ctx);
@@ -295,10 +307,16 @@ int pt_accum_ptr(pt_ctx* ctx, void** dev_ptr, size_t* bytes);
  * count travels inside the buffer (the .a of every pixel), so rendering k passes, pt_read_accum,
  * a new context with the same scene / uniforms / row partition, pt_load_accum and k more passes
  * give the bits of 2k uninterrupted passes.  `dst` / `src`: host or device pointers to
- * local_rows*width*16 bytes.  Both synchronise the stream. */
+ * local_rows*width*16 bytes.  Both synchronise the stream.  pt_load_accum returns PT_ERR_INVALID, nothing changed, when `bytes` is not
+ * exactly that size, and when the buffer is not an accumulation of whole passes: the sample counts of its first and last pixel
+ * differ (a frame after a partial round of pt_render_adaptive is no checkpoint) or are not counts.  PtStats.segments keeps counting;
+ * total_spp and samples follow the loaded count. */
 int pt_read_accum(pt_ctx* ctx, float* dst, size_t bytes);
 int pt_load_accum(pt_ctx* ctx, const float* src, size_t bytes);
-/* Render into caller-owned device memory (e.g. a torch tensor) instead; NULL restores. */
+/* Render into caller-owned device memory (e.g. a torch tensor) instead.  The caller owns the contents: passes add to what the
+ * buffer holds, and the .a of its pixels is the sample count from then on.  NULL restores the context's own buffer, CLEARED (what
+ * it held when the caller's buffer took its place is another frame's, possibly another row partition's).  Either way the error
+ * estimate is cleared and the statistics keep counting.  PT_ERR_CAPACITY when `bytes` is below local_rows*width*16. */
 int pt_bind_accum(pt_ctx* ctx, void* dev_ptr, size_t bytes);
 /* Use a caller-owned hipStream_t (e.g. torch's current stream); NULL restores the own stream.  The
  * device's default stream IS the NULL handle: name it as hipStreamLegacy, PT_STREAM_LEGACY. */
@@ -477,6 +495,7 @@ int pt_blend_rgba8(pt_ctx* ctx, const uint8_t* prev_rgba8, uint8_t* out_rgba8);
  * texture[(even_odd_count + 1) % 2] by the shader's render() rule using params.render_count /
  * should_average / last_frame_weight, draw the result to the canvas and, when should_average, to
  * texture[even_odd_count % 2].  Asynchronous on the context's stream; nothing crosses PCIe.
+ * Neither frame call advances params.first_pass or touches the accumulation; their segments count in PtStats.segments.
  * pt_render_frames replays n_frames ticks at a constant frame interval from captured hipGraphs —
  * groups of 64 (while their slabs stay below 1 GiB), 16 and 4 frames (ONE trace launch renders a group's frames as its passes into slabs of
  * their own, allocated by the first call that needs them; their blends follow in order; advance) and
@@ -518,7 +537,11 @@ int pt_set_option(pt_ctx* ctx, int key, int value);
  * enable == 0); takes effect from the next pt_render / pt_render_passes / pt_render_frame / pt_render_frames, whose graphs
  * are captured again when the values change, as for any uniform.  enable == 0 restores the kernels and the bits of a context
  * that never enabled it.  The overlay runs in builds of the trace kernels of its own (loaded at first use) and excludes
- * PT_OPT_RUSSIAN_ROULETTE and PT_OPT_COUNT_WORK: turning one on while the other is on returns PT_ERR_INVALID.  A context
+ * PT_OPT_RUSSIAN_ROULETTE and PT_OPT_COUNT_WORK.  Overlay and roulette: turning one on while the other is on returns
+ * PT_ERR_INVALID and changes nothing.  PT_OPT_COUNT_WORK beside the overlay or beside roulette: the option calls succeed in either
+ * order, and every render call (pt_render*, pt_tune's launches) returns PT_ERR_INVALID and enqueues nothing while both are on;
+ * pt_render_frame(s), pt_render_adaptive and a pt_render_passes inside a stream capture return PT_ERR_INVALID under
+ * PT_OPT_COUNT_WORK alone.  A context
  * set to PT_GEOM_LDS renders through the scalar walk meanwhile, as with roulette. */
 int pt_set_debug_overlay(pt_ctx* ctx, int enable, int32_t selected_object, const float cursor_point[3]);
 /* Which build of the trace kernel the most recent launch was: 0 plain, 1 Russian roulette, 2 measuring twin, 3 debug overlay. */

@@ -854,7 +854,11 @@ PT_API int pt_bind_accum(pt_ctx* c, void* dev_ptr, size_t bytes) {
     c->accum = nullptr;
     int rc = ensure_buffers(c);
     c->total_spp = 0;
-    return rc != PT_OK ? rc : clear_error(c);
+    if (rc != PT_OK) return rc;
+    // the own buffer comes back EMPTY: what it held when the caller's buffer took its place belongs to another frame — possibly to
+    // another row partition, set while it was out of use — and the sample count above has just restarted
+    if (const size_t pix = n_pixels(c)) PT_HIP(c, hipMemsetAsync(c->accum, 0, pix * sizeof(float4), c->stream));
+    return clear_error(c);
   }
   size_t need = n_pixels(c) * sizeof(float4);
   if (bytes < need) return fail(c, PT_ERR_CAPACITY, "pt_bind_accum: %zu bytes < %zu needed", bytes, need);
