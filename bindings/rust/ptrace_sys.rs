@@ -83,6 +83,11 @@ extern "C" {
     // the variance-guided filtered read-out of the estimate: each pixel's mean averaged with the neighbours within `radius` whose
     // means differ by no more than kappa standard errors of the difference; out.a = accepted taps
     pub fn pt_resolve_filtered(ctx: *mut PtCtx, rgba_out: *mut f32, radius: u32, kappa: f32, gamma: c_int) -> c_int;
+    // the first-hit feature planes (pt_set_option PT_OPT_FEATURES 1): one pinhole ray per pixel, four planes of 16-byte texels —
+    // {albedo.rgb, t}, {normal, 0}, {hit point, 0}, int32 {list index, uuid, type, front_face}; a device pick is IDS[y][x]
+    pub fn pt_render_features(ctx: *mut PtCtx) -> c_int;
+    pub fn pt_features_ptr(ctx: *mut PtCtx, plane: c_int, dev_ptr: *mut *mut c_void, bytes: *mut usize) -> c_int;
+    pub fn pt_read_features(ctx: *mut PtCtx, plane: c_int, out: *mut c_void) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;
@@ -104,6 +109,12 @@ extern "C" {
 
 pub const PT_OPT_GEOMETRY_PATH: c_int = 1;      // PT_GEOM_AUTO 0 / LDS 1 / SCALAR 2 / BVH 3 / GRID 4 / SMALL 5
 pub const PT_OPT_ERROR_ESTIMATE: c_int = 7;     // opt-in, 0 = off; the image bits do not depend on it
+pub const PT_OPT_FEATURES: c_int = 8;           // opt-in, 0 = off; the image bits do not depend on it
+pub const PT_FEAT_ALBEDO: c_int = 0;
+pub const PT_FEAT_NORMAL: c_int = 1;
+pub const PT_FEAT_POINT: c_int = 2;
+pub const PT_FEAT_IDS: c_int = 3;
+pub const PT_FEAT_PLANES: c_int = 4;
 pub const PT_FILTER_MAX_RADIUS: u32 = 4;        // pt_resolve_filtered: the largest radius
 pub const PT_FILTER_KAPPA_DEFAULT: f32 = 2.0;   // ... and the kappa its callers start from
 pub const PT_OPT_RUSSIAN_ROULETTE: c_int = 5;   // opt-in, 0 = off: the reference's estimator has none (shader.frag:297-339)

@@ -101,6 +101,9 @@ enum {
   PT_OPT_ERROR_ESTIMATE = 7, /* 1: keep a per-pixel error estimate beside the accumulation (see pt_error_ptr below); allocates
                              and zeroes two float4 per local pixel.  0 (default): off, releases them.  The image bits of a
                              context are the same either way. */
+  PT_OPT_FEATURES = 8,    /* 1: allocate the four first-hit feature planes (see pt_render_features below; 64 bytes per local
+                             pixel) and keep the uuid arrays on the device.  0 (default): release them.  The image bits of a
+                             context are the same either way. */
 };
 
 /* ---- background modes ----------------------------------------------------------------------- */
@@ -481,6 +484,44 @@ int pt_adaptive_tiles(pt_ctx* ctx, uint32_t* base_out, uint32_t* order_out, uint
 #define PT_FILTER_KAPPA_DEFAULT 2.0f
 int pt_resolve_filtered(pt_ctx* ctx, float* rgba_out, uint32_t radius, float kappa, int gamma);
 
+/* ---- first-hit feature planes: albedo, normal, hit point and ids per pixel (build extension, opt-in: PT_OPT_FEATURES) ----
+ * What a denoiser, a picker or a compositor wants beside the colour: for every local pixel the first surface ONE deterministic
+ * ray through the pixel centre meets.  pt_render_features is one launch of the trace kernels' feature builds (a code object of
+ * their own, loaded when the option is turned on), asynchronous on the context's stream, no allocation; it goes through the
+ * geometry path forced or settled (an unsettled PT_GEOM_AUTO: its cold path; PT_GEOM_LDS: the scalar walk, as with roulette),
+ * is never one of PT_GEOM_AUTO's measuring launches, and leaves the accumulation, the estimate, the textures, the canvas,
+ * first_pass, the tile order and the tile costs alone.  Of PtStats it moves only `segments`, by one per in-image local pixel
+ * (and `far_rays`, which counts segments of the grid walk's far path, by those of them that take it);
+ * pt_last_trace_build returns 4 after it.  The debug overlay and Russian roulette do not act on it.
+ * THE RAY, fp32, for local pixel (px, ly), row 0 the lowest owned row, image row y = pt_band_row(..., ly):
+ *     vx = float(2 px + 1) / float(width) - 1          vy = float(2 y + 1) / float(height) - 1     (the pixel centre)
+ *     s = (vx + 1) * 0.5                               t = (vy + 1) * 0.5
+ *     dd.c = fma(t, vertical.c, fma(s, horizontal.c, lower_left_corner.c))
+ *     o = camera_origin                                d.c = dd.c - camera_origin.c
+ * No jitter, no lens, no seed: lens_radius, time, time_step, samples_per_pixel, max_depth and first_pass do not enter.
+ * hit_world(o, d, t_min, t_max) is the trace kernels' own: ties go to the later sphere, a negative radius flips the normal.
+ * THE RECORD: four planes of local_rows*width 16-byte texels, row 0 = lowest owned row:
+ *     plane              texel on a hit                                             texel on a miss
+ *     PT_FEAT_ALBEDO 0   {albedo.r, albedo.g, albedo.b, t}: PtSphere.albedo as      {bg.r, bg.g, bg.b, +0}: what the path tracer
+ *                        uploaded; t the accepted root, in units of unnormalised d  returns for this ray (sky gradient / zeros)
+ *     PT_FEAT_NORMAL 1   {n.x, n.y, n.z, +0}: the face-forward normal               all +0
+ *     PT_FEAT_POINT  2   {hp.x, hp.y, hp.z, +0}: hp.c = fma(d.c, t, o.c)            all +0
+ *     PT_FEAT_IDS    3   int32 x4 {list index, PtSphere.uuid, PtSphere.type as      {-1, -1, -1, 0}
+ *                        uploaded (any value), front_face}
+ * The floats of a hit are the bits the path tracer's own hit record holds for that segment.  A device pick is IDS[y][x].
+ * The planes are one allocation: pt_features_ptr(plane) is its device pointer (and bytes = local_rows*width*16) while the
+ * option is on; pt_resize and a repartition reallocate them.  They speak for the scene and uniforms of the last
+ * pt_render_features: pt_set_spheres, pt_set_params, pt_resize, a pt_refit_grid or pt_tune that rebuilds the grid, and turning
+ * the option off end that, and pt_read_features (host or device pointer; synchronises like pt_resolve) returns PT_ERR_NOT_READY
+ * until the next pt_render_features.  Per band, like every buffer.
+ * PT_ERR_INVALID: NULL ctx (or out pointer), a plane out of range, pt_render_features / pt_read_features under PT_OPT_COUNT_WORK
+ * or inside a stream capture.  PT_ERR_NOT_READY: no scene or no uniforms yet, or the option is off.  A band that owns no rows:
+ * PT_OK, nothing to do. */
+enum { PT_FEAT_ALBEDO = 0, PT_FEAT_NORMAL = 1, PT_FEAT_POINT = 2, PT_FEAT_IDS = 3, PT_FEAT_PLANES = 4 };
+int pt_render_features(pt_ctx* ctx);
+int pt_features_ptr(pt_ctx* ctx, int plane, void** dev_ptr, size_t* bytes);
+int pt_read_features(pt_ctx* ctx, int plane, void* out);
+
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)
  * using params.render_count / should_average / last_frame_weight, writes RGBA8 to `out_rgba8`.
@@ -544,7 +585,8 @@ int pt_set_option(pt_ctx* ctx, int key, int value);
  * PT_OPT_COUNT_WORK alone.  A context
  * set to PT_GEOM_LDS renders through the scalar walk meanwhile, as with roulette. */
 int pt_set_debug_overlay(pt_ctx* ctx, int enable, int32_t selected_object, const float cursor_point[3]);
-/* Which build of the trace kernel the most recent launch was: 0 plain, 1 Russian roulette, 2 measuring twin, 3 debug overlay. */
+/* Which build of the trace kernel the most recent launch was: 0 plain, 1 Russian roulette, 2 measuring twin, 3 debug overlay,
+ * 4 first-hit features (pt_render_features). */
 int pt_last_trace_build(pt_ctx* ctx);
 /* Fits the context to scene AND uniforms.  (i) The uniform grid pt_set_spheres built for rays that start within twice the
  * scene's radius of its middle is rebuilt for the margin class that renders THIS view fastest: the smallest class that

@@ -30,12 +30,14 @@ PT_BG_BLACK = 1
 
 PT_GEOM_AUTO, PT_GEOM_LDS, PT_GEOM_SCALAR, PT_GEOM_BVH, PT_GEOM_GRID, PT_GEOM_SMALL = 0, 1, 2, 3, 4, 5
 PT_OPT_GEOMETRY_PATH, PT_OPT_COUNT_WORK, PT_OPT_CARRY_LANES, PT_OPT_REFILL_MIN, PT_OPT_RUSSIAN_ROULETTE, PT_OPT_GRID_FIT = 1, 2, 3, 4, 5, 6
+PT_OPT_FEATURES = 8  # the first-hit feature planes (pt_render_features, pt_features_ptr, pt_read_features)
+PT_FEAT_ALBEDO, PT_FEAT_NORMAL, PT_FEAT_POINT, PT_FEAT_IDS, PT_FEAT_PLANES = 0, 1, 2, 3, 4
 PT_OPT_ERROR_ESTIMATE = 7  # the per-pixel error estimate (pt_error_ptr, pt_resolve_error, pt_error_tiles, pt_error_stats, pt_render_until)
 PT_TIME_STEP_DECORRELATED = 0.3618034  # include/ptrace.h
 PT_FILTER_MAX_RADIUS = 4        # pt_resolve_filtered: the largest radius
 PT_FILTER_KAPPA_DEFAULT = 2.0   # ... and the kappa its callers start from
 NO_SELECTED_OBJECT_ID = 1000  # src/state.rs:12: State.selected_object while the crosshair is on nothing
-BUILD_PLAIN, BUILD_ROULETTE, BUILD_TWIN, BUILD_DEBUG_OVERLAY = 0, 1, 2, 3  # pt_last_trace_build
+BUILD_PLAIN, BUILD_ROULETTE, BUILD_TWIN, BUILD_DEBUG_OVERLAY, BUILD_FEATURES = 0, 1, 2, 3, 4  # pt_last_trace_build
 PT_STREAM_LEGACY = 1  # include/ptrace.h: hipStreamLegacy, the default (NULL) stream by name
 GEOM_NAMES = {0: "auto", 1: "lds", 2: "scalar", 3: "bvh", 4: "grid", 5: "small"}
 

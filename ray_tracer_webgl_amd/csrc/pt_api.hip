@@ -172,6 +172,11 @@ struct pt_ctx {
   float dbg_cursor[3] = {0.f, 0.f, 0.f};
   bool uuid_valid = false;          // the three uuid arrays match the scene and structures in place
   int last_build = 0;               // which build the most recent trace launch was (pt_last_trace_build)
+  // first-hit feature planes (PT_OPT_FEATURES; pt_kernels_features.hip): four planes of one 16-byte texel per local pixel in one
+  // allocation, plane k at k * local pixels; written by pt_render_features, which also needs the uuid arrays above
+  bool feat_on = false;
+  bool feat_valid = false;          // the planes speak for the scene, uniforms and partition in place (pt_read_features)
+  DevBuf<float4> d_feat;
   // work-queue ordering feedback, one entry per tile
   DevBuf<uint32_t> d_tile_cost;
   DevBuf<uint32_t> d_tile_order;
@@ -334,6 +339,11 @@ int ensure_buffers(pt_ctx* c) {
     }
     if (c->d_err_tiles.capacity() < 2 * tiles) PT_HIP(c, c->d_err_tiles.reserve(2 * tiles));
   }
+  if (c->feat_on && c->d_feat.capacity() != PT_FEAT_PLANES * pix) {  // (sized for the local rows in place: plane k begins at k * pix)
+    c->feat_valid = false;
+    if (pix > 0x3fffffffu / PT_FEAT_PLANES) return fail(c, PT_ERR_CAPACITY, "feature planes: %zu local pixels exceed the kernels' 32-bit texel index", pix);
+    PT_HIP(c, c->d_feat.reserve(PT_FEAT_PLANES * pix));
+  }
   return PT_OK;
 }
 
@@ -465,43 +475,57 @@ const void* debug_kernel(int device, int id) {
   return k;
 }
 
+// a kernel of pt_kernels_features.hip, likewise
+const void* feature_kernel(int device, int id) {
+  static std::once_flag once[64][PT_F_COUNT];
+  const void* k = pt_feature_kernel(id);
+  if (k)
+    std::call_once(once[device & 63][id], [k] {
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
+      (void)hipGetLastError();
+    });
+  return k;
+}
+
 // Every trace kernel, by how it reads the list (row) and which build runs (column), with the wave count it is built for
 // (its PT_BUILT_FOR).  A kernel of this object has `main`; one of pt_kernels_extra.hip a PT_X_* id (`extra`), one of
-// pt_kernels_small.hip the list length's remainder modulo four (`small`), one of pt_kernels_debug.hip a PT_D_* id (`debug`):
-// those three objects are loaded only when one of their kernels is first launched, so their handles are taken when an entry
-// is chosen, not here.  Where a way to read the list has no roulette build, no measuring twin or no overlay build, its
-// column holds the plain build, which then runs (the LDS list walk: pt_geom_plan.hpp steers roulette and overlay launches
-// to the scalar row).
-struct TraceKernel { const void* main; int extra, small, waves; int debug = -1; };
+// pt_kernels_small.hip the list length's remainder modulo four (`small`), one of pt_kernels_debug.hip a PT_D_* id (`debug`), one
+// of pt_kernels_features.hip a PT_F_* id (`feature`):
+// those four objects are loaded only when one of their kernels is first launched, so their handles are taken when an entry
+// is chosen, not here.  Where a way to read the list has no roulette build, no measuring twin, no overlay or no feature build, its
+// column holds the plain build, which then runs (the LDS list walk: pt_geom_plan.hpp steers roulette, overlay and feature
+// launches to the scalar row).
+struct TraceKernel { const void* main; int extra, small, waves; int debug = -1; int feature = -1; };
 // ROW_SMALL + list length % 4; ROW_BVH / ROW_GRID + what is staged in the LDS (bind_hierarchy, bind_grid); ROW_GRID itself is
 // the LDS-staged build on a grid of one layer along y, ROW_GRID_LAYERS the same build on any other grid (grid_walk_flat)
 enum TraceRow { ROW_LIST_LDS, ROW_SCALAR, ROW_SCALAR_NOLDS, ROW_SMALL, ROW_BVH = ROW_SMALL + 4, ROW_GRID = ROW_BVH + 3, ROW_GRID_LAYERS = ROW_GRID + 3,
                 ROW_COUNT };
-enum TraceBuild { BUILD_PLAIN, BUILD_RR, BUILD_TWIN, BUILD_DBG, BUILD_COUNT };
+enum TraceBuild { BUILD_PLAIN, BUILD_RR, BUILD_TWIN, BUILD_DBG, BUILD_FEAT, BUILD_COUNT };
 
 template <class K>
 TraceKernel in_main(K* k, int waves) { return {reinterpret_cast<const void*>(k), -1, -1, waves}; }
 TraceKernel in_extra(int id, int waves = PT_WAVES_WALK) { return {nullptr, id, -1, waves}; }
 TraceKernel in_small(int rem) { return {nullptr, -1, rem, PT_WAVES_SMALL}; }
 TraceKernel in_debug(int id, int waves = PT_WAVES_WALK) { return {nullptr, -1, -1, waves, id}; }
+TraceKernel in_feature(int id, int waves = PT_WAVES_WALK) { return {nullptr, -1, -1, waves, -1, id}; }
 
 const TraceKernel kTraceKernels[ROW_COUNT][BUILD_COUNT] = {
-    // plain                                                roulette                                         measuring twin                                    debug overlay
-    {in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),           in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),     in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),  in_main(pt_trace_kernel, PT_WAVES_LIST_LDS)},
-    {in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),        in_extra(PT_X_SCALAR_RR, PT_WAVES_LIST),         in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),  in_debug(PT_D_SCALAR, PT_WAVES_LIST)},
-    {in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_extra(PT_X_SCALAR_NOLDS_RR, PT_WAVES_LIST),   in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_debug(PT_D_SCALAR_NOLDS, PT_WAVES_LIST)},
-    {in_small(0),                                           in_extra(PT_X_SMALL_RR + 0, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 0, PT_WAVES_SMALL)},
-    {in_small(1),                                           in_extra(PT_X_SMALL_RR + 1, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 1, PT_WAVES_SMALL)},
-    {in_small(2),                                           in_extra(PT_X_SMALL_RR + 2, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 2, PT_WAVES_SMALL)},
-    {in_small(3),                                           in_extra(PT_X_SMALL_RR + 3, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 3, PT_WAVES_SMALL)},
-    {in_main(pt_trace_kernel_bvh, PT_WAVES_WALK),           in_extra(PT_X_BVH_RR),                           in_extra(PT_X_BVH_COUNT),  in_debug(PT_D_BVH)},
-    {in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),     in_extra(PT_X_BVH_NODES_RR),                     in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),  in_debug(PT_D_BVH_NODES)},
-    {in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),      in_extra(PT_X_BVH_GMEM_RR),                      in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),  in_debug(PT_D_BVH_GMEM)},
-    {in_main(pt_trace_kernel_grid, PT_WAVES_WALK),          in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_COUNT),  in_debug(PT_D_GRID)},
-    {in_main(pt_trace_kernel_grid_cells, PT_WAVES_WALK),    in_extra(PT_X_GRID_CELLS_RR),                    in_extra(PT_X_GRID_CELLS_COUNT, PT_WAVES_TWIN_CELLS),  in_debug(PT_D_GRID_CELLS)},
-    {in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),     in_extra(PT_X_GRID_GMEM_RR),                     in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),  in_debug(PT_D_GRID_GMEM)},
-    // (the roulette and overlay builds walk three axes on a one-layer grid too — right on any grid, and not measured: one build each serves both rows)
-    {in_main(pt_trace_kernel_grid_layers, PT_WAVES_WALK),   in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_LAYERS_COUNT),  in_debug(PT_D_GRID)},
+    // plain                                                roulette                                         measuring twin                                    debug overlay                    first-hit features
+    {in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),           in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),     in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),  in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),  in_main(pt_trace_kernel, PT_WAVES_LIST_LDS)},
+    {in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),        in_extra(PT_X_SCALAR_RR, PT_WAVES_LIST),         in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),  in_debug(PT_D_SCALAR, PT_WAVES_LIST),  in_feature(PT_F_SCALAR, PT_WAVES_LIST)},
+    {in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_extra(PT_X_SCALAR_NOLDS_RR, PT_WAVES_LIST),   in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_debug(PT_D_SCALAR_NOLDS, PT_WAVES_LIST),  in_feature(PT_F_SCALAR_NOLDS, PT_WAVES_LIST)},
+    {in_small(0),                                           in_extra(PT_X_SMALL_RR + 0, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 0, PT_WAVES_SMALL),  in_feature(PT_F_SMALL + 0, PT_WAVES_SMALL)},
+    {in_small(1),                                           in_extra(PT_X_SMALL_RR + 1, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 1, PT_WAVES_SMALL),  in_feature(PT_F_SMALL + 1, PT_WAVES_SMALL)},
+    {in_small(2),                                           in_extra(PT_X_SMALL_RR + 2, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 2, PT_WAVES_SMALL),  in_feature(PT_F_SMALL + 2, PT_WAVES_SMALL)},
+    {in_small(3),                                           in_extra(PT_X_SMALL_RR + 3, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 3, PT_WAVES_SMALL),  in_feature(PT_F_SMALL + 3, PT_WAVES_SMALL)},
+    {in_main(pt_trace_kernel_bvh, PT_WAVES_WALK),           in_extra(PT_X_BVH_RR),                           in_extra(PT_X_BVH_COUNT),  in_debug(PT_D_BVH),  in_feature(PT_F_BVH)},
+    {in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),     in_extra(PT_X_BVH_NODES_RR),                     in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),  in_debug(PT_D_BVH_NODES),  in_feature(PT_F_BVH_NODES)},
+    {in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),      in_extra(PT_X_BVH_GMEM_RR),                      in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),  in_debug(PT_D_BVH_GMEM),  in_feature(PT_F_BVH_GMEM)},
+    {in_main(pt_trace_kernel_grid, PT_WAVES_WALK),          in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_COUNT),  in_debug(PT_D_GRID),  in_feature(PT_F_GRID)},
+    {in_main(pt_trace_kernel_grid_cells, PT_WAVES_WALK),    in_extra(PT_X_GRID_CELLS_RR),                    in_extra(PT_X_GRID_CELLS_COUNT, PT_WAVES_TWIN_CELLS),  in_debug(PT_D_GRID_CELLS),  in_feature(PT_F_GRID_CELLS)},
+    {in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),     in_extra(PT_X_GRID_GMEM_RR),                     in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),  in_debug(PT_D_GRID_GMEM),  in_feature(PT_F_GRID_GMEM)},
+    // (the roulette, overlay and feature builds walk three axes on a one-layer grid too — right on any grid, and not measured: one build each serves both rows)
+    {in_main(pt_trace_kernel_grid_layers, PT_WAVES_WALK),   in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_LAYERS_COUNT),  in_debug(PT_D_GRID),  in_feature(PT_F_GRID)},
 };
 
 } // namespace
@@ -632,7 +656,7 @@ template <class T>
 void release(std::vector<T>& v) { std::vector<T>().swap(v); }
 
 // no scene is in place (until an install has wholly succeeded: the render calls answer PT_ERR_NOT_READY meanwhile)
-void drop_scene(pt_ctx* c) { c->have_spheres = c->bvh.present = c->grid.present = c->uuid_valid = false; }
+void drop_scene(pt_ctx* c) { c->have_spheres = c->bvh.present = c->grid.present = c->uuid_valid = c->feat_valid = false; }
 
 // (list.n and list.host follow when the whole scene is in place: pt_set_spheres)
 int install_list(pt_ctx* c, const ptscene::Split& sp, size_t n) {
@@ -682,9 +706,10 @@ int install_grid(pt_ctx* c, ptgrid::Grid& grid, const ptscene::Split& sp) {
   return PT_OK;
 }
 
-// The debug overlay's uuid arrays: PtSphere.uuid in list order and per slot of the structures in place (the walk kernels
-// shade from a slot, like slot_mat).  Made when the overlay is turned on and again whenever the scene or the grid changes while
-// it is on; a context that never enables the overlay never allocates them.  Synchronises: a set-up call's work.
+// The uuid arrays of the debug overlay and of the feature planes: PtSphere.uuid in list order and per slot of the structures in
+// place (the walk kernels shade from a slot, like slot_mat).  Made when either is turned on and again whenever the scene or the
+// grid changes while either is on (wants_uuids); a context that never enables one never allocates them.  Synchronises: a set-up call's work.
+inline bool wants_uuids(const pt_ctx* c) { return c->dbg_enable || c->feat_on; }
 int upload_uuids(pt_ctx* c, const std::vector<int32_t>& uuid) {
   PT_HIP(c, hipSetDevice(c->device));
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight may read the arrays in place
@@ -699,12 +724,12 @@ int upload_uuids(pt_ctx* c, const std::vector<int32_t>& uuid) {
   return PT_OK;
 }
 
-// the device half of pt_set_spheres: list, hierarchy, grid, and the uuid arrays when the overlay is on
+// the device half of pt_set_spheres: list, hierarchy, grid, and the uuid arrays when the overlay or the feature planes are on
 int install_scene(pt_ctx* c, const ptscene::Split& sp, uint32_t n, ptbvh::Bvh* bvh, ptgrid::Grid* grid) {
   PT_TRY(install_list(c, sp, n));
   if (bvh) PT_TRY(install_bvh(c, *bvh, sp));
   if (grid) PT_TRY(install_grid(c, *grid, sp));
-  return c->dbg_enable ? upload_uuids(c, sp.uuid) : PT_OK;
+  return wants_uuids(c) ? upload_uuids(c, sp.uuid) : PT_OK;
 }
 
 } // namespace
@@ -769,6 +794,7 @@ PT_API int pt_set_params(pt_ctx* c, const PtParams* p) {
   // validate first, commit afterwards: a refused call leaves the context as it was
   if (repartition && c->accum_bound && (size_t)rows * c->width > c->accum_pixels)
     return fail(c, PT_ERR_CAPACITY, "pt_set_params: bound accumulation buffer too small for %u rows", rows);
+  c->feat_valid = false;  // the feature planes speak for the uniforms they were rendered with
   if (repartition) {
     const uint32_t old_rows = c->local_rows;
     c->local_rows = rows;
@@ -803,6 +829,7 @@ PT_API int pt_resize(pt_ctx* c, uint32_t width, uint32_t height) {
   c->height = height;
   c->have_params = false; // uniforms must be re-uploaded for the new size
   c->adapt_valid = false;
+  c->feat_valid = false;
   c->params.band_count = 0;
   c->local_rows = height;
   if (c->accum_bound) { c->accum_bound = false; c->accum = nullptr; }
@@ -1091,6 +1118,9 @@ struct LaunchUse {
   // full permutation of the tiles, and is planned for that many items; tiles_x, tiles_y and div_per_tile stay the frame's
   uint32_t n_first_tiles = 0;
   const uint32_t* table = nullptr;
+  // pt_render_features' launch: the feature build of the path forced or settled (the cold path while PT_GEOM_AUTO measures),
+  // one pass into the planes; it is no trial, settles nothing and leaves `geom` as it finds it
+  bool features = false;
 };
 
 // (what fill_uniforms zeroed and nothing here sets stays zero: wave_log and cell_hist, which only a measuring twin gets)
@@ -1106,15 +1136,17 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   }
   const LaunchKnobs knobs = read_launch_knobs();
   if (knobs.carry_lanes) A.carry_lanes = *knobs.carry_lanes;
-  if (c->geom.policy == PT_GEOM_AUTO) try_finish_tuning(c);
-  const bool rr = c->rr_min_depth > 0, dbg = c->dbg_enable;
+  const bool feat = use.features;
+  if (c->geom.policy == PT_GEOM_AUTO && !feat) try_finish_tuning(c);
+  const bool rr = !feat && c->rr_min_depth > 0, dbg = !feat && c->dbg_enable;
   if (rr && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and PT_OPT_RUSSIAN_ROULETTE exclude each other");
   if (dbg && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and the debug overlay exclude each other");
   if (dbg && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "debug overlay: the uuid arrays are not in place (pt_set_debug_overlay after a failed upload?)");
   // (the overlay builds exist for the ways to read the list that have a roulette build: the same steering away from the LDS walk)
-  const PathChoice choice = c->geom.choose(path_scene(c), use.allow_trials, rr || dbg);
+  if (feat && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "feature planes: the uuid arrays are not in place (PT_OPT_FEATURES after a failed upload?)");
+  const PathChoice choice = c->geom.choose(path_scene(c), use.allow_trials && !feat, rr || dbg || feat);
   const int path = choice.path;
-  c->geom.last = path;
+  if (!feat) c->geom.last = path;
 
   // the kernel, its workgroup size and its dynamic LDS (staged scene + the parked path state of every
   // lane of a walk kernel's workgroup)
@@ -1135,7 +1167,13 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
     row = path == PT_GEOM_SMALL ? ROW_SMALL + (int)(c->list.n & 3u)
                                 : (path == PT_GEOM_LDS ? ROW_LIST_LDS : (have_lds ? ROW_SCALAR : ROW_SCALAR_NOLDS));
   }
-  const int build = dbg ? BUILD_DBG : (rr ? BUILD_RR : (c->count_work ? BUILD_TWIN : BUILD_PLAIN));
+  const int build = feat ? BUILD_FEAT : (dbg ? BUILD_DBG : (rr ? BUILD_RR : (c->count_work ? BUILD_TWIN : BUILD_PLAIN)));
+  if (feat) {  // one deterministic segment per pixel into the planes; the overlay and roulette do not act
+    A.uuid = c->list.uuid.get();
+    A.slot_uuid = path == PT_GEOM_BVH ? c->bvh.uuid.get() : (path == PT_GEOM_GRID ? c->grid.uuid.get() : nullptr);
+    A.slab = reinterpret_cast<float*>(c->d_feat.get());
+    A.spp = 1; A.max_depth = 1; A.rr_min_depth = 0;
+  }
   // the two-axis walk (pt_trace_kernel_grid and its twin; the roulette and overlay builds of that row walk three axes) reads
   // the ring layout; it is what `scene` was sized for (staged_cells)
   if (walk && path == PT_GEOM_GRID && row == ROW_GRID && (build == BUILD_PLAIN || build == BUILD_TWIN)) {
@@ -1144,7 +1182,8 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   }
   const TraceKernel& tk = kTraceKernels[row][build];
   const void* kfn = tk.main ? tk.main
-                            : (tk.debug >= 0 ? debug_kernel(c->device, tk.debug)
+                            : (tk.feature >= 0 ? feature_kernel(c->device, tk.feature)
+                            : tk.debug >= 0 ? debug_kernel(c->device, tk.debug)
                                              : (tk.extra >= 0 ? extra_kernel(c->device, tk.extra) : pt_small_kernel((unsigned)tk.small)));
   c->last_build = build;
   const uint32_t block = walk ? walk_block_threads(kfn, tk.waves, scene, kWalkLdsMax, knobs.bvh_block) : list_block_threads(scene);
@@ -1153,11 +1192,12 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   int per_cu = 0;
   PT_HIP(c, resident_blocks(kfn, block, lds, tk.waves, &per_cu));
 
-  const LaunchPlan P = plan_launch({A.n_items, c->params.samples_per_pixel, n_passes, block, per_cu, (uint32_t)c->num_cus, walk,
+  const LaunchPlan P = plan_launch({A.n_items, feat ? 1 : c->params.samples_per_pixel, n_passes, block, per_cu, (uint32_t)c->num_cus, walk,
                                     c->list.n, knobs});
   A.queue_chunk = P.queue_chunk; A.queue_static = (uint32_t)P.deal; A.queue_groups = P.queue_groups;
   A.n_waves = P.n_waves; A.coop_max_live = P.coop_max_live;
   A.cost_feedback = use.feedback == LaunchUse::PLANNED ? P.cost_feedback : (use.feedback == LaunchUse::ON ? 1u : 0u);
+  if (feat) A.cost_feedback = 0u;
   L->kfn = kfn; L->grid = P.grid; L->block = block; L->lds = lds; L->path = path; L->trial = choice.trial;
   return PT_OK;
 }
@@ -1990,6 +2030,25 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     if (rc != PT_OK) { c->err_on = false; c->d_err = DevBuf<float4>(); c->d_err_tiles = DevBuf<float4>(); }
     return rc;
   }
+  if (key == PT_OPT_FEATURES) { // the image does not depend on it; the planes are allocated here, released when turned off
+    if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: feature planes %d", value);
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipStreamSynchronize(c->stream));  // (a feature launch in flight writes the planes)
+    if (!value) {
+      c->feat_on = c->feat_valid = false;
+      c->d_feat = DevBuf<float4>();
+      return PT_OK;
+    }
+    if (c->feat_on) return PT_OK;
+    // (asking for a kernel's attributes loads the feature builds' code object now: a set-up call's work, not a render call's)
+    hipFuncAttributes attr;
+    PT_HIP(c, hipFuncGetAttributes(&attr, pt_feature_kernel(PT_F_SCALAR)));
+    c->feat_on = true;
+    int rc = ensure_buffers(c);
+    if (rc == PT_OK && !c->uuid_valid && c->have_spheres) rc = upload_uuids(c, c->list.host.uuid);  // the scene in place
+    if (rc != PT_OK) { c->feat_on = false; c->d_feat = DevBuf<float4>(); }
+    return rc;
+  }
   return fail(c, PT_ERR_INVALID, "pt_set_option: unknown key %d", key);
 }
 
@@ -2016,10 +2075,68 @@ PT_API int pt_set_debug_overlay(pt_ctx* c, int enable, int32_t selected_object, 
   return PT_OK;
 }
 
-// which build of the trace kernel the most recent launch was: 0 plain, 1 Russian roulette, 2 measuring twin, 3 debug overlay
+// which build of the trace kernel the most recent launch was: 0 plain, 1 Russian roulette, 2 measuring twin, 3 debug overlay,
+// 4 first-hit features
 PT_API int pt_last_trace_build(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   return c->last_build;
+}
+
+// ---- first-hit feature planes (PT_OPT_FEATURES; include/ptrace.h has the record) ---------------------------------------------
+// are the planes allocated for the local rows in place?  (They are unless an allocation failed: ensure_buffers sizes them wherever
+// the rows change.)
+static bool feature_planes_in_place(const pt_ctx* c) {
+  const size_t pix = n_pixels(c) ? n_pixels(c) : 1;
+  return c->feat_on && c->d_feat.get() && c->d_feat.capacity() == PT_FEAT_PLANES * pix;
+}
+
+// ONE launch of the feature build of whichever kernel the context renders with, into the planes.  Nothing else of the context
+// moves: no fold, no timing events, no tile costs, no order kernel, no trial of PT_GEOM_AUTO (prepare_launch, LaunchUse::features);
+// the kernel adds its segments to the device counter like every trace launch.
+PT_API int pt_render_features(pt_ctx* c) {
+  if (!c) return PT_ERR_INVALID;
+  if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_render_features: not with PT_OPT_COUNT_WORK (the measuring twins have no feature build)");
+  if (!c->have_spheres || !c->have_params)
+    return fail(c, PT_ERR_NOT_READY, "pt_render_features: pt_set_spheres and pt_set_params must come first");
+  if (!c->feat_on) return fail(c, PT_ERR_NOT_READY, "pt_render_features: the feature planes are off (pt_set_option PT_OPT_FEATURES)");
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_render_features: not inside a stream capture");
+  if (!feature_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "pt_render_features: the planes are not allocated for the rows in place (an earlier allocation failed)");
+  if (c->local_rows == 0) { c->feat_valid = true; return PT_OK; }  // this band owns no rows: nothing to do, and its (empty) planes speak
+  Launch L;
+  LaunchUse use;
+  use.features = true;
+  use.feedback = LaunchUse::OFF;
+  if (int rc = prepare_launch(c, 1, use, &L); rc != PT_OK) return rc;
+  PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
+  if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
+  c->feat_valid = true;
+  return PT_OK;
+}
+
+PT_API int pt_features_ptr(pt_ctx* c, int plane, void** dev_ptr, size_t* bytes) {
+  if (!c || !dev_ptr) return fail(c, PT_ERR_INVALID, "pt_features_ptr: NULL argument");
+  if (plane < 0 || plane >= PT_FEAT_PLANES) return fail(c, PT_ERR_INVALID, "pt_features_ptr: plane %d out of range", plane);
+  if (!c->feat_on) return fail(c, PT_ERR_NOT_READY, "pt_features_ptr: the feature planes are off (pt_set_option PT_OPT_FEATURES)");
+  if (!feature_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "pt_features_ptr: the planes are not allocated for the rows in place (an earlier allocation failed)");
+  *dev_ptr = c->d_feat.get() + (size_t)plane * n_pixels(c);
+  if (bytes) *bytes = n_pixels(c) * sizeof(float4);
+  return PT_OK;
+}
+
+PT_API int pt_read_features(pt_ctx* c, int plane, void* out) {
+  if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_read_features: NULL argument");
+  if (plane < 0 || plane >= PT_FEAT_PLANES) return fail(c, PT_ERR_INVALID, "pt_read_features: plane %d out of range", plane);
+  if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_read_features: not with PT_OPT_COUNT_WORK");
+  if (!c->feat_on) return fail(c, PT_ERR_NOT_READY, "pt_read_features: the feature planes are off (pt_set_option PT_OPT_FEATURES)");
+  if (!c->feat_valid)
+    return fail(c, PT_ERR_NOT_READY, "pt_read_features: no pt_render_features since the scene, the uniforms or the size last changed");
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_read_features: not inside a stream capture (a read-out synchronises)");
+  const size_t need = n_pixels(c) * sizeof(float4);
+  if (need) PT_HIP(c, hipMemcpyAsync(out, c->d_feat.get() + (size_t)plane * n_pixels(c), need, hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
 }
 
 namespace {
@@ -2056,7 +2173,8 @@ int rebuild_grid(pt_ctx* c, double factor, bool keep_tuned) {
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight read the grid in place
   const int tuned = c->geom.tuned;
   int rc = install_grid(c, grid, sp);
-  if (rc == PT_OK && c->dbg_enable) rc = upload_uuids(c, sp.uuid);
+  c->feat_valid = false;
+  if (rc == PT_OK && wants_uuids(c)) rc = upload_uuids(c, sp.uuid);
   c->geom.list_paths(path_scene(c));  // (which kernels the grid can feed, and whether PT_GEOM_AUTO has anything to measure, follow its size — or its absence, had the upload failed)
   if (keep_tuned && rc == PT_OK && tuned == PT_GEOM_GRID && c->grid.present) c->geom.tuned = tuned;  // a refit keeps the settled choice
   return rc;

@@ -16,6 +16,13 @@ enum {
   PT_D_GRID, PT_D_GRID_CELLS, PT_D_GRID_GMEM, PT_D_COUNT
 };
 extern "C" const void* pt_debug_kernel(int id);
+// pt_kernels_features.hip (a code object of its own): the first-hit feature builds (pt_render_features), one per launch that has a
+// roulette build
+enum {
+  PT_F_SMALL = 0 /* + list length % 4: four builds */, PT_F_SCALAR = PT_F_SMALL + 4, PT_F_SCALAR_NOLDS, PT_F_BVH, PT_F_BVH_NODES, PT_F_BVH_GMEM,
+  PT_F_GRID, PT_F_GRID_CELLS, PT_F_GRID_GMEM, PT_F_COUNT
+};
+extern "C" const void* pt_feature_kernel(int id);
 // pt_kernels_error.hip (a code object of its own): the error estimate's fold, read-out and tile kernels (PT_OPT_ERROR_ESTIMATE), and
 // a partial round's fold and tile table (pt_render_adaptive), and the filtered read-out (pt_resolve_filtered)
 enum { PT_E_FOLD = 0, PT_E_RESOLVE, PT_E_TILES, PT_E_FOLD_TILES, PT_E_PARTITION, PT_E_FILTER, PT_E_COUNT };

@@ -29,8 +29,21 @@ __device__ __forceinline__ PixelDiv pixel_div() {
 
 // start the next camera path of this lane's item: static/shader.frag:365-370 + :342-351
 // the pixel jitter is divided by the image size (:367-368)
+// FEAT: the first-hit feature build's ray (include/ptrace.h pt_render_features) — the pixel centre through the pinhole: the
+// same dd, tt and cam_o as below with no jitter and no lens; no draw is made and the seed is neither read nor moved
+template <bool FEAT = false>
 __device__ __forceinline__ void start_sample(Path& p, const PixelDiv& pd) {
   karg_t& K = *kargs();
+  if constexpr (FEAT) {
+    const float s = p.st_s, t = p.st_t;
+    const V3 dd = mk(fma_(t, K.vertical[0], fma_(s, K.horizontal[0], K.llc[0])),
+                     fma_(t, K.vertical[1], fma_(s, K.horizontal[1], K.llc[1])),
+                     fma_(t, K.vertical[2], fma_(s, K.horizontal[2], K.llc[2])));
+    const V3 cam_o = mk(K.origin[0], K.origin[1], K.origin[2]);
+    const V3 d = mk(dd.x - cam_o.x, dd.y - cam_o.y, dd.z - cam_o.z);
+    p.o = cam_o; p.d = d; p.a = dot3(d, d); p.col = mk(1.0f, 1.0f, 1.0f); p.depth = 0;
+    return;
+  }
   float seed = p.seed;  // (local copies, written back at the end: see pt_grid_walk.hpp)
   const float st_s = p.st_s, st_t = p.st_t;
   const bool wh_ok = pd.wh_ok;

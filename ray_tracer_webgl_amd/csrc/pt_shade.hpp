@@ -19,7 +19,9 @@ namespace ptk {
 // RR: the opt-in Russian-roulette build of a kernel (PT_OPT_RUSSIAN_ROULETTE); the kernels without it
 // carry none of its code or registers
 // DBG: the opt-in debug-overlay build (pt_set_debug_overlay; pt_kernels_debug.hip), carried the same way
-template <typename S, bool RR, bool COUNT, bool DBG = false>
+// FEAT: the opt-in first-hit feature build (pt_render_features; pt_kernels_features.hip): the complete hit record — or the
+// miss — goes to the four planes behind A.slab and the path ends; no draw, no scatter, no colour store
+template <typename S, bool RR, bool COUNT, bool DBG = false, bool FEAT = false>
 __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, const Hit& h, const Carry& cw, Tally<COUNT>& tally) {
   tally.flag(PT_REG_SHADE_ANY);
   // local copies, written back at the end (see pt_grid_walk.hpp: references would be memory to the
@@ -93,6 +95,39 @@ __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, co
         mtype = 4;
       }
     }
+  }
+  if constexpr (FEAT) {
+    // FIRST-HIT FEATURES — opt-in (PT_OPT_FEATURES, pt_render_features; include/ptrace.h has the record).  Four planes of
+    // local_rows * width 16-byte texels behind A.slab, plane k at k * local_rows * width; the launch has one pass, so
+    // slab_index is the local pixel.  A hit stores what the record above holds and nothing else; a miss stores what the sky
+    // branch below adds for a throughput of 1.  The uuid arrays are read from the kernarg segment here, as the overlay reads them.
+    karg_t* K = kargs();
+    float4* planes = reinterpret_cast<float4*>(A.slab);
+    const uint32_t plane = K->local_rows * K->width;
+    float4 t_alb = make_float4(0.f, 0.f, 0.f, 0.f), t_n = t_alb, t_hp = t_alb;
+    int4 t_ids = make_int4(-1, -1, -1, 0);
+    if (hit >= 0) {
+      int index = hit;
+      const int32_t* up = K->uuid + hit;
+      if constexpr (S::TREE) {
+        if (hit_pos != 0xffffffffu) { index = (int)A.bvh_slot_index[hit_pos]; up = K->slot_uuid + hit_pos; }
+      }
+      t_alb = make_float4(alb.x, alb.y, alb.z, closest);
+      t_n = make_float4(n.x, n.y, n.z, 0.f);
+      t_hp = make_float4(hp.x, hp.y, hp.z, 0.f);
+      t_ids = make_int4(index, *up, mtype, front ? 1 : 0);
+    } else if (A.background_mode == 0) { // background(), :289-294, times a throughput of 1 into a sum of 0
+      const float uy = d.y * inv_sqrt_rn(a);
+      const float t = 0.5f * (uy + 1.0f);
+      const float omt = 1.0f - t;
+      t_alb = make_float4(0.0f + col.x * fma_(0.5f, t, omt), 0.0f + col.y * fma_(0.7f, t, omt), 0.0f + col.z * fma_(1.0f, t, omt), 0.f);
+    }
+    planes[slab_index] = t_alb;
+    planes[plane + slab_index] = t_n;
+    planes[2u * plane + slab_index] = t_hp;
+    reinterpret_cast<int4*>(planes)[3u * plane + slab_index] = t_ids;
+    p.alive = false; p.new_path = false; p.item_segs = item_segs;
+    return;
   }
   const bool sky = hit < 0 && A.background_mode == 0;
   const float inv = inv_sqrt_rn(a); // background() :290, GLASS :253

@@ -1,8 +1,8 @@
-// pt_trace_body.hpp — the path-tracing kernel body shared by the four device translation units (each a gfx950
+// pt_trace_body.hpp — the path-tracing kernel body shared by the five device translation units that trace (each a gfx950
 // code object of its own, loaded when one of its kernels is first asked for): pt_kernels.hip (list and walk
 // kernels), pt_kernels_small.hip (the small-list kernels, one per list length modulo four),
-// pt_kernels_extra.hip (the opt-in builds: the Russian-roulette kernels and the measuring twins) and
-// pt_kernels_debug.hip (the opt-in debug-overlay builds).
+// pt_kernels_extra.hip (the opt-in builds: the Russian-roulette kernels and the measuring twins),
+// pt_kernels_debug.hip (the opt-in debug-overlay builds) and pt_kernels_features.hip (the opt-in first-hit feature builds).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,9 +23,10 @@ using namespace ptd;
 // Template parameters: pt_scene.hpp `Scene`; COUNT = the measuring twin (tallies live); RR = the
 // opt-in Russian-roulette build (pt_shade.hpp); TAIL = the small-list builds' list remainder (pt_scene.hpp SMALL_TAIL);
 // FLAT_Y = the grid walk of a one-layer grid (pt_scene.hpp, pt_grid_walk.hpp); DBG = the opt-in debug-overlay build
-// (pt_shade.hpp).
+// (pt_shade.hpp); FEAT = the opt-in first-hit feature build (pt_render_features: one pinhole ray per pixel, its hit record
+// written to four planes, no scatter; pt_refill.hpp start_sample, pt_shade.hpp).
 // --------------------------------------------------------------------------------------------
-template <bool SCAN_LDS, bool HAVE_LDS, int WALK = 0, bool COUNT = false, bool RR = false, int TAIL = -1, bool FLAT_Y = false, bool DBG = false>
+template <bool SCAN_LDS, bool HAVE_LDS, int WALK = 0, bool COUNT = false, bool RR = false, int TAIL = -1, bool FLAT_Y = false, bool DBG = false, bool FEAT = false>
 __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
   using namespace ptk;
   using S = Scene<SCAN_LDS, HAVE_LDS, WALK, TAIL, FLAT_Y>;
@@ -48,7 +49,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
     // pulled an item and those whose previous path ended in the last step
     if (p.alive && p.new_path) {
       tally.flag(PT_REG_CAMERA_RAY);
-      start_sample(p, pd);
+      start_sample<FEAT>(p, pd);
       p.new_path = false;
     }
     tally.phase(1);
@@ -111,7 +112,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
     const bool shade = p.alive && !cw.carried;
     seg_count += (uint32_t)__popcll(pt_ballot(shade));
     tally.timebin(A, shade);
-    if (shade) shade_segment<S, RR, COUNT, DBG>(A, p, h, cw, tally);
+    if (shade) shade_segment<S, RR, COUNT, DBG, FEAT>(A, p, h, cw, tally);
     tally.collect();
     tally.phase(7);
   }

@@ -49,6 +49,10 @@ def main(argv=None):
                          "(pt_resolve_filtered: a pixel is averaged with the neighbours within R whose means differ by no more than "
                          "KAPPA standard errors; default 2,%g; R at most %d); prints the mean accepted taps"
                          % (abi.PT_FILTER_KAPPA_DEFAULT, abi.PT_FILTER_MAX_RADIUS))
+    ap.add_argument("--features", metavar="PREFIX",
+                    help="also write the first-hit feature planes of the frame's camera (pt_render_features: one pinhole ray per "
+                         "pixel) as PREFIX_albedo.npy, PREFIX_normal.npy, PREFIX_point.npy (float32) and PREFIX_ids.npy (int32: list "
+                         "index, uuid, type, front_face), each (rows, width, 4), row 0 = the image's lowest row")
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--checkpoint", help="also save the fp32 accumulation buffer (.npz)")
     args = ap.parse_args(argv)
@@ -118,6 +122,15 @@ def main(argv=None):
         image_io.write_png(args.samples_out, img)
     if args.checkpoint:
         image_io.save_accum(args.checkpoint, acc, st.total_spp)
+    if args.features:
+        pt.feature_planes(True)
+        pt.render_features()
+        planes = pt.features()
+        for name in ("albedo", "normal", "point", "ids"):
+            np.save("%s_%s.npy" % (args.features, name), planes[name])
+        hit = planes["ids"][..., 0] >= 0
+        print("features: %d of %d pixels hit, %d different spheres -> %s_{albedo,normal,point,ids}.npy" % (
+            int(hit.sum()), hit.size, len(np.unique(planes["ids"][..., 0][hit])), args.features))
     print("%s: %dx%d, %d spheres, %d spp, depth %d: %.2f s, %.0f Mray/s -> %s" % (
         sc.name, p.width, p.height, len(sc.spheres), st.total_spp, p.max_depth, dt, st.segments / dt / 1e6, args.out))
     pt.close()

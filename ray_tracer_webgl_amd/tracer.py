@@ -367,6 +367,46 @@ class PathTracer:
         self._check(self.lib.pt_adaptive_tiles(self._ctx, base.ctypes.data_as(u32p), order.ctypes.data_as(u32p), C.byref(n), C.byref(na)))
         return base, order, int(na.value)
 
+    # -- first-hit feature planes (include/ptrace.h PT_OPT_FEATURES) -------------------------------
+    def feature_planes(self, on=True):
+        """Allocate (or release) the four first-hit feature planes: albedo + distance, normal, hit point and ids of the
+        surface one pinhole ray through each pixel centre meets.  Off by default; the image bits are the same either way."""
+        self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_FEATURES, 1 if on else 0))
+
+    def render_features(self):
+        """One launch that fills the planes for the scene and uniforms in place (pt_render_features): asynchronous, and
+        nothing of the accumulation, the estimate or the frame textures moves."""
+        self._check(self.lib.pt_render_features(self._ctx))
+
+    def features(self):
+        """{"albedo", "normal", "point": float32, "ids": int32}, each (local_rows, width, 4), row 0 = lowest owned row:
+        {albedo.rgb, t}, {n.xyz, 0}, {hit point.xyz, 0} and {list index, uuid, type, front_face} on a hit; {background.rgb, 0},
+        zeros, zeros and {-1, -1, -1, 0} on a miss.  numpy copies — or, under use_torch, torch views of the device planes
+        (no copy, ordered on torch's stream like the accumulation tensor: they answer while the planes exist, change with
+        the next render_features and die with the planes).  The numpy read-out raises PtError(PT_ERR_NOT_READY) when the
+        scene, the uniforms or the size changed since the last render_features."""
+        names = (("albedo", abi.PT_FEAT_ALBEDO), ("normal", abi.PT_FEAT_NORMAL), ("point", abi.PT_FEAT_POINT), ("ids", abi.PT_FEAT_IDS))
+        shape = (self.local_rows, self.width, 4)
+        out = {}
+        if not self.use_torch:
+            for name, plane in names:
+                a = np.empty(shape, dtype=np.int32 if plane == abi.PT_FEAT_IDS else np.float32)
+                # (an empty band too: the call says whether the planes speak)
+                self._check(self.lib.pt_read_features(self._ctx, plane, a.ctypes.data_as(C.c_void_p)))
+                out[name] = a
+            return out
+        torch = self._torch
+        for name, plane in names:
+            ptr, nbytes = C.c_void_p(), C.c_size_t()
+            self._check(self.lib.pt_features_ptr(self._ctx, plane, C.byref(ptr), C.byref(nbytes)))
+            dtype = torch.int32 if plane == abi.PT_FEAT_IDS else torch.float32
+            if nbytes.value == 0:
+                out[name] = torch.empty(shape, dtype=dtype, device="cuda:%d" % self.device)
+                continue
+            view = _DeviceView(ptr.value, shape, "<i4" if plane == abi.PT_FEAT_IDS else "<f4")
+            out[name] = torch.as_tensor(view, device="cuda:%d" % self.device)
+        return out
+
     def sample_counts(self):
         """(local_rows, width) fp32: the samples each pixel holds (accum's fourth channel)."""
         return self.accum()[..., 3]
@@ -387,6 +427,14 @@ class PathTracer:
 
 
 _D2H, _H2D = 2, 1  # hipMemcpyDeviceToHost, hipMemcpyHostToDevice
+
+
+class _DeviceView:
+    """A device buffer the library owns, as PyTorch's array interface reads it (PathTracer.features under use_torch)."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2,
+                                         "strides": None}
 
 
 def _memcpy(dst, src, nbytes, kind):
