@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import hierarchy_edges as E
 from ray_tracer_webgl_amd import _lib, abi, scenes
 
 INNER = 0xFFFFFFFF
@@ -71,6 +72,7 @@ SCENES = {
     "field300": lambda: random_field(300, 1),
     "field17_no_giant": lambda: random_field(17, 2, giants=0),
     "clumps": lambda: np.concatenate([random_field(64, 3, extent=1.0, giants=0), random_field(64, 4, extent=300.0, giants=0)]),
+    "edge_limit": lambda: E.prefix(E.M_LIMIT),  # 65 528 slots, 32 761 nodes: the largest tree the 16-bit links and queues allow
 }
 
 
@@ -270,3 +272,68 @@ def test_walk_reaches_every_sphere_that_can_pass(name):
     # and the walk does cull: it looks at a small part of the scene
     if len(sph) >= 100:
         assert total_seen < 0.35 * 4 * n_rays * real.sum()
+
+
+# ---- the edges of what the walk kernels stage, and of the 16-bit links and queues (tests/hierarchy_edges.py) ----
+@pytest.mark.parametrize("name", E.EDGES)
+def test_edge_constants_still_have_their_property(name):
+    """The prefixes tests/test_gpu_hierarchy_edges.py renders are constants found by search; a changed builder moves the edges,
+    and then this fails here, on the CPU, instead of the GPU test quietly rendering some scene inside a row."""
+    m = getattr(E, name)
+    assert E.holds(name, m), ("%s = %d no longer has its property (%r): the builder has changed - run `python tests/hierarchy_edges.py` "
+                              "and put the constants it prints into tests/hierarchy_edges.py" % (name, m, E.properties(m)))
+
+
+def test_edge_constants_are_told_apart():
+    """(the check above can fail: the prefix next to an edge does not have the edge's property)"""
+    assert not E.holds("M_BVH_FULL", E.M_NODES_FIRST) and not E.holds("M_NODES_FIRST", E.M_BVH_FULL)
+    assert not E.holds("M_NODES_FULL", E.M_GMEM_FIRST) and not E.holds("M_GMEM_FIRST", E.M_NODES_FULL)
+    assert not E.holds("M_LIMIT", E.M_OVER) and not E.holds("M_OVER", E.M_LIMIT) and not E.holds("M_LIMIT", 60000)
+    assert E.M_BVH_FULL < E.M_NODES_FIRST < E.M_NODES_FULL < E.M_GMEM_FIRST < E.M_LIMIT < E.M_OVER <= E.N_FIELD
+    assert np.array_equal(E.prefix(300), scenes.field_spheres(300))
+
+
+def test_sixteen_bit_links_and_leaf_numbers_at_the_limit():
+    """M_LIMIT: what the kernels read still fits its 16 bits — leaf numbers below the inner-node mark 0xffff, links up to
+    n_nodes <= 0xfffe, slot numbers (what both per-lane queues hold) below 0xffff — and every sphere has its one slot."""
+    rc, b = build(E.prefix(E.M_LIMIT))
+    assert rc == 0
+    _, _, skip16, leaf16 = unpack16(b)
+    is_leaf = b["nodes"][:, 7].view(np.uint32) != INNER
+    n_nodes, n_slots = b["n_nodes"], b["n_slots"]
+    assert 0xFFFF - 64 <= n_slots <= 0xFFFF and n_slots % 4 == 0
+    assert np.all(leaf16[:-1][is_leaf] < 0xFFFF) and np.all(leaf16[:-1][~is_leaf] == 0xFFFF) and leaf16[-1] == 0xFFFF
+    assert 4 * int(leaf16[:-1][is_leaf].max()) + 3 < b["n_tree_slots"] + 0 <= n_slots
+    assert skip16[-1] == n_nodes <= 0xFFFE and skip16.max() == n_nodes
+    assert np.array_equal(b["nodes16"][:, 3], skip16.astype(np.uint32) | (leaf16.astype(np.uint32) << 16))  # nothing lost in the packing
+    real = b["index"] != INNER
+    assert np.array_equal(np.sort(b["index"][real]), np.arange(E.M_LIMIT + 1))
+
+
+@pytest.mark.parametrize("name", ["M_NODES_FULL", "M_LIMIT"])
+def test_walk_reaches_every_sphere_that_can_pass_at_the_edges(name):
+    """test_walk_reaches_every_sphere_that_can_pass on the largest trees: 500 rays, the rays x spheres matrices in chunks."""
+    sph = E.prefix(getattr(E, name))
+    rc, b = build(sph)
+    assert rc == 0
+    real = b["index"] != INNER
+    cs, r2 = b["slots"][real, :3], b["slots"][real, 3]
+    o, d = rays_for(sph, 500, 11)
+    a = np.einsum("ij,ij->i", d.astype(np.float64), d.astype(np.float64))
+    ok = (a > 1e-12) & (a < 1e6)
+    o, d = o[ok], d[ok]
+    assert len(o) > 400
+    seen = visited_slots(b, o, d)[:, real]
+    seen32 = visited_slots(b, o, d, packed=False)[:, real]
+    total_pass = 0
+    for k in range(0, len(o), 50):
+        disc, hb, cc = literal_disc(o[k:k + 50], d[k:k + 50], cs, r2)
+        can_pass = ~(disc < 0) & ~((cc > 0) & (hb >= 0))
+        missed = can_pass & ~seen[k:k + 50]
+        assert not missed.any(), (name, np.argwhere(missed)[:5] + (k, 0))
+        missed = can_pass & ~seen32[k:k + 50]
+        assert not missed.any(), (name, "fp32 boxes", np.argwhere(missed)[:5] + (k, 0))
+        total_pass += int(can_pass.sum())
+    assert seen32.sum() <= seen.sum()
+    assert total_pass > len(o)  # (the rays do meet spheres: more than one that can pass per ray)
+    assert seen.sum() < 0.35 * len(o) * real.sum()

@@ -28,6 +28,7 @@ import overlay_ref as R
 from ray_tracer_webgl_amd import abi, scenes
 from ray_tracer_webgl_amd.tracer import PathTracer, PtError
 from test_gpu_fuzz import random_scene
+from trace_builds import build_of
 
 pytestmark = pytest.mark.gpu
 
@@ -35,8 +36,6 @@ PLANES = ("albedo", "normal", "point", "ids")
 KERNELS = ["small_t0_feat", "small_t1_feat", "small_t2_feat", "small_t3_feat", "scalar_feat", "scalar_nolds_feat", "bvh_feat",
            "bvh_nodes_feat", "bvh_gmem_feat", "grid_feat", "grid_cells_feat", "grid_gmem_feat"]
 REACHED = {}
-MAX_SPHERES_LDS = 10232  # csrc/pt_kernel_args.h
-WALK_LDS_ROOM = (((MAX_SPHERES_LDS + 7) & ~7) + 4) * 16 - 15 * 4 * 1024  # csrc/pt_geom_plan.hpp walk_lds_room
 W, H = 37, 21
 
 
@@ -55,18 +54,10 @@ def kernel_of(t, path):
     """the feature kernel a launch through the forced `path` is (kTraceKernels of csrc/pt_api.hip, by row)"""
     assert t.last_trace_build() == abi.BUILD_FEATURES
     st = t.stats()
-    n = st.n_spheres
-    if path == abi.PT_GEOM_SMALL:
-        return "small_t%d_feat" % (n & 3)
-    if path in (abi.PT_GEOM_SCALAR, abi.PT_GEOM_LDS):
-        return "scalar_feat" if n <= MAX_SPHERES_LDS else "scalar_nolds_feat"
-    if path == abi.PT_GEOM_BVH:
-        if ((st.bvh_nodes + 1) * 2 + st.bvh_slots) * 16 <= WALK_LDS_ROOM:
-            return "bvh_feat"
-        return "bvh_nodes_feat" if (st.bvh_nodes + 1) * 16 <= WALK_LDS_ROOM else "bvh_gmem_feat"
-    if path == abi.PT_GEOM_GRID:
-        return ("grid_feat", "grid_cells_feat", "grid_gmem_feat")[st.grid_kernel_build - 1]
-    raise AssertionError("features through geometry path %d" % path)
+    if path == abi.PT_GEOM_AUTO:
+        raise AssertionError("features through geometry path %d" % path)
+    # (a feature launch leaves PtStats.geometry_path as it finds it; PT_GEOM_LDS is steered to the scalar row)
+    return build_of(st, "_feat", path=abi.PT_GEOM_SCALAR if path == abi.PT_GEOM_LDS else path)
 
 
 def context(sph, p, path=None, features=True):

@@ -23,14 +23,13 @@ import overlay_ref as R
 from ray_tracer_webgl_amd import abi, scenes
 from ray_tracer_webgl_amd.tracer import PathTracer, PtError
 from test_gpu_fuzz import random_scene
+from trace_builds import build_of
 
 pytestmark = pytest.mark.gpu
 
 KERNELS = ["small_t0_dbg", "small_t1_dbg", "small_t2_dbg", "small_t3_dbg", "scalar_dbg", "scalar_nolds_dbg", "bvh_dbg", "bvh_nodes_dbg",
            "bvh_gmem_dbg", "grid_dbg", "grid_cells_dbg", "grid_gmem_dbg"]
 REACHED = {}
-MAX_SPHERES_LDS = 10232  # csrc/pt_kernel_args.h
-WALK_LDS_ROOM = (((MAX_SPHERES_LDS + 7) & ~7) + 4) * 16 - 15 * 4 * 1024  # csrc/pt_geom_plan.hpp walk_lds_room
 
 
 def bits(a):
@@ -50,18 +49,9 @@ def kernel_of(t):
     """the overlay kernel the last launch of this context was (kTraceKernels of csrc/pt_api.hip, by row)"""
     assert t.last_trace_build() == abi.BUILD_DEBUG_OVERLAY
     st = t.stats()
-    path, n = st.geometry_path, st.n_spheres
-    if path == abi.PT_GEOM_SMALL:
-        return "small_t%d_dbg" % (n & 3)
-    if path == abi.PT_GEOM_SCALAR:
-        return "scalar_dbg" if n <= MAX_SPHERES_LDS else "scalar_nolds_dbg"
-    if path == abi.PT_GEOM_BVH:
-        if ((st.bvh_nodes + 1) * 2 + st.bvh_slots) * 16 <= WALK_LDS_ROOM:
-            return "bvh_dbg"
-        return "bvh_nodes_dbg" if (st.bvh_nodes + 1) * 16 <= WALK_LDS_ROOM else "bvh_gmem_dbg"
-    if path == abi.PT_GEOM_GRID:
-        return ("grid_dbg", "grid_cells_dbg", "grid_gmem_dbg")[st.grid_kernel_build - 1]
-    raise AssertionError("the overlay through geometry path %d" % path)
+    if st.geometry_path == abi.PT_GEOM_LDS:
+        raise AssertionError("the overlay through geometry path %d" % st.geometry_path)
+    return build_of(st, "_dbg")
 
 
 def context(sph, w, h, path, overlay):

@@ -1145,12 +1145,16 @@ def test_small_list_kernel_on_random_scenes(ora):
 
 
 def test_hierarchy_in_global_memory(ora):
-    """10 001 spheres: nodes + slots (335 KB) exceed the LDS, pt_trace_kernel_bvh_gmem walks them
-    in global memory / L2.  Window-checked against the oracle, whole frame against the list walk."""
+    """10 001 spheres: nodes + slots (335 KB) exceed the LDS, the packed nodes (84 KB) fit it beside the parked path state:
+    pt_trace_kernel_bvh_nodes walks the nodes in the LDS and gathers the slots from global memory / L2.  (The kernel with
+    both in global memory, pt_trace_kernel_bvh_gmem, starts at about 12 200 field spheres: tests/test_gpu_plain_builds.py,
+    tests/test_gpu_hierarchy_edges.py.)  Window-checked against the oracle, whole frame against the list walk."""
+    from trace_builds import row_of
+
     sc = scenes.config5(160, 90, 2, 1, 20)
     t, got, ref = _check_scene(ora, sc, window=(60, 84, 30, 46), geometry_path=abi.PT_GEOM_BVH)
     st = t.stats()
-    assert st.geometry_path == abi.PT_GEOM_BVH and (2 * st.bvh_nodes + st.bvh_slots) * 16 > 160 * 1024
+    assert st.geometry_path == abi.PT_GEOM_BVH and row_of(st) == "bvh_nodes"
     t2, got2 = render_scene(sc, geometry_path=abi.PT_GEOM_SCALAR)
     assert_bit_equal(got, got2, "hierarchy walk vs list walk, whole frame")
     assert t2.stats().segments == st.segments

@@ -27,6 +27,7 @@ import pytest
 from ray_tracer_webgl_amd import abi, scenes
 from ray_tracer_webgl_amd.tracer import PathTracer
 from test_gpu_fuzz import random_scene
+from trace_builds import build_of
 
 pytestmark = pytest.mark.gpu
 
@@ -35,10 +36,6 @@ K_MAX = 1000000  # the largest value pt_set_option accepts
 KERNELS = ["small_t0_rr", "small_t1_rr", "small_t2_rr", "small_t3_rr", "scalar_rr", "scalar_nolds_rr", "bvh_rr", "bvh_nodes_rr",
            "bvh_gmem_rr", "grid_rr", "grid_cells_rr", "grid_gmem_rr"]
 REACHED = {}  # kernel -> what was compared through it
-
-# csrc/pt_kernel_args.h, csrc/pt_geom_plan.hpp: what a walk kernel may stage beside a 1024-thread workgroup's parked state
-MAX_SPHERES_LDS = 10232
-WALK_LDS_ROOM = (((MAX_SPHERES_LDS + 7) & ~7) + 4) * 16 - 15 * 4 * 1024
 
 
 def bits(a):
@@ -57,21 +54,9 @@ def assert_bit_equal(got, ref, what):
 def kernel_of(st, roulette=True):
     """the roulette kernel the last launch of this context was (kTraceKernels of csrc/pt_api.hip, by row), from PtStats"""
     assert roulette
-    path, n = st.geometry_path, st.n_spheres
-    if path == abi.PT_GEOM_SMALL:
-        assert n <= 16
-        return "small_t%d_rr" % (n & 3)
-    if path == abi.PT_GEOM_SCALAR:
-        return "scalar_rr" if n <= MAX_SPHERES_LDS else "scalar_nolds_rr"
-    if path == abi.PT_GEOM_BVH:  # hierarchy_staging
-        assert st.bvh_nodes > 0
-        if ((st.bvh_nodes + 1) * 2 + st.bvh_slots) * 16 <= WALK_LDS_ROOM:
-            return "bvh_rr"
-        return "bvh_nodes_rr" if (st.bvh_nodes + 1) * 16 <= WALK_LDS_ROOM else "bvh_gmem_rr"
-    if path == abi.PT_GEOM_GRID:  # grid_staging, as the library reports it; one roulette build serves one and several layers
-        assert st.grid_entries > 0 and st.grid_kernel_build in (1, 2, 3)
-        return ("grid_rr", "grid_cells_rr", "grid_gmem_rr")[st.grid_kernel_build - 1]
-    raise AssertionError("roulette through geometry path %d: the LDS list walk has no roulette build" % path)
+    if st.geometry_path == abi.PT_GEOM_LDS:
+        raise AssertionError("roulette through geometry path %d: the LDS list walk has no roulette build" % st.geometry_path)
+    return build_of(st, "_rr")  # (one roulette build serves a grid of one layer and of several)
 
 
 def oracle(ora, sph, p, n_passes, k):

@@ -1,0 +1,137 @@
+"""tests/trace_builds.py — the tests' rule for "which kernel was that launch" — pinned to the library's rule
+(csrc/pt_geom_plan.hpp hierarchy_staging, grid_staging and walk_lds_room through tests/geom_plan_shim.cpp).  A kernel audit is
+worth what its naming is worth: a restatement of the staging arithmetic that drifts from the library's would let a test
+believe it reached a kernel that never ran.  CPU only."""
+import ctypes as C
+import itertools
+
+import pytest
+
+import trace_builds as tb
+from ray_tracer_webgl_amd import abi
+from test_geom_plan import shim  # noqa: F401  (the fixture that compiles and loads the shim)
+
+
+def lib_hierarchy(lib, n_nodes, n_slots, room):
+    b = C.c_uint64()
+    return lib.gp_hierarchy_staging(n_nodes, n_slots, room, C.byref(b)), b.value
+
+
+def lib_grid(lib, n_cells, n_entries, room, cells_build, fit):
+    b = C.c_uint64()
+    return lib.gp_grid_staging(n_cells, n_entries, room, cells_build, fit, C.byref(b)), b.value
+
+
+def test_the_room_is_the_librarys(shim):
+    assert tb.WALK_LDS_ROOM == shim.gp_walk_lds_room() == 102336
+    assert tb.WALK_LDS_MAX == 163776 and tb.MAX_SPHERES_LDS == 10232
+
+
+def hierarchy_sweep(room):
+    """(n_nodes, n_slots) over both thresholds +- 2 records — nodes and slots fit: ((n + 1) 2 + s) 16 <= room, the nodes fit:
+    (n + 1) 16 <= room — with the other count at its corners, and the corners of the 16-bit limits"""
+    rec = room // 16
+    out = set()
+    for d in range(-2, 3):
+        # all-in-LDS threshold, at a few splits between nodes and slots (slots come in fours; odd counts too: the rule is arithmetic)
+        for n in (0, 1, 15, 255, 1597, rec // 2 - 3, rec // 2 - 2, rec // 2 - 1):
+            s = rec - 2 * (n + 1) + d
+            if s >= 0:
+                out.add((n, s))
+        for s in (0, 4, 516, 3200, rec - 2):
+            n2 = rec - s + d * 2
+            for n in (n2 // 2 - 1, n2 // 2, (n2 + 1) // 2 - 1):
+                if n >= 0:
+                    out.add((n, s))
+        # nodes-in-LDS threshold, whatever the slots
+        for s in (0, 4, 12792, 12800, 0xFFFC, 0xFFFF):
+            out.add((rec - 1 + d, s))
+    for n, s in itertools.product((0, 1, rec // 2, rec, 0xFFFE), (0, 4, rec, 0xFFFC, 0xFFFF)):
+        out.add((n, s))
+    return sorted(out)
+
+
+def test_hierarchy_rows_follow_the_librarys_staging(shim):
+    room = shim.gp_walk_lds_room()
+    kinds = set()
+    for n, s in hierarchy_sweep(room):
+        want = lib_hierarchy(shim, n, s, room)
+        assert tb.hierarchy_staging(n, s) == want, (n, s, want)
+        kinds.add(want[0])
+    assert kinds == {0, 1, 2}
+    # the thresholds themselves: the last record that fits and the first that does not
+    rec = room // 16
+    assert tb.hierarchy_staging(rec // 2 - 1, 0) == (0, room) and tb.hierarchy_staging(rec // 2 - 1, 1)[0] == 1
+    assert tb.hierarchy_staging(1597, 3200) == (0, room) and tb.hierarchy_staging(1597, 3201)[0] == 1
+    assert tb.hierarchy_staging(rec - 1, 0xFFFF) == (1, room) and tb.hierarchy_staging(rec, 0xFFFF) == (2, 0)
+    # another room: the rule, not this room's numbers
+    for n, s in ((10, 20), (10, 21), (41, 4), (42, 0), (42, 4), (63, 0), (64, 0)):
+        assert tb.hierarchy_staging(n, s, 1024) == lib_hierarchy(shim, n, s, 1024)
+
+
+@pytest.mark.parametrize("cells_build", [0, 1])
+@pytest.mark.parametrize("fit", [0, 1, 2])
+def test_grid_builds_follow_the_librarys_staging(shim, cells_build, fit):
+    room = shim.gp_walk_lds_room()
+    rec = room // 16
+    cases = set()
+    for d in range(-2, 3):
+        for cells in (1, 4, 5, 256, 5400, 4 * (rec // 2)):
+            cell_recs = (cells + 3) // 4
+            if rec - cell_recs + d >= 0:
+                cases.add((cells, rec - cell_recs + d))   # cells and entries fit / do not
+        for entries in (0, 1, 798, 19482, 0xFFFF, 200000):
+            cases.add((4 * (rec + d), entries))           # the cell records alone fit / do not
+            cases.add((4 * (rec + d) - 3, entries))
+    for cells, entries in itertools.product((1, 4 * rec, 4 * rec + 1, 31000, 1 << 20), (0, 1, rec, rec + 1, 130000)):
+        cases.add((cells, entries))
+    kinds = set()
+    for cells, entries in sorted(cases):
+        want = lib_grid(shim, cells, entries, room, cells_build, fit)
+        assert tb.grid_staging(cells, entries, room, bool(cells_build), fit) == want, (cells, entries, want)
+        kinds.add(want[0])
+    assert kinds == ({1, 2, 3} if not cells_build and fit != 1 else {2, 3})
+
+
+class Stats:
+    """the fields of PtStats row_of reads"""
+
+    def __init__(self, path, n, nodes=0, slots=0, entries=0, build=0, flat=0):
+        self.geometry_path, self.n_spheres, self.bvh_nodes, self.bvh_slots = path, n, nodes, slots
+        self.grid_entries, self.grid_kernel_build, self.grid_walk_flat = entries, build, flat
+
+
+ROWS = [
+    (Stats(abi.PT_GEOM_LDS, 9), "list_lds", None),
+    (Stats(abi.PT_GEOM_LDS, 10232), "list_lds", None),
+    (Stats(abi.PT_GEOM_SCALAR, 10232), "scalar", None),
+    (Stats(abi.PT_GEOM_SCALAR, 10233), "scalar_nolds", None),
+    (Stats(abi.PT_GEOM_SMALL, 12), "small_t0", "small_count"),
+    (Stats(abi.PT_GEOM_SMALL, 9), "small_t1", "small_count"),
+    (Stats(abi.PT_GEOM_SMALL, 10), "small_t2", "small_count"),
+    (Stats(abi.PT_GEOM_SMALL, 11), "small_t3", "small_count"),
+    (Stats(abi.PT_GEOM_BVH, 484, 255, 516), "bvh", "bvh_count"),                # config 2
+    (Stats(abi.PT_GEOM_BVH, 10001, 5243, 10492), "bvh_nodes", None),            # config 5 (tests/test_geom_plan.py)
+    (Stats(abi.PT_GEOM_BVH, 3037, 1597, 3200), "bvh", "bvh_count"),
+    (Stats(abi.PT_GEOM_BVH, 3038, 1603, 3212), "bvh_nodes", None),
+    (Stats(abi.PT_GEOM_BVH, 12224, 6395, 12792), "bvh_nodes", None),
+    (Stats(abi.PT_GEOM_BVH, 12225, 6396, 12800), "bvh_gmem", None),
+    (Stats(abi.PT_GEOM_GRID, 484, entries=798, build=1, flat=1), "grid", "grid_count"),
+    (Stats(abi.PT_GEOM_GRID, 1501, entries=3000, build=1, flat=0), "grid_layers", "grid_layers_count"),
+    (Stats(abi.PT_GEOM_GRID, 10001, entries=19482, build=2), "grid_cells", "grid_cells_count"),
+    (Stats(abi.PT_GEOM_GRID, 60001, entries=130000, build=3), "grid_gmem", None),
+]
+
+
+def test_rows_twins_and_the_columns_with_one_grid_build():
+    for st, row, twin in ROWS:
+        assert tb.row_of(st) == row and tb.twin_of(row) == twin, (row, twin)
+        assert tb.build_of(st, "_rr") == ("grid" if row == "grid_layers" else row) + "_rr"
+    assert sorted(r for _, r, _ in ROWS) != [] and {r for _, r, _ in ROWS} == set(tb.ROWS) and len(tb.ROWS) == 14
+    assert {t for _, _, t in ROWS if t} == set(tb.TWINS) and len(tb.TWINS) == 5
+    # a launch that leaves PtStats.geometry_path alone names its path itself
+    assert tb.row_of(Stats(abi.PT_GEOM_LDS, 484, 255, 516), path=abi.PT_GEOM_BVH) == "bvh"
+    for bad in (Stats(abi.PT_GEOM_AUTO, 9), Stats(abi.PT_GEOM_SMALL, 17), Stats(abi.PT_GEOM_BVH, 484), Stats(abi.PT_GEOM_GRID, 484, entries=798),
+                Stats(abi.PT_GEOM_GRID, 484, entries=798, build=2, flat=1)):
+        with pytest.raises(AssertionError):
+            tb.row_of(bad)
