@@ -83,6 +83,9 @@ extern "C" {
     // the variance-guided filtered read-out of the estimate: each pixel's mean averaged with the neighbours within `radius` whose
     // means differ by no more than kappa standard errors of the difference; out.a = accepted taps
     pub fn pt_resolve_filtered(ctx: *mut PtCtx, rgba_out: *mut f32, radius: u32, kappa: f32, gamma: c_int) -> c_int;
+    // the same read-out with the test summed over the (2 patch + 1)^2 neighbourhoods around the two pixels; patch 0 gives
+    // pt_resolve_filtered's bits
+    pub fn pt_resolve_filtered_patch(ctx: *mut PtCtx, rgba_out: *mut f32, radius: u32, patch: u32, kappa: f32, gamma: c_int) -> c_int;
     // the first-hit feature planes (pt_set_option PT_OPT_FEATURES 1): one pinhole ray per pixel, four planes of 16-byte texels —
     // {albedo.rgb, t}, {normal, 0}, {hit point, 0}, int32 {list index, uuid, type, front_face}; a device pick is IDS[y][x]
     pub fn pt_render_features(ctx: *mut PtCtx) -> c_int;
@@ -117,6 +120,8 @@ pub const PT_FEAT_IDS: c_int = 3;
 pub const PT_FEAT_PLANES: c_int = 4;
 pub const PT_FILTER_MAX_RADIUS: u32 = 4;        // pt_resolve_filtered: the largest radius
 pub const PT_FILTER_KAPPA_DEFAULT: f32 = 2.0;   // ... and the kappa its callers start from
+pub const PT_FILTER_MAX_PATCH: u32 = 1;               // pt_resolve_filtered_patch: the largest patch radius
+pub const PT_FILTER_PATCH_KAPPA_DEFAULT: f32 = 1.5;   // ... and the kappa its callers start from
 pub const PT_OPT_RUSSIAN_ROULETTE: c_int = 5;   // opt-in, 0 = off: the reference's estimator has none (shader.frag:297-339)
 
 // The rAF closure of src/lib.rs:65-104 with webgl::render replaced (one tick):

@@ -484,6 +484,56 @@ int pt_adaptive_tiles(pt_ctx* ctx, uint32_t* base_out, uint32_t* order_out, uint
 #define PT_FILTER_KAPPA_DEFAULT 2.0f
 int pt_resolve_filtered(pt_ctx* ctx, float* rgba_out, uint32_t radius, float kappa, int gamma);
 
+/* ---- patch-wise filtered read-out: neighbourhoods, not pixels, pass the test (build extension, opt-in: PT_OPT_ERROR_ESTIMATE) --
+ * pt_resolve_filtered_patch: pt_resolve_filtered with another acceptance test.  A neighbour q is averaged into p when the
+ * (2 patch + 1)^2 neighbourhoods around p and q, compared texel by texel, differ by no more than their standard errors explain:
+ * the squared differences and the variances are summed over the patch before they are compared.  One noisy pixel no longer
+ * decides; the same error in a whole neighbourhood (a shadow's or a reflection's edge on a diffuse surface) does.  Only m_q
+ * enters the average: the patch decides, it is not averaged.  rgba_out, the synchronisation and what the call reads and leaves
+ * alone are pt_resolve_filtered's: the estimate's state only, never accum, never the feature planes.
+ * PT_ERR_INVALID for a NULL ctx or rgba_out, for radius > PT_FILTER_MAX_RADIUS, for patch > PT_FILTER_MAX_PATCH, for a kappa
+ * that is not finite or is below 0, in this order; PT_ERR_NOT_READY while the estimate is off.  A context with no pixels: PT_OK.
+ * fp32, ONE IEEE operation per statement, nothing fused, `/` and sqrtf correctly rounded, P = patch:
+ *     patch-wise test: (se, m, known), counted, v.c, k2 and the rows p may look at are pt_resolve_filtered's (§4.8d)
+ *     centre p = (x, y) not counted:
+ *         f = m                                   (0 where unknown, non-finite stays non-finite)
+ *         cnt = 0
+ *     centre p counted:
+ *         sum = {+0, +0, +0}
+ *         cnt = +0
+ *         for dy = -R .. R ascending, for dx = -R .. R ascending:
+ *             q = (x + dx, y + dy)
+ *             skip unless 0 <= q.x < width, q.y is a row p may look at, and q is counted
+ *             if (dx, dy) != (0, 0):
+ *                 T = +0
+ *                 U = +0
+ *                 for oy = -P .. P ascending, for ox = -P .. P ascending:
+ *                     a = (x + ox, y + oy), b = (q.x + ox, q.y + oy)
+ *                     skip unless 0 <= a.x < width, 0 <= b.x < width, a.y and b.y are rows p may look at, a and b are counted
+ *                     d.c = m_a.c - m_b.c
+ *                     d2.c = d.c * d.c
+ *                     t = (d2.r + d2.g) + d2.b
+ *                     s.c = v_a.c + v_b.c
+ *                     u = (s.r + s.g) + s.b
+ *                     T = T + t
+ *                     U = U + u
+ *                 rhs = k2 * U
+ *                 skip unless T <= rhs            (a NaN on either side skips)
+ *             sum.c = sum.c + m_q.c
+ *             cnt = cnt + 1.0f
+ *         f.c = sum.c / cnt
+ *     gamma != 0: f.c = sqrtf(f.c)                (every pixel)
+ *     out = {f.r, f.g, f.b, cnt}                  (.a = accepted taps of the patch-wise test, 0 for an uncounted centre)
+ * The term (ox, oy) = (0, 0) is always present for such a tap (a = p and b = q are counted rows p may look at), and +0 + t and
+ * +0 + u are exact: patch = 0 IS pt_resolve_filtered's test, the two calls give the same bits.  An uncounted a or b drops its
+ * term, never the tap.  The test is symmetric in p and q inside one chunk and in a context that is no band; at a chunk border
+ * "rows p may look at" is p's chunk, and p and q of one chunk still see the same terms.  Multi-GPU: the gathered frame of a band
+ * differs from the single-GPU frame within radius + patch rows of a chunk border (gather the raw states and filter in one
+ * full-height context, as with pt_resolve_filtered).  There is no standard error of the filtered frame. */
+#define PT_FILTER_MAX_PATCH 1
+#define PT_FILTER_PATCH_KAPPA_DEFAULT 1.5f
+int pt_resolve_filtered_patch(pt_ctx* ctx, float* rgba_out, uint32_t radius, uint32_t patch, float kappa, int gamma);
+
 /* ---- first-hit feature planes: albedo, normal, hit point and ids per pixel (build extension, opt-in: PT_OPT_FEATURES) ----
  * What a denoiser, a picker or a compositor wants beside the colour: for every local pixel the first surface ONE deterministic
  * ray through the pixel centre meets.  pt_render_features is one launch of the trace kernels' feature builds (a code object of

@@ -58,6 +58,7 @@ SIGNATURES = {
     "pt_adaptive_tiles": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                     C.POINTER(C.c_uint32)]),
     "pt_resolve_filtered": (C.c_int, [_ctx, _vp, C.c_uint32, C.c_float, C.c_int]),
+    "pt_resolve_filtered_patch": (C.c_int, [_ctx, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_int]),
     "pt_render_features": (C.c_int, [_ctx]),
     "pt_features_ptr": (C.c_int, [_ctx, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "pt_read_features": (C.c_int, [_ctx, C.c_int, _vp]),
@@ -108,11 +109,11 @@ SIGNATURES = {
 
 
 # entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay, the error
-# estimate, adaptive sampling, the filtered read-out, the first-hit feature planes
+# estimate, adaptive sampling, the filtered read-out, the first-hit feature planes, the patch-wise filtered read-out
 ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_set_debugging", "pt_state_debug_overlay",
                       "pt_error_ptr", "pt_resolve_error", "pt_error_tiles", "pt_error_stats", "pt_render_until",
                       "pt_render_adaptive", "pt_adaptive_tiles", "pt_resolve_filtered", "pt_render_features", "pt_features_ptr",
-                      "pt_read_features")
+                      "pt_read_features", "pt_resolve_filtered_patch")
 
 
 def _elf_dynamic_strings(path, tags):

@@ -36,6 +36,8 @@ PT_OPT_ERROR_ESTIMATE = 7  # the per-pixel error estimate (pt_error_ptr, pt_reso
 PT_TIME_STEP_DECORRELATED = 0.3618034  # include/ptrace.h
 PT_FILTER_MAX_RADIUS = 4        # pt_resolve_filtered: the largest radius
 PT_FILTER_KAPPA_DEFAULT = 2.0   # ... and the kappa its callers start from
+PT_FILTER_MAX_PATCH = 1               # pt_resolve_filtered_patch: the largest patch radius (3x3 neighbourhoods)
+PT_FILTER_PATCH_KAPPA_DEFAULT = 1.5   # ... and the kappa its callers start from
 NO_SELECTED_OBJECT_ID = 1000  # src/state.rs:12: State.selected_object while the crosshair is on nothing
 BUILD_PLAIN, BUILD_ROULETTE, BUILD_TWIN, BUILD_DEBUG_OVERLAY, BUILD_FEATURES = 0, 1, 2, 3, 4  # pt_last_trace_build
 PT_STREAM_LEGACY = 1  # include/ptrace.h: hipStreamLegacy, the default (NULL) stream by name

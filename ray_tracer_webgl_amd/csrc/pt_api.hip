@@ -1684,12 +1684,14 @@ PT_API int pt_resolve_error(pt_ctx* c, float* rgba_out) {
   return PT_OK;
 }
 
-// the variance-guided filtered read-out (include/ptrace.h): reads the estimate's state only
-PT_API int pt_resolve_filtered(pt_ctx* c, float* rgba_out, uint32_t radius, float kappa, int gamma) {
-  if (!c || !rgba_out) return fail(c, PT_ERR_INVALID, "pt_resolve_filtered: NULL argument");
-  if (radius > PT_FILTER_MAX_RADIUS) return fail(c, PT_ERR_INVALID, "pt_resolve_filtered: radius %u > PT_FILTER_MAX_RADIUS", radius);
-  if (!std::isfinite(kappa) || kappa < 0.0f) return fail(c, PT_ERR_INVALID, "pt_resolve_filtered: kappa must be finite and >= 0");
-  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_resolve_filtered: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+// the two filtered read-outs (include/ptrace.h): they read the estimate's state only.  `patch` NULL:
+// pt_resolve_filtered and its kernel, else pt_resolve_filtered_patch and the patch-wise one; the checks and their order are shared
+static int resolve_filtered(pt_ctx* c, const char* who, float* rgba_out, uint32_t radius, const uint32_t* patch, float kappa, int gamma) {
+  if (!c || !rgba_out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
+  if (radius > PT_FILTER_MAX_RADIUS) return fail(c, PT_ERR_INVALID, "%s: radius %u > PT_FILTER_MAX_RADIUS", who, radius);
+  if (patch && *patch > PT_FILTER_MAX_PATCH) return fail(c, PT_ERR_INVALID, "%s: patch %u > PT_FILTER_MAX_PATCH", who, *patch);
+  if (!std::isfinite(kappa) || kappa < 0.0f) return fail(c, PT_ERR_INVALID, "%s: kappa must be finite and >= 0", who);
+  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "%s: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", who);
   PT_HIP(c, hipSetDevice(c->device));
   uint32_t n_pix = (uint32_t)n_pixels(c);
   if (n_pix == 0) return PT_OK;
@@ -1697,11 +1699,26 @@ PT_API int pt_resolve_filtered(pt_ctx* c, float* rgba_out, uint32_t radius, floa
   float4* out = c->d_resolve.get();
   uint32_t width = c->width, rows = c->local_rows;
   uint32_t band_rows = c->params.band_count > 1 ? c->params.band_rows : 0u;  // (0: no band, every local row is a neighbour)
-  void* kargs[] = {&est, &out, &width, &rows, &band_rows, &radius, &kappa, &gamma};
-  PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FILTER), dim3((width + 31u) / 32u, (rows + 7u) / 8u), dim3(256), kargs, 0, c->stream));
+  const dim3 grid((width + 31u) / 32u, (rows + 7u) / 8u);
+  if (patch) {
+    uint32_t P = *patch;
+    void* kargs[] = {&est, &out, &width, &rows, &band_rows, &radius, &P, &kappa, &gamma};
+    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FILTER_PATCH), grid, dim3(256), kargs, 0, c->stream));
+  } else {
+    void* kargs[] = {&est, &out, &width, &rows, &band_rows, &radius, &kappa, &gamma};
+    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FILTER), grid, dim3(256), kargs, 0, c->stream));
+  }
   PT_HIP(c, hipMemcpyAsync(rgba_out, c->d_resolve.get(), (size_t)n_pix * sizeof(float4), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
+}
+
+PT_API int pt_resolve_filtered(pt_ctx* c, float* rgba_out, uint32_t radius, float kappa, int gamma) {
+  return resolve_filtered(c, "pt_resolve_filtered", rgba_out, radius, nullptr, kappa, gamma);
+}
+
+PT_API int pt_resolve_filtered_patch(pt_ctx* c, float* rgba_out, uint32_t radius, uint32_t patch, float kappa, int gamma) {
+  return resolve_filtered(c, "pt_resolve_filtered_patch", rgba_out, radius, &patch, kappa, gamma);
 }
 
 // the tile kernel over the current state: records into d_err_tiles[0, n), tallies into [n, 2 n); enqueued, not awaited

@@ -24,6 +24,7 @@ enum {
 };
 extern "C" const void* pt_feature_kernel(int id);
 // pt_kernels_error.hip (a code object of its own): the error estimate's fold, read-out and tile kernels (PT_OPT_ERROR_ESTIMATE), and
-// a partial round's fold and tile table (pt_render_adaptive), and the filtered read-out (pt_resolve_filtered)
-enum { PT_E_FOLD = 0, PT_E_RESOLVE, PT_E_TILES, PT_E_FOLD_TILES, PT_E_PARTITION, PT_E_FILTER, PT_E_COUNT };
+// a partial round's fold and tile table (pt_render_adaptive), and the filtered read-outs (pt_resolve_filtered,
+// pt_resolve_filtered_patch)
+enum { PT_E_FOLD = 0, PT_E_RESOLVE, PT_E_TILES, PT_E_FOLD_TILES, PT_E_PARTITION, PT_E_FILTER, PT_E_FILTER_PATCH, PT_E_COUNT };
 extern "C" const void* pt_error_kernel(int id);

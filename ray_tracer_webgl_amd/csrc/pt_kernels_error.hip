@@ -1,6 +1,6 @@
 // pt_kernels_error.hip — the PER-PIXEL ERROR ESTIMATE (pt_set_option PT_OPT_ERROR_ESTIMATE; include/ptrace.h, DESIGN.md
 // §error estimate), a translation unit and gfx950 code object of its own: the HIP runtime loads it when the estimate is
-// first turned on, so a context that never asks for it pays nothing.  Six kernels, none of them a trace kernel:
+// first turned on, so a context that never asks for it pays nothing.  Seven kernels, none of them a trace kernel:
 //   pt_fold_error_kernel     takes pt_accumulate_kernel's place: the same four fp32 adds per pass in the same order (accum
 //                            keeps its bits) and, beside them, Welford's update of the pass sums' mean and M2 per channel
 //   pt_resolve_error_kernel  the standard error of each pixel's mean as linear radiance
@@ -9,6 +9,8 @@
 //                            the active tiles first, and the fold over those tiles' pixels only
 //   pt_filter_kernel         the variance-guided filtered read-out (pt_resolve_filtered): each pixel's mean averaged with the
 //                            neighbours whose means differ by no more than the standard errors explain
+//   pt_filter_patch_kernel   the same read-out with the test summed over the patches around the two pixels
+//                            (pt_resolve_filtered_patch)
 // The arithmetic is a contract (tests/error_ref.py restates it statement by statement): ONE IEEE fp32 operation per
 // statement, nothing fused (-ffp-contract=off), `/` and sqrtf correctly rounded.  pt_api.hip reaches the kernels through
 // pt_error_kernel() only.
@@ -283,8 +285,112 @@ extern "C" __global__ __launch_bounds__(256) void pt_filter_kernel(const float4*
   out[(size_t)y * width + (size_t)x] = f;
 }
 
+// THE PATCH-WISE FILTERED READ-OUT (pt_resolve_filtered_patch; the statements: include/ptrace.h, DESIGN.md §4.8f,
+// tests/patch_filter_ref.py).  pt_filter_kernel's shape — a 256-thread workgroup per 32x8 tile, the seven planes staged once, one
+// barrier — with a halo of PT_FILTER_MAX_RADIUS + PT_FILTER_MAX_PATCH = 5 texels: b = q + (ox, oy) lies up to radius + patch
+// from the pixel.  42x18 texels, 21 168 B static.  Each pixel evaluates the (2P+1)^2 pair terms of a tap from the LDS (form (a)
+// of §4.8f); a term whose row a.y or b.y lies outside the pixel's chunk is rejected by the same two compares as a tap row,
+// a term outside the image by its staged counted flag.
+// Row stride 42, no padding: every LDS access is again a dword access, served in two groups of 32 lanes over 32 banks, and a
+// group is one 32-pixel row of the tile at ONE offset (dx + ox, dy + oy): 32 consecutive dwords, conflict-free at any stride,
+// 42 included.
+#define PATCH_HALO (PT_FILTER_MAX_RADIUS + PT_FILTER_MAX_PATCH)
+#define PATCH_SW (FILTER_TW + 2 * PATCH_HALO)
+#define PATCH_SH (FILTER_TH + 2 * PATCH_HALO)
+struct PatchTile {
+  float m[3][PATCH_SH * PATCH_SW], v[3][PATCH_SH * PATCH_SW];
+  uint32_t counted[PATCH_SH * PATCH_SW];
+};
+
+// one pixel's taps; all four loops run over launch-uniform bounds at run time (pt_filter_kernel's finding: unrolled, the
+// scheduler hoists the loads).  A pair term is thirteen LDS reads (the flags of a and b beside the twelve operands) and some
+// twenty VALU operations.
+__device__ __forceinline__ float4 filter_patch_taps(const PatchTile& s, int centre, int y, int first_row, int last_row, int R, int P,
+                                                    float k2) {
+  float sum[3] = {0.0f, 0.0f, 0.0f};
+  float cnt = 0.0f;
+  for (int dy = -R; dy <= R; dy++) {
+    if (y + dy < first_row || y + dy > last_row) continue;   // (uniform over a row of the tile: half a wave)
+    for (int dx = -R; dx <= R; dx++) {
+      const int q = centre + dy * PATCH_SW + dx;
+      float T = 0.0f, U = 0.0f;
+      for (int oy = -P; oy <= P; oy++) {
+        if (y + oy < first_row || y + oy > last_row || y + dy + oy < first_row || y + dy + oy > last_row) continue;
+        for (int ox = -P; ox <= P; ox++) {
+          const int a = centre + oy * PATCH_SW + ox, b = q + oy * PATCH_SW + ox;
+          const float d0 = s.m[0][a] - s.m[0][b], d1 = s.m[1][a] - s.m[1][b], d2 = s.m[2][a] - s.m[2][b];
+          const float e0 = d0 * d0, e1 = d1 * d1, e2 = d2 * d2;
+          const float t01 = e0 + e1;
+          const float t = t01 + e2;
+          const float s0 = s.v[0][a] + s.v[0][b], s1 = s.v[1][a] + s.v[1][b], s2 = s.v[2][a] + s.v[2][b];
+          const float u01 = s0 + s1;
+          const float u = u01 + s2;
+          const bool both = s.counted[a] != 0u && s.counted[b] != 0u;
+          const float Tt = T + t, Uu = U + u;
+          T = both ? Tt : T;
+          U = both ? Uu : U;
+        }
+      }
+      const float rhs = k2 * U;
+      const bool ok = s.counted[q] != 0u && ((dx == 0 && dy == 0) || T <= rhs);   // the centre is accepted untested
+      const float mq[3] = {s.m[0][q], s.m[1][q], s.m[2][q]};
+      const float a0 = sum[0] + mq[0], a1 = sum[1] + mq[1], a2 = sum[2] + mq[2];
+      const float c1 = cnt + 1.0f;
+      sum[0] = ok ? a0 : sum[0];
+      sum[1] = ok ? a1 : sum[1];
+      sum[2] = ok ? a2 : sum[2];
+      cnt = ok ? c1 : cnt;
+    }
+  }
+  return make_float4(sum[0] / cnt, sum[1] / cnt, sum[2] / cnt, cnt);
+}
+
+// grid and band_rows as pt_filter_kernel's; radius <= PT_FILTER_MAX_RADIUS and patch <= PT_FILTER_MAX_PATCH (the host checks
+// both: the halo is sized by them)
+extern "C" __global__ __launch_bounds__(256) void pt_filter_patch_kernel(const float4* est, float4* out, uint32_t width, uint32_t rows,
+                                                                         uint32_t band_rows, uint32_t radius, uint32_t patch, float kappa,
+                                                                         int gamma) {
+  __shared__ PatchTile s;
+  const int x0 = (int)(blockIdx.x * FILTER_TW), y0 = (int)(blockIdx.y * FILTER_TH);
+  for (int i = (int)threadIdx.x; i < PATCH_SH * PATCH_SW; i += 256) {
+    const int gx = x0 + i % PATCH_SW - PATCH_HALO, gy = y0 + i / PATCH_SW - PATCH_HALO;
+    const bool inside = gx >= 0 && gx < (int)width && gy >= 0 && gy < (int)rows;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+    if (inside) {
+      const size_t j = (size_t)gy * width + (size_t)gx;
+      a = est[2 * j];
+      b = est[2 * j + 1];
+    }
+    const PixelError r = pixel_error(a, b);
+    s.counted[i] = (inside && r.known && finite3(r.se) && finite3(r.m)) ? 1u : 0u;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      s.m[c][i] = r.m[c];
+      s.v[c][i] = r.se[c] * r.se[c];
+    }
+  }
+  __syncthreads();
+  const int tx = (int)(threadIdx.x % FILTER_TW), ty = (int)(threadIdx.x / FILTER_TW);
+  const int x = x0 + tx, y = y0 + ty;
+  if (x >= (int)width || y >= (int)rows) return;
+  const int centre = (ty + PATCH_HALO) * PATCH_SW + tx + PATCH_HALO;
+  float4 f = make_float4(s.m[0][centre], s.m[1][centre], s.m[2][centre], 0.0f);   // an uncounted centre passes through
+  if (s.counted[centre] != 0u) {
+    const pterr::ChunkRows ch = pterr::chunk_rows((uint32_t)y, band_rows, rows);
+    const float k2 = kappa * kappa;
+    f = filter_patch_taps(s, centre, y, (int)ch.first, (int)ch.last, (int)radius, (int)patch, k2);
+  }
+  if (gamma != 0) {
+    f.x = __builtin_sqrtf(f.x);
+    f.y = __builtin_sqrtf(f.y);
+    f.z = __builtin_sqrtf(f.z);
+  }
+  out[(size_t)y * width + (size_t)x] = f;
+}
+
 extern "C" const void* pt_error_kernel(int id) {
   switch (id) {
+    case PT_E_FILTER_PATCH: return reinterpret_cast<const void*>(pt_filter_patch_kernel);
     case PT_E_FILTER: return reinterpret_cast<const void*>(pt_filter_kernel);
     case PT_E_FOLD: return reinterpret_cast<const void*>(pt_fold_error_kernel);
     case PT_E_RESOLVE: return reinterpret_cast<const void*>(pt_resolve_error_kernel);

@@ -6,6 +6,7 @@ src/dom.rs:126-143, without a browser).
     python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.02 --max-spp 4096 --error-out cover_error.png
     python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.02 --adaptive --samples-out cover_samples.png
     python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.05 --denoise --out cover_filtered.png
+    python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.05 --denoise-patch --out cover_patch_filtered.png
 """
 import argparse
 import math
@@ -49,6 +50,10 @@ def main(argv=None):
                          "(pt_resolve_filtered: a pixel is averaged with the neighbours within R whose means differ by no more than "
                          "KAPPA standard errors; default 2,%g; R at most %d); prints the mean accepted taps"
                          % (abi.PT_FILTER_KAPPA_DEFAULT, abi.PT_FILTER_MAX_RADIUS))
+    ap.add_argument("--denoise-patch", nargs="?", const="2", metavar="R[,KAPPA]",
+                    help="like --denoise, with the patch-wise test (pt_resolve_filtered_patch: a neighbour is averaged in when the "
+                         "3x3 neighbourhoods around the two pixels differ by no more than KAPPA standard errors; default 2,%g); "
+                         "not together with --denoise" % abi.PT_FILTER_PATCH_KAPPA_DEFAULT)
     ap.add_argument("--features", metavar="PREFIX",
                     help="also write the first-hit feature planes of the frame's camera (pt_render_features: one pinhole ray per "
                          "pixel) as PREFIX_albedo.npy, PREFIX_normal.npy, PREFIX_point.npy (float32) and PREFIX_ids.npy (int32: list "
@@ -94,6 +99,16 @@ def main(argv=None):
             denoise = parse_denoise(args.denoise)
         except ValueError as e:
             ap.error("--denoise: %s" % e)
+    denoise_patch = None
+    if args.denoise_patch is not None:
+        if denoise is not None:
+            ap.error("--denoise-patch takes --denoise's place: give one of them")
+        if args.noise_target is None and not args.error_out:
+            ap.error("--denoise-patch filters by the error estimate: only with --noise-target or --error-out")
+        try:
+            denoise_patch = parse_denoise(args.denoise_patch, abi.PT_FILTER_PATCH_KAPPA_DEFAULT)
+        except ValueError as e:
+            ap.error("--denoise-patch: %s" % e)
     if args.noise_target is not None or args.error_out:
         if overlay is not None:
             ap.error("--noise-target / --error-out measure the frame's noise: not with --debug-overlay")
@@ -107,6 +122,11 @@ def main(argv=None):
         frame = pt.filtered_image(denoise[0], denoise[1], gamma=True)
         print("denoise: radius %d, kappa %g, %.2f accepted taps per pixel" % (denoise[0], denoise[1], float(frame[..., 3].mean())))
         frame[..., 3] = 1.0   # (the taps are no alpha)
+    elif denoise_patch is not None:
+        frame = pt.patch_filtered_image(denoise_patch[0], abi.PT_FILTER_MAX_PATCH, denoise_patch[1], gamma=True)
+        print("denoise: radius %d, patch %d, kappa %g, %.2f accepted taps per pixel" % (
+            denoise_patch[0], abi.PT_FILTER_MAX_PATCH, denoise_patch[1], float(frame[..., 3].mean())))
+        frame[..., 3] = 1.0
     else:
         frame = pt.resolve(gamma=True)
     image_io.write_png(args.out, frame)
@@ -136,13 +156,13 @@ def main(argv=None):
     pt.close()
 
 
-def parse_denoise(text):
-    """--denoise's value "R" or "R,KAPPA" -> (radius, kappa); ValueError says what is wrong with it."""
+def parse_denoise(text, kappa_default=abi.PT_FILTER_KAPPA_DEFAULT):
+    """--denoise's (or --denoise-patch's) value "R" or "R,KAPPA" -> (radius, kappa); ValueError says what is wrong with it."""
     parts = text.split(",")
     if len(parts) > 2:
         raise ValueError("R or R,KAPPA, not %r" % text)
     radius = int(parts[0])
-    kappa = float(parts[1]) if len(parts) == 2 else abi.PT_FILTER_KAPPA_DEFAULT
+    kappa = float(parts[1]) if len(parts) == 2 else kappa_default
     if not 0 <= radius <= abi.PT_FILTER_MAX_RADIUS:
         raise ValueError("the radius is 0 to %d" % abi.PT_FILTER_MAX_RADIUS)
     if not math.isfinite(kappa) or kappa < 0.0:

@@ -322,6 +322,17 @@ class PathTracer:
             self._check(self.lib.pt_resolve_filtered(self._ctx, out.ctypes.data_as(C.c_void_p), int(radius), float(kappa), 1 if gamma else 0))
         return out
 
+    def patch_filtered_image(self, radius=2, patch=abi.PT_FILTER_MAX_PATCH, kappa=abi.PT_FILTER_PATCH_KAPPA_DEFAULT, gamma=True):
+        """filtered_image with the patch-wise test (include/ptrace.h pt_resolve_filtered_patch): a neighbour is averaged in when
+        the (2 patch + 1)^2 neighbourhoods around the two pixels differ by no more than `kappa` standard errors, squared
+        differences and variances summed over the patch; patch at most abi.PT_FILTER_MAX_PATCH, patch 0 gives filtered_image's
+        bits.  a = the accepted taps.  Reads the estimate's state only; a band context filters inside its own row chunks."""
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
+        if out.size:
+            self._check(self.lib.pt_resolve_filtered_patch(self._ctx, out.ctypes.data_as(C.c_void_p), int(radius), int(patch),
+                                                           float(kappa), 1 if gamma else 0))
+        return out
+
     def error_tiles(self):
         """(tiles_y, tiles_x, 4) fp32 per 8x8 tile of the local rows: {sum se^2, sum mean^2, counted pixels, min passes}."""
         tx, ty = C.c_uint32(), C.c_uint32()

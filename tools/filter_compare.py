@@ -1,13 +1,17 @@
 """Dev tool: what pt_resolve_filtered is worth on the bench configs, at the bench sizes (profiles/r13_filter.txt).
 
-    python tools/filter_compare.py [config2 config4 config5 default]
+    python tools/filter_compare.py [--patch] [config2 config4 config5 default]
 
 Per config: (1) a context renders the config's whole spp in 16-spp decorrelated passes at a clock of its own: THE CONVERGED
 FRAME, linear radiance.  (2) A fresh context renders a quarter of that spp at the config's clock with the error estimate on
 and reads out the estimate's own mean (radius 0) and the filtered frame at radius 1 to 4, kappa PT_FILTER_KAPPA_DEFAULT, all
 linear.  Printed: the mean squared error of each against the converged frame over the pixels both hold finite, the ratio to
 the unfiltered one, the mean accepted taps, the wall time of the read-out call (kernel, 16 B per pixel to the host, the
-synchronise).  Both frames come from this process; the converged frame's own noise is in every figure alike."""
+synchronise).  Both frames come from this process; the converged frame's own noise is in every figure alike.
+
+--patch adds, under each radius from 1 on, the patch-wise read-out (pt_resolve_filtered_patch, profiles/r17_filter_patch.txt) of
+the same state: patch 0 at kappa PT_FILTER_KAPPA_DEFAULT, which must give the line above bit for bit, and patch 1 at kappa
+PT_FILTER_PATCH_KAPPA_DEFAULT.  Without the option the output is what it was."""
 import os
 import sys
 import time
@@ -46,8 +50,21 @@ def rendered(sc, p, passes):
     return pt, es
 
 
+def measured(read_out, converged):
+    """(mse over the pixels both frames hold finite, those pixels, the frame, wall ms of the second call) of a read-out."""
+    read_out()   # (warm: the first call loads nothing new, but pays the first pinned copy)
+    t0 = time.perf_counter()
+    out = read_out()
+    wall = (time.perf_counter() - t0) * 1e3
+    d = out[..., :3].astype(np.float64) - converged
+    ok = np.isfinite(d).all(axis=-1)
+    return float((d[ok] ** 2).sum() / (3 * max(int(ok.sum()), 1))), ok, out, wall
+
+
 def main():
-    names = sys.argv[1:] or list(CONFIGS)
+    args = sys.argv[1:]
+    with_patch = "--patch" in args
+    names = [a for a in args if a != "--patch"] or list(CONFIGS)
     for name in names:
         make, whole = CONFIGS[name]
         sc = make()
@@ -75,6 +92,13 @@ def main():
             print("  radius %d kappa %g: mse %.6g  filtered / unfiltered %.3f  mean taps %.2f  pixels compared %d of %d  call %.3f ms%s" % (
                 radius, abi.PT_FILTER_KAPPA_DEFAULT, mse, mse / base if base > 0 else float("nan"), float(out[..., 3].mean()),
                 int(ok.sum()), ok.size, wall, "  (rel_error %.5f)" % es.rel_error if radius == 0 else ""), flush=True)
+            if with_patch and radius > 0:
+                for patch, kappa in ((0, abi.PT_FILTER_KAPPA_DEFAULT), (1, abi.PT_FILTER_PATCH_KAPPA_DEFAULT)):
+                    pmse, pok, pout, pwall = measured(lambda: pt.patch_filtered_image(radius, patch, kappa, gamma=False), converged)
+                    same = "" if patch else ("  same bits as the line above" if pout.tobytes() == out.tobytes() else "  BITS DIFFER from the line above")
+                    print("  radius %d patch %d kappa %g: mse %.6g  filtered / unfiltered %.3f  mean taps %.2f  pixels compared %d of %d  call %.3f ms%s" % (
+                        radius, patch, kappa, pmse, pmse / base if base > 0 else float("nan"), float(pout[..., 3].mean()),
+                        int(pok.sum()), pok.size, pwall, same), flush=True)
         pt.close()
 
 
