@@ -88,7 +88,10 @@ enum {
                              run (scenes of long walks).  Scheduling only — images do not depend on it.
                              0 = lockstep.  Default 12. */
   PT_OPT_REFILL_MIN = 4,  /* lanes of a busy wave that wait for a new work item before the (wave-wide) item
-                             decode runs for them.  Scheduling only.  1 = refill at once.  Default 4. */
+                             decode runs for them.  Scheduling only.  1 = refill at once.  Default 4.
+                             Builds with the look-ahead refill (every lane holds one decoded next item and
+                             takes it the moment its item ends: csrc/pt_deal.hpp) do not consult it: no lane
+                             waits.  The option is still accepted, stored and read back. */
   PT_OPT_RUSSIAN_ROULETTE = 5, /* value k > 0: after k bounces a path survives each further bounce with
                              probability q = min(max(throughput), 1) and carries throughput / q (unbiased:
                              every pixel's EXPECTATION is the reference's, depth-exhaustion term included).

@@ -10,6 +10,15 @@ import os
 import sys
 from collections import defaultdict
 
+def full_size_floor(durations):
+    """The shortest duration that still counts as a FULL-SIZE dispatch of a kernel: 85 % of the MEDIAN of its long dispatches
+    (those of at least half the longest).  (Until round 18: 85 % of the longest — one slow first launch then decided which of
+    the timed launches counted, and when the kernel got 8 % faster only the slowest 13 of 44 were left.)"""
+    longest = max(durations)
+    long_ones = sorted(x for x in durations if x >= 0.5 * longest)
+    return 0.85 * long_ones[len(long_ones) // 2]
+
+
 if sys.argv[1] == "--merge":
     dst = os.path.join(os.path.dirname(os.path.abspath(__file__)), "pmc_traffic.json")
     doc = json.load(open(dst)) if os.path.exists(dst) else {}
@@ -56,7 +65,7 @@ for f in glob.glob(os.path.join(d, "kt", "**", "*_kernel_trace.csv"), recursive=
         by[r["Kernel_Name"]].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
     print("== full-size dispatches per trace kernel (%s)" % os.path.relpath(f, d))
     for k, v in sorted(by.items()):
-        full = [x for x in v if x >= 0.85 * max(v)]
+        full = [x for x in v if x >= full_size_floor(v)]
         print("  %-32s %d of %d dispatches full-size: avg %.3f ms  min %.3f  max %.3f" % (k, len(full), len(v), sum(full) / len(full), min(full), max(full)))
         out.setdefault("kernel_full", {})[k] = {"calls": len(full), "avg_ms": sum(full) / len(full)}
 # the other configs: every trace-kernel dispatch in order (pt_tune's trials of each usable path, then
@@ -77,19 +86,22 @@ for f in glob.glob(os.path.join(d, "kt_configs.log")):
             print("  " + line.rstrip())
 # PMC passes: per kernel, only the FULL-SIZE dispatches count (bench.py's autotune and first-frame legs
 # launch the same kernels on 8 passes; the timed launches are the long ones): a dispatch is kept when its
-# duration is within 15 % of that kernel's longest in the same pass
+# duration is at least full_size_floor() of that kernel's dispatches in the same pass
 ctr = defaultdict(lambda: defaultdict(list))
 seen_in = defaultdict(set)  # a counter collected in two passes (two pmc directories) counts ONCE, not twice
 for f in sorted(glob.glob(os.path.join(d, "pmc*", "**", "*_counter_collection.csv"), recursive=True)):
     rows = [r for r in csv.DictReader(open(f))]
     pass_dir = os.path.relpath(f, d).split(os.sep)[0]
-    longest = defaultdict(float)
+    durations = defaultdict(list)
+    for row in rows:
+        durations[(row["Kernel_Name"], row["Dispatch_Id"])] = [float(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))]
+    per_kernel = defaultdict(list)
+    for (kname, _), dur in durations.items():
+        per_kernel[kname] += dur
+    floor = {kname: full_size_floor(v) for kname, v in per_kernel.items()}
     for row in rows:
         dur = float(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
-        longest[row["Kernel_Name"]] = max(longest[row["Kernel_Name"]], dur)
-    for row in rows:
-        dur = float(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
-        if dur >= 0.85 * longest[row["Kernel_Name"]]:
+        if dur >= floor[row["Kernel_Name"]]:
             key = (row["Kernel_Name"], row["Counter_Name"])
             if seen_in[key] and pass_dir not in seen_in[key]:
                 continue  # (a counter collected in two passes: the first pass that holds it counts)

@@ -1195,7 +1195,7 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   const LaunchPlan P = plan_launch({A.n_items, feat ? 1 : c->params.samples_per_pixel, n_passes, block, per_cu, (uint32_t)c->num_cus, walk,
                                     c->list.n, knobs});
   A.queue_chunk = P.queue_chunk; A.queue_static = (uint32_t)P.deal; A.queue_groups = P.queue_groups;
-  A.n_waves = P.n_waves; A.coop_max_live = P.coop_max_live;
+  A.n_waves = P.n_waves; A.coop_max_live = P.coop_max_live; A.refill_ahead = P.refill_ahead;
   A.cost_feedback = use.feedback == LaunchUse::PLANNED ? P.cost_feedback : (use.feedback == LaunchUse::ON ? 1u : 0u);
   if (feat) A.cost_feedback = 0u;
   L->kfn = kfn; L->grid = P.grid; L->block = block; L->lds = lds; L->path = path; L->trial = choice.trial;

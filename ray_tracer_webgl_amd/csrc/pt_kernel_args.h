@@ -74,7 +74,7 @@ struct PtKernelArgs {
   float grid_lo_n[3], grid_hi_n[3];  // [lo, hi] widened by 1e-6 d_near: the entry slab test of those rays
   uint32_t lds_scene_bytes;        // dynamic LDS taken by the staged scene; the parked path state follows
   unsigned long long* wave_log;    // COUNT twins only (NULL otherwise): per wave PT_WAVE_LOG_WORDS x u64 {start, queue dry, end in 100 MHz ticks; HW_ID | XCC_ID << 32}
-  uint32_t refill_min;             // lanes that must be waiting for an item before a busy wave runs the refill code
+  uint32_t refill_min;             // PT_OPT_REFILL_MIN, stored and reported; the look-ahead refill (pt_refill.hpp) does not consult it
   uint32_t carry_lanes;            // the walk moves on when fewer lanes than this (and less than half) still walk
   float bvh_kinv;                  // boxes are stored in the frame (x - c0) / kinv
   uint32_t block_threads;          // blockDim.x of the launch
@@ -104,6 +104,8 @@ struct PtKernelArgs {
   const int32_t* slot_uuid;        // n_slots: the slot's sphere's uuid (walk kernels, like slot_mat)
   float dbg_cursor[3];             // u_cursor_point, static/shader.frag:102
   int32_t dbg_selected;            // u_selected_object, :101
+  uint32_t refill_ahead;           // 1: empty next slots are filled ahead of the lanes' need; 0: the decode serves only lanes without an item
+                                   // (pt_launch_plan.hpp refill_ahead; pt_deal.hpp wants_item).  Last, like the fields above.
 };
 
 // ---- waves per SIMD each trace kernel is BUILT FOR -------------------------------------------------------------
@@ -134,11 +136,12 @@ struct PtKernelArgs {
 enum { PT_WAVE_LOG_WORDS = 4 };
 enum { PT_COH_BINS = 66, PT_HIST_WAVE_STRIDE = 8 };  // cell_hist: bins 0..64 = distinct entry runs in a sampled leaf round, bin 65 = sampled rounds' lanes  // u64 per wave in PtKernelArgs.wave_log
 // regions of a wave step the measuring twins count (Tally::flag / collect): [PT_CTR_REGIONS + 2 k] wave steps in which any lane
-// ran region k, [+ 2 k + 1] lanes that did
+// ran region k, [+ 2 k + 1] lanes that did (regions 16 and up: [PT_CTR_REGIONS_MORE + 2 (k - 16)], room for one)
 enum { PT_REG_REFILL_DECODE = 0, PT_REG_REFILL_RESERVE, PT_REG_CAMERA_RAY, PT_REG_SHADE_HIT_RECORD, PT_REG_SHADE_SKY, PT_REG_SHADE_DIFFUSE,
        PT_REG_SHADE_METAL, PT_REG_SHADE_GLASS, PT_REG_SHADE_GLASS_REFRACT, PT_REG_SHADE_CONTINUES, PT_REG_SHADE_FINISHED, PT_REG_SHADE_ITEM_STORE,
-       PT_REG_WALK_ENTRY, PT_REG_WALK_ENTER_CELL, PT_REG_WALK_FAR_RAY, PT_REG_SHADE_ANY, PT_N_REGIONS };
-enum { PT_CTR_HEAD = 0, PT_CTR_SEGMENTS = 1, PT_CTR_SAMPLES = 2, PT_CTR_FAR_RAYS = 3 /* grid walk: segments handed to the whole list because they reached the grid from outside its near region */, PT_CTR_SCRATCH = 7 /* host-side save / restore of a counter around a probe launch */, PT_CTR_WORK = 8, PT_CTR_LITERAL = 16, PT_CTR_PHASES = 24, PT_N_PHASES = 8, PT_CTR_REGIONS = 32, PT_CTR_TIMEBINS = 64, PT_CTR_COUNT = 128,
+       PT_REG_WALK_ENTRY, PT_REG_WALK_ENTER_CELL, PT_REG_WALK_FAR_RAY, PT_REG_SHADE_ANY,
+       PT_REG_REFILL_PROMOTE /* a lane takes its decoded next item (pt_refill.hpp promote) */, PT_N_REGIONS };
+enum { PT_CTR_HEAD = 0, PT_CTR_SEGMENTS = 1, PT_CTR_SAMPLES = 2, PT_CTR_FAR_RAYS = 3 /* grid walk: segments handed to the whole list because they reached the grid from outside its near region */, PT_CTR_REGIONS_MORE = 4 /* [4..5]: region 16 of the COUNT twins */, PT_CTR_SCRATCH = 7 /* host-side save / restore of a counter around a probe launch */, PT_CTR_WORK = 8, PT_CTR_LITERAL = 16, PT_CTR_PHASES = 24, PT_N_PHASES = 8, PT_CTR_REGIONS = 32, PT_CTR_TIMEBINS = 64, PT_CTR_COUNT = 128,
        PT_QUEUE_GROUPS_MAX = 256, PT_CTR_GROUP_HEADS = 128 /* then PT_QUEUE_GROUPS_MAX heads, 8 u64 (one 64-byte line) apart */,
        PT_CTR_ALLOC = PT_CTR_GROUP_HEADS + 8 * PT_QUEUE_GROUPS_MAX };  // [64..127]: COUNT twins, segments shaded per 0.655 ms bin of s_memrealtime
 

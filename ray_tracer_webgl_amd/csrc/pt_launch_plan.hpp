@@ -46,13 +46,32 @@ struct LaunchPlan {
   uint32_t n_waves = 0;
   uint32_t cost_feedback = 0;
   uint32_t coop_max_live = 0;
+  uint32_t refill_ahead = 1;  // the look-ahead refill fills empty next slots ahead of need (pt_deal.hpp); 0: lanes are served directly
 };
 
 // 256-thread workgroups while several fit per CU; one 1024-thread workgroup per CU when the list takes most of the
 // 160 KiB LDS (the list kernels; `lds` = the list's LDS copy)
 inline uint32_t list_block_threads(uint64_t lds) { return lds > 40 * 1024 ? 1024u : 256u; }
 
+// WHEN the refill fills ahead (round 18).  A held next item saves decodes in proportion to how often items end (1 / spp) and
+// costs drain in proportion to one item's share of a lane's work (1 / items per lane): a lane that still holds an item when the
+// queue runs dry ends up to an item later than its neighbours.  Measured, look-ahead against the parent's refill on one device
+// (profiles/r18_ab_runs.txt): 16-spp items at 337 / 28 items per lane -5.2 % / -2.7 %, 25-spp items at 31 per lane -4.7 %,
+// 1-spp frames 0; but 64-spp items at 21 (config 5) and 18 (config 4) items per lane +3.0 % and +1.6 %, the wave log showing
+// the last wave 2 % later.  So items of 32 samples or more are filled ahead only where a lane gets at least spp / 2 of them.
+inline uint32_t refill_ahead(uint64_t items, int spp, uint32_t n_waves) {
+  const unsigned long long lanes = (unsigned long long)n_waves * 64ull;
+  return (spp < 32 || 2ull * items >= (unsigned long long)spp * lanes) ? 1u : 0u;
+}
+
+inline LaunchPlan plan_queue(const LaunchPlanIn& in);
 inline LaunchPlan plan_launch(const LaunchPlanIn& in) {
+  LaunchPlan P = plan_queue(in);
+  P.refill_ahead = refill_ahead(in.items, in.spp, P.n_waves);
+  return P;
+}
+
+inline LaunchPlan plan_queue(const LaunchPlanIn& in) {
   const LaunchKnobs& k = in.knobs;
   const uint64_t items = in.items;
   const uint32_t block = in.block;

@@ -97,43 +97,40 @@ __device__ __forceinline__ void start_sample(Path& p, const PixelDiv& pd) {
   p.seed = seed; p.o = o; p.d = d; p.a = a; p.col = col; p.depth = depth;
 }
 
-// ---- refill: lanes without a ray pull work items -------------------------------------------------
+// ---- refill: the wave pulls work items for the lanes that will need one ----------------------------
 // The wave reserves A.queue_chunk consecutive items from the global queue with ONE atomic
 // (a memory-side atomic moves 64 B, so per-item atomics would dominate the kernel's HBM
-// traffic) and deals them to its lanes from a wave-uniform local pool.
-// Lanes that finish an item wait until a few of them can be refilled together: the item decode
-// below costs ~115 VALU instructions for the whole wave whether one lane needs it or sixty,
-// and with 16-spp items about one lane per wave step does.  A wave that is mostly idle (the
-// drain of the launch, or its start) refills at once.
-// Every wave reaches the "queue dry" exit: the head counter is monotone.
+// traffic) and deals them to its lanes from a wave-uniform local pool (the arithmetic: pt_deal.hpp).
+// LOOK-AHEAD: the item decode below costs ~115 VALU instructions for the whole wave whether one lane
+// needs it or sixty, and with 16-spp items about one lane per wave step runs out.  So the decode does
+// not serve the lane that ran out: every lane keeps one decoded NEXT item (Path::nx_*), a lane whose
+// item ends takes it at once (promote() below), and the decode runs only when some lane has neither a
+// current nor a next item — then for every lane whose next slot is empty, most of the wave.  Which lane
+// runs an item and when is free (exactness argument (i)), so is when it is decoded: the decode reads
+// launch constants only (frame_ctr included: the frame-advance kernel of a replayed series runs between
+// trace launches, never beside one).
+// Every wave reaches the "queue dry" exit: the head counter is monotone, every trip of the loop deals
+// an item or finds the queue dry; a wave leaves when every lane is dead after promote(), i.e. every
+// slot is empty too, which the loop below lets happen only on a dry queue.
 template <bool COUNT>
 __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q, const PixelDiv& pd, Tally<COUNT>& tally) {
   karg_t& K = *kargs();
   // (local copies, written back at the end: see pt_grid_walk.hpp)
-  bool alive = p.alive, new_path = p.new_path;
+  const bool alive = p.alive;
   bool dry = q.dry; // wave-uniform: a reservation came back empty, so no lane of this wave will get another item
-  uint32_t slab_index = p.slab_index, item_tile = p.item_tile, item_segs = p.item_segs;
-  int sample = p.sample; float seed = p.seed, st_s = p.st_s, st_t = p.st_t; V3 sum = p.sum;
-  uint32_t pool_next = q.pool_next, pool_end = q.pool_end, refill_waited = q.refill_waited;
+  uint32_t nx_slab = p.nx_slab, nx_tile = p.nx_tile;
+  float nx_seed = p.nx_seed, nx_s = p.nx_s, nx_t = p.nx_t;
+  uint32_t pool_next = q.pool_next, pool_end = q.pool_end;
   uint32_t pool_tp0 = q.pool_tp0, pool_split = q.pool_split, pool_tile0 = q.pool_tile0, pool_tile1 = q.pool_tile1;
   uint32_t q_round = q.round;
   const bool wh_ok = pd.wh_ok;
   const float y_fw = pd.y_fw, y_fh = pd.y_fh;
-  // (`waited` is reset after the loop, not inside it: a loop-carried value that becomes invariant after
-  // the first trip makes the compiler peel that trip off, i.e. emit the whole item decode twice)
-  bool dealt = false, put_off = false;
   for (;;) {
-    bool need = !alive && !dry;
-    unsigned long long mask = pt_ballot(need);
-    if (mask == 0ull) break;
-    // ... but not for long: with long items the next lane may be hundreds of steps away
-    if ((uint32_t)__popcll(mask) < K.refill_min && (uint32_t)__popcll(pt_ballot(alive)) >= 32u &&
-        (dealt ? 0u : refill_waited) < 8u) {
-      put_off = true;
-      break;
-    }
-    dealt = true;
-    if (pool_next == pool_end) { // wave-uniform
+    const bool slot_empty = nx_slab == ptdeal::kSlotEmpty;
+    if (pt_ballot(ptdeal::starving(alive, slot_empty, dry)) == 0ull) break;
+    bool need = ptdeal::wants_item(alive, slot_empty, dry, K.refill_ahead != 0u);
+    const unsigned long long mask = pt_ballot(need);
+    if (ptdeal::pool_used_up(pool_next, pool_end)) { // wave-uniform
       tally.flag(PT_REG_REFILL_RESERVE);
       unsigned long long base = 0;
       if (K.queue_static == 2u) {
@@ -143,15 +140,15 @@ __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q,
         // every ~13 ns: too slow for items of a few segments; no atomics at all — static dealing — leaves every wave
         // alone with the cost of the ~31 tiles it happens to get)
         const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        const uint32_t group = wave & (K.queue_groups - 1u);
+        const uint32_t group = ptdeal::group_of(wave, K.queue_groups);
         unsigned long long r = 0;
         if (lane_id() == 0u) r = atomicAdd(&A.counters[PT_CTR_GROUP_HEADS + 8u * group], 1ull);
         const uint32_t r_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)r);
-        base = ((unsigned long long)r_lo * K.queue_groups + group) * (unsigned long long)A.queue_chunk;
+        base = ptdeal::grouped_base(r_lo, K.queue_groups, group, A.queue_chunk);
       } else if (K.queue_static != 0u) {
         // reservations dealt round-robin, no atomics (a wave's number is the same in all its lanes)
         const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        base = ((unsigned long long)q_round * K.n_waves + wave) * (unsigned long long)A.queue_chunk;
+        base = ptdeal::static_base(q_round, K.n_waves, wave, A.queue_chunk);
         q_round++;
       } else {
         if (lane_id() == 0u) base = atomicAdd(&A.counters[PT_CTR_HEAD], (unsigned long long)A.queue_chunk);
@@ -160,14 +157,13 @@ __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q,
       // from it then lives in SGPRs instead of occupying VGPRs for the kernel's lifetime
       base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
              (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-      if (base >= (unsigned long long)A.n_items) { // queue dry: these lanes are done
+      if (ptdeal::reservation_dry(base, A.n_items)) { // queue dry: no lane of this wave gets another item
         tally.queue_dry();
         dry = true;
         need = false;  // nothing to deal in this trip; the loop ends at its next test
       } else {
         pool_next = (uint32_t)base;
-        unsigned long long end = base + A.queue_chunk;
-        pool_end = end < (unsigned long long)A.n_items ? (uint32_t)end : A.n_items;
+        pool_end = ptdeal::reservation_end(base, A.queue_chunk, A.n_items);
         // a reservation no longer than one tile's items touches at most two tiles: look their numbers
         // up once, here, instead of one dependent global load per lane in every refill
         pool_tp0 = div_by(pool_next, K.div_per_tile.m, K.div_per_tile.s1, K.div_per_tile.s2);
@@ -178,13 +174,12 @@ __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q,
       }
     }
     const uint32_t avail = pool_end - pool_next;
-    const uint32_t cnt = (uint32_t)__popcll(mask);
-    const uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane_id()) - 1ull));
+    const uint32_t rank = ptdeal::rank_of(mask, lane_id());
     const uint32_t pool_base = pool_next;
-    pool_next += cnt < avail ? cnt : avail;
-    if (need && rank < avail) {
+    pool_next += ptdeal::taken(mask, avail);
+    if (ptdeal::gets_item(need, rank, avail)) {
       tally.flag(PT_REG_REFILL_DECODE);
-      uint32_t item = pool_base + rank;
+      uint32_t item = ptdeal::item_of(pool_base, rank);
       uint32_t per_tile = 64u * K.n_passes;
       uint32_t tile_pos, tile; // heaviest tiles are dealt first (tile_order)
       if (K.queue_chunk <= per_tile) { // wave-uniform
@@ -215,33 +210,41 @@ __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q,
         const uint32_t frame_k = *(const uint32_t __attribute__((address_space(4)))*)K.frame_ctr;
         float u_time = K.time0 + (float)(K.first_pass + pass + frame_k) * K.time_step;
         // init_global_seed, static/shader.frag:354-357
-        seed = (float)base_hash(f2u(vx), f2u(vy)) * (1.0f / 4294967296.0f) + u_time;
-        st_s = (vx + 1.0f) * 0.5f; // :410
-        st_t = (vy + 1.0f) * 0.5f;
-        slab_index = (pass * K.local_rows + ly) * K.width + px;
+        nx_seed = (float)base_hash(f2u(vx), f2u(vy)) * (1.0f / 4294967296.0f) + u_time;
+        nx_s = (vx + 1.0f) * 0.5f; // :410
+        nx_t = (vy + 1.0f) * 0.5f;
+        nx_slab = (pass * K.local_rows + ly) * K.width + px;
         // only the launch's first pass reports its cost (atomicMax per pixel: the tile's
         // heaviest item): plenty for ordering tiles, and a memory-side atomic moves 64 B.  Launches of
         // one short pass (the reference's 1-spp frame) report nothing: there EVERY item would, the 64
         // lanes of a tile on one address, and — loads, stores and atomics complete in order — the next
         // material load of each wave would wait for them (measured on the 1280x702 1-spp frame:
         // 85 % of the wave time in s_waitcnt).
-        item_tile = (pass == 0u && K.cost_feedback != 0u) ? tile : 0xffffffffu;
-        item_segs = 0;
-        sum = mk(0.f, 0.f, 0.f);
-        sample = 0;
-        new_path = true;
-        alive = true;
+        nx_tile = (pass == 0u && K.cost_feedback != 0u) ? tile : 0xffffffffu;
       }
-      // an item that falls outside the image (edge tile) is simply dropped
+      // an item that falls outside the image (edge tile) is simply dropped: the slot stays empty
     }
   }
-  refill_waited = (dealt ? 0u : refill_waited) + (put_off ? 1u : 0u);
-  p.alive = alive; p.new_path = new_path;
-  p.slab_index = slab_index; p.item_tile = item_tile; p.item_segs = item_segs;
-  p.sample = sample; p.seed = seed; p.st_s = st_s; p.st_t = st_t; p.sum = sum;
-  q.pool_next = pool_next; q.pool_end = pool_end; q.refill_waited = refill_waited;
+  p.nx_slab = nx_slab; p.nx_tile = nx_tile; p.nx_seed = nx_seed; p.nx_s = nx_s; p.nx_t = nx_t;
+  q.pool_next = pool_next; q.pool_end = pool_end;
   q.pool_tp0 = pool_tp0; q.pool_split = pool_split; q.pool_tile0 = pool_tile0; q.pool_tile1 = pool_tile1;
   q.round = q_round; q.dry = dry;
+}
+
+// ---- promote: a lane whose item has ended takes its decoded next item --------------------------------
+// At the head of the wave step, after refill() and before the camera ray: a handful of moves, no waiting.
+template <bool COUNT>
+__device__ __forceinline__ void promote(Path& p, Tally<COUNT>& tally) {
+  if (ptdeal::promotes(p.alive, p.nx_slab == ptdeal::kSlotEmpty)) {
+    tally.flag(PT_REG_REFILL_PROMOTE);
+    p.seed = p.nx_seed; p.st_s = p.nx_s; p.st_t = p.nx_t;
+    p.slab_index = p.nx_slab; p.item_tile = p.nx_tile; p.item_segs = 0;
+    p.sum = mk(0.f, 0.f, 0.f);
+    p.sample = 0;
+    p.new_path = true;
+    p.alive = true;
+    p.nx_slab = ptdeal::kSlotEmpty;
+  }
 }
 
 } // namespace ptk

@@ -8,6 +8,7 @@
 // paths give bit-identical images (tests/test_gpu_parity.py::test_geometry_paths_are_bit_identical).
 #pragma once
 #include "pt_arith.hpp"
+#include "pt_deal.hpp"
 #include "pt_kernel_args.h"
 
 namespace ptk {
@@ -50,12 +51,15 @@ struct Path {
   V3 o = mk(0, 0, 0), d = mk(0, 0, 0);
   float a = 0.f; // dot(d,d), hoisted out of the sphere loop (static/shader.frag:147)
   V3 col = mk(1, 1, 1), sum = mk(0, 0, 0);
+  // the lane's NEXT item, decoded ahead of its need (pt_deal.hpp, pt_refill.hpp): what the item decode makes of a queue item;
+  // nx_slab == ptdeal::kSlotEmpty marks the slot empty.  These five live in VGPRs across the walk (they are not parked).
+  uint32_t nx_slab = ptdeal::kSlotEmpty, nx_tile = 0xffffffffu;
+  float nx_seed = 0.f, nx_s = 0.f, nx_t = 0.f;
 };
 
 // ---- wave-uniform work-queue state (pt_refill.hpp) ------------------------------------------------
 struct Queue {
   uint32_t pool_next = 0, pool_end = 0;  // this wave's reserved queue items
-  uint32_t refill_waited = 0;            // steps the waiting lanes have been put off
   uint32_t pool_tp0 = 0, pool_split = 0, pool_tile0 = 0, pool_tile1 = 0;  // the reservation's tile(s)
   uint32_t round = 0;                    // static dealing (A.queue_static): reservations this wave has taken
   bool dry = false;                      // a reservation came back empty: this wave gets no more items
@@ -354,7 +358,9 @@ struct Tally {
   }
   __device__ __forceinline__ void flush(const PtKernelArgs& A) {
     if constexpr (COUNT) {
-      if (lane_id() < 2u * PT_N_REGIONS && reg_acc != 0u) atomicAdd(&A.counters[PT_CTR_REGIONS + lane_id()], (unsigned long long)reg_acc);
+      // (regions 0 .. 15 fill [PT_CTR_REGIONS, PT_CTR_TIMEBINS); the regions after them continue at PT_CTR_REGIONS_MORE)
+      if (lane_id() < 2u * PT_N_REGIONS && reg_acc != 0u)
+        atomicAdd(&A.counters[lane_id() < 32u ? PT_CTR_REGIONS + lane_id() : PT_CTR_REGIONS_MORE + (lane_id() - 32u)], (unsigned long long)reg_acc);
       if (lane_id() == 0) {
         atomicAdd(&A.counters[PT_CTR_WORK + 0], (unsigned long long)n_walk_it);
         atomicAdd(&A.counters[PT_CTR_WORK + 1], (unsigned long long)n_walk_ln);

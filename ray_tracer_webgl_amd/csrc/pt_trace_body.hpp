@@ -44,6 +44,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
 
   for (;;) {
     refill<COUNT>(A, p, q, pd, tally);
+    promote<COUNT>(p, tally);
     tally.phase(0);
     // one copy of the camera-ray code per step serves both kinds of lanes: those that just
     // pulled an item and those whose previous path ended in the last step
@@ -54,7 +55,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
     }
     tally.phase(1);
     const unsigned long long live = pt_ballot(p.alive);
-    if (live == 0ull) break; // every lane is exhausted: the queue is dry
+    if (live == 0ull) break; // every lane is dead after promote(), so every next slot is empty too: the queue is dry
     tally.step();
 
     // ---- hit_world: static/shader.frag:175-196 -------------------------------------------------

@@ -122,6 +122,7 @@ class PathTracer:
 
     def set_refill_min(self, n):
         """Lanes of a busy wave that wait for a new item before the item decode runs (1 = at once).
+        Stored and accepted; the look-ahead refill (every lane holds a decoded next item) does not consult it.
         Scheduling only: images do not depend on it."""
         self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_REFILL_MIN, int(n)))
 

@@ -109,7 +109,7 @@ GRID_REGIONS = anchors("pt_grid_walk.hpp", [
     ("walk: entry (first cell)", "if (enter) {", "tally.phase(3)"),
     ("walk: cell step", "#define PT_CELL_STEP", "#undef PT_CELL_STEP"),
     ("walk: leaf round", "tally.phase(4)", "tally.phase(5)"),
-    ("walk: loop control", "tally.phase(5)", "carried = rem != 0u"),
+    ("walk: loop control", "tally.phase(5)", "carried = on() || pend"),
 ])
 SHADE_REGIONS = anchors("pt_shade.hpp", [
     ("shade: hit record + normal", "if (hit >= 0) {", "const bool sky = hit < 0"),
@@ -125,8 +125,9 @@ SHADE_REGIONS = anchors("pt_shade.hpp", [
     ("shade: sample / item end", "  if (finished) {", "p.alive = alive; p.new_path = new_path; p.item_segs"),
 ])
 REFILL_REGIONS = anchors("pt_refill.hpp", [
-    ("refill: reservation", "if (pool_next == pool_end) {", "const uint32_t avail = pool_end - pool_next;"),
-    ("refill: deal + item decode", "const uint32_t avail = pool_end - pool_next;", "refill_waited = (dealt ? 0u"),
+    ("refill: reservation", "if (ptdeal::pool_used_up(pool_next, pool_end)) {", "const uint32_t avail = pool_end - pool_next;"),
+    ("refill: deal + item decode", "const uint32_t avail = pool_end - pool_next;", "p.nx_slab = nx_slab; p.nx_tile = nx_tile;"),
+    ("refill: promote", "void promote(Path& p", "} // namespace ptk"),
 ])
 
 
@@ -158,6 +159,8 @@ def region_of(stack):
         ln = line_in("pt_shade.hpp")
         hit = [r for r, a, b in SHADE_REGIONS if a <= ln < b]
         return hit[0] if hit else ("shade: entry / write-back" if ln else None)
+    if phase == "promote":
+        return "refill: promote"
     if phase == "refill":
         ln = line_in("pt_refill.hpp")
         hit = [r for r, a, b in REFILL_REGIONS if a <= ln < b]
@@ -374,8 +377,10 @@ def main():
     R = {k: float(ctr[32 + 2 * k]) for k in range(16)}
     RL = {k: float(ctr[32 + 2 * k + 1]) for k in range(16)}
     names = ["REFILL_DECODE", "REFILL_RESERVE", "CAMERA_RAY", "SHADE_HIT_RECORD", "SHADE_SKY", "SHADE_DIFFUSE", "SHADE_METAL", "SHADE_GLASS",
-             "SHADE_GLASS_REFRACT", "SHADE_CONTINUES", "SHADE_FINISHED", "SHADE_ITEM_STORE", "WALK_ENTRY", "WALK_ENTER_CELL", "WALK_FAR_RAY", "SHADE_ANY"]
-    reg = dict(zip(names, range(16)))
+             "SHADE_GLASS_REFRACT", "SHADE_CONTINUES", "SHADE_FINISHED", "SHADE_ITEM_STORE", "WALK_ENTRY", "WALK_ENTER_CELL", "WALK_FAR_RAY", "SHADE_ANY",
+             "REFILL_PROMOTE"]
+    reg = dict(zip(names, range(17)))
+    R[16], RL[16] = float(ctr[4]), float(ctr[5])  # region 16 lives at PT_CTR_REGIONS_MORE (pt_kernel_args.h); 0 in tallies from before it existed
     n_waves = float(T["waves"])
     lit_steps = float(ctr[16 + 2])
     exact_always, walk_first = float(ctr[16 + 5]), float(ctr[16 + 7])
@@ -386,6 +391,7 @@ def main():
         "refill: loop head / write-back": W,
         "refill: reservation": R[reg["REFILL_RESERVE"]],
         "refill: deal + item decode": R[reg["REFILL_DECODE"]],
+        "refill: promote": R[reg["REFILL_PROMOTE"]],
         "camera ray": R[reg["CAMERA_RAY"]],
         "park / unpark (LDS)": W,
         "walk: set-up / write-back": W,
