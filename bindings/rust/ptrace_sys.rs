@@ -42,6 +42,16 @@ pub struct PtAdaptiveStats {     // what one pt_render_adaptive call did
     pub tile_passes: u64, pub samples: u64,
 }
 
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct PtReprojectOptions {  // one pt_reproject: the caps are whole numbers in [0, 2^24), the tolerance is in pixel footprints
+    pub cap_diffuse: f32, pub cap_other: f32, pub tolerance_px: f32, pub _pad: u32,
+}
+
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtReprojectStats {    // the tallies of the last pt_reproject
+    pub pixels: u64, pub pixels_hit: u64, pub pixels_kept: u64, pub samples_kept: u64,
+}
+
 #[repr(C)] pub struct PtCtx { _private: [u8; 0] }
 
 #[link(name = "ptrace")]
@@ -91,6 +101,13 @@ extern "C" {
     pub fn pt_render_features(ctx: *mut PtCtx) -> c_int;
     pub fn pt_features_ptr(ctx: *mut PtCtx, plane: c_int, dev_ptr: *mut *mut c_void, bytes: *mut usize) -> c_int;
     pub fn pt_read_features(ctx: *mut PtCtx, plane: c_int, out: *mut c_void) -> c_int;
+    // temporal reprojection (pt_set_option PT_OPT_REPROJECT 1, beside PT_OPT_FEATURES): carry the accumulation across a camera
+    // move.  A tick: pt_keep_history, pt_set_params(next), pt_render_features, pt_reproject, pt_render_passes
+    pub fn pt_keep_history(ctx: *mut PtCtx) -> c_int;
+    pub fn pt_load_history(ctx: *mut PtCtx, prev: *const PtParams, ids: *const c_void, point: *const c_void) -> c_int;
+    pub fn pt_reproject(ctx: *mut PtCtx, options: *const PtReprojectOptions) -> c_int;
+    pub fn pt_reproject_stats(ctx: *mut PtCtx, out: *mut PtReprojectStats) -> c_int;
+    pub fn pt_reproject_constants(prev: *const PtParams, tolerance_px: f32, out16: *mut f32) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;
@@ -113,6 +130,10 @@ extern "C" {
 pub const PT_OPT_GEOMETRY_PATH: c_int = 1;      // PT_GEOM_AUTO 0 / LDS 1 / SCALAR 2 / BVH 3 / GRID 4 / SMALL 5
 pub const PT_OPT_ERROR_ESTIMATE: c_int = 7;     // opt-in, 0 = off; the image bits do not depend on it
 pub const PT_OPT_FEATURES: c_int = 8;           // opt-in, 0 = off; the image bits do not depend on it
+pub const PT_OPT_REPROJECT: c_int = 9;          // opt-in, 0 = off; needs PT_OPT_FEATURES on
+pub const PT_REPROJECT_TOLERANCE_DEFAULT: f32 = 2.0;
+pub const PT_REPROJECT_CAP_DIFFUSE_DEFAULT: f32 = 32.0;
+pub const PT_REPROJECT_CAP_OTHER_DEFAULT: f32 = 8.0;
 pub const PT_FEAT_ALBEDO: c_int = 0;
 pub const PT_FEAT_NORMAL: c_int = 1;
 pub const PT_FEAT_POINT: c_int = 2;

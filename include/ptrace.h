@@ -107,6 +107,10 @@ enum {
   PT_OPT_FEATURES = 8,    /* 1: allocate the four first-hit feature planes (see pt_render_features below; 64 bytes per local
                              pixel) and keep the uuid arrays on the device.  0 (default): release them.  The image bits of a
                              context are the same either way. */
+  PT_OPT_REPROJECT = 9,   /* 1: allocate the history planes of temporal reprojection (see pt_reproject below; ids + point, 32 bytes
+                             per local pixel).  Needs PT_OPT_FEATURES on (PT_ERR_INVALID otherwise).  0 (default): release them.
+                             Turning PT_OPT_FEATURES off turns this off too.  The image bits of a context that never calls
+                             pt_reproject are the same either way. */
 };
 
 /* ---- background modes ----------------------------------------------------------------------- */
@@ -574,6 +578,93 @@ enum { PT_FEAT_ALBEDO = 0, PT_FEAT_NORMAL = 1, PT_FEAT_POINT = 2, PT_FEAT_IDS = 
 int pt_render_features(pt_ctx* ctx);
 int pt_features_ptr(pt_ctx* ctx, int plane, void** dev_ptr, size_t* bytes);
 int pt_read_features(pt_ctx* ctx, int plane, void* out);
+
+/* ---- temporal reprojection: carry the accumulation across a camera move (build extension, opt-in: PT_OPT_REPROJECT) ---------
+ * The reference restarts its image whenever the camera moves (render_count = 0, src/state.rs:343-346), and so does a host that
+ * calls pt_reset_accum.  pt_reproject instead moves the accumulated radiance to where the same surface lies in the NEW view: for
+ * each pixel of the new view its first-hit point (the feature planes) is projected into the camera of an earlier view, the
+ * HISTORY; where the history planes show the same sphere and side at that place, within a distance of tolerance_px pixel
+ * footprints, the accumulation is fetched from there, bilinearly, and its sample count capped, so that fresh samples soon
+ * outweigh what no longer holds (reflections and refractions move with the camera: they get the smaller cap).
+ * A host's tick while the camera moves:
+ *     pt_keep_history(ctx);  pt_set_params(ctx, next);  pt_render_features(ctx);  pt_reproject(ctx, &opt);  pt_render_passes(ctx, n);
+ * with `time` advanced from tick to tick, so that the fresh samples are new ones.
+ * pt_keep_history: needs the option on and valid feature planes (PT_ERR_NOT_READY otherwise: pt_read_features' rule); copies the
+ * PT_FEAT_IDS and PT_FEAT_POINT planes device-to-device into the history planes and remembers the PtParams they were rendered
+ * with.  Asynchronous on the context's stream, no synchronisation, no allocation.
+ * pt_load_history: the same from caller memory (host or device pointers to local_rows*width*16 bytes each) and an explicit
+ * `prev`, which must have the context's width, height and row partition (PT_ERR_INVALID otherwise).  Synchronises.
+ * THE HISTORY ENDS — pt_reproject returns PT_ERR_NOT_READY afterwards — at pt_set_spheres (its indices would name other spheres),
+ * at pt_resize, at a pt_set_params that changes the row partition, when the option is turned off, and at pt_reproject itself:
+ * the call is one-shot, afterwards the accumulation belongs to the new view.  An ordinary pt_set_params does NOT end it.
+ * pt_reproject: needs the option on, a valid history and valid CURRENT planes, i.e. a pt_render_features after the
+ * pt_set_params of the new view (PT_ERR_NOT_READY otherwise).  PT_ERR_INVALID: NULL arguments, a cap that is not a whole number
+ * in [0, 2^24), a tolerance_px that is not finite or is below 0, a history camera pt_reproject_constants refuses, a call inside
+ * a stream capture.  A context with no local pixels: PT_OK.  Asynchronous, no synchronisation, no allocation: one kernel writes
+ * the staging buffer pt_load_accum uses, one device-to-device copy brings it into the accumulation — pt_accum_ptr and a
+ * caller-bound buffer keep their addresses.  The error estimate is cleared, as pt_load_accum clears it (history is sums, not
+ * passes).  first_pass, the textures, the canvas, the tile order, the tile costs and PtStats.segments do not move.  Afterwards
+ * the pixels of the frame hold DIFFERENT sample counts: every read-out divides by the pixel's own count and a zero count reads
+ * 0, PtStats.total_spp is pixel (0, 0)'s count as after a partial round of pt_render_adaptive (0 where that pixel kept
+ * nothing), and the buffer is no checkpoint for pt_load_accum.  PtStats.samples counts camera paths started and does not move.
+ * HOST CONSTANTS (pt_reproject_constants: pure host arithmetic, no device; csrc/pt_reproject_plan.hpp), computed in double from
+ * the float fields of `prev`, one IEEE operation per statement, each result narrowed ONCE:
+ *     O = camera_origin;  Hh = horizontal;  V = vertical;  L = lower_left_corner
+ *     e = L - O;  n = Hh x V;  N = n / (e.n)
+ *     A = (V x n) / (Hh.(V x n));  B = (n x Hh) / (V.(n x Hh))
+ *     ea = e.A;  eb = e.B                                        (A and B as doubles)
+ *     k = tolerance_px^2 * (Hh.Hh) / width^2
+ *     out16 = {O.xyz, N.xyz, A.xyz, B.xyz, ea, eb, k, 0}
+ * (a x b = {a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x};  a.b = (a.x*b.x + a.y*b.y) + a.z*b.z.)  PT_ERR_INVALID when
+ * e.n or either denominator is 0, or when any result is not finite.  The lens does not enter: the planes are pinhole.
+ * PER LOCAL PIXEL p = (px, ly), fp32, ONE IEEE operation per statement, nothing fused, `/` correctly rounded.  ids and Pn come
+ * from the CURRENT planes (PT_FEAT_IDS, PT_FEAT_POINT), HIDS, HPNT and ACC from the history planes and the accumulation as the
+ * call finds them; out starts as {+0, +0, +0, +0}:
+ *     done if ids.x < 0                                            (a miss: sky needs no history)
+ *     w.c = Pn.c - O.c
+ *     lam = (w.x*N.x + w.y*N.y) + w.z*N.z ;  done unless lam > 0
+ *     ws, wt likewise with A, B
+ *     s = ws / lam ;  s = s - ea ;  t = wt / lam ;  t = t - eb
+ *     fx = s * float(width) ;  fx = fx - 0.5f ;  fy = t * float(height) ;  fy = fy - 0.5f     (fy is an IMAGE row, 0 = bottom)
+ *     done unless fx > -1 && fx < float(width) && fy > -1 && fy < float(height)              (NaN: done; only now convert to int)
+ *     x0f = floorf(fx); ax = fx - x0f; y0f = floorf(fy); ay = fy - y0f;  x0 = (int)x0f, y0 = (int)y0f
+ *     lam2 = lam*lam ;  rhs = k * lam2
+ *     cap = ids.z == PT_DIFFUSE ? cap_diffuse : cap_other
+ *     sum = {+0,+0,+0}; cnt = +0; wsum = +0
+ *     for dy in 0,1 (outer), dx in 0,1:
+ *         q = (x0+dx, y0+dy); skip unless 0 <= q.x < width, 0 <= q.y < height and q.y is a row this context owns (the inverse of
+ *             pt_band_row; band_count <= 1: every row); lq = its local row
+ *         skip unless HIDS[q].x == ids.x && HIDS[q].w == ids.w
+ *         d.c = HPNT[q].c - Pn.c ;  d2 = (d.x*d.x + d.y*d.y) + d.z*d.z ;  skip unless d2 <= rhs
+ *         a = ACC[q] ;  skip unless a.w > 0
+ *         wx = dx ? ax : 1.0f - ax ;  wy = dy ? ay : 1.0f - ay ;  g = wx*wy ;  skip unless g > 0
+ *         m.c = a.c / a.w ;  sum.c = sum.c + g*m.c (two statements) ;  cnt = cnt + g*a.w (two) ;  wsum = wsum + g
+ *     done unless wsum > 0
+ *     nq = cnt / wsum ;  nq = floorf(nq) ;  if (nq > cap) nq = cap ;  done unless nq >= 1
+ *     col.c = sum.c / wsum ;  out = {col.r*nq, col.g*nq, col.b*nq, nq}
+ * Counts stay whole numbers; non-finite colour stays non-finite.  The distance test is in pixel footprints at the history
+ * camera's depth: it catches the far side of the same sphere and the horizon.  A band context gathers from its own rows only: a
+ * tap on a row another band owns is skipped (no history rows are exchanged between ranks).
+ * pt_reproject_stats: synchronises; the tallies of the last pt_reproject (PT_ERR_NOT_READY before the first): pixels =
+ * local_rows*width, pixels_hit those with ids.x >= 0, pixels_kept those with out.w > 0, samples_kept the sum of nq.  Integers,
+ * summed per workgroup and added with one integer atomic each: exact, whatever the order. */
+#define PT_REPROJECT_TOLERANCE_DEFAULT 2.0f
+#define PT_REPROJECT_CAP_DIFFUSE_DEFAULT 32.0f
+#define PT_REPROJECT_CAP_OTHER_DEFAULT 8.0f
+typedef struct PtReprojectOptions {
+  float cap_diffuse;  /* the most samples a kept PT_DIFFUSE pixel carries over */
+  float cap_other;    /* ... and a pixel of any other material (0: diffuse surfaces only) */
+  float tolerance_px;
+  uint32_t _pad;
+} PtReprojectOptions;
+typedef struct PtReprojectStats {
+  uint64_t pixels, pixels_hit, pixels_kept, samples_kept;
+} PtReprojectStats;
+int pt_keep_history(pt_ctx* ctx);
+int pt_load_history(pt_ctx* ctx, const PtParams* prev, const void* ids, const void* point);
+int pt_reproject(pt_ctx* ctx, const PtReprojectOptions* options);
+int pt_reproject_stats(pt_ctx* ctx, PtReprojectStats* out);
+int pt_reproject_constants(const PtParams* prev, float tolerance_px, float out16[16]);
 
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)

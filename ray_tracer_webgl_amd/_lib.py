@@ -62,6 +62,11 @@ SIGNATURES = {
     "pt_render_features": (C.c_int, [_ctx]),
     "pt_features_ptr": (C.c_int, [_ctx, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "pt_read_features": (C.c_int, [_ctx, C.c_int, _vp]),
+    "pt_keep_history": (C.c_int, [_ctx]),
+    "pt_load_history": (C.c_int, [_ctx, C.POINTER(abi.PtParams), _vp, _vp]),
+    "pt_reproject": (C.c_int, [_ctx, C.POINTER(abi.PtReprojectOptions)]),
+    "pt_reproject_stats": (C.c_int, [_ctx, C.POINTER(abi.PtReprojectStats)]),
+    "pt_reproject_constants": (C.c_int, [C.POINTER(abi.PtParams), C.c_float, C.POINTER(C.c_float)]),
     "pt_refit_grid": (C.c_int, [_ctx, C.c_int]),
     "pt_grid_fit": (C.c_int, [_ctx]),
     "pt_build_bvh": (C.c_int, [C.POINTER(abi.PtSphere), C.c_uint32, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp,
@@ -109,11 +114,13 @@ SIGNATURES = {
 
 
 # entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay, the error
-# estimate, adaptive sampling, the filtered read-out, the first-hit feature planes, the patch-wise filtered read-out
+# estimate, adaptive sampling, the filtered read-out, the first-hit feature planes, the patch-wise filtered read-out, temporal
+# reprojection
 ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_set_debugging", "pt_state_debug_overlay",
                       "pt_error_ptr", "pt_resolve_error", "pt_error_tiles", "pt_error_stats", "pt_render_until",
                       "pt_render_adaptive", "pt_adaptive_tiles", "pt_resolve_filtered", "pt_render_features", "pt_features_ptr",
-                      "pt_read_features", "pt_resolve_filtered_patch")
+                      "pt_read_features", "pt_resolve_filtered_patch", "pt_keep_history", "pt_load_history", "pt_reproject",
+                      "pt_reproject_stats", "pt_reproject_constants")
 
 
 def _elf_dynamic_strings(path, tags):

@@ -33,6 +33,10 @@ PT_OPT_GEOMETRY_PATH, PT_OPT_COUNT_WORK, PT_OPT_CARRY_LANES, PT_OPT_REFILL_MIN, 
 PT_OPT_FEATURES = 8  # the first-hit feature planes (pt_render_features, pt_features_ptr, pt_read_features)
 PT_FEAT_ALBEDO, PT_FEAT_NORMAL, PT_FEAT_POINT, PT_FEAT_IDS, PT_FEAT_PLANES = 0, 1, 2, 3, 4
 PT_OPT_ERROR_ESTIMATE = 7  # the per-pixel error estimate (pt_error_ptr, pt_resolve_error, pt_error_tiles, pt_error_stats, pt_render_until)
+PT_OPT_REPROJECT = 9  # temporal reprojection's history planes (pt_keep_history, pt_load_history, pt_reproject, pt_reproject_stats)
+PT_REPROJECT_TOLERANCE_DEFAULT = 2.0      # pt_reproject: the distance test, in pixel footprints at the history camera's depth
+PT_REPROJECT_CAP_DIFFUSE_DEFAULT = 32.0   # ... the most samples a kept diffuse pixel carries over
+PT_REPROJECT_CAP_OTHER_DEFAULT = 8.0      # ... and a pixel of any other material
 PT_TIME_STEP_DECORRELATED = 0.3618034  # include/ptrace.h
 PT_FILTER_MAX_RADIUS = 4        # pt_resolve_filtered: the largest radius
 PT_FILTER_KAPPA_DEFAULT = 2.0   # ... and the kappa its callers start from
@@ -192,6 +196,32 @@ class PtAdaptiveStats(C.Structure):
         ("tiles_active", C.c_uint32),
         ("tile_passes", C.c_uint64),
         ("samples", C.c_uint64),
+    ]
+
+
+class PtReprojectOptions(C.Structure):
+    """include/ptrace.h PtReprojectOptions: the caps (whole numbers below 2^24) and the distance tolerance of one pt_reproject."""
+
+    _fields_ = [
+        ("cap_diffuse", C.c_float),
+        ("cap_other", C.c_float),
+        ("tolerance_px", C.c_float),
+        ("_pad", C.c_uint32),
+    ]
+
+    def __init__(self, cap_diffuse=PT_REPROJECT_CAP_DIFFUSE_DEFAULT, cap_other=PT_REPROJECT_CAP_OTHER_DEFAULT,
+                 tolerance_px=PT_REPROJECT_TOLERANCE_DEFAULT):
+        super().__init__(cap_diffuse, cap_other, tolerance_px, 0)
+
+
+class PtReprojectStats(C.Structure):
+    """include/ptrace.h PtReprojectStats: the tallies of the last pt_reproject."""
+
+    _fields_ = [
+        ("pixels", C.c_uint64),
+        ("pixels_hit", C.c_uint64),
+        ("pixels_kept", C.c_uint64),
+        ("samples_kept", C.c_uint64),
     ]
 
 

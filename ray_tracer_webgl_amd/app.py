@@ -10,7 +10,8 @@ run_setters -> render -> (save).  Two display modes:
     groups of 64, 16 and 4 frames, each traced by one launch) with the per-frame state counted on the device.
   * "linear": passes accumulate as fp32 linear radiance (north_star's "accumulated radiance")
     and are resolved at read-out; a camera change (render_count reset to 0,
-    src/state.rs:343-346) clears the accumulation.
+    src/state.rs:343-346) clears the accumulation — or, with `reproject` options given, carries it over
+    into the new view (temporal reprojection, include/ptrace.h pt_reproject).
 """
 import time
 
@@ -25,9 +26,11 @@ class FrameLoop:
     # is refitted; a grid that is too SMALL (== 1: every primary ray tested against the whole list) is refitted at once
     LOOSE_FRAMES = 32
 
-    def __init__(self, width, height, device=0, mode="reference", host_spheres=None, debugging=False):
+    def __init__(self, width, height, device=0, mode="reference", host_spheres=None, debugging=False, reproject=None):
         assert mode in ("reference", "linear")
+        assert reproject is None or mode == "linear", "temporal reprojection carries the fp32 accumulation: linear mode only"
         self.mode = mode
+        self.reproject = reproject  # abi.PtReprojectOptions, or None: a camera change clears the accumulation
         self.debugging = bool(debugging)
         self.state = State(width, height)
         if self.debugging:  # State.enable_debugging (src/state.rs:87): the shader's cursor dot and selected-object outline
@@ -36,6 +39,9 @@ class FrameLoop:
             self.state.set_spheres(host_spheres)
         self.tracer = PathTracer(width, height, device=device)
         self.tracer.set_spheres(self.state.spheres())  # set_geometry, once (src/lib.rs:57)
+        if self.reproject is not None:
+            self.tracer.feature_planes(True)
+            self.tracer.reproject_option(True)
         self.grid_refits = 0
         self._loose = 0
         # two RGBA8 textures cleared to 0 (alpha 0 = "no data", shader.frag:391): in HBM, owned by the context
@@ -101,11 +107,21 @@ class FrameLoop:
             # to the canvas (:193-194) and, when averaging, to the other texture (:197-204)
             self.tracer.render_frame(v.even_odd_count)
         else:
-            if v.render_count <= 1:  # accumulation restarts after any camera change
+            moved = v.render_count <= 1  # accumulation restarts after any camera change
+            carry = moved and self.reproject is not None and self.frames_rendered > 0
+            if moved and not carry:
                 self.tracer.reset()
             self.tracer.set_params(p)
             self._upload_debug_overlay()
             self._keep_the_grid_fitted()
+            if moved and self.reproject is not None:
+                # the tick of include/ptrace.h (keep_history, set_params, render_features, reproject, render), with
+                # keep_history issued by the tick that RENDERED the planes: every tick uploads a new clock, and the planes
+                # answer only until the next set_params, so the view is remembered while they still speak for it
+                self.tracer.render_features()
+                if carry:
+                    self.tracer.reproject(self.reproject)
+                self.tracer.keep_history()
             self.tracer.render()
             self._canvas = self.tracer.resolve_rgba8(True)
         self.frames_rendered += 1

@@ -32,6 +32,8 @@
 #include "pt_launch_plan.hpp"
 #include "pt_tile_order.hpp"
 #include "pt_error_plan.hpp"
+#include "pt_reproject_plan.hpp"
+#include "pt_reproject.hpp"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -177,6 +179,14 @@ struct pt_ctx {
   bool feat_on = false;
   bool feat_valid = false;          // the planes speak for the scene, uniforms and partition in place (pt_read_features)
   DevBuf<float4> d_feat;
+  // temporal reprojection (PT_OPT_REPROJECT; pt_kernels_reproject.hip): the history planes — the ids plane, then the point plane,
+  // of an earlier view (pt_keep_history / pt_load_history) — the uniforms they were rendered with, and the last call's tallies
+  bool reproj_on = false;
+  bool hist_valid = false;          // the history speaks for the scene and partition in place, and no pt_reproject has used it
+  PtParams hist_params{};
+  DevBuf<float4> d_hist;
+  DevBuf<unsigned long long> d_reproj_tally;  // {pixels_hit, pixels_kept, samples_kept}
+  bool reproj_ran = false;          // the tallies are those of a pt_reproject (pt_reproject_stats)
   // work-queue ordering feedback, one entry per tile
   DevBuf<uint32_t> d_tile_cost;
   DevBuf<uint32_t> d_tile_order;
@@ -343,6 +353,10 @@ int ensure_buffers(pt_ctx* c) {
     c->feat_valid = false;
     if (pix > 0x3fffffffu / PT_FEAT_PLANES) return fail(c, PT_ERR_CAPACITY, "feature planes: %zu local pixels exceed the kernels' 32-bit texel index", pix);
     PT_HIP(c, c->d_feat.reserve(PT_FEAT_PLANES * pix));
+  }
+  if (c->reproj_on && c->d_hist.capacity() != 2 * pix) {  // (likewise: the ids plane, then the point plane at pix)
+    c->hist_valid = false;
+    PT_HIP(c, c->d_hist.reserve(2 * pix));
   }
   return PT_OK;
 }
@@ -755,6 +769,7 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
   PT_HIP(c, hipStreamSynchronize(c->stream));
   // validate first, commit afterwards: from the first device write until everything is in place the context has no scene
   drop_scene(c);
+  c->hist_valid = false;  // (the history's list indices would name other spheres)
   if (int rc = install_scene(c, sp, n, have_bvh ? &bvh : nullptr, have_grid ? &grid : nullptr); rc != PT_OK) return drop_scene(c), rc;
   c->list.n = n;
   c->list.host = std::move(sp);
@@ -796,6 +811,7 @@ PT_API int pt_set_params(pt_ctx* c, const PtParams* p) {
     return fail(c, PT_ERR_CAPACITY, "pt_set_params: bound accumulation buffer too small for %u rows", rows);
   c->feat_valid = false;  // the feature planes speak for the uniforms they were rendered with
   if (repartition) {
+    c->hist_valid = false;  // (the history planes held other rows; an ordinary pt_set_params leaves them alone)
     const uint32_t old_rows = c->local_rows;
     c->local_rows = rows;
     int rc = ensure_buffers(c);
@@ -830,6 +846,7 @@ PT_API int pt_resize(pt_ctx* c, uint32_t width, uint32_t height) {
   c->have_params = false; // uniforms must be re-uploaded for the new size
   c->adapt_valid = false;
   c->feat_valid = false;
+  c->hist_valid = false;
   c->params.band_count = 0;
   c->local_rows = height;
   if (c->accum_bound) { c->accum_bound = false; c->accum = nullptr; }
@@ -1990,6 +2007,13 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
   return PT_OK;
 }
 
+// PT_OPT_REPROJECT off: the history planes, the tallies and the history itself go (the caller has drained the stream)
+static void release_reproject(pt_ctx* c) {
+  c->reproj_on = c->hist_valid = c->reproj_ran = false;
+  c->d_hist = DevBuf<float4>();
+  c->d_reproj_tally = DevBuf<unsigned long long>();
+}
+
 PT_API int pt_set_option(pt_ctx* c, int key, int value) {
   if (!c) return PT_ERR_INVALID;
   if (key == PT_OPT_GEOMETRY_PATH) {
@@ -2054,6 +2078,7 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     if (!value) {
       c->feat_on = c->feat_valid = false;
       c->d_feat = DevBuf<float4>();
+      release_reproject(c);  // (it reads the planes: off with them)
       return PT_OK;
     }
     if (c->feat_on) return PT_OK;
@@ -2064,6 +2089,25 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     int rc = ensure_buffers(c);
     if (rc == PT_OK && !c->uuid_valid && c->have_spheres) rc = upload_uuids(c, c->list.host.uuid);  // the scene in place
     if (rc != PT_OK) { c->feat_on = false; c->d_feat = DevBuf<float4>(); }
+    return rc;
+  }
+  if (key == PT_OPT_REPROJECT) { // the image does not depend on it; the history planes are allocated here, released when turned off
+    if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: reprojection %d", value);
+    if (value && !c->feat_on) return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_REPROJECT needs PT_OPT_FEATURES on (it reads the feature planes)");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipStreamSynchronize(c->stream));  // (a copy or a gather in flight uses the history planes)
+    if (!value) { release_reproject(c); return PT_OK; }
+    if (c->reproj_on) return PT_OK;
+    // (asking for the kernel's attributes loads its code object now: a set-up call's work, not pt_reproject's)
+    hipFuncAttributes attr;
+    PT_HIP(c, hipFuncGetAttributes(&attr, pt_reproject_kernel_handle()));
+    c->reproj_on = true;
+    int rc = ensure_buffers(c);
+    if (rc == PT_OK && c->d_reproj_tally.capacity() < 3) {
+      hipError_t e = c->d_reproj_tally.reserve(3);
+      if (e != hipSuccess) rc = fail(c, PT_ERR_HIP, "pt_set_option: the reprojection tallies: %s", hipGetErrorString(e));
+    }
+    if (rc != PT_OK) release_reproject(c);
     return rc;
   }
   return fail(c, PT_ERR_INVALID, "pt_set_option: unknown key %d", key);
@@ -2153,6 +2197,133 @@ PT_API int pt_read_features(pt_ctx* c, int plane, void* out) {
   const size_t need = n_pixels(c) * sizeof(float4);
   if (need) PT_HIP(c, hipMemcpyAsync(out, c->d_feat.get() + (size_t)plane * n_pixels(c), need, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+// ---- temporal reprojection (PT_OPT_REPROJECT; include/ptrace.h has the contract) ------------------------------
+// are the history planes allocated for the local rows in place?  (As with the feature planes: unless an allocation failed.)
+static bool history_planes_in_place(const pt_ctx* c) {
+  const size_t pix = n_pixels(c) ? n_pixels(c) : 1;
+  return c->reproj_on && c->d_hist.get() && c->d_hist.capacity() == 2 * pix;
+}
+
+// the row partition a set of uniforms names, as pt_set_params compares it (band_count <= 1: "all rows" whatever the rest holds)
+static bool same_partition(const PtParams& a, const PtParams& b) {
+  const bool band_a = a.band_count > 1 && a.band_rows != 0, band_b = b.band_count > 1 && b.band_rows != 0;
+  if (!band_a || !band_b) return band_a == band_b;
+  return a.band_rows == b.band_rows && a.band_index == b.band_index && a.band_count == b.band_count;
+}
+
+static int reproject_ready(pt_ctx* c, const char* who) {
+  if (!c->reproj_on) return fail(c, PT_ERR_NOT_READY, "%s: reprojection is off (pt_set_option PT_OPT_REPROJECT)", who);
+  if (!history_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "%s: the history planes are not allocated for the rows in place (an earlier allocation failed)", who);
+  return PT_OK;
+}
+
+PT_API int pt_keep_history(pt_ctx* c) {
+  if (!c) return PT_ERR_INVALID;
+  if (int rc = reproject_ready(c, "pt_keep_history"); rc != PT_OK) return rc;
+  if (!c->feat_on || !c->feat_valid || !feature_planes_in_place(c))
+    return fail(c, PT_ERR_NOT_READY, "pt_keep_history: no pt_render_features since the scene, the uniforms or the size last changed");
+  PT_HIP(c, hipSetDevice(c->device));
+  if (const size_t pix = n_pixels(c)) {
+    const size_t bytes = pix * sizeof(float4);
+    PT_HIP(c, hipMemcpyAsync(c->d_hist.get(), c->d_feat.get() + (size_t)PT_FEAT_IDS * pix, bytes, hipMemcpyDeviceToDevice, c->stream));
+    PT_HIP(c, hipMemcpyAsync(c->d_hist.get() + pix, c->d_feat.get() + (size_t)PT_FEAT_POINT * pix, bytes, hipMemcpyDeviceToDevice, c->stream));
+  }
+  c->hist_params = c->params;
+  c->hist_valid = true;
+  return PT_OK;
+}
+
+PT_API int pt_load_history(pt_ctx* c, const PtParams* prev, const void* ids, const void* point) {
+  if (!c || !prev || !ids || !point) return fail(c, PT_ERR_INVALID, "pt_load_history: NULL argument");
+  if (int rc = reproject_ready(c, "pt_load_history"); rc != PT_OK) return rc;
+  if (prev->width != c->width || prev->height != c->height || !same_partition(*prev, c->params))
+    return fail(c, PT_ERR_INVALID, "pt_load_history: the history view's size or row partition is not the context's");
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_load_history: synchronises; not inside a stream capture");
+  if (const size_t pix = n_pixels(c)) {
+    const size_t bytes = pix * sizeof(float4);
+    PT_HIP(c, hipMemcpyAsync(c->d_hist.get(), ids, bytes, hipMemcpyDefault, c->stream));
+    PT_HIP(c, hipMemcpyAsync(c->d_hist.get() + pix, point, bytes, hipMemcpyDefault, c->stream));
+  }
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  c->hist_params = *prev;
+  c->hist_valid = true;
+  return PT_OK;
+}
+
+PT_API int pt_reproject_constants(const PtParams* prev, float tolerance_px, float out16[16]) {
+  if (!prev || !out16 || prev->width == 0) return PT_ERR_INVALID;
+  if (!std::isfinite(tolerance_px) || tolerance_px < 0.0f) return PT_ERR_INVALID;
+  return ptrep::constants(prev->camera_origin, prev->horizontal, prev->vertical, prev->lower_left_corner, prev->width, tolerance_px, out16)
+             ? PT_OK : PT_ERR_INVALID;
+}
+
+PT_API int pt_reproject(pt_ctx* c, const PtReprojectOptions* opt) {
+  if (!c || !opt) return fail(c, PT_ERR_INVALID, "pt_reproject: NULL argument");
+  for (const float cap : {opt->cap_diffuse, opt->cap_other})
+    if (!(cap >= 0.0f) || !(cap < 16777216.0f) || cap != std::floor(cap))
+      return fail(c, PT_ERR_INVALID, "pt_reproject: a cap of %g is not a whole number in [0, 2^24)", (double)cap);
+  if (!std::isfinite(opt->tolerance_px) || opt->tolerance_px < 0.0f)
+    return fail(c, PT_ERR_INVALID, "pt_reproject: tolerance_px must be finite and >= 0");
+  if (int rc = reproject_ready(c, "pt_reproject"); rc != PT_OK) return rc;
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_reproject: not inside a stream capture");
+  if (!c->hist_valid) return fail(c, PT_ERR_NOT_READY, "pt_reproject: no history (pt_keep_history / pt_load_history; one pt_reproject uses it up)");
+  if (!c->feat_on || !c->feat_valid || !feature_planes_in_place(c))
+    return fail(c, PT_ERR_NOT_READY, "pt_reproject: no pt_render_features since the uniforms of the new view went up");
+  float k16[ptrep::K_COUNT];
+  if (pt_reproject_constants(&c->hist_params, opt->tolerance_px, k16) != PT_OK)
+    return fail(c, PT_ERR_INVALID, "pt_reproject: the history view's camera is degenerate");
+  c->hist_valid = false;  // one-shot: from here on the accumulation belongs to the new view
+  c->reproj_ran = true;
+  const size_t pix = n_pixels(c);
+  PT_HIP(c, hipMemsetAsync(c->d_reproj_tally.get(), 0, 3 * sizeof(unsigned long long), c->stream));
+  if (pix == 0) return PT_OK;  // this band owns no rows
+  ptrep::Consts K;
+  for (int k = 0; k < 3; k++) {
+    K.O[k] = k16[ptrep::K_O + k];
+    K.N[k] = k16[ptrep::K_N + k];
+    K.A[k] = k16[ptrep::K_A + k];
+    K.B[k] = k16[ptrep::K_B + k];
+  }
+  K.ea = k16[ptrep::K_EA];
+  K.eb = k16[ptrep::K_EB];
+  K.k = k16[ptrep::K_K];
+  K.cap_diffuse = opt->cap_diffuse;
+  K.cap_other = opt->cap_other;
+  const bool band = c->params.band_count > 1 && c->params.band_rows != 0;
+  ptrep::Frame F = {c->width, c->height, c->local_rows, band ? c->params.band_rows : 0u, band ? c->params.band_index : 0u,
+                    band ? c->params.band_count : 1u};
+  const float4* cur_ids = c->d_feat.get() + (size_t)PT_FEAT_IDS * pix;
+  const float4* cur_pnt = c->d_feat.get() + (size_t)PT_FEAT_POINT * pix;
+  const float4* hist_ids = c->d_hist.get();
+  const float4* hist_pnt = c->d_hist.get() + pix;
+  const float4* accum = c->accum;
+  float4* out = c->d_resolve.get();  // (the staging buffer pt_load_accum uses: the gather reads accum at other pixels' places)
+  unsigned long long* tally = c->d_reproj_tally.get();
+  void* kargs[] = {&cur_ids, &cur_pnt, &hist_ids, &hist_pnt, &accum, &out, &K, &F, &tally};
+  const dim3 grid((c->width + 31u) / 32u, (c->local_rows + 7u) / 8u);
+  PT_HIP(c, hipLaunchKernel(pt_reproject_kernel_handle(), grid, dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, hipMemcpyAsync(c->accum, out, pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  return clear_error(c);  // (history is sums, not the passes they came from: as pt_load_accum)
+}
+
+PT_API int pt_reproject_stats(pt_ctx* c, PtReprojectStats* out) {
+  if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_reproject_stats: NULL argument");
+  if (!c->reproj_on) return fail(c, PT_ERR_NOT_READY, "pt_reproject_stats: reprojection is off (pt_set_option PT_OPT_REPROJECT)");
+  if (!c->reproj_ran) return fail(c, PT_ERR_NOT_READY, "pt_reproject_stats: no pt_reproject yet");
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_reproject_stats: synchronises; not inside a stream capture");
+  unsigned long long h[3] = {0, 0, 0};
+  PT_HIP(c, hipMemcpyAsync(h, c->d_reproj_tally.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  out->pixels = (uint64_t)n_pixels(c);
+  out->pixels_hit = h[0];
+  out->pixels_kept = h[1];
+  out->samples_kept = h[2];
   return PT_OK;
 }
 

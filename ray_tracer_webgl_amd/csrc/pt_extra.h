@@ -28,3 +28,5 @@ extern "C" const void* pt_feature_kernel(int id);
 // pt_resolve_filtered_patch)
 enum { PT_E_FOLD = 0, PT_E_RESOLVE, PT_E_TILES, PT_E_FOLD_TILES, PT_E_PARTITION, PT_E_FILTER, PT_E_FILTER_PATCH, PT_E_COUNT };
 extern "C" const void* pt_error_kernel(int id);
+// pt_kernels_reproject.hip (a code object of its own): temporal reprojection's one kernel (PT_OPT_REPROJECT, pt_reproject)
+extern "C" const void* pt_reproject_kernel_handle(void);

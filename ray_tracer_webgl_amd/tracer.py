@@ -419,6 +419,41 @@ class PathTracer:
             out[name] = torch.as_tensor(view, device="cuda:%d" % self.device)
         return out
 
+    # -- temporal reprojection (include/ptrace.h PT_OPT_REPROJECT) ---------------------------------
+    def reproject_option(self, on=True):
+        """Allocate (or release) the history planes of temporal reprojection; needs feature_planes(True) first.  Off by
+        default; the image bits of a context that never calls reproject() are the same either way."""
+        self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_REPROJECT, 1 if on else 0))
+
+    def keep_history(self):
+        """Remember the view in place (pt_keep_history): its ids and hit-point planes and the uniforms they were rendered
+        with.  Needs a render_features() of that view.  Asynchronous."""
+        self._check(self.lib.pt_keep_history(self._ctx))
+
+    def load_history(self, prev, ids, point):
+        """The same from host arrays (pt_load_history): `prev` the history view's PtParams, `ids` int32 and `point` float32,
+        each (local_rows, width, 4)."""
+        i = np.ascontiguousarray(ids, dtype=np.int32)
+        p = np.ascontiguousarray(point, dtype=np.float32)
+        shape = (self.local_rows, self.width, 4)
+        if i.shape != shape or p.shape != shape:
+            raise ValueError("history planes are %s and %s, this context holds %s" % (i.shape, p.shape, shape))
+        q = prev.copy()
+        self._check(self.lib.pt_load_history(self._ctx, C.byref(q), i.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p)))
+
+    def reproject(self, options=None):
+        """Carry the accumulation over from the history view into the view in place (pt_reproject): after set_params of the
+        new view and render_features.  One-shot: it uses the history up.  `options`: abi.PtReprojectOptions (default: the
+        header's caps and tolerance).  Asynchronous; the error estimate is cleared."""
+        opt = options if options is not None else abi.PtReprojectOptions()
+        self._check(self.lib.pt_reproject(self._ctx, C.byref(opt)))
+
+    def reproject_stats(self):
+        """abi.PtReprojectStats of the last reproject(): pixels, pixels_hit, pixels_kept, samples_kept.  Synchronises."""
+        st = abi.PtReprojectStats()
+        self._check(self.lib.pt_reproject_stats(self._ctx, C.byref(st)))
+        return st
+
     def sample_counts(self):
         """(local_rows, width) fp32: the samples each pixel holds (accum's fourth channel)."""
         return self.accum()[..., 3]
