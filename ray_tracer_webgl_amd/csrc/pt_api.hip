@@ -30,6 +30,7 @@
 #include "pt_kernel_args.h"
 #include "pt_geom_plan.hpp"
 #include "pt_launch_plan.hpp"
+#include "pt_trace_table.hpp"
 #include "pt_tile_order.hpp"
 #include "pt_error_plan.hpp"
 #include "pt_reproject_plan.hpp"
@@ -40,7 +41,7 @@
 // the kernels every context uses are compiled into this object (no -fgpu-rdc needed); the opt-in builds
 // (Russian roulette, measuring twins) are the translation unit pt_kernels_extra.hip, the debug-overlay builds
 // pt_kernels_debug.hip — code objects of their own, which the HIP runtime loads when one of their kernels is first
-// asked for (extra_kernel, debug_kernel below)
+// asked for (cell_kernel below)
 #include "pt_kernels.hip"
 
 static thread_local std::string g_create_error;
@@ -465,82 +466,22 @@ Staging grid_build(const pt_ctx* c) {
   return grid_staging(ptscene::staged_cells(g), g.n_entries, walk_lds_room(), c->grid_cells_build, fit_state(c));
 }
 
-// a kernel of pt_kernels_extra.hip; its first use loads that code object and lifts its dynamic-LDS limit
-const void* extra_kernel(int device, int id) {
-  static std::once_flag once[64][PT_X_COUNT];  // (function attributes belong to a device: the context's is current here)
-  const void* k = pt_extra_kernel(id);
-  if (k)
-    std::call_once(once[device & 63][id], [k] {  // (every caller returns with the attribute set: no launch can overtake it)
-      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
+// The handle of a table cell's kernel (pt_trace_table.hpp), from its object's accessor.  The first use of a kernel of the three
+// opt-in objects (roulette builds and twins, overlay builds, feature builds) loads that code object and lifts the kernel's
+// dynamic-LDS limit, once per device and id; the main kernels' limit is lifted at pt_create, the small-list kernels need none.
+const void* cell_kernel(int device, const TraceCell& k) {
+#define PT_TRACE_ACCESSOR_OF(object, accessor, n_ids) accessor,
+  static const void* (*const accessors[OBJ_COUNT])(int) = {PT_TRACE_OBJECTS(PT_TRACE_ACCESSOR_OF)};
+  static std::once_flag once[64][OBJ_COUNT][PT_EXTRA_COUNT];  // (function attributes belong to a device: the context's is current here)
+  static_assert(PT_EXTRA_COUNT >= PT_VARIANT_COUNT, "the extra object has the most ids");
+  const void* fn = accessors[k.object](k.id);
+  if (fn && k.object >= OBJ_EXTRA)
+    std::call_once(once[device & 63][k.object][k.id], [fn] {  // (every caller returns with the attribute set: no launch can overtake it)
+      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
       (void)hipGetLastError();  // a refused attribute only limits that kernel to the default 64 KiB; the launch code checks sizes
     });
-  return k;
+  return fn;
 }
-
-// a kernel of pt_kernels_debug.hip, likewise
-const void* debug_kernel(int device, int id) {
-  static std::once_flag once[64][PT_D_COUNT];
-  const void* k = pt_debug_kernel(id);
-  if (k)
-    std::call_once(once[device & 63][id], [k] {
-      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
-      (void)hipGetLastError();
-    });
-  return k;
-}
-
-// a kernel of pt_kernels_features.hip, likewise
-const void* feature_kernel(int device, int id) {
-  static std::once_flag once[64][PT_F_COUNT];
-  const void* k = pt_feature_kernel(id);
-  if (k)
-    std::call_once(once[device & 63][id], [k] {
-      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
-      (void)hipGetLastError();
-    });
-  return k;
-}
-
-// Every trace kernel, by how it reads the list (row) and which build runs (column), with the wave count it is built for
-// (its PT_BUILT_FOR).  A kernel of this object has `main`; one of pt_kernels_extra.hip a PT_X_* id (`extra`), one of
-// pt_kernels_small.hip the list length's remainder modulo four (`small`), one of pt_kernels_debug.hip a PT_D_* id (`debug`), one
-// of pt_kernels_features.hip a PT_F_* id (`feature`):
-// those four objects are loaded only when one of their kernels is first launched, so their handles are taken when an entry
-// is chosen, not here.  Where a way to read the list has no roulette build, no measuring twin, no overlay or no feature build, its
-// column holds the plain build, which then runs (the LDS list walk: pt_geom_plan.hpp steers roulette, overlay and feature
-// launches to the scalar row).
-struct TraceKernel { const void* main; int extra, small, waves; int debug = -1; int feature = -1; };
-// ROW_SMALL + list length % 4; ROW_BVH / ROW_GRID + what is staged in the LDS (bind_hierarchy, bind_grid); ROW_GRID itself is
-// the LDS-staged build on a grid of one layer along y, ROW_GRID_LAYERS the same build on any other grid (grid_walk_flat)
-enum TraceRow { ROW_LIST_LDS, ROW_SCALAR, ROW_SCALAR_NOLDS, ROW_SMALL, ROW_BVH = ROW_SMALL + 4, ROW_GRID = ROW_BVH + 3, ROW_GRID_LAYERS = ROW_GRID + 3,
-                ROW_COUNT };
-enum TraceBuild { BUILD_PLAIN, BUILD_RR, BUILD_TWIN, BUILD_DBG, BUILD_FEAT, BUILD_COUNT };
-
-template <class K>
-TraceKernel in_main(K* k, int waves) { return {reinterpret_cast<const void*>(k), -1, -1, waves}; }
-TraceKernel in_extra(int id, int waves = PT_WAVES_WALK) { return {nullptr, id, -1, waves}; }
-TraceKernel in_small(int rem) { return {nullptr, -1, rem, PT_WAVES_SMALL}; }
-TraceKernel in_debug(int id, int waves = PT_WAVES_WALK) { return {nullptr, -1, -1, waves, id}; }
-TraceKernel in_feature(int id, int waves = PT_WAVES_WALK) { return {nullptr, -1, -1, waves, -1, id}; }
-
-const TraceKernel kTraceKernels[ROW_COUNT][BUILD_COUNT] = {
-    // plain                                                roulette                                         measuring twin                                    debug overlay                    first-hit features
-    {in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),           in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),     in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),  in_main(pt_trace_kernel, PT_WAVES_LIST_LDS),  in_main(pt_trace_kernel, PT_WAVES_LIST_LDS)},
-    {in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),        in_extra(PT_X_SCALAR_RR, PT_WAVES_LIST),         in_main(pt_trace_kernel_scalar, PT_WAVES_LIST),  in_debug(PT_D_SCALAR, PT_WAVES_LIST),  in_feature(PT_F_SCALAR, PT_WAVES_LIST)},
-    {in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_extra(PT_X_SCALAR_NOLDS_RR, PT_WAVES_LIST),   in_main(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST),  in_debug(PT_D_SCALAR_NOLDS, PT_WAVES_LIST),  in_feature(PT_F_SCALAR_NOLDS, PT_WAVES_LIST)},
-    {in_small(0),                                           in_extra(PT_X_SMALL_RR + 0, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 0, PT_WAVES_SMALL),  in_feature(PT_F_SMALL + 0, PT_WAVES_SMALL)},
-    {in_small(1),                                           in_extra(PT_X_SMALL_RR + 1, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 1, PT_WAVES_SMALL),  in_feature(PT_F_SMALL + 1, PT_WAVES_SMALL)},
-    {in_small(2),                                           in_extra(PT_X_SMALL_RR + 2, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 2, PT_WAVES_SMALL),  in_feature(PT_F_SMALL + 2, PT_WAVES_SMALL)},
-    {in_small(3),                                           in_extra(PT_X_SMALL_RR + 3, PT_WAVES_SMALL),     in_extra(PT_X_SMALL_COUNT, PT_WAVES_SMALL),  in_debug(PT_D_SMALL + 3, PT_WAVES_SMALL),  in_feature(PT_F_SMALL + 3, PT_WAVES_SMALL)},
-    {in_main(pt_trace_kernel_bvh, PT_WAVES_WALK),           in_extra(PT_X_BVH_RR),                           in_extra(PT_X_BVH_COUNT),  in_debug(PT_D_BVH),  in_feature(PT_F_BVH)},
-    {in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),     in_extra(PT_X_BVH_NODES_RR),                     in_main(pt_trace_kernel_bvh_nodes, PT_WAVES_WALK),  in_debug(PT_D_BVH_NODES),  in_feature(PT_F_BVH_NODES)},
-    {in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),      in_extra(PT_X_BVH_GMEM_RR),                      in_main(pt_trace_kernel_bvh_gmem, PT_WAVES_WALK),  in_debug(PT_D_BVH_GMEM),  in_feature(PT_F_BVH_GMEM)},
-    {in_main(pt_trace_kernel_grid, PT_WAVES_WALK),          in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_COUNT),  in_debug(PT_D_GRID),  in_feature(PT_F_GRID)},
-    {in_main(pt_trace_kernel_grid_cells, PT_WAVES_WALK),    in_extra(PT_X_GRID_CELLS_RR),                    in_extra(PT_X_GRID_CELLS_COUNT, PT_WAVES_TWIN_CELLS),  in_debug(PT_D_GRID_CELLS),  in_feature(PT_F_GRID_CELLS)},
-    {in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),     in_extra(PT_X_GRID_GMEM_RR),                     in_main(pt_trace_kernel_grid_gmem, PT_WAVES_WALK),  in_debug(PT_D_GRID_GMEM),  in_feature(PT_F_GRID_GMEM)},
-    // (the roulette, overlay and feature builds walk three axes on a one-layer grid too — right on any grid, and not measured: one build each serves both rows)
-    {in_main(pt_trace_kernel_grid_layers, PT_WAVES_WALK),   in_extra(PT_X_GRID_RR),                          in_extra(PT_X_GRID_LAYERS_COUNT),  in_debug(PT_D_GRID),  in_feature(PT_F_GRID)},
-};
 
 } // namespace
 
@@ -604,8 +545,7 @@ static int create_common(pt_ctx** out, int device, uint32_t width, uint32_t heig
   const double t_small_allocs = host_ms();
   // allow the trace kernels to use the CU's whole 160 KiB LDS for big sphere lists
   // (the first hipFuncSetAttribute of a process also LOADS this translation unit's code object onto the device)
-  for (const auto& row : kTraceKernels)
-    if (row[BUILD_PLAIN].main) (void)hipFuncSetAttribute(row[BUILD_PLAIN].main, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
+  for (int id = 0; id < PT_MAIN_COUNT; id++) (void)hipFuncSetAttribute(pt_main_kernel(id), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
   (void)hipGetLastError(); // a refused attribute only limits that kernel to the default 64 KiB; the launch code checks sizes
   const double t_code = host_ms();
   int rc = ensure_buffers(c);
@@ -1169,39 +1109,31 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   // lane of a walk kernel's workgroup)
   const bool walk = path == PT_GEOM_BVH || path == PT_GEOM_GRID;
   size_t scene = 0;
-  int row = 0;
+  Staging st;
   if (walk) {
-    const Staging st = path == PT_GEOM_BVH ? bind_hierarchy(c, A) : bind_grid(c, A);
+    st = path == PT_GEOM_BVH ? bind_hierarchy(c, A) : bind_grid(c, A);
     scene = st.bytes;
-    row = path == PT_GEOM_BVH ? ROW_BVH + st.kind : ROW_GRID + st.kind - 1;
-    if (path == PT_GEOM_GRID && st.kind == 1 && !grid_walk_flat(st.kind, c->grid.head.n[1])) row = ROW_GRID_LAYERS;
     A.lds_scene_bytes = (uint32_t)scene;
   } else {
     // the LDS copy exists whenever the list fits; the scalar and small-list walks only change how the
     // SCAN reads (their per-lane gathers — shading, tail mode — still come from the copy)
-    const bool have_lds = c->list.n <= PT_MAX_SPHERES_LDS;
-    scene = have_lds ? (size_t)PT_LDS_ENTRIES(c->list.n) * 16 : 0;
-    row = path == PT_GEOM_SMALL ? ROW_SMALL + (int)(c->list.n & 3u)
-                                : (path == PT_GEOM_LDS ? ROW_LIST_LDS : (have_lds ? ROW_SCALAR : ROW_SCALAR_NOLDS));
+    scene = c->list.n <= PT_MAX_SPHERES_LDS ? (size_t)PT_LDS_ENTRIES(c->list.n) * 16 : 0;
   }
-  const int build = feat ? BUILD_FEAT : (dbg ? BUILD_DBG : (rr ? BUILD_RR : (c->count_work ? BUILD_TWIN : BUILD_PLAIN)));
+  const int row = trace_row(path, c->list.n, st.kind, c->grid.head.n[1]);
+  const int build = trace_build(feat, dbg, rr, c->count_work);
   if (feat) {  // one deterministic segment per pixel into the planes; the overlay and roulette do not act
     A.uuid = c->list.uuid.get();
     A.slot_uuid = path == PT_GEOM_BVH ? c->bvh.uuid.get() : (path == PT_GEOM_GRID ? c->grid.uuid.get() : nullptr);
     A.slab = reinterpret_cast<float*>(c->d_feat.get());
     A.spp = 1; A.max_depth = 1; A.rr_min_depth = 0;
   }
-  // the two-axis walk (pt_trace_kernel_grid and its twin; the roulette and overlay builds of that row walk three axes) reads
-  // the ring layout; it is what `scene` was sized for (staged_cells)
-  if (walk && path == PT_GEOM_GRID && row == ROW_GRID && (build == BUILD_PLAIN || build == BUILD_TWIN)) {
+  // the two-axis walk reads the ring layout; it is what `scene` was sized for (staged_cells)
+  if (reads_ring_layout(row, build)) {
     A.grid_cells = c->grid.ring.get();
     A.n_cells = (uint32_t)ptrec::ring_cells(c->grid.head.n[0], c->grid.head.n[2]);
   }
-  const TraceKernel& tk = kTraceKernels[row][build];
-  const void* kfn = tk.main ? tk.main
-                            : (tk.feature >= 0 ? feature_kernel(c->device, tk.feature)
-                            : tk.debug >= 0 ? debug_kernel(c->device, tk.debug)
-                                             : (tk.extra >= 0 ? extra_kernel(c->device, tk.extra) : pt_small_kernel((unsigned)tk.small)));
+  const TraceCell& tk = kTraceKernels[row][build];
+  const void* kfn = cell_kernel(c->device, tk);
   c->last_build = build;
   const uint32_t block = walk ? walk_block_threads(kfn, tk.waves, scene, kWalkLdsMax, knobs.bvh_block) : list_block_threads(scene);
   const size_t lds = walk ? scene + (size_t)PT_PARK_STRIDE * 4 * block : scene;
@@ -2084,7 +2016,7 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     if (c->feat_on) return PT_OK;
     // (asking for a kernel's attributes loads the feature builds' code object now: a set-up call's work, not a render call's)
     hipFuncAttributes attr;
-    PT_HIP(c, hipFuncGetAttributes(&attr, pt_feature_kernel(PT_F_SCALAR)));
+    PT_HIP(c, hipFuncGetAttributes(&attr, pt_feature_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar))));
     c->feat_on = true;
     int rc = ensure_buffers(c);
     if (rc == PT_OK && !c->uuid_valid && c->have_spheres) rc = upload_uuids(c, c->list.host.uuid);  // the scene in place

@@ -1,28 +1,89 @@
-// pt_extra.h — the kernels of pt_kernels_extra.hip and pt_kernels_small.hip (code objects of their own): how pt_api.hip reaches them.
+// pt_extra.h — THE LIST of the trace kernel's builds, and how pt_api.hip reaches the kernels of every code object.
+//
+// Each of the 55 trace kernels is stated once, below: its symbol, the waves per SIMD it is built for (PT_BUILT_FOR,
+// pt_kernel_args.h) and its build type (pt_trace_body.hpp).  From an entry come the kernel's definition and the `case` of its
+// object's accessor (pt_trace_body.hpp PT_TRACE_KERNEL...), its id, and its cell of the host's table with the same wave count
+// and the symbol as a string (pt_trace_table.hpp).  Plain preprocessor and enums: the device units and the host-only table
+// header read the same text.  A list's order is the order of the definitions in its translation unit.
+//
+// HOW TO ADD A COLUMN of builds (one more flag on every variant row): the flag and its adaptor in pt_trace_body.hpp; a new
+// pt_kernels_<name>.hip that is its header comment, PT_VARIANT_ROWS(PT_TRACE_VARIANT, _<suffix>, <Adaptor>) and an accessor
+// over PT_VARIANT_ROWS(PT_TRACE_VARIANT_CASE, ...), added to the Makefile's SRCS; one entry in PT_TRACE_OBJECTS here; and
+// in pt_trace_table.hpp one value of TraceBuild, one cell expansion, one suffix in PT_TABLE_ROW and the option's place in
+// trace_build().
 #pragma once
-enum {
-  PT_X_BVH_COUNT = 0, PT_X_GRID_COUNT, PT_X_GRID_CELLS_COUNT, PT_X_SMALL_COUNT,
-  PT_X_SMALL_RR /* + list length % 4: four builds */, PT_X_SCALAR_RR = PT_X_SMALL_RR + 4, PT_X_SCALAR_NOLDS_RR, PT_X_BVH_RR, PT_X_BVH_NODES_RR, PT_X_BVH_GMEM_RR,
-  PT_X_GRID_RR, PT_X_GRID_CELLS_RR, PT_X_GRID_GMEM_RR, PT_X_GRID_LAYERS_COUNT, PT_X_COUNT
-};
-// the kernel's host-side handle (what hipLaunchKernel takes); asking for it loads nothing yet
-extern "C" const void* pt_extra_kernel(int id);
-// pt_kernels_small.hip (a code object of its own): the small-list kernel built for this list length's remainder modulo four
-extern "C" const void* pt_small_kernel(unsigned n_spheres);
-// pt_kernels_debug.hip (a code object of its own): the debug-overlay builds (pt_set_debug_overlay), one per launch that has a
-// roulette build
-enum {
-  PT_D_SMALL = 0 /* + list length % 4: four builds */, PT_D_SCALAR = PT_D_SMALL + 4, PT_D_SCALAR_NOLDS, PT_D_BVH, PT_D_BVH_NODES, PT_D_BVH_GMEM,
-  PT_D_GRID, PT_D_GRID_CELLS, PT_D_GRID_GMEM, PT_D_COUNT
-};
-extern "C" const void* pt_debug_kernel(int id);
-// pt_kernels_features.hip (a code object of its own): the first-hit feature builds (pt_render_features), one per launch that has a
-// roulette build
-enum {
-  PT_F_SMALL = 0 /* + list length % 4: four builds */, PT_F_SCALAR = PT_F_SMALL + 4, PT_F_SCALAR_NOLDS, PT_F_BVH, PT_F_BVH_NODES, PT_F_BVH_GMEM,
-  PT_F_GRID, PT_F_GRID_CELLS, PT_F_GRID_GMEM, PT_F_COUNT
-};
-extern "C" const void* pt_feature_kernel(int id);
+
+// pt_kernels.hip (compiled into pt_api.hip's object): the list and walk kernels
+#define PT_MAIN_KERNELS(X)                                          \
+  X(pt_trace_kernel,              PT_WAVES_LIST_LDS, ListLds)       \
+  X(pt_trace_kernel_scalar,       PT_WAVES_LIST,     Scalar)        \
+  X(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST,     ScalarNolds)   \
+  X(pt_trace_kernel_bvh,          PT_WAVES_WALK,     Bvh)           \
+  X(pt_trace_kernel_bvh_nodes,    PT_WAVES_WALK,     BvhNodes)      \
+  X(pt_trace_kernel_bvh_gmem,     PT_WAVES_WALK,     BvhGmem)       \
+  X(pt_trace_kernel_grid,         PT_WAVES_WALK,     Grid)          \
+  X(pt_trace_kernel_grid_layers,  PT_WAVES_WALK,     GridLayers)    \
+  X(pt_trace_kernel_grid_cells,   PT_WAVES_WALK,     GridCells)     \
+  X(pt_trace_kernel_grid_gmem,    PT_WAVES_WALK,     GridGmem)
+
+// pt_kernels_small.hip: the small-list kernels, one per list length modulo four
+#define PT_SMALL_KERNELS(X)                                  \
+  X(pt_trace_kernel_small_t0, PT_WAVES_SMALL, Small<0>)      \
+  X(pt_trace_kernel_small_t1, PT_WAVES_SMALL, Small<1>)      \
+  X(pt_trace_kernel_small_t2, PT_WAVES_SMALL, Small<2>)      \
+  X(pt_trace_kernel_small_t3, PT_WAVES_SMALL, Small<3>)
+
+// pt_kernels_extra.hip: the measuring twins (PT_OPT_COUNT_WORK); the small-list twin tests the padding (no TAIL)
+#define PT_TWIN_KERNELS(X)                                                          \
+  X(pt_trace_kernel_bvh_count,         PT_WAVES_WALK,       Count<Bvh>)             \
+  X(pt_trace_kernel_grid_count,        PT_WAVES_WALK,       Count<Grid>)            \
+  X(pt_trace_kernel_grid_layers_count, PT_WAVES_WALK,       Count<GridLayers>)      \
+  X(pt_trace_kernel_grid_cells_count,  PT_WAVES_TWIN_CELLS, Count<GridCells>)       \
+  X(pt_trace_kernel_small_count,       PT_WAVES_SMALL,      Count<Small<-1>>)
+
+// The VARIANT ROWS: the twelve ways to read the list that have a Russian-roulette build (pt_kernels_extra.hip, suffix _rr), a
+// debug-overlay build (pt_kernels_debug.hip, _dbg) and a first-hit feature build (pt_kernels_features.hip, _feat), each the
+// row's build under one adaptor with the same launch shape as its namesake.  The LDS list walk has none (pt_geom_plan.hpp
+// steers those launches to the scalar row), and a one-layer grid is walked along three axes by the ..._grid_<suffix> build —
+// right on any grid, and not measured: one build each serves the rows `grid` and `grid_layers`.
+// X(stem, waves, row type, what the expansion passes on: suffix, adaptor)
+#define PT_VARIANT_ROWS(X, ...)                                                \
+  X(pt_trace_kernel_small_t0,     PT_WAVES_SMALL, Small<0>,    __VA_ARGS__)    \
+  X(pt_trace_kernel_small_t1,     PT_WAVES_SMALL, Small<1>,    __VA_ARGS__)    \
+  X(pt_trace_kernel_small_t2,     PT_WAVES_SMALL, Small<2>,    __VA_ARGS__)    \
+  X(pt_trace_kernel_small_t3,     PT_WAVES_SMALL, Small<3>,    __VA_ARGS__)    \
+  X(pt_trace_kernel_scalar,       PT_WAVES_LIST,  Scalar,      __VA_ARGS__)    \
+  X(pt_trace_kernel_scalar_nolds, PT_WAVES_LIST,  ScalarNolds, __VA_ARGS__)    \
+  X(pt_trace_kernel_bvh,          PT_WAVES_WALK,  Bvh,         __VA_ARGS__)    \
+  X(pt_trace_kernel_bvh_nodes,    PT_WAVES_WALK,  BvhNodes,    __VA_ARGS__)    \
+  X(pt_trace_kernel_bvh_gmem,     PT_WAVES_WALK,  BvhGmem,     __VA_ARGS__)    \
+  X(pt_trace_kernel_grid,         PT_WAVES_WALK,  GridLayers,  __VA_ARGS__)    \
+  X(pt_trace_kernel_grid_cells,   PT_WAVES_WALK,  GridCells,   __VA_ARGS__)    \
+  X(pt_trace_kernel_grid_gmem,    PT_WAVES_WALK,  GridGmem,    __VA_ARGS__)
+
+// The ids an accessor takes.  A variant's id is its row, in each of the three objects that hold variants; the twins of
+// pt_kernels_extra.hip follow its roulette builds.
+#define PT_KERNEL_ID(sym) PT_ID_##sym
+#define PT_VARIANT_ID(stem) PT_VARIANT_##stem
+#define PT_KERNEL_ID_ENTRY(sym, waves, Build) PT_KERNEL_ID(sym),
+#define PT_VARIANT_ID_ENTRY(stem, waves, Row, ...) PT_VARIANT_ID(stem),
+enum { PT_MAIN_KERNELS(PT_KERNEL_ID_ENTRY) PT_MAIN_COUNT };
+enum { PT_SMALL_KERNELS(PT_KERNEL_ID_ENTRY) PT_SMALL_COUNT };
+enum { PT_VARIANT_ROWS(PT_VARIANT_ID_ENTRY, ) PT_VARIANT_COUNT };
+enum { PT_ROULETTE_LAST = PT_VARIANT_COUNT - 1, PT_TWIN_KERNELS(PT_KERNEL_ID_ENTRY) PT_EXTRA_COUNT };
+
+// The five code objects that hold trace kernels and the accessor of each: the kernel's host-side handle (what hipLaunchKernel
+// takes) by id, NULL for an id the object does not have.  Asking for a handle loads nothing yet; the HIP runtime loads a code
+// object when one of its kernels is first used.  X(object, accessor, number of ids)
+#define PT_TRACE_OBJECTS(X)                             \
+  X(MAIN,    pt_main_kernel,    PT_MAIN_COUNT)          \
+  X(SMALL,   pt_small_kernel,   PT_SMALL_COUNT)         \
+  X(EXTRA,   pt_extra_kernel,   PT_EXTRA_COUNT)         \
+  X(DEBUG,   pt_debug_kernel,   PT_VARIANT_COUNT)       \
+  X(FEATURE, pt_feature_kernel, PT_VARIANT_COUNT)
+#define PT_TRACE_ACCESSOR_DECL(object, accessor, n_ids) extern "C" const void* accessor(int id);
+PT_TRACE_OBJECTS(PT_TRACE_ACCESSOR_DECL)
+
 // pt_kernels_error.hip (a code object of its own): the error estimate's fold, read-out and tile kernels (PT_OPT_ERROR_ESTIMATE), and
 // a partial round's fold and tile table (pt_render_adaptive), and the filtered read-outs (pt_resolve_filtered,
 // pt_resolve_filtered_patch)

@@ -178,7 +178,7 @@ constexpr size_t kWalkLdsMax = (size_t)PT_LDS_ENTRIES(PT_MAX_SPHERES_LDS) * 16;
 constexpr size_t walk_lds_room() { return kWalkLdsMax - (size_t)PT_PARK_STRIDE * 4 * 1024; }
 
 struct Staging {
-  int kind = 0;      // grid: the build (1 / 2 / 3); hierarchy: the kernel's row past ROW_BVH (0 / 1 / 2)
+  int kind = 0;      // grid: the build (1 / 2 / 3); hierarchy: what is staged (0 / 1 / 2); pt_trace_table.hpp trace_row makes the kernel's row of it
   size_t bytes = 0;  // staged in the LDS
 };
 

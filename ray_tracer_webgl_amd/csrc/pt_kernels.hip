@@ -34,55 +34,35 @@
 // __builtin_fmaf.
 #include "pt_trace_body.hpp"
 
-// blockDim.x is a multiple of 64 (256 normally, 1024 when the staged list is large and only one
-// workgroup fits per CU); dynamic LDS = PT_LDS_ENTRIES(n_spheres) * 16 bytes.
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_LIST_LDS) void pt_trace_kernel(const PtKernelArgs A) {
-  pt_trace_body<true, true>(A);
-}
-
-// the scalar-load walk (PT_GEOM_SCALAR) with the LDS copy kept for the per-lane gathers
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_LIST) void pt_trace_kernel_scalar(const PtKernelArgs A) {
-  pt_trace_body<false, true>(A);
-}
-
-// lists beyond the LDS (10 232 < n <= 65 528): scalar-load walk, gathers from global memory
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_LIST) void pt_trace_kernel_scalar_nolds(const PtKernelArgs A) {
-  pt_trace_body<false, false>(A);
-}
-
+// The ten list and walk kernels: the list PT_MAIN_KERNELS of pt_extra.h (symbol, waves per SIMD, build type), expanded here
+// into their definitions and into the accessor pt_api.hip reaches them through.
+//   pt_trace_kernel              blockDim.x is a multiple of 64 (256 normally, 1024 when the staged list is large and only one
+//                                workgroup fits per CU); dynamic LDS = PT_LDS_ENTRIES(n_spheres) * 16 bytes
+//   ..._scalar                   the scalar-load walk (PT_GEOM_SCALAR) with the LDS copy kept for the per-lane gathers
+//   ..._scalar_nolds             lists beyond the LDS (10 232 < n <= 65 528): scalar-load walk, gathers from global memory
+//   ..._bvh                      the hierarchy walk (PT_GEOM_BVH): nodes + slots staged in LDS (dynamic LDS =
+//                                PT_BVH_LDS_BYTES32(n_nodes, n_slots) + parking)
+//   ..._bvh_nodes                nodes staged (dynamic LDS = (n_nodes + 1) * 16 bytes + parking), slots read from global memory
+//   ..._bvh_gmem                 nodes and slots read from global memory / L2 when they do not fit
+//   ..._grid, ..._grid_layers    the grid walk (PT_GEOM_GRID), cells + entries staged in LDS: pt_trace_kernel_grid walks a grid of
+//                                ONE layer along y with the two-axis walk of pt_grid_walk.hpp — the common large scene, a field
+//                                on a ground —, pt_trace_kernel_grid_layers any other with the three-axis walk; the host chooses
+//                                by grid_n[1], pt_geom_plan.hpp grid_walk_flat
+//   ..._grid_cells, ..._grid_gmem  cells only staged, or nothing
 // The walk kernels are latency-bound, not issue-bound: for scenes small enough that LDS
 // leaves room for them, six waves per SIMD (80 VGPRs) beat five with no spills (config 2: -5 %).
 // The kernels for larger scenes are held to four waves by their LDS footprint and keep their
 // registers.
 // (PT_BUILT_FOR / PT_WAVES_*: pt_kernel_args.h — what a kernel is built for is what the host launches)
-// the hierarchy walk (PT_GEOM_BVH): nodes + slots staged in LDS (dynamic LDS =
-// PT_BVH_LDS_BYTES32(n_nodes, n_slots) + parking), or read from global memory / L2 when they do not fit
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_bvh(const PtKernelArgs A) {
-  pt_trace_body<false, false, 1>(A);
+PT_MAIN_KERNELS(PT_TRACE_KERNEL)
+
+extern "C" const void* pt_main_kernel(int id) {
+  switch (id) {
+    PT_MAIN_KERNELS(PT_TRACE_KERNEL_CASE)
+    default: return nullptr;
+  }
 }
-// nodes staged (dynamic LDS = (n_nodes + 1) * 16 bytes + parking), slots read from global memory
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_bvh_nodes(const PtKernelArgs A) {
-  pt_trace_body<false, false, 2>(A);
-}
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_bvh_gmem(const PtKernelArgs A) {
-  pt_trace_body<false, false, 3>(A);
-}
-// the grid walk (PT_GEOM_GRID): cells + entries staged in LDS, cells only, or nothing
-// (cells + entries staged: pt_trace_kernel_grid walks a grid of ONE layer along y with the two-axis walk of pt_grid_walk.hpp
-// — the common large scene, a field on a ground —, pt_trace_kernel_grid_layers any other with the three-axis walk; the host
-// chooses by grid_n[1], pt_geom_plan.hpp grid_walk_flat)
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_grid(const PtKernelArgs A) {
-  pt_trace_body<false, false, 4, false, false, -1, true>(A);
-}
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_grid_layers(const PtKernelArgs A) {
-  pt_trace_body<false, false, 4>(A);
-}
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_grid_cells(const PtKernelArgs A) {
-  pt_trace_body<false, false, 5>(A);
-}
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_WALK) void pt_trace_kernel_grid_gmem(const PtKernelArgs A) {
-  pt_trace_body<false, false, 6>(A);
-}
+
 // --------------------------------------------------------------------------------------------
 // Work-queue order for the NEXT launch: tiles sorted by the segment count of their HEAVIEST
 // item in the previous launch (pass 0), largest first.  A short launch cannot end before its

@@ -9,27 +9,15 @@
 // spheres (State::default; BASELINE config 4 has nine too) pay one test in their last group instead of four:
 // config 4 -6.2 %, State::default 16 x 25 spp -5.6 %, its 1-spp frame -2.7 % against the build that tests the
 // padding (A/B on one device, profiles/r04_ab_runs.txt).
+// The four are the list PT_SMALL_KERNELS of pt_extra.h (symbol, waves per SIMD, build type), expanded here into their
+// definitions and into the accessor pt_api.hip reaches them through.
 #include "pt_trace_body.hpp"
-#include "pt_extra.h"
 
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_SMALL) void pt_trace_kernel_small_t0(const PtKernelArgs A) {
-  pt_trace_body<false, true, 7, false, false, 0>(A);
-}
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_SMALL) void pt_trace_kernel_small_t1(const PtKernelArgs A) {
-  pt_trace_body<false, true, 7, false, false, 1>(A);
-}
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_SMALL) void pt_trace_kernel_small_t2(const PtKernelArgs A) {
-  pt_trace_body<false, true, 7, false, false, 2>(A);
-}
-extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(PT_WAVES_SMALL) void pt_trace_kernel_small_t3(const PtKernelArgs A) {
-  pt_trace_body<false, true, 7, false, false, 3>(A);
-}
+PT_SMALL_KERNELS(PT_TRACE_KERNEL)
 
-extern "C" const void* pt_small_kernel(unsigned n_spheres) {
-  switch (n_spheres & 3u) {
-    case 0: return reinterpret_cast<const void*>(pt_trace_kernel_small_t0);
-    case 1: return reinterpret_cast<const void*>(pt_trace_kernel_small_t1);
-    case 2: return reinterpret_cast<const void*>(pt_trace_kernel_small_t2);
-    default: return reinterpret_cast<const void*>(pt_trace_kernel_small_t3);
+extern "C" const void* pt_small_kernel(int id) {
+  switch (id) {
+    PT_SMALL_KERNELS(PT_TRACE_KERNEL_CASE)
+    default: return nullptr;
   }
 }

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "pt_kernel_args.h"
+#include "pt_extra.h"
 #include "pt_arith.hpp"
 #include "pt_scene.hpp"
 #include "pt_refill.hpp"
@@ -19,16 +20,54 @@
 using namespace ptd;
 
 // --------------------------------------------------------------------------------------------
-// The path-tracing kernel body: one persistent wave working through (pixel, pass) items.
-// Template parameters: pt_scene.hpp `Scene`; COUNT = the measuring twin (tallies live); RR = the
-// opt-in Russian-roulette build (pt_shade.hpp); TAIL = the small-list builds' list remainder (pt_scene.hpp SMALL_TAIL);
-// FLAT_Y = the grid walk of a one-layer grid (pt_scene.hpp, pt_grid_walk.hpp); DBG = the opt-in debug-overlay build
-// (pt_shade.hpp); FEAT = the opt-in first-hit feature build (pt_render_features: one pinhole ray per pixel, its hit record
-// written to four planes, no scatter; pt_refill.hpp start_sample, pt_shade.hpp).
+// What a trace kernel is built as: a TYPE whose constants the body reads by name.  ptb::Defaults holds the defaults; a ROW type
+// says how the kernel reads the sphere list (pt_scene.hpp `Scene`) and an adaptor switches one flag on top of a row:
+//   SCAN_LDS, HAVE_LDS, WALK   pt_scene.hpp `Scene`
+//   COUNT    the measuring twin (tallies live)
+//   RR       the opt-in Russian-roulette build (pt_shade.hpp)
+//   TAIL     the small-list builds' list remainder (pt_scene.hpp SMALL_TAIL)
+//   FLAT_Y   the grid walk of a one-layer grid (pt_scene.hpp, pt_grid_walk.hpp)
+//   DBG      the opt-in debug-overlay build (pt_shade.hpp)
+//   FEAT     the opt-in first-hit feature build (pt_render_features: one pinhole ray per pixel, its hit record written to four
+//            planes, no scatter; pt_refill.hpp start_sample, pt_shade.hpp)
+// Which kernel is which row under which adaptor is stated once, in the lists of pt_extra.h.
 // --------------------------------------------------------------------------------------------
-template <bool SCAN_LDS, bool HAVE_LDS, int WALK = 0, bool COUNT = false, bool RR = false, int TAIL = -1, bool FLAT_Y = false, bool DBG = false, bool FEAT = false>
+namespace ptb {
+struct Defaults {
+  static constexpr bool SCAN_LDS = false, HAVE_LDS = false, COUNT = false, RR = false, FLAT_Y = false, DBG = false, FEAT = false;
+  static constexpr int WALK = 0, TAIL = -1;
+};
+struct ListLds : Defaults { static constexpr bool SCAN_LDS = true, HAVE_LDS = true; };
+struct Scalar : Defaults { static constexpr bool HAVE_LDS = true; };
+struct ScalarNolds : Defaults {};
+template <int T> struct Small : Defaults { static constexpr bool HAVE_LDS = true; static constexpr int WALK = 7, TAIL = T; };
+struct Bvh : Defaults { static constexpr int WALK = 1; };
+struct BvhNodes : Defaults { static constexpr int WALK = 2; };
+struct BvhGmem : Defaults { static constexpr int WALK = 3; };
+struct GridLayers : Defaults { static constexpr int WALK = 4; };
+struct Grid : GridLayers { static constexpr bool FLAT_Y = true; };
+struct GridCells : Defaults { static constexpr int WALK = 5; };
+struct GridGmem : Defaults { static constexpr int WALK = 6; };
+template <class Row> struct Count : Row { static constexpr bool COUNT = true; };
+template <class Row> struct Rr : Row { static constexpr bool RR = true; };
+template <class Row> struct Dbg : Row { static constexpr bool DBG = true; };
+template <class Row> struct Feat : Row { static constexpr bool FEAT = true; };
+}  // namespace ptb
+
+// One entry of a kernel list (pt_extra.h) as the kernel's definition and as the `case` of its object's accessor; a row of
+// the variant list is built under the column's adaptor and named with its suffix.
+#define PT_TRACE_KERNEL(sym, waves, Build) \
+  extern "C" __global__ __launch_bounds__(1024) PT_BUILT_FOR(waves) void sym(const PtKernelArgs A) { using namespace ptb; pt_trace_body<Build>(A); }
+#define PT_TRACE_KERNEL_CASE(sym, waves, Build) case PT_KERNEL_ID(sym): return reinterpret_cast<const void*>(sym);
+#define PT_TRACE_VARIANT(stem, waves, Row, suffix, Adaptor) PT_TRACE_KERNEL(stem##suffix, waves, Adaptor<Row>)
+#define PT_TRACE_VARIANT_CASE(stem, waves, Row, suffix, Adaptor) case PT_VARIANT_ID(stem): return reinterpret_cast<const void*>(stem##suffix);
+
+// The path-tracing kernel body: one persistent wave working through (pixel, pass) items.
+template <class B>
 __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
   using namespace ptk;
+  constexpr bool SCAN_LDS = B::SCAN_LDS, HAVE_LDS = B::HAVE_LDS, COUNT = B::COUNT, RR = B::RR, FLAT_Y = B::FLAT_Y, DBG = B::DBG, FEAT = B::FEAT;
+  constexpr int WALK = B::WALK, TAIL = B::TAIL;
   using S = Scene<SCAN_LDS, HAVE_LDS, WALK, TAIL, FLAT_Y>;
   S::stage(A);
 

@@ -51,7 +51,7 @@ def assert_planes_equal(got, ref, what):
 
 
 def kernel_of(t, path):
-    """the feature kernel a launch through the forced `path` is (kTraceKernels of csrc/pt_api.hip, by row)"""
+    """the feature kernel a launch through the forced `path` is (kTraceKernels of csrc/pt_trace_table.hpp, by row)"""
     assert t.last_trace_build() == abi.BUILD_FEATURES
     st = t.stats()
     if path == abi.PT_GEOM_AUTO:

@@ -46,7 +46,7 @@ def assert_bit_equal(got, ref, what):
 
 
 def kernel_of(t):
-    """the overlay kernel the last launch of this context was (kTraceKernels of csrc/pt_api.hip, by row)"""
+    """the overlay kernel the last launch of this context was (kTraceKernels of csrc/pt_trace_table.hpp, by row)"""
     assert t.last_trace_build() == abi.BUILD_DEBUG_OVERLAY
     st = t.stats()
     if st.geometry_path == abi.PT_GEOM_LDS:

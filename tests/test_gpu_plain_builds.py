@@ -1,4 +1,4 @@
-"""The plain column of kTraceKernels (csrc/pt_api.hip) — the fourteen kernels that ship and that bench.py times — and the five
+"""The plain column of kTraceKernels (csrc/pt_trace_table.hpp) — the fourteen kernels that ship and that bench.py times — and the five
 measuring twins, build by build and bit for bit.
 
 The roulette, overlay and feature columns each have such a matrix (test_gpu_roulette_exact.py, test_gpu_overlay.py,

@@ -52,7 +52,7 @@ def assert_bit_equal(got, ref, what):
 
 
 def kernel_of(st, roulette=True):
-    """the roulette kernel the last launch of this context was (kTraceKernels of csrc/pt_api.hip, by row), from PtStats"""
+    """the roulette kernel the last launch of this context was (kTraceKernels of csrc/pt_trace_table.hpp, by row), from PtStats"""
     assert roulette
     if st.geometry_path == abi.PT_GEOM_LDS:
         raise AssertionError("roulette through geometry path %d: the LDS list walk has no roulette build" % st.geometry_path)

@@ -1,9 +1,13 @@
 """tests/trace_builds.py — the tests' rule for "which kernel was that launch" — pinned to the library's rule
-(csrc/pt_geom_plan.hpp hierarchy_staging, grid_staging and walk_lds_room through tests/geom_plan_shim.cpp).  A kernel audit is
-worth what its naming is worth: a restatement of the staging arithmetic that drifts from the library's would let a test
-believe it reached a kernel that never ran.  CPU only."""
+(csrc/pt_geom_plan.hpp hierarchy_staging, grid_staging and walk_lds_room through tests/geom_plan_shim.cpp; the table of kernels,
+its rows and columns, csrc/pt_trace_table.hpp through tests/trace_table_shim.cpp).  A kernel audit is worth what its naming is
+worth: a restatement of the staging arithmetic or of the table that drifts from the library's would let a test believe it
+reached a kernel that never ran.  CPU only."""
 import ctypes as C
 import itertools
+import os
+import subprocess
+import tempfile
 
 import pytest
 
@@ -135,3 +139,108 @@ def test_rows_twins_and_the_columns_with_one_grid_build():
                 Stats(abi.PT_GEOM_GRID, 484, entries=798, build=2, flat=1)):
         with pytest.raises(AssertionError):
             tb.row_of(bad)
+
+
+# ---- the table itself (csrc/pt_trace_table.hpp through tests/trace_table_shim.cpp): which symbol sits in which cell, built for
+# ---- how many waves, and the row, the column and the ring layout of a launch
+
+TABLE_SHIM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "trace_table_shim.cpp")
+COLUMNS = (abi.BUILD_PLAIN, abi.BUILD_ROULETTE, abi.BUILD_TWIN, abi.BUILD_DEBUG_OVERLAY, abi.BUILD_FEATURES)
+
+
+@pytest.fixture(scope="module")
+def table():
+    so = os.path.join(tempfile.mkdtemp(prefix="trace_table_"), "libtrace_table_shim.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Werror", TABLE_SHIM, "-o", so])
+    lib = C.CDLL(so)
+    IP = C.POINTER(C.c_int)
+    lib.tt_shape.restype, lib.tt_shape.argtypes = None, [IP]
+    lib.tt_objects.restype, lib.tt_objects.argtypes = C.c_int, [IP]
+    lib.tt_cell.restype, lib.tt_cell.argtypes = C.c_char_p, [C.c_int, C.c_int, IP]
+    lib.tt_row.restype, lib.tt_row.argtypes = C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_uint32]
+    lib.tt_build.restype, lib.tt_build.argtypes = C.c_int, [C.c_int] * 4
+    lib.tt_reads_ring_layout.restype, lib.tt_reads_ring_layout.argtypes = C.c_int, [C.c_int, C.c_int]
+    return lib
+
+
+def lib_cell(lib, row, build):
+    """(name, object, id, waves) of a cell"""
+    out = (C.c_int * 3)()
+    return (lib.tt_cell(row, build, out).decode(),) + tuple(out)
+
+
+def lib_row(lib, st):
+    """the library's row for the launch the `Stats` describe: the staging kind as the library's own staging rule gives it (pinned
+    above), a flat grid as one layer along y"""
+    kind = 0
+    if st.geometry_path == abi.PT_GEOM_BVH:
+        kind = tb.hierarchy_staging(st.bvh_nodes, st.bvh_slots)[0]
+    if st.geometry_path == abi.PT_GEOM_GRID:
+        kind = st.grid_kernel_build
+    return lib.tt_row(st.geometry_path, st.n_spheres, kind, 1 if st.grid_walk_flat else 3)
+
+
+def test_every_case_names_the_librarys_cell_in_every_column(table):
+    assert len(ROWS) == 18
+    for st, _, _ in ROWS:
+        r, row = lib_row(table, st), tb.row_of(st)
+        plain = "" if row == "list_lds" else "_" + row
+        twin = tb.twin_of(row)
+        want = {
+            abi.BUILD_PLAIN: plain,
+            abi.BUILD_TWIN: "_" + twin if twin else plain,
+            abi.BUILD_ROULETTE: "_" + tb.build_of(st, "_rr"),
+            abi.BUILD_DEBUG_OVERLAY: "_" + tb.build_of(st, "_dbg"),
+            abi.BUILD_FEATURES: "_" + tb.build_of(st, "_feat"),
+        }
+        if row == "list_lds":  # no roulette, overlay or feature build: the plain kernel in every column
+            want = dict.fromkeys(COLUMNS, "")
+        for col in COLUMNS:
+            assert lib_cell(table, r, col)[0] == "pt_trace_kernel" + want[col], (row, col)
+
+
+def waves_of(name):
+    """the waves per SIMD a kernel is built for, by its family (csrc/pt_kernel_args.h PT_WAVES_*)"""
+    stem = name[len("pt_trace_kernel"):]
+    if stem == "":
+        return 6
+    if stem == "_grid_cells_count":
+        return 4
+    return 7 if stem.startswith(("_scalar", "_small")) else 6
+
+
+def test_the_whole_table(table):
+    shape = (C.c_int * 2)()
+    table.tt_shape(shape)
+    assert tuple(shape) == (14, 5) == (len(tb.ROWS), len(COLUMNS))
+    ids = (C.c_int * 16)()
+    n_objects = table.tt_objects(ids)
+    assert n_objects == 5 and list(ids[:5]) == [10, 4, 17, 12, 12]  # main, small, extra, debug, features
+    cells = {(r, c): lib_cell(table, r, c) for r in range(14) for c in COLUMNS}
+    by_name = {}
+    for name, obj, kid, waves in cells.values():
+        assert name.startswith("pt_trace_kernel") and waves == waves_of(name), (name, waves)
+        assert by_name.setdefault(name, (obj, kid)) == (obj, kid), name   # one kernel, one object and id
+    assert len(by_name) == 55 == 10 + 4 + 17 + 12 + 12
+    assert len(set(by_name.values())) == 55                                # ... and one id, one kernel
+    # every id of every object is used by some cell
+    assert set(by_name.values()) == {(obj, kid) for obj in range(5) for kid in range(ids[obj])}
+    assert {n for n, _, _, w in cells.values() if w == 4} == {"pt_trace_kernel_grid_cells_count"}
+    # the names are the tests' names: every plain row, twin and variant of tests/trace_builds.py, nothing else
+    variants = sorted({"grid" if r == "grid_layers" else r for r in tb.ROWS if r != "list_lds"})
+    want = {"pt_trace_kernel"} | {"pt_trace_kernel_" + r for r in tb.ROWS if r != "list_lds"} | {"pt_trace_kernel_" + t for t in tb.TWINS}
+    want |= {"pt_trace_kernel_%s%s" % (v, s) for v in variants for s in ("_rr", "_dbg", "_feat")}
+    assert set(by_name) == want and len(variants) == 12
+    # the ring layout: the two-axis walk's two kernels
+    ring = [(r, c) for r in range(14) for c in COLUMNS if table.tt_reads_ring_layout(r, c)]
+    assert sorted(cells[rc][0] for rc in ring) == ["pt_trace_kernel_grid", "pt_trace_kernel_grid_count"] and len(ring) == 2
+    assert sorted(c for _, c in ring) == [abi.BUILD_PLAIN, abi.BUILD_TWIN]
+
+
+def test_column_precedence(table):
+    """features > overlay > roulette > count-work > plain"""
+    for feat, dbg, rr, count in itertools.product((0, 1), repeat=4):
+        want = (abi.BUILD_FEATURES if feat else abi.BUILD_DEBUG_OVERLAY if dbg else abi.BUILD_ROULETTE if rr
+                else abi.BUILD_TWIN if count else abi.BUILD_PLAIN)
+        assert table.tt_build(feat, dbg, rr, count) == want, (feat, dbg, rr, count)
+    assert COLUMNS == (0, 1, 2, 3, 4)

@@ -1,4 +1,4 @@
-"""Which trace kernel a launch was: the row of kTraceKernels (csrc/pt_api.hip), read from PtStats after the launch.
+"""Which trace kernel a launch was: the row of kTraceKernels (csrc/pt_trace_table.hpp), read from PtStats after the launch.
 
 One place for the arithmetic that decides what a walk kernel stages in the LDS (csrc/pt_geom_plan.hpp hierarchy_staging and
 grid_staging, the sizes of csrc/pt_kernel_args.h), so that the tests which audit the kernels they reached — the plain builds and
