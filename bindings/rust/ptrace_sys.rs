@@ -108,6 +108,8 @@ extern "C" {
     pub fn pt_reproject(ctx: *mut PtCtx, options: *const PtReprojectOptions) -> c_int;
     pub fn pt_reproject_stats(ctx: *mut PtCtx, out: *mut PtReprojectStats) -> c_int;
     pub fn pt_reproject_constants(prev: *const PtParams, tolerance_px: f32, out16: *mut f32) -> c_int;
+    // pt_reproject that also carries the error estimate's state (needs PT_OPT_ERROR_ESTIMATE too): the same accumulation bits
+    pub fn pt_reproject_estimate(ctx: *mut PtCtx, options: *const PtReprojectOptions) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;

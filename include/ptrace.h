@@ -110,7 +110,8 @@ enum {
   PT_OPT_REPROJECT = 9,   /* 1: allocate the history planes of temporal reprojection (see pt_reproject below; ids + point, 32 bytes
                              per local pixel).  Needs PT_OPT_FEATURES on (PT_ERR_INVALID otherwise).  0 (default): release them.
                              Turning PT_OPT_FEATURES off turns this off too.  The image bits of a context that never calls
-                             pt_reproject are the same either way. */
+                             pt_reproject are the same either way.  While PT_OPT_ERROR_ESTIMATE is on as well, 32 more bytes
+                             per local pixel: the staging buffer of pt_reproject_estimate. */
 };
 
 /* ---- background modes ----------------------------------------------------------------------- */
@@ -665,6 +666,43 @@ int pt_load_history(pt_ctx* ctx, const PtParams* prev, const void* ids, const vo
 int pt_reproject(pt_ctx* ctx, const PtReprojectOptions* options);
 int pt_reproject_stats(pt_ctx* ctx, PtReprojectStats* out);
 int pt_reproject_constants(const PtParams* prev, float tolerance_px, float out16[16]);
+
+/* ---- temporal reprojection WITH the error estimate (build extension, opt-in: PT_OPT_REPROJECT and PT_OPT_ERROR_ESTIMATE) -------
+ * pt_reproject clears the estimate's state, so while the camera moves nothing that reads the state (pt_resolve_filtered,
+ * pt_resolve_filtered_patch, pt_error_tiles, pt_error_stats) knows of the history.  pt_reproject_estimate is pt_reproject in
+ * every respect — the same preconditions and errors in the same order, the history used up, the SAME BITS in the accumulation,
+ * the same three tallies, the same things that do not move, asynchronous, no synchronisation, no allocation, refused inside a
+ * stream capture, PT_OK for a context with no local pixels — but for the state (pt_error_ptr: A = {mean.rgb, n}, B = {M2.rgb, k}
+ * per local pixel), which is gathered from the history's places by the same kernel pass instead of being cleared.  In the tick
+ * above it takes pt_reproject's place.  Additionally: PT_ERR_NOT_READY while PT_OPT_ERROR_ESTIMATE is off (checked after
+ * PT_OPT_REPROJECT, before the capture, the history and the planes).  The state's staging buffer (2 texels per local pixel: the
+ * gather reads the state at other pixels' places) is allocated wherever the context sizes its buffers while both options are on.
+ * The remembered samples_per_pixel of the folded passes stays as it is, so the next fold with another value is refused until a
+ * clear, as ever.  With nothing folded since the last clear the call IS pt_reproject and the state stays zero.
+ * THE STATE'S STATEMENTS, fp32, ONE IEEE operation per statement, nothing fused, `/` correctly rounded.  Up to and including the
+ * per-tap tests on range, row ownership, HIDS == ids, d2 <= rhs, and g = wx*wy, g > 0 they are pt_reproject's; the accumulation's
+ * sums are pt_reproject's own (under their `a.w > 0`), the estimate's sums are separate and do NOT depend on a.w > 0:
+ *     host, once: S = err_spp ;  Sf = float(S) ;  S2 = Sf*Sf ;  capP_x = floorf(cap_x / Sf) for the two caps
+ *     per pixel: mu = W = {+0,+0,+0} ;  cntE = wsumE = +0 ;  capP = ids.z == PT_DIFFUSE ? capP_diffuse : capP_other
+ *     per tap that passed the common tests, Aq = A[q], Bq = B[q]:
+ *         skip (estimate only) unless Aq.w >= 2 && Bq.w > 0
+ *         qq = Aq.w / Bq.w ;  qq2 = qq*qq ;  n1 = Aq.w - 1.0f
+ *         per channel: m = Aq.c*qq ; gm = g*m ; mu.c = mu.c + gm ;
+ *                      pv = Bq.c / n1 ; pv = pv*qq2 ; gp = g*pv ; W.c = W.c + gp
+ *         gn = g*Aq.w ; cntE = cntE + gn ; wsumE = wsumE + g
+ *     after the taps: A' = B' = all +0 unless wsumE > 0
+ *         nE = cntE / wsumE ; nE = floorf(nE) ; if (nE > capP) nE = capP ; all +0 unless nE >= 2
+ *         n1 = nE - 1.0f ; kE = nE*Sf
+ *         per channel: a = mu.c / wsumE ; mean'.c = a*Sf ; b = W.c / wsumE ; b = b*n1 ; M2'.c = b*S2
+ *         A' = {mean', nE} ;  B' = {M2', kE}
+ *     (a pixel that is `done` before the taps leaves A' = B' = all +0)
+ * The per-sample mean is blended bilinearly; the per-pass variance of a sample is blended the same way (as SVGF blends moments:
+ * conservative against the variance of the blended mean); the pass count is the floor of the blended count, capped in PASSES.
+ * The read-out of the carried state gives se'^2 = W / nE: a cap that bites widens the standard error.  A class whose cap is below
+ * 2 passes carries no estimate.  Non-finite operands stay non-finite (the read-outs' "counted" rule deals with them).
+ * The carried estimate steers a filter; it is NO stopping criterion: what lags behind the camera (reflections) is bias the
+ * standard error does not know of (DESIGN.md §4.8h has the measured calibration). */
+int pt_reproject_estimate(pt_ctx* ctx, const PtReprojectOptions* options);
 
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)

@@ -65,6 +65,7 @@ SIGNATURES = {
     "pt_keep_history": (C.c_int, [_ctx]),
     "pt_load_history": (C.c_int, [_ctx, C.POINTER(abi.PtParams), _vp, _vp]),
     "pt_reproject": (C.c_int, [_ctx, C.POINTER(abi.PtReprojectOptions)]),
+    "pt_reproject_estimate": (C.c_int, [_ctx, C.POINTER(abi.PtReprojectOptions)]),
     "pt_reproject_stats": (C.c_int, [_ctx, C.POINTER(abi.PtReprojectStats)]),
     "pt_reproject_constants": (C.c_int, [C.POINTER(abi.PtParams), C.c_float, C.POINTER(C.c_float)]),
     "pt_refit_grid": (C.c_int, [_ctx, C.c_int]),
@@ -115,12 +116,12 @@ SIGNATURES = {
 
 # entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay, the error
 # estimate, adaptive sampling, the filtered read-out, the first-hit feature planes, the patch-wise filtered read-out, temporal
-# reprojection
+# reprojection, temporal reprojection with the error estimate
 ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_set_debugging", "pt_state_debug_overlay",
                       "pt_error_ptr", "pt_resolve_error", "pt_error_tiles", "pt_error_stats", "pt_render_until",
                       "pt_render_adaptive", "pt_adaptive_tiles", "pt_resolve_filtered", "pt_render_features", "pt_features_ptr",
                       "pt_read_features", "pt_resolve_filtered_patch", "pt_keep_history", "pt_load_history", "pt_reproject",
-                      "pt_reproject_stats", "pt_reproject_constants")
+                      "pt_reproject_stats", "pt_reproject_constants", "pt_reproject_estimate")
 
 
 def _elf_dynamic_strings(path, tags):

@@ -33,7 +33,7 @@ PT_OPT_GEOMETRY_PATH, PT_OPT_COUNT_WORK, PT_OPT_CARRY_LANES, PT_OPT_REFILL_MIN, 
 PT_OPT_FEATURES = 8  # the first-hit feature planes (pt_render_features, pt_features_ptr, pt_read_features)
 PT_FEAT_ALBEDO, PT_FEAT_NORMAL, PT_FEAT_POINT, PT_FEAT_IDS, PT_FEAT_PLANES = 0, 1, 2, 3, 4
 PT_OPT_ERROR_ESTIMATE = 7  # the per-pixel error estimate (pt_error_ptr, pt_resolve_error, pt_error_tiles, pt_error_stats, pt_render_until)
-PT_OPT_REPROJECT = 9  # temporal reprojection's history planes (pt_keep_history, pt_load_history, pt_reproject, pt_reproject_stats)
+PT_OPT_REPROJECT = 9  # temporal reprojection's history planes (pt_keep_history, pt_load_history, pt_reproject, pt_reproject_estimate, pt_reproject_stats)
 PT_REPROJECT_TOLERANCE_DEFAULT = 2.0      # pt_reproject: the distance test, in pixel footprints at the history camera's depth
 PT_REPROJECT_CAP_DIFFUSE_DEFAULT = 32.0   # ... the most samples a kept diffuse pixel carries over
 PT_REPROJECT_CAP_OTHER_DEFAULT = 8.0      # ... and a pixel of any other material

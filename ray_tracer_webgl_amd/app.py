@@ -11,7 +11,9 @@ run_setters -> render -> (save).  Two display modes:
   * "linear": passes accumulate as fp32 linear radiance (north_star's "accumulated radiance")
     and are resolved at read-out; a camera change (render_count reset to 0,
     src/state.rs:343-346) clears the accumulation — or, with `reproject` options given, carries it over
-    into the new view (temporal reprojection, include/ptrace.h pt_reproject).
+    into the new view (temporal reprojection, include/ptrace.h pt_reproject); with `carry_estimate` the
+    per-pixel error estimate is kept and carried too (pt_reproject_estimate), so the filtered read-outs of the
+    tracer know of the history while the camera moves.
 """
 import time
 
@@ -26,11 +28,15 @@ class FrameLoop:
     # is refitted; a grid that is too SMALL (== 1: every primary ray tested against the whole list) is refitted at once
     LOOSE_FRAMES = 32
 
-    def __init__(self, width, height, device=0, mode="reference", host_spheres=None, debugging=False, reproject=None):
+    def __init__(self, width, height, device=0, mode="reference", host_spheres=None, debugging=False, reproject=None,
+                 carry_estimate=False):
         assert mode in ("reference", "linear")
         assert reproject is None or mode == "linear", "temporal reprojection carries the fp32 accumulation: linear mode only"
+        assert not carry_estimate or reproject is not None, "carry_estimate needs `reproject` options"
         self.mode = mode
         self.reproject = reproject  # abi.PtReprojectOptions, or None: a camera change clears the accumulation
+        self.carry_estimate = bool(carry_estimate)  # keep the error estimate and carry it with the accumulation
+        self._estimate_spp = 0  # samples_per_pixel of the ticks the estimate holds (0: none): a fold needs the same value
         self.debugging = bool(debugging)
         self.state = State(width, height)
         if self.debugging:  # State.enable_debugging (src/state.rs:87): the shader's cursor dot and selected-object outline
@@ -42,6 +48,8 @@ class FrameLoop:
         if self.reproject is not None:
             self.tracer.feature_planes(True)
             self.tracer.reproject_option(True)
+            if self.carry_estimate:
+                self.tracer.error_estimate(True)
         self.grid_refits = 0
         self._loose = 0
         # two RGBA8 textures cleared to 0 (alpha 0 = "no data", shader.frag:391): in HBM, owned by the context
@@ -111,6 +119,7 @@ class FrameLoop:
             carry = moved and self.reproject is not None and self.frames_rendered > 0
             if moved and not carry:
                 self.tracer.reset()
+                self._estimate_spp = 0
             self.tracer.set_params(p)
             self._upload_debug_overlay()
             self._keep_the_grid_fitted()
@@ -119,10 +128,16 @@ class FrameLoop:
                 # keep_history issued by the tick that RENDERED the planes: every tick uploads a new clock, and the planes
                 # answer only until the next set_params, so the view is remembered while they still speak for it
                 self.tracer.render_features()
-                if carry:
-                    self.tracer.reproject(self.reproject)
+                if carry and self.carry_estimate and self._estimate_spp == p.samples_per_pixel:
+                    self.tracer.reproject_estimate(self.reproject)
+                elif carry:
+                    self.tracer.reproject(self.reproject)  # (clears the estimate: passes of another size cannot join it)
+                    self._estimate_spp = 0
                 self.tracer.keep_history()
+            if self.carry_estimate and self._estimate_spp not in (0, p.samples_per_pixel):
+                self.tracer.reset()  # the view stands still but the tick's samples_per_pixel changed: the estimate cannot follow
             self.tracer.render()
+            self._estimate_spp = p.samples_per_pixel
             self._canvas = self.tracer.resolve_rgba8(True)
         self.frames_rendered += 1
         return True

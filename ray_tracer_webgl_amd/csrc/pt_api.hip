@@ -155,6 +155,7 @@ struct pt_ctx {
   int err_spp = 0;                  // samples_per_pixel of the passes folded since the last clear (0 = none yet)
   DevBuf<float4> d_err;
   DevBuf<float4> d_err_tiles;       // tiles records, then tiles tallies (pt_error_tiles_kernel)
+  DevBuf<float4> d_err_stage;       // pt_reproject_estimate's staging of the state, 2 x local pixels: while PT_OPT_REPROJECT is on too
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   PathTuner geom;
   hipEvent_t trial_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // begin/end per trial
@@ -349,6 +350,8 @@ int ensure_buffers(pt_ctx* c) {
       c->err_spp = 0;
     }
     if (c->d_err_tiles.capacity() < 2 * tiles) PT_HIP(c, c->d_err_tiles.reserve(2 * tiles));
+    // (pt_reproject_estimate gathers the state from other pixels' places: it cannot write in place, and it does not allocate)
+    if (c->reproj_on && c->d_err_stage.capacity() < 2 * pix) PT_HIP(c, c->d_err_stage.reserve(2 * pix));
   }
   if (c->feat_on && c->d_feat.capacity() != PT_FEAT_PLANES * pix) {  // (sized for the local rows in place: plane k begins at k * pix)
     c->feat_valid = false;
@@ -1943,6 +1946,7 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
 static void release_reproject(pt_ctx* c) {
   c->reproj_on = c->hist_valid = c->reproj_ran = false;
   c->d_hist = DevBuf<float4>();
+  c->d_err_stage = DevBuf<float4>();
   c->d_reproj_tally = DevBuf<unsigned long long>();
 }
 
@@ -1991,6 +1995,7 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
       c->err_spp = 0;
       c->d_err = DevBuf<float4>();
       c->d_err_tiles = DevBuf<float4>();
+      c->d_err_stage = DevBuf<float4>();
       return PT_OK;
     }
     if (c->err_on) return PT_OK;
@@ -2000,7 +2005,7 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     c->err_on = true;
     int rc = ensure_buffers(c);
     if (rc == PT_OK) rc = clear_error(c);
-    if (rc != PT_OK) { c->err_on = false; c->d_err = DevBuf<float4>(); c->d_err_tiles = DevBuf<float4>(); }
+    if (rc != PT_OK) { c->err_on = false; c->d_err = DevBuf<float4>(); c->d_err_tiles = DevBuf<float4>(); c->d_err_stage = DevBuf<float4>(); }
     return rc;
   }
   if (key == PT_OPT_FEATURES) { // the image does not depend on it; the planes are allocated here, released when turned off
@@ -2193,25 +2198,32 @@ PT_API int pt_reproject_constants(const PtParams* prev, float tolerance_px, floa
              ? PT_OK : PT_ERR_INVALID;
 }
 
-PT_API int pt_reproject(pt_ctx* c, const PtReprojectOptions* opt) {
-  if (!c || !opt) return fail(c, PT_ERR_INVALID, "pt_reproject: NULL argument");
+// pt_reproject and pt_reproject_estimate (`carry`): the same checks in the same order, the same history, accumulation and tallies;
+// they differ in what becomes of the error estimate's state — cleared, or gathered by the same kernel pass
+static int reproject_call(pt_ctx* c, const PtReprojectOptions* opt, const char* who, bool carry) {
+  if (!c || !opt) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
   for (const float cap : {opt->cap_diffuse, opt->cap_other})
     if (!(cap >= 0.0f) || !(cap < 16777216.0f) || cap != std::floor(cap))
-      return fail(c, PT_ERR_INVALID, "pt_reproject: a cap of %g is not a whole number in [0, 2^24)", (double)cap);
+      return fail(c, PT_ERR_INVALID, "%s: a cap of %g is not a whole number in [0, 2^24)", who, (double)cap);
   if (!std::isfinite(opt->tolerance_px) || opt->tolerance_px < 0.0f)
-    return fail(c, PT_ERR_INVALID, "pt_reproject: tolerance_px must be finite and >= 0");
-  if (int rc = reproject_ready(c, "pt_reproject"); rc != PT_OK) return rc;
+    return fail(c, PT_ERR_INVALID, "%s: tolerance_px must be finite and >= 0", who);
+  if (int rc = reproject_ready(c, who); rc != PT_OK) return rc;
+  if (carry && !c->err_on) return fail(c, PT_ERR_NOT_READY, "%s: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", who);
   PT_HIP(c, hipSetDevice(c->device));
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_reproject: not inside a stream capture");
-  if (!c->hist_valid) return fail(c, PT_ERR_NOT_READY, "pt_reproject: no history (pt_keep_history / pt_load_history; one pt_reproject uses it up)");
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "%s: not inside a stream capture", who);
+  if (!c->hist_valid) return fail(c, PT_ERR_NOT_READY, "%s: no history (pt_keep_history / pt_load_history; one pt_reproject uses it up)", who);
   if (!c->feat_on || !c->feat_valid || !feature_planes_in_place(c))
-    return fail(c, PT_ERR_NOT_READY, "pt_reproject: no pt_render_features since the uniforms of the new view went up");
+    return fail(c, PT_ERR_NOT_READY, "%s: no pt_render_features since the uniforms of the new view went up", who);
+  // (nothing folded since the last clear: the state is zero and there is nothing to carry — the call is pt_reproject)
+  carry = carry && c->err_spp != 0;
+  const size_t pix = n_pixels(c);
+  if (carry && pix && c->d_err_stage.capacity() < 2 * pix)
+    return fail(c, PT_ERR_CAPACITY, "%s: the state's staging buffer is not allocated for the rows in place (an earlier allocation failed)", who);
   float k16[ptrep::K_COUNT];
   if (pt_reproject_constants(&c->hist_params, opt->tolerance_px, k16) != PT_OK)
-    return fail(c, PT_ERR_INVALID, "pt_reproject: the history view's camera is degenerate");
+    return fail(c, PT_ERR_INVALID, "%s: the history view's camera is degenerate", who);
   c->hist_valid = false;  // one-shot: from here on the accumulation belongs to the new view
   c->reproj_ran = true;
-  const size_t pix = n_pixels(c);
   PT_HIP(c, hipMemsetAsync(c->d_reproj_tally.get(), 0, 3 * sizeof(unsigned long long), c->stream));
   if (pix == 0) return PT_OK;  // this band owns no rows
   ptrep::Consts K;
@@ -2236,12 +2248,27 @@ PT_API int pt_reproject(pt_ctx* c, const PtReprojectOptions* opt) {
   const float4* accum = c->accum;
   float4* out = c->d_resolve.get();  // (the staging buffer pt_load_accum uses: the gather reads accum at other pixels' places)
   unsigned long long* tally = c->d_reproj_tally.get();
-  void* kargs[] = {&cur_ids, &cur_pnt, &hist_ids, &hist_pnt, &accum, &out, &K, &F, &tally};
   const dim3 grid((c->width + 31u) / 32u, (c->local_rows + 7u) / 8u);
-  PT_HIP(c, hipLaunchKernel(pt_reproject_kernel_handle(), grid, dim3(256), kargs, 0, c->stream));
+  if (!carry) {
+    void* kargs[] = {&cur_ids, &cur_pnt, &hist_ids, &hist_pnt, &accum, &out, &K, &F, &tally};
+    PT_HIP(c, hipLaunchKernel(pt_reproject_kernel_handle(), grid, dim3(256), kargs, 0, c->stream));
+    PT_HIP(c, hipMemcpyAsync(c->accum, out, pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    return clear_error(c);  // (history is sums, not the passes they came from: as pt_load_accum)
+  }
+  // the estimate's constants: the caps in passes of err_spp samples; err_spp stays, so the next fold must use the same value
+  const ptrep::EstConsts E = ptrep::est_consts(c->err_spp, opt->cap_diffuse, opt->cap_other);
+  const float4* err = c->d_err.get();
+  float4* out_err = c->d_err_stage.get();
+  void* kargs[] = {&cur_ids, &cur_pnt, &hist_ids, &hist_pnt, &accum, &err, &out, &out_err, &K, (void*)&E, &F, &tally};
+  PT_HIP(c, hipLaunchKernel(pt_reproject_estimate_kernel_handle(), grid, dim3(256), kargs, 0, c->stream));
   PT_HIP(c, hipMemcpyAsync(c->accum, out, pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-  return clear_error(c);  // (history is sums, not the passes they came from: as pt_load_accum)
+  PT_HIP(c, hipMemcpyAsync(c->d_err.get(), out_err, 2 * pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  return PT_OK;
 }
+
+PT_API int pt_reproject(pt_ctx* c, const PtReprojectOptions* opt) { return reproject_call(c, opt, "pt_reproject", false); }
+
+PT_API int pt_reproject_estimate(pt_ctx* c, const PtReprojectOptions* opt) { return reproject_call(c, opt, "pt_reproject_estimate", true); }
 
 PT_API int pt_reproject_stats(pt_ctx* c, PtReprojectStats* out) {
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_reproject_stats: NULL argument");

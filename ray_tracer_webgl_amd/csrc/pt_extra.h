@@ -89,5 +89,7 @@ PT_TRACE_OBJECTS(PT_TRACE_ACCESSOR_DECL)
 // pt_resolve_filtered_patch)
 enum { PT_E_FOLD = 0, PT_E_RESOLVE, PT_E_TILES, PT_E_FOLD_TILES, PT_E_PARTITION, PT_E_FILTER, PT_E_FILTER_PATCH, PT_E_COUNT };
 extern "C" const void* pt_error_kernel(int id);
-// pt_kernels_reproject.hip (a code object of its own): temporal reprojection's one kernel (PT_OPT_REPROJECT, pt_reproject)
+// pt_kernels_reproject.hip (a code object of its own): temporal reprojection's kernels (PT_OPT_REPROJECT): pt_reproject's, and
+// pt_reproject_estimate's, which gathers the error estimate's state in the same pass
 extern "C" const void* pt_reproject_kernel_handle(void);
+extern "C" const void* pt_reproject_estimate_kernel_handle(void);

@@ -448,8 +448,16 @@ class PathTracer:
         opt = options if options is not None else abi.PtReprojectOptions()
         self._check(self.lib.pt_reproject(self._ctx, C.byref(opt)))
 
+    def reproject_estimate(self, options=None):
+        """reproject() that carries the error estimate's state too (pt_reproject_estimate): the accumulation gets the bits
+        reproject() would leave, the state is gathered from the same places instead of being cleared, so the filtered
+        read-outs and error_stats() know of the history while the camera moves.  Needs error_estimate(True); the next fold
+        must use the samples_per_pixel of the carried passes.  Good enough to steer a filter, no stopping criterion."""
+        opt = options if options is not None else abi.PtReprojectOptions()
+        self._check(self.lib.pt_reproject_estimate(self._ctx, C.byref(opt)))
+
     def reproject_stats(self):
-        """abi.PtReprojectStats of the last reproject(): pixels, pixels_hit, pixels_kept, samples_kept.  Synchronises."""
+        """abi.PtReprojectStats of the last reproject() or reproject_estimate(): pixels, pixels_hit, pixels_kept, samples_kept.  Synchronises."""
         st = abi.PtReprojectStats()
         self._check(self.lib.pt_reproject_stats(self._ctx, C.byref(st)))
         return st
