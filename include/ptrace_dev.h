@@ -50,6 +50,18 @@ int pt_debug_wait(pt_ctx* ctx, unsigned timeout_ms);
 int pt_build_grid_runs(const PtSphere* spheres, uint32_t n, uint32_t* counts8, float* geom12, float* margin4,
                        float* delta_g, uint32_t* cells, size_t n_cells, float* entries, size_t entry_floats,
                        uint32_t* entry_index, size_t n_index);
+/* The work queue's two tile-table kernels on the CALLER's arrays of n entries (for tests/test_gpu_tile_tables.py: the product
+ * runs them on buffers nobody can read).  Each call uploads its inputs into scratch device buffers of its own, fills the output
+ * buffers with 0xFF bytes (an entry the kernel never wrote reads 0xFFFFFFFF), launches the shipped kernel as the product does —
+ * one workgroup of 1024 threads on the context's stream —, copies the results back and synchronises.  Neither touches the
+ * context's order, costs or adaptive tables.  PT_ERR_INVALID for a NULL pointer or n == 0.
+ *   pt_debug_tile_order:      pt_tile_order_kernel; order_out = the queue order of the tiles with the costs `cost`, cost_out =
+ *                             the cost array as the kernel leaves it (cleared).
+ *   pt_debug_partition_order: pt_partition_order_kernel; part_out = the stable partition of `order` by flags[tile] != 0,
+ *                             base_out = `order` as the kernel found it. */
+int pt_debug_tile_order(pt_ctx* ctx, const uint32_t* cost, uint32_t n, uint32_t* order_out, uint32_t* cost_out);
+int pt_debug_partition_order(pt_ctx* ctx, const uint32_t* order, const uint32_t* flags, uint32_t n, uint32_t* part_out,
+                             uint32_t* base_out);
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,14 @@ ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_s
                       "pt_read_features", "pt_resolve_filtered_patch", "pt_keep_history", "pt_load_history", "pt_reproject",
                       "pt_reproject_stats", "pt_reproject_constants", "pt_reproject_estimate")
 
+# include/ptrace_dev.h: developer diagnostics outside the versioned ABI, declared when the library in use has them (the other
+# pt_debug_* are declared where they are called, tracer.py and tools/)
+_u32p = C.POINTER(C.c_uint32)
+DEV_SIGNATURES = {
+    "pt_debug_tile_order": (C.c_int, [_ctx, _u32p, C.c_uint32, _u32p, _u32p]),
+    "pt_debug_partition_order": (C.c_int, [_ctx, _u32p, _u32p, C.c_uint32, _u32p, _u32p]),
+}
+
 
 def _elf_dynamic_strings(path, tags):
     """The strings of an ELF64 shared object's dynamic section for the given tags (1 = DT_NEEDED, 14 = DT_SONAME)."""
@@ -234,6 +242,11 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in DEV_SIGNATURES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     if lib.pt_abi_version() != abi.PT_ABI_VERSION:
         raise ImportError("libptrace.so ABI %d != expected %d" % (lib.pt_abi_version(), abi.PT_ABI_VERSION))
     _lib = lib

@@ -1565,6 +1565,55 @@ PT_API int pt_debug_wait(pt_ctx* c, unsigned timeout_ms) {
   return rc;
 }
 
+// The two tile-table kernels on the caller's arrays, for tests/test_gpu_tile_tables.py: scratch buffers of the call's own (the
+// context's order, costs, adaptive tables and TileOrder state are neither read nor written), the outputs filled with 0xFF bytes
+// first, the launch the product makes — one workgroup of 1024 threads on the context's stream.
+PT_API int pt_debug_tile_order(pt_ctx* c, const uint32_t* cost, uint32_t n, uint32_t* order_out, uint32_t* cost_out) {
+  if (!c || !cost || !order_out || !cost_out || n == 0) return fail(c, PT_ERR_INVALID, "pt_debug_tile_order: NULL argument or no tiles");
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_debug_tile_order: synchronises; not inside a stream capture");
+  PT_HIP(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)n * sizeof(uint32_t);
+  DevBuf<uint32_t> d_cost, d_order;
+  PT_HIP(c, d_cost.reserve(n));
+  PT_HIP(c, d_order.reserve(n));
+  PT_HIP(c, hipMemcpyAsync(d_cost.get(), cost, bytes, hipMemcpyHostToDevice, c->stream));
+  PT_HIP(c, hipMemsetAsync(d_order.get(), 0xFF, bytes, c->stream));
+  hipLaunchKernelGGL(pt_tile_order_kernel, dim3(1), dim3(1024), 0, c->stream, d_cost.get(), d_order.get(), n);
+  PT_HIP(c, hipGetLastError());
+  PT_HIP(c, hipMemcpyAsync(order_out, d_order.get(), bytes, hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipMemcpyAsync(cost_out, d_cost.get(), bytes, hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+PT_API int pt_debug_partition_order(pt_ctx* c, const uint32_t* order, const uint32_t* flags, uint32_t n, uint32_t* part_out,
+                                    uint32_t* base_out) {
+  if (!c || !order || !flags || !part_out || !base_out || n == 0)
+    return fail(c, PT_ERR_INVALID, "pt_debug_partition_order: NULL argument or no tiles");
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_debug_partition_order: synchronises; not inside a stream capture");
+  PT_HIP(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)n * sizeof(uint32_t);
+  DevBuf<uint32_t> d_in, d_out;  // {order, flags} and {part, base}
+  PT_HIP(c, d_in.reserve(2 * (size_t)n));
+  PT_HIP(c, d_out.reserve(2 * (size_t)n));
+  PT_HIP(c, hipMemcpyAsync(d_in.get(), order, bytes, hipMemcpyHostToDevice, c->stream));
+  PT_HIP(c, hipMemcpyAsync(d_in.get() + n, flags, bytes, hipMemcpyHostToDevice, c->stream));
+  PT_HIP(c, hipMemsetAsync(d_out.get(), 0xFF, 2 * bytes, c->stream));
+  {
+    const uint32_t* od = d_in.get();
+    const uint32_t* fl = d_in.get() + n;
+    uint32_t* part = d_out.get();
+    uint32_t* base = d_out.get() + n;
+    uint32_t tiles = n;
+    void* kargs[] = {&od, &fl, &part, &base, &tiles};
+    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_PARTITION), dim3(1), dim3(1024), kargs, 0, c->stream));
+  }
+  PT_HIP(c, hipMemcpyAsync(part_out, d_out.get(), bytes, hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipMemcpyAsync(base_out, d_out.get() + n, bytes, hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
 PT_API int pt_synchronize(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   PT_HIP(c, hipSetDevice(c->device));

@@ -344,9 +344,9 @@ FRAME_SERIES = [
 ]
 
 
-def frame_scene(band=None):
+def frame_scene(band=None, w=WIDTH, h=HEIGHT):
     """The default scene at 1 spp; (spheres, params) with the series' clock."""
-    sc = scenes.default_scene(WIDTH, HEIGHT, spp=1, max_depth=6)
+    sc = scenes.default_scene(w, h, spp=1, max_depth=6)
     p = sc.params.copy()
     p.time, p.time_step, p.first_pass = T0, DT, 0
     if band is not None:

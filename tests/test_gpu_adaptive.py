@@ -157,6 +157,19 @@ def test_static_deal_against_the_restatement(ora, name):
     t.close()
 
 
+def test_static_deal_with_more_tiles_than_the_partition_kernel_has_threads(ora):
+    """264x256: 33 x 32 = 1 056 tiles, so pt_partition_order_kernel's runs are per = ceil(1056 / 1024) = 2 positions long — 528
+    of its 1024 threads own a run and 496 own none; every smaller case has one position per thread.  At most 12 passes: six
+    rounds, five of them partial."""
+    t, st, ad, ref = _run(ora, "264x256", _default(ora, w=264, h=256), cap=12)
+    assert ad.tiles == 1056 and (ad.tiles + 1023) // 1024 == 2
+    assert (ad.rounds, ad.partial_rounds) == (6, 5) and ad.tiles_active <= 3 * ad.tiles // 4
+    assert st.passes_min < st.passes_max == st.passes_rendered == 12
+    stats = t.stats()
+    assert stats.samples == ad.samples and stats.render_launches == ad.rounds
+    t.close()
+
+
 def test_a_single_tile_equals_render_until(ora):
     """3x5: one tile, a partial round can never happen; state, accum and PtErrorStats have the bytes of pt_render_until."""
     spheres, p, solo = _default(ora, 3, 5)
