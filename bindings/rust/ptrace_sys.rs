@@ -52,6 +52,17 @@ pub struct PtReprojectStats {    // the tallies of the last pt_reproject
     pub pixels: u64, pub pixels_hit: u64, pub pixels_kept: u64, pub samples_kept: u64,
 }
 
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtRay {               // one ray of pt_query_rays, 32 bytes; the direction is not normalised, the pads are not read
+    pub origin: [f32; 3], pub _pad0: f32, pub direction: [f32; 3], pub _pad1: f32,
+}
+
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtRayHit {            // its record, 64 bytes: the four feature texels; index -1 a miss, PT_RAY_INVALID an invalid ray
+    pub albedo: [f32; 3], pub t: f32, pub normal: [f32; 3], pub _pad0: f32, pub point: [f32; 3], pub _pad1: f32,
+    pub index: i32, pub uuid: i32, pub type_: i32, pub front_face: i32,
+}
+
 #[repr(C)] pub struct PtCtx { _private: [u8; 0] }
 
 #[link(name = "ptrace")]
@@ -110,6 +121,11 @@ extern "C" {
     pub fn pt_reproject_constants(prev: *const PtParams, tolerance_px: f32, out16: *mut f32) -> c_int;
     // pt_reproject that also carries the error estimate's state (needs PT_OPT_ERROR_ESTIMATE too): the same accumulation bits
     pub fn pt_reproject_estimate(ctx: *mut PtCtx, options: *const PtReprojectOptions) -> c_int;
+    // ray queries (pt_set_option PT_OPT_RAY_QUERIES 1): the closest hit of the caller's rays through the trace kernels' own
+    // intersection — the autofocus and selection ray (src/state.rs get_center_hit), picks, visibility probes; host or device
+    // pointers, synchronous; pt_query_batch: the rays one launch takes
+    pub fn pt_query_rays(ctx: *mut PtCtx, rays: *const PtRay, n: u32, hits: *mut PtRayHit) -> c_int;
+    pub fn pt_query_batch(ctx: *mut PtCtx) -> u32;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;
@@ -133,6 +149,8 @@ pub const PT_OPT_GEOMETRY_PATH: c_int = 1;      // PT_GEOM_AUTO 0 / LDS 1 / SCAL
 pub const PT_OPT_ERROR_ESTIMATE: c_int = 7;     // opt-in, 0 = off; the image bits do not depend on it
 pub const PT_OPT_FEATURES: c_int = 8;           // opt-in, 0 = off; the image bits do not depend on it
 pub const PT_OPT_REPROJECT: c_int = 9;          // opt-in, 0 = off; needs PT_OPT_FEATURES on
+pub const PT_OPT_RAY_QUERIES: c_int = 10;       // opt-in, 0 = off; the image bits do not depend on it
+pub const PT_RAY_INVALID: i32 = -2;             // PtRayHit.index / uuid / type of an invalid ray
 pub const PT_REPROJECT_TOLERANCE_DEFAULT: f32 = 2.0;
 pub const PT_REPROJECT_CAP_DIFFUSE_DEFAULT: f32 = 32.0;
 pub const PT_REPROJECT_CAP_OTHER_DEFAULT: f32 = 8.0;

@@ -112,6 +112,9 @@ enum {
                              Turning PT_OPT_FEATURES off turns this off too.  The image bits of a context that never calls
                              pt_reproject are the same either way.  While PT_OPT_ERROR_ESTIMATE is on as well, 32 more bytes
                              per local pixel: the staging buffer of pt_reproject_estimate. */
+  PT_OPT_RAY_QUERIES = 10, /* 1: allocate the query planes of pt_query_rays (see below; 64 bytes per local pixel), keep the uuid
+                             arrays on the device and load the query builds' code object.  0 (default): release the planes.
+                             The image bits of a context are the same either way. */
 };
 
 /* ---- background modes ----------------------------------------------------------------------- */
@@ -703,6 +706,55 @@ int pt_reproject_constants(const PtParams* prev, float tolerance_px, float out16
  * The carried estimate steers a filter; it is NO stopping criterion: what lags behind the camera (reflections) is bias the
  * standard error does not know of (DESIGN.md §4.8h has the measured calibration). */
 int pt_reproject_estimate(pt_ctx* ctx, const PtReprojectOptions* options);
+
+/* ---- ray queries: the closest hit of the CALLER's rays (build extension, opt-in: PT_OPT_RAY_QUERIES) ---------------------------
+ * pt_render_features answers "what does the ray through this pixel centre meet"; pt_query_rays answers it for any ray: an
+ * autofocus or selection ray, a pick under a cursor while the uniforms are already the next tick's, a visibility probe between
+ * two points, a probe that starts on a surface, a batch from a baking tool.  Ray i is hit_world(origin, direction, t_min, t_max)
+ * of the trace kernels themselves, through the geometry path forced or settled exactly as pt_render_features chooses it (the
+ * query builds: the feature builds with the ray read from memory, a code object of their own): the direction is NOT normalised
+ * (t is in its units, and t_min = 0.001 and t_max = 1e5 are too: a short direction sees less far), ties go to the later sphere, a negative radius flips the normal.  There is no camera, no jitter, no lens
+ * and no seed: of PtParams the camera, time, time_step, samples_per_pixel, max_depth and first_pass do not enter; width, height
+ * and the row partition only shape the work items (which is why pt_set_params must have come first), background_mode gives a
+ * miss its colour.
+ * THE RECORD of ray i, hits[i], is the feature record of pt_render_features above, field for field: {albedo, t}, {normal,
+ * _pad0}, {point, _pad1} and {index, uuid, type, front_face} are the texels of PT_FEAT_ALBEDO, PT_FEAT_NORMAL, PT_FEAT_POINT
+ * and PT_FEAT_IDS on a hit and on a miss as the table there states them (a miss: the background for THIS ray, ids -1, -1, -1, 0);
+ * the pads are +0.
+ * INVALID RAYS: a ray with a non-finite component (NaN, +inf, -inf) in origin or direction, or whose three direction components
+ * are all +0 or -0, is invalid.  That is decided on the device before any walk; its record is all +0 with the ids
+ * {PT_RAY_INVALID, PT_RAY_INVALID, PT_RAY_INVALID, 0}, and it is not counted in PtStats.segments.  Every other ray is valid and
+ * is answered, however long, short or far away (|d|^2 outside (1e-12, 1e6), an origin component at or beyond 1e15: the trace
+ * kernels' literal loop, as for such a bounce ray).  The pads of PtRay are not read.
+ * `rays` and `hits` are host or device pointers (n of each), as pt_resolve takes them.  The call is synchronous on the context's
+ * stream: it returns when hits[0..n) are written, and writes nothing else.  It works through n in batches of pt_query_batch(ctx)
+ * rays, one launch each (ray i of a batch is work item "local pixel i"; a launch covers only the tile rows its rays occupy, so
+ * one ray costs one tile row, not a frame); n == 0 is PT_OK with nothing done.
+ * What it leaves alone: the accumulation, the estimate, the feature and history planes and their validity, the textures and the
+ * canvas, first_pass, the tile order and costs, the geometry path (never a measuring launch of PT_GEOM_AUTO, nothing settles)
+ * and pt_last_trace_build.  Of PtStats it moves `segments` by one per valid ray and `far_rays` by those of them that take the
+ * grid walk's far path; nothing else.
+ * PT_ERR_INVALID: NULL ctx, rays or hits (n > 0), PT_OPT_COUNT_WORK on, or inside a stream capture (refused before anything is
+ * enqueued).  PT_ERR_NOT_READY: the option is off, no scene or no uniforms yet, or a band that owns no rows (it has no work
+ * items to decode rays against: ask another rank; the answer does not depend on the rows a context owns).  PT_ERR_CAPACITY: the
+ * planes are not in place after a failed allocation.
+ * pt_query_batch: the rays one launch takes, i.e. the local pixel count; 0 for a NULL ctx or while pt_query_rays would return
+ * PT_ERR_NOT_READY or PT_ERR_CAPACITY. */
+#define PT_RAY_INVALID (-2)
+typedef struct PtRay {
+  float origin[3];
+  float _pad0;
+  float direction[3];
+  float _pad1;
+} PtRay; /* 32 bytes */
+typedef struct PtRayHit {
+  float albedo[3], t;
+  float normal[3], _pad0;
+  float point[3], _pad1;
+  int32_t index, uuid, type, front_face;
+} PtRayHit; /* 64 bytes */
+int pt_query_rays(pt_ctx* ctx, const PtRay* rays, uint32_t n, PtRayHit* hits);
+uint32_t pt_query_batch(pt_ctx* ctx);
 
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)

@@ -34,7 +34,9 @@ PT_OPT_FEATURES = 8  # the first-hit feature planes (pt_render_features, pt_feat
 PT_FEAT_ALBEDO, PT_FEAT_NORMAL, PT_FEAT_POINT, PT_FEAT_IDS, PT_FEAT_PLANES = 0, 1, 2, 3, 4
 PT_OPT_ERROR_ESTIMATE = 7  # the per-pixel error estimate (pt_error_ptr, pt_resolve_error, pt_error_tiles, pt_error_stats, pt_render_until)
 PT_OPT_REPROJECT = 9  # temporal reprojection's history planes (pt_keep_history, pt_load_history, pt_reproject, pt_reproject_estimate, pt_reproject_stats)
-PT_REPROJECT_TOLERANCE_DEFAULT = 2.0      # pt_reproject: the distance test, in pixel footprints at the history camera's depth
+PT_OPT_RAY_QUERIES = 10  # the query planes of pt_query_rays (closest hits for the caller's rays), pt_query_batch
+PT_RAY_INVALID = -2  # PtRayHit.index, .uuid and .type of an invalid ray (a non-finite component, or a direction of three zeros)
+PT_REPROJECT_TOLERANCE_DEFAULT = 2.0     # pt_reproject: the distance test, in pixel footprints at the history camera's depth
 PT_REPROJECT_CAP_DIFFUSE_DEFAULT = 32.0   # ... the most samples a kept diffuse pixel carries over
 PT_REPROJECT_CAP_OTHER_DEFAULT = 8.0      # ... and a pixel of any other material
 PT_TIME_STEP_DECORRELATED = 0.3618034  # include/ptrace.h
@@ -222,6 +224,34 @@ class PtReprojectStats(C.Structure):
         ("pixels_hit", C.c_uint64),
         ("pixels_kept", C.c_uint64),
         ("samples_kept", C.c_uint64),
+    ]
+
+
+class PtRay(C.Structure):
+    """include/ptrace.h PtRay: one ray of pt_query_rays, 32 bytes; the direction is not normalised, the pads are not read."""
+
+    _fields_ = [
+        ("origin", C.c_float * 3),
+        ("_pad0", C.c_float),
+        ("direction", C.c_float * 3),
+        ("_pad1", C.c_float),
+    ]
+
+
+class PtRayHit(C.Structure):
+    """include/ptrace.h PtRayHit: the record of one ray, 64 bytes — the four feature texels of pt_render_features in order."""
+
+    _fields_ = [
+        ("albedo", C.c_float * 3),
+        ("t", C.c_float),
+        ("normal", C.c_float * 3),
+        ("_pad0", C.c_float),
+        ("point", C.c_float * 3),
+        ("_pad1", C.c_float),
+        ("index", C.c_int32),
+        ("uuid", C.c_int32),
+        ("type", C.c_int32),
+        ("front_face", C.c_int32),
     ]
 
 

@@ -35,6 +35,7 @@
 #include "pt_error_plan.hpp"
 #include "pt_reproject_plan.hpp"
 #include "pt_reproject.hpp"
+#include "pt_query.hpp"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -181,6 +182,12 @@ struct pt_ctx {
   bool feat_on = false;
   bool feat_valid = false;          // the planes speak for the scene, uniforms and partition in place (pt_read_features)
   DevBuf<float4> d_feat;
+  // ray queries (PT_OPT_RAY_QUERIES; pt_kernels_query.hip): the query planes — the feature planes' layout, rays staged into the
+  // point and normal planes, records read back from all four — and the identity tile order a query launch is dealt by (the
+  // frame's own order belongs to the render launches); pt_query_rays also needs the uuid arrays above
+  bool query_on = false;
+  DevBuf<float4> d_query;
+  DevBuf<uint32_t> d_query_order;
   // temporal reprojection (PT_OPT_REPROJECT; pt_kernels_reproject.hip): the history planes — the ids plane, then the point plane,
   // of an earlier view (pt_keep_history / pt_load_history) — the uniforms they were rendered with, and the last call's tallies
   bool reproj_on = false;
@@ -358,6 +365,16 @@ int ensure_buffers(pt_ctx* c) {
     if (pix > 0x3fffffffu / PT_FEAT_PLANES) return fail(c, PT_ERR_CAPACITY, "feature planes: %zu local pixels exceed the kernels' 32-bit texel index", pix);
     PT_HIP(c, c->d_feat.reserve(PT_FEAT_PLANES * pix));
   }
+  if (c->query_on && (c->d_query.capacity() != PT_FEAT_PLANES * pix || c->d_query_order.capacity() != tiles)) {  // (likewise)
+    if (pix > 0x3fffffffu / PT_FEAT_PLANES) return fail(c, PT_ERR_CAPACITY, "query planes: %zu local pixels exceed the kernels' 32-bit texel index", pix);
+    PT_HIP(c, hipStreamSynchronize(c->stream));
+    c->d_query = DevBuf<float4>();  // (what pt_query_rays tests: both in place, or neither)
+    PT_HIP(c, c->d_query_order.reserve(tiles));
+    std::vector<uint32_t> ident(tiles);
+    for (size_t i = 0; i < tiles; i++) ident[i] = (uint32_t)i;
+    PT_HIP(c, hipMemcpy(c->d_query_order.get(), ident.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+    PT_HIP(c, c->d_query.reserve(PT_FEAT_PLANES * pix));
+  }
   if (c->reproj_on && c->d_hist.capacity() != 2 * pix) {  // (likewise: the ids plane, then the point plane at pix)
     c->hist_valid = false;
     PT_HIP(c, c->d_hist.reserve(2 * pix));
@@ -482,6 +499,20 @@ const void* cell_kernel(int device, const TraceCell& k) {
     std::call_once(once[device & 63][k.object][k.id], [fn] {  // (every caller returns with the attribute set: no launch can overtake it)
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
       (void)hipGetLastError();  // a refused attribute only limits that kernel to the default 64 KiB; the launch code checks sizes
+    });
+  return fn;
+}
+
+// The query build that serves a row: the handle pt_query_kernel gives for the id of the row's feature cell (a cell of the
+// table's BUILD_FEAT column: the query builds share its variant rows, wave counts and launch shapes, and are no column
+// themselves).  Its dynamic-LDS limit is lifted on first use, like cell_kernel's.
+const void* query_kernel(int device, const TraceCell& feat_cell) {
+  static std::once_flag once[64][PT_VARIANT_COUNT];
+  const void* fn = pt_query_kernel(feat_cell.id);
+  if (fn)
+    std::call_once(once[device & 63][feat_cell.id], [fn] {
+      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
+      (void)hipGetLastError();
     });
   return fn;
 }
@@ -663,10 +694,10 @@ int install_grid(pt_ctx* c, ptgrid::Grid& grid, const ptscene::Split& sp) {
   return PT_OK;
 }
 
-// The uuid arrays of the debug overlay and of the feature planes: PtSphere.uuid in list order and per slot of the structures in
-// place (the walk kernels shade from a slot, like slot_mat).  Made when either is turned on and again whenever the scene or the
-// grid changes while either is on (wants_uuids); a context that never enables one never allocates them.  Synchronises: a set-up call's work.
-inline bool wants_uuids(const pt_ctx* c) { return c->dbg_enable || c->feat_on; }
+// The uuid arrays of the debug overlay, of the feature planes and of ray queries: PtSphere.uuid in list order and per slot of the structures in
+// place (the walk kernels shade from a slot, like slot_mat).  Made when one of them is turned on and again whenever the scene or the
+// grid changes while one is on (wants_uuids); a context that never enables one never allocates them.  Synchronises: a set-up call's work.
+inline bool wants_uuids(const pt_ctx* c) { return c->dbg_enable || c->feat_on || c->query_on; }
 int upload_uuids(pt_ctx* c, const std::vector<int32_t>& uuid) {
   PT_HIP(c, hipSetDevice(c->device));
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight may read the arrays in place
@@ -1081,6 +1112,10 @@ struct LaunchUse {
   // pt_render_features' launch: the feature build of the path forced or settled (the cold path while PT_GEOM_AUTO measures),
   // one pass into the planes; it is no trial, settles nothing and leaves `geom` as it finds it
   bool features = false;
+  // pt_query_rays' launch: as `features` in everything but the kernel (the row's query build), the planes (the query planes), the
+  // ray count (query_rays: the first that many work items carry a ray) and c->last_build, which it does not store
+  bool query = false;
+  uint32_t query_rays = 0;
 };
 
 // (what fill_uniforms zeroed and nothing here sets stays zero: wave_log and cell_hist, which only a measuring twin gets)
@@ -1096,14 +1131,16 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   }
   const LaunchKnobs knobs = read_launch_knobs();
   if (knobs.carry_lanes) A.carry_lanes = *knobs.carry_lanes;
-  const bool feat = use.features;
+  const bool query = use.query;
+  const bool feat = use.features || query;
   if (c->geom.policy == PT_GEOM_AUTO && !feat) try_finish_tuning(c);
   const bool rr = !feat && c->rr_min_depth > 0, dbg = !feat && c->dbg_enable;
   if (rr && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and PT_OPT_RUSSIAN_ROULETTE exclude each other");
   if (dbg && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and the debug overlay exclude each other");
   if (dbg && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "debug overlay: the uuid arrays are not in place (pt_set_debug_overlay after a failed upload?)");
   // (the overlay builds exist for the ways to read the list that have a roulette build: the same steering away from the LDS walk)
-  if (feat && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "feature planes: the uuid arrays are not in place (PT_OPT_FEATURES after a failed upload?)");
+  if (feat && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "%s: the uuid arrays are not in place (%s after a failed upload?)", query ? "ray queries" : "feature planes",
+                                             query ? "PT_OPT_RAY_QUERIES" : "PT_OPT_FEATURES");
   const PathChoice choice = c->geom.choose(path_scene(c), use.allow_trials && !feat, rr || dbg || feat);
   const int path = choice.path;
   if (!feat) c->geom.last = path;
@@ -1127,8 +1164,9 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   if (feat) {  // one deterministic segment per pixel into the planes; the overlay and roulette do not act
     A.uuid = c->list.uuid.get();
     A.slot_uuid = path == PT_GEOM_BVH ? c->bvh.uuid.get() : (path == PT_GEOM_GRID ? c->grid.uuid.get() : nullptr);
-    A.slab = reinterpret_cast<float*>(c->d_feat.get());
+    A.slab = reinterpret_cast<float*>(query ? c->d_query.get() : c->d_feat.get());
     A.spp = 1; A.max_depth = 1; A.rr_min_depth = 0;
+    if (query) A.dbg_selected = (int32_t)use.query_rays;  // (the overlay's field: no build but the overlay's reads it as that)
   }
   // the two-axis walk reads the ring layout; it is what `scene` was sized for (staged_cells)
   if (reads_ring_layout(row, build)) {
@@ -1136,8 +1174,8 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
     A.n_cells = (uint32_t)ptrec::ring_cells(c->grid.head.n[0], c->grid.head.n[2]);
   }
   const TraceCell& tk = kTraceKernels[row][build];
-  const void* kfn = cell_kernel(c->device, tk);
-  c->last_build = build;
+  const void* kfn = query ? query_kernel(c->device, tk) : cell_kernel(c->device, tk);
+  if (!query) c->last_build = build;
   const uint32_t block = walk ? walk_block_threads(kfn, tk.waves, scene, kWalkLdsMax, knobs.bvh_block) : list_block_threads(scene);
   const size_t lds = walk ? scene + (size_t)PT_PARK_STRIDE * 4 * block : scene;
   A.block_threads = block;
@@ -2077,6 +2115,26 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     if (rc != PT_OK) { c->feat_on = false; c->d_feat = DevBuf<float4>(); }
     return rc;
   }
+  if (key == PT_OPT_RAY_QUERIES) { // the image does not depend on it; the query planes are allocated here, released when turned off
+    if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: ray queries %d", value);
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipStreamSynchronize(c->stream));
+    if (!value) {
+      c->query_on = false;
+      c->d_query = DevBuf<float4>();
+      c->d_query_order = DevBuf<uint32_t>();
+      return PT_OK;
+    }
+    if (c->query_on) return PT_OK;
+    // (asking for a kernel's attributes loads the query builds' code object now: a set-up call's work, not a query's)
+    hipFuncAttributes attr;
+    PT_HIP(c, hipFuncGetAttributes(&attr, pt_query_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar))));
+    c->query_on = true;
+    int rc = ensure_buffers(c);
+    if (rc == PT_OK && !c->uuid_valid && c->have_spheres) rc = upload_uuids(c, c->list.host.uuid);  // the scene in place
+    if (rc != PT_OK) { c->query_on = false; c->d_query = DevBuf<float4>(); c->d_query_order = DevBuf<uint32_t>(); }
+    return rc;
+  }
   if (key == PT_OPT_REPROJECT) { // the image does not depend on it; the history planes are allocated here, released when turned off
     if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: reprojection %d", value);
     if (value && !c->feat_on) return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_REPROJECT needs PT_OPT_FEATURES on (it reads the feature planes)");
@@ -2183,6 +2241,96 @@ PT_API int pt_read_features(pt_ctx* c, int plane, void* out) {
   const size_t need = n_pixels(c) * sizeof(float4);
   if (need) PT_HIP(c, hipMemcpyAsync(out, c->d_feat.get() + (size_t)plane * n_pixels(c), need, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+// ---- ray queries (PT_OPT_RAY_QUERIES; include/ptrace.h has the contract) --------------------------------------
+// are the query planes and their tile order allocated for the local rows in place?  (As with the feature planes.)
+static bool query_planes_in_place(const pt_ctx* c) {
+  const size_t pix = n_pixels(c) ? n_pixels(c) : 1, tiles = n_tiles(c) ? n_tiles(c) : 1;
+  return c->query_on && c->d_query.get() && c->d_query.capacity() == PT_FEAT_PLANES * pix && c->d_query_order.get() &&
+         c->d_query_order.capacity() == tiles;
+}
+
+// can the device read (and write) this pointer of the caller's?  A pointer the runtime does not know is the host's.
+static bool device_pointer(const void* p) {
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+}
+
+PT_API uint32_t pt_query_batch(pt_ctx* c) {
+  if (!c || !c->query_on || !c->have_spheres || !c->have_params || c->local_rows == 0 || !query_planes_in_place(c)) return 0u;
+  return (uint32_t)n_pixels(c);
+}
+
+// n rays in batches of the local pixel count; a batch: stage the rays into the point and normal planes (device arrays: the pack
+// kernel; host arrays: packed on the host, two copies), ONE launch of the query build over the tile rows the rays occupy, the
+// records out of the four planes (the unpack kernel, or four copies and the host's unpack).  Nothing else of the context moves:
+// prepare_launch's LaunchUse::query is LaunchUse::features with another kernel, other planes and no c->last_build.
+PT_API int pt_query_rays(pt_ctx* c, const PtRay* rays, uint32_t n, PtRayHit* hits) {
+  if (!c) return PT_ERR_INVALID;
+  if (n == 0) return PT_OK;
+  if (!rays || !hits) return fail(c, PT_ERR_INVALID, "pt_query_rays: NULL argument");
+  if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_query_rays: not with PT_OPT_COUNT_WORK (the measuring twins have no query build)");
+  if (!c->query_on) return fail(c, PT_ERR_NOT_READY, "pt_query_rays: ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)");
+  if (!c->have_spheres || !c->have_params)
+    return fail(c, PT_ERR_NOT_READY, "pt_query_rays: pt_set_spheres and pt_set_params must come first");
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_query_rays: synchronises; not inside a stream capture");
+  if (c->local_rows == 0) return fail(c, PT_ERR_NOT_READY, "pt_query_rays: this band owns no rows, so it has no work items to decode rays against");
+  if (!query_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "pt_query_rays: the planes are not allocated for the rows in place (an earlier allocation failed)");
+  const uint32_t plane = (uint32_t)n_pixels(c);
+  const bool rays_on_device = device_pointer(rays), hits_on_device = device_pointer(hits);
+  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->d_query.get());
+  std::vector<ptq::F4> h_in, h_out;  // host arrays only: the two planes going up, the four coming down
+  const uint32_t batches = ptq::n_batches(n, plane);
+  for (uint32_t k = 0; k < batches; k++) {
+    const size_t first = (size_t)k * plane;
+    uint32_t m = ptq::batch_rays(n, plane, k);
+    if (rays_on_device) {
+      const PtRay* src = rays + first;
+      uint32_t pl = plane;
+      void* kargs[] = {&src, &m, &planes, &pl};
+      PT_HIP(c, hipLaunchKernel(pt_query_pack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+    } else {
+      h_in.resize(2 * (size_t)m);
+      for (uint32_t i = 0; i < m; i++) ptq::pack_ray(rays[first + i], &h_in[i], &h_in[(size_t)m + i]);
+      PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_POINT * plane, h_in.data(), (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
+      PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_NORMAL * plane, h_in.data() + m, (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
+    }
+    Launch L;
+    LaunchUse use;
+    use.query = true;
+    use.query_rays = m;
+    use.feedback = LaunchUse::OFF;
+    use.n_first_tiles = ptq::tiles_covered(m, c->width);
+    use.table = c->d_query_order.get();
+    if (int rc = prepare_launch(c, 1, use, &L); rc != PT_OK) return rc;
+    PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
+    if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
+    if (hits_on_device) {
+      const ptq::F4* src = planes;
+      PtRayHit* dst = hits + first;
+      uint32_t pl = plane;
+      void* kargs[] = {&src, &pl, &m, &dst};
+      PT_HIP(c, hipLaunchKernel(pt_query_unpack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+    } else {
+      h_out.resize(PT_FEAT_PLANES * (size_t)m);
+      for (int q = 0; q < PT_FEAT_PLANES; q++)
+        PT_HIP(c, hipMemcpyAsync(h_out.data() + (size_t)q * m, planes + (size_t)q * plane, (size_t)m * sizeof(ptq::F4), hipMemcpyDeviceToHost, c->stream));
+    }
+    // (the next batch stages into the planes this one reads out of, and a host batch is unpacked from h_out)
+    PT_HIP(c, hipStreamSynchronize(c->stream));
+    if (!hits_on_device) {
+      const ptq::I4* ids = reinterpret_cast<const ptq::I4*>(h_out.data() + (size_t)PT_FEAT_IDS * m);
+      for (uint32_t i = 0; i < m; i++)
+        hits[first + i] = ptq::unpack_hit(h_out[(size_t)PT_FEAT_ALBEDO * m + i], h_out[(size_t)PT_FEAT_NORMAL * m + i], h_out[(size_t)PT_FEAT_POINT * m + i], ids[i]);
+    }
+  }
   return PT_OK;
 }
 

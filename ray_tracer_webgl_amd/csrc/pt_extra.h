@@ -1,6 +1,7 @@
 // pt_extra.h — THE LIST of the trace kernel's builds, and how pt_api.hip reaches the kernels of every code object.
 //
-// Each of the 55 trace kernels is stated once, below: its symbol, the waves per SIMD it is built for (PT_BUILT_FOR,
+// Each of the 55 trace kernels of the host's table is stated once, below (the twelve ray-query builds of a sixth code object,
+// pt_kernels_query.hip, come from the same variant rows and stand outside the table: see the end of this file): its symbol, the waves per SIMD it is built for (PT_BUILT_FOR,
 // pt_kernel_args.h) and its build type (pt_trace_body.hpp).  From an entry come the kernel's definition and the `case` of its
 // object's accessor (pt_trace_body.hpp PT_TRACE_KERNEL...), its id, and its cell of the host's table with the same wave count
 // and the symbol as a string (pt_trace_table.hpp).  Plain preprocessor and enums: the device units and the host-only table
@@ -72,7 +73,7 @@ enum { PT_SMALL_KERNELS(PT_KERNEL_ID_ENTRY) PT_SMALL_COUNT };
 enum { PT_VARIANT_ROWS(PT_VARIANT_ID_ENTRY, ) PT_VARIANT_COUNT };
 enum { PT_ROULETTE_LAST = PT_VARIANT_COUNT - 1, PT_TWIN_KERNELS(PT_KERNEL_ID_ENTRY) PT_EXTRA_COUNT };
 
-// The five code objects that hold trace kernels and the accessor of each: the kernel's host-side handle (what hipLaunchKernel
+// The five code objects that hold the table's trace kernels (of the library's eight) and the accessor of each: the kernel's host-side handle (what hipLaunchKernel
 // takes) by id, NULL for an id the object does not have.  Asking for a handle loads nothing yet; the HIP runtime loads a code
 // object when one of its kernels is first used.  X(object, accessor, number of ids)
 #define PT_TRACE_OBJECTS(X)                             \
@@ -93,3 +94,11 @@ extern "C" const void* pt_error_kernel(int id);
 // pt_reproject_estimate's, which gathers the error estimate's state in the same pass
 extern "C" const void* pt_reproject_kernel_handle(void);
 extern "C" const void* pt_reproject_estimate_kernel_handle(void);
+// pt_kernels_query.hip (a code object of its own): the ray-query builds of the variant rows (PT_OPT_RAY_QUERIES, pt_query_rays),
+// by the row's variant id — the id of its _feat cell, whose wave count and launch shape they share.  Deliberately neither an
+// entry of PT_TRACE_OBJECTS nor a column of the host's table: a query is no render launch, pt_last_trace_build never reports
+// one, and the table's five columns and 55 kernels stay what they are.  And the two kernels that move a batch of rays and
+// records between the caller's device arrays and the query planes.
+extern "C" const void* pt_query_kernel(int id);
+extern "C" const void* pt_query_pack_kernel_handle(void);
+extern "C" const void* pt_query_unpack_kernel_handle(void);

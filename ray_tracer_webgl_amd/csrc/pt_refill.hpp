@@ -10,6 +10,7 @@
 // inside div_core's range; a +0 numerator gives +0 either way) and the plain operators otherwise.
 #pragma once
 #include "pt_scene.hpp"
+#include "pt_query.hpp"
 
 namespace ptk {
 
@@ -31,9 +32,21 @@ __device__ __forceinline__ PixelDiv pixel_div() {
 // the pixel jitter is divided by the image size (:367-368)
 // FEAT: the first-hit feature build's ray (include/ptrace.h pt_render_features) — the pixel centre through the pinhole: the
 // same dd, tt and cam_o as below with no jitter and no lens; no draw is made and the seed is neither read nor moved
-template <bool FEAT = false>
+// QRY: the query build's ray (include/ptrace.h pt_query_rays) — the caller's, read from the query planes behind A.slab at the
+// lane's work item: the origin from PT_FEAT_POINT's plane and the direction from PT_FEAT_NORMAL's, where the host staged them.
+// A lane reads its own two texels here and overwrites them in shade_segment, so nobody else touches them.  Only admitted items
+// come here (query_admit below): the ray is valid and within the launch's count.
+template <bool FEAT = false, bool QRY = false>
 __device__ __forceinline__ void start_sample(Path& p, const PixelDiv& pd) {
   karg_t& K = *kargs();
+  if constexpr (QRY) {
+    const uint32_t i = p.slab_index, plane = K.local_rows * K.width;
+    const float4* planes = reinterpret_cast<const float4*>(K.slab);
+    const float4 qo = planes[2u * plane + i], qd = planes[plane + i];
+    const V3 o = mk(qo.x, qo.y, qo.z), d = mk(qd.x, qd.y, qd.z);
+    p.o = o; p.d = d; p.a = dot3(d, d); p.col = mk(1.0f, 1.0f, 1.0f); p.depth = 0;
+    return;
+  }
   if constexpr (FEAT) {
     const float s = p.st_s, t = p.st_t;
     const V3 dd = mk(fma_(t, K.vertical[0], fma_(s, K.horizontal[0], K.llc[0])),
@@ -97,6 +110,29 @@ __device__ __forceinline__ void start_sample(Path& p, const PixelDiv& pd) {
   p.seed = seed; p.o = o; p.d = d; p.a = a; p.col = col; p.depth = depth;
 }
 
+// QRY: does work item i (a local pixel of the query planes) carry a ray to walk?  Decided where the item is decoded, so that an
+// item that does not is dropped like one outside the image and the wave step never begins with a lane that has nothing to walk
+// (ending such a lane in start_sample needs a way back from there to the refill, and with that edge in the wave-step loop the
+// six walk builds spill 28-43 vector registers: profiles/r23_kernel_resources.txt).  An item at or beyond the launch's ray count
+// (dbg_selected: the overlay's field, which no build but the overlay's reads as that) is dropped without a store; an invalid
+// ray (pt_query.hpp ray_valid) gets its sentinel record here and is dropped too.  The two texels are read again by
+// start_sample, from the cache: a refill keeps nothing of them.
+__device__ __forceinline__ bool query_admit(uint32_t i) {
+  karg_t& K = *kargs();
+  if (i >= (uint32_t)K.dbg_selected) return false;
+  const uint32_t plane = K.local_rows * K.width;
+  float4* planes = reinterpret_cast<float4*>(K.slab);
+  const float4 qo = planes[2u * plane + i], qd = planes[plane + i];
+  if (ptq::ray_valid(qo.x, qo.y, qo.z, qd.x, qd.y, qd.z)) return true;
+  ptq::F4 t_alb, t_n, t_hp; ptq::I4 t_ids;
+  ptq::invalid_texels(&t_alb, &t_n, &t_hp, &t_ids);
+  planes[i] = make_float4(t_alb.x, t_alb.y, t_alb.z, t_alb.w);
+  planes[plane + i] = make_float4(t_n.x, t_n.y, t_n.z, t_n.w);
+  planes[2u * plane + i] = make_float4(t_hp.x, t_hp.y, t_hp.z, t_hp.w);
+  reinterpret_cast<int4*>(planes)[3u * plane + i] = make_int4(t_ids.x, t_ids.y, t_ids.z, t_ids.w);
+  return false;
+}
+
 // ---- refill: the wave pulls work items for the lanes that will need one ----------------------------
 // The wave reserves A.queue_chunk consecutive items from the global queue with ONE atomic
 // (a memory-side atomic moves 64 B, so per-item atomics would dominate the kernel's HBM
@@ -112,7 +148,8 @@ __device__ __forceinline__ void start_sample(Path& p, const PixelDiv& pd) {
 // Every wave reaches the "queue dry" exit: the head counter is monotone, every trip of the loop deals
 // an item or finds the queue dry; a wave leaves when every lane is dead after promote(), i.e. every
 // slot is empty too, which the loop below lets happen only on a dry queue.
-template <bool COUNT>
+// QRY: items that carry no ray to walk are dropped at the decode (query_admit above).
+template <bool COUNT, bool QRY = false>
 __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q, const PixelDiv& pd, Tally<COUNT>& tally) {
   karg_t& K = *kargs();
   // (local copies, written back at the end: see pt_grid_walk.hpp)
@@ -195,7 +232,9 @@ __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q,
       uint32_t pass = rem_i >> 6, l = rem_i & 63u;
       uint32_t ty = div_by(tile, K.div_tiles_x.m, K.div_tiles_x.s1, K.div_tiles_x.s2), tx = tile - ty * K.tiles_x;
       uint32_t px = tx * 8u + (l & 7u), ly = ty * 8u + (l >> 3);
-      if (px < K.width && ly < K.local_rows) {
+      bool inside = px < K.width && ly < K.local_rows;
+      if constexpr (QRY) { if (inside) inside = query_admit((pass * K.local_rows + ly) * K.width + px); }
+      if (inside) {
         uint32_t y = ly;
         if (K.band_count > 1u) {
           uint32_t b = div_by(ly, K.div_band_rows.m, K.div_band_rows.s1, K.div_band_rows.s2), r = ly - b * K.band_rows;

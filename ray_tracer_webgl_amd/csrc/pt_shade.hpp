@@ -21,7 +21,9 @@ namespace ptk {
 // DBG: the opt-in debug-overlay build (pt_set_debug_overlay; pt_kernels_debug.hip), carried the same way
 // FEAT: the opt-in first-hit feature build (pt_render_features; pt_kernels_features.hip): the complete hit record — or the
 // miss — goes to the four planes behind A.slab and the path ends; no draw, no scatter, no colour store
-template <typename S, bool RR, bool COUNT, bool DBG = false, bool FEAT = false>
+// QRY: the opt-in ray-query build (pt_query_rays; pt_kernels_query.hip): FEAT's store IS its store — the planes behind A.slab are
+// the query planes, the work item is the ray's place — and nothing in here differs
+template <typename S, bool RR, bool COUNT, bool DBG = false, bool FEAT = false, bool QRY = false>
 __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, const Hit& h, const Carry& cw, Tally<COUNT>& tally) {
   tally.flag(PT_REG_SHADE_ANY);
   // local copies, written back at the end (see pt_grid_walk.hpp: references would be memory to the

@@ -419,6 +419,59 @@ class PathTracer:
             out[name] = torch.as_tensor(view, device="cuda:%d" % self.device)
         return out
 
+    # -- ray queries (include/ptrace.h PT_OPT_RAY_QUERIES) ------------------------------------------
+    def ray_queries(self, on=True):
+        """Allocate (or release) the query planes of query_rays.  Off by default; the image bits are the same either way."""
+        self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_RAY_QUERIES, 1 if on else 0))
+
+    def query_batch(self):
+        """Rays one launch of query_rays takes (the local pixel count); 0 while it could not answer."""
+        return int(self.lib.pt_query_batch(self._ctx))
+
+    _HIT_FIELDS = (("albedo", 0, 3, False), ("t", 3, 4, False), ("normal", 4, 7, False), ("point", 8, 11, False),
+                   ("index", 12, 13, True), ("uuid", 13, 14, True), ("type", 14, 15, True), ("front_face", 15, 16, True))
+
+    def query_rays(self, origins, directions):
+        """The closest hit of each of the caller's rays (pt_query_rays), through the trace kernels' own intersection: two
+        (n, 3) float32 arrays in (directions are not normalised; t is in their units), a dict out — "albedo", "normal",
+        "point": (n, 3) float32; "t": (n,) float32; "index", "uuid", "type", "front_face": (n,) int32.  A miss has index
+        -1 and the background in "albedo"; an invalid ray (a non-finite component, a direction of three zeros) has index
+        abi.PT_RAY_INVALID.  numpy arrays give numpy arrays; under use_torch, torch device tensors give torch device tensors
+        (no host copy, ordered on torch's stream).  Synchronous; nothing else of the context moves."""
+        on_device = self.use_torch and self._torch.is_tensor(origins) and origins.is_cuda
+        if on_device:
+            torch = self._torch
+            o = origins.to(torch.float32).reshape(-1, 3)
+            d = directions.to(device=o.device, dtype=torch.float32).reshape(-1, 3)
+            if o.shape != d.shape:
+                raise ValueError("query_rays: %d origins, %d directions" % (o.shape[0], d.shape[0]))
+            n = int(o.shape[0])
+            rays = torch.zeros((n, 8), dtype=torch.float32, device=o.device)
+            rays[:, 0:3] = o
+            rays[:, 4:7] = d
+            hits = torch.zeros((n, 16), dtype=torch.int32, device=o.device)
+            if n:
+                self._check(self.lib.pt_query_rays(self._ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(hits.data_ptr())))
+            fl = hits.view(torch.float32)
+        else:
+            o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+            d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+            if o.shape != d.shape:
+                raise ValueError("query_rays: %d origins, %d directions" % (o.shape[0], d.shape[0]))
+            n = int(o.shape[0])
+            rays = np.zeros((n, 8), np.float32)
+            rays[:, 0:3] = o
+            rays[:, 4:7] = d
+            hits = np.zeros((n, 16), np.int32)
+            if n:
+                self._check(self.lib.pt_query_rays(self._ctx, rays.ctypes.data_as(C.c_void_p), n, hits.ctypes.data_as(C.c_void_p)))
+            fl = hits.view(np.float32)
+        out = {}
+        for name, a, b, integer in self._HIT_FIELDS:
+            col = (hits if integer else fl)[:, a:b]
+            out[name] = col if b - a > 1 else col[:, 0]
+        return out
+
     # -- temporal reprojection (include/ptrace.h PT_OPT_REPROJECT) ---------------------------------
     def reproject_option(self, on=True):
         """Allocate (or release) the history planes of temporal reprojection; needs feature_planes(True) first.  Off by
