@@ -63,6 +63,11 @@ pub struct PtRayHit {            // its record, 64 bytes: the four feature texel
     pub index: i32, pub uuid: i32, pub type_: i32, pub front_face: i32,
 }
 
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtRayRadiance {       // the record of one ray of pt_query_radiance, 16 bytes: an accumulation texel; samples 0 marks an invalid ray
+    pub sum: [f32; 3], pub samples: f32,
+}
+
 #[repr(C)] pub struct PtCtx { _private: [u8; 0] }
 
 #[link(name = "ptrace")]
@@ -126,6 +131,10 @@ extern "C" {
     // pointers, synchronous; pt_query_batch: the rays one launch takes
     pub fn pt_query_rays(ctx: *mut PtCtx, rays: *const PtRay, n: u32, hits: *mut PtRayHit) -> c_int;
     pub fn pt_query_batch(ctx: *mut PtCtx) -> u32;
+    // radiance queries (PT_OPT_RAY_QUERIES on): the path-traced radiance along the caller's rays — probes, a baker's batch, a second
+    // view — by the plain estimator, n_passes passes (at most those reserved) of samples_per_pixel samples per ray; host or device
+    // pointers, synchronous; the camera, the accumulation and first_pass do not move
+    pub fn pt_query_radiance(ctx: *mut PtCtx, rays: *const PtRay, n: u32, n_passes: u32, out: *mut PtRayRadiance) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;

@@ -756,6 +756,59 @@ typedef struct PtRayHit {
 int pt_query_rays(pt_ctx* ctx, const PtRay* rays, uint32_t n, PtRayHit* hits);
 uint32_t pt_query_batch(pt_ctx* ctx);
 
+/* ---- radiance queries: the path-traced radiance along the CALLER's rays (needs PT_OPT_RAY_QUERIES on; no option of its own) ----
+ * pt_query_rays says what a ray meets; pt_query_radiance says how much light arrives along it: an irradiance or reflection
+ * probe, a baking tool's batch, a second view (a mirror, a minimap), auto-exposure from a point in the scene — without moving
+ * the camera and without touching the accumulation.  Ray i is walked n_passes * samples_per_pixel times by the plain estimator
+ * of pt_render_passes (static/shader.frag:297-339 with the emissive and background extensions), through the geometry path
+ * forced or settled exactly as pt_query_rays chooses it (the radiance builds: the plain builds with the ray read from memory, a
+ * code object of their own, loaded at the first call); PT_OPT_RUSSIAN_ROULETTE and the debug overlay do not act, as with
+ * pt_render_features.
+ * THE RAY: hit_world of the trace kernels themselves, as pt_query_rays states it: the direction is NOT normalised, t_min = 0.001
+ * and t_max = 1e5 are in its units, ties go to the later sphere, a negative radius flips the normal.
+ * WHAT ENTERS of PtParams: time, time_step (0 means 1), first_pass, samples_per_pixel, max_depth and background_mode; width,
+ * height and the row partition shape the work items and therefore the SEEDS.  The camera, the lens and render_count do not
+ * enter.  first_pass is NOT advanced: the same call again gives the same bits.
+ * THE RECORD of ray i, out[i], fp32, one IEEE operation per statement.  B = pt_query_batch(ctx); ray i lies in batch b = i / B
+ * at place j = i % B:
+ *   px = j % width;  ly = j / width;  y = pt_band_row(band_rows, band_index, band_count, ly)   (band_count <= 1: y = ly)
+ *   vx = float(2 px + 1) / float(width) - 1;   vy = float(2 y + 1) / float(height) - 1
+ *   out = {+0, +0, +0, +0}
+ *   for p = 0 .. n_passes - 1:
+ *       u_time = time + float(first_pass + b * n_passes + p) * step        (multiply, then add: the render calls' rule)
+ *       seed = init_global_seed(vx, vy, u_time)                            (static/shader.frag:354-357)
+ *       s = {+0, +0, +0}
+ *       for k = 0 .. samples_per_pixel - 1:
+ *           c = ray_color(origin_i, direction_i, seed)     (shader.frag:297-339; the seed is carried from sample to sample;
+ *                                                           NO jitter draw and NO lens draws precede it)
+ *           s.c = s.c + c.c
+ *       out.sum.c = out.sum.c + s.c ;  out.samples = out.samples + float(samples_per_pixel)
+ * The estimate of the radiance is sum / samples.
+ * PASSES PER BATCH: a batch takes passes of its own (b * n_passes): rays at the same place of different batches share no random
+ * numbers.  The record of a ray therefore depends on its INDEX in the call and on the context's SIZE (width, height, the row
+ * partition), not on the ray alone: two rays with the same origin and direction at different indices get different samples of
+ * the same expectation.  The second batch of a call is the first batch of a call at first_pass + n_passes.
+ * INVALID RAYS: invalid as pt_query_rays states it (a non-finite component, or a direction of three zeros), decided on the
+ * device before any walk; the record is {+0, +0, +0, +0}, and samples == 0 is the mark.  Every other ray has samples ==
+ * n_passes * samples_per_pixel.
+ * `rays` and `out` are host or device pointers (n of each).  The call is synchronous on the context's stream: it returns when
+ * out[0..n) are written, and writes nothing else.  One launch plus one fold per batch, over the tile rows the batch's rays
+ * occupy; n == 0 is PT_OK with nothing done.  n_passes is at least 1 and at most the passes reserved with pt_reserve_passes:
+ * the context's pass slabs are the workspace (they are free between calls: every render call folds them before it returns).
+ * What it moves: PtStats.segments by exactly the segments traced (invalid rays add none) and far_rays as a render would.  What
+ * it leaves alone: everything pt_query_rays leaves alone — the accumulation, the estimate, the feature and history planes and
+ * their validity, the textures and the canvas, first_pass, the tile order and costs (no cost feedback), the geometry path
+ * (never a measuring launch) and pt_last_trace_build — and PtStats.samples, total_spp, render_launches and render_kernel_ms.
+ * PT_ERR_INVALID: NULL ctx, rays or out (n > 0), PT_OPT_COUNT_WORK on, inside a stream capture, n_passes == 0.
+ * PT_ERR_NOT_READY: PT_OPT_RAY_QUERIES is off, no scene or no uniforms yet, or a band that owns no rows.  PT_ERR_CAPACITY: the
+ * query planes are not in place after a failed allocation, or n_passes exceeds the reservation.  (Checked in pt_query_rays'
+ * order, then n_passes.) */
+typedef struct PtRayRadiance {
+  float sum[3];
+  float samples;
+} PtRayRadiance; /* 16 bytes: an accumulation texel */
+int pt_query_radiance(pt_ctx* ctx, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out);
+
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)
  * using params.render_count / should_average / last_frame_weight, writes RGBA8 to `out_rgba8`.

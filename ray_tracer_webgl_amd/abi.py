@@ -255,6 +255,15 @@ class PtRayHit(C.Structure):
     ]
 
 
+class PtRayRadiance(C.Structure):
+    """include/ptrace.h PtRayRadiance: the record of one ray of pt_query_radiance, 16 bytes — an accumulation texel; samples 0 marks an invalid ray."""
+
+    _fields_ = [
+        ("sum", C.c_float * 3),
+        ("samples", C.c_float),
+    ]
+
+
 class PtHostSphere(C.Structure):
     """src/glsl.rs:27-40: f64 centre/radius/albedo, f32 fuzz/refraction_index."""
 

@@ -36,6 +36,7 @@
 #include "pt_reproject_plan.hpp"
 #include "pt_reproject.hpp"
 #include "pt_query.hpp"
+#include "pt_radiance.hpp"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -509,6 +510,19 @@ const void* cell_kernel(int device, const TraceCell& k) {
 const void* query_kernel(int device, const TraceCell& feat_cell) {
   static std::once_flag once[64][PT_VARIANT_COUNT];
   const void* fn = pt_query_kernel(feat_cell.id);
+  if (fn)
+    std::call_once(once[device & 63][feat_cell.id], [fn] {
+      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
+      (void)hipGetLastError();
+    });
+  return fn;
+}
+
+// The radiance build that serves a row, likewise: the handle pt_radiance_kernel gives for the id of the row's feature cell.
+// Asking for it the first time is what loads the radiance builds' code object.
+const void* radiance_kernel(int device, const TraceCell& feat_cell) {
+  static std::once_flag once[64][PT_VARIANT_COUNT];
+  const void* fn = pt_radiance_kernel(feat_cell.id);
   if (fn)
     std::call_once(once[device & 63][feat_cell.id], [fn] {
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
@@ -1116,6 +1130,12 @@ struct LaunchUse {
   // ray count (query_rays: the first that many work items carry a ray) and c->last_build, which it does not store
   bool query = false;
   uint32_t query_rays = 0;
+  // pt_query_radiance's launch: the door of `query` (the row's variant through the path forced or settled, no trial, nothing
+  // settled, no cost feedback, c->last_build not stored, query_rays rays) in front of the PLAIN estimator — the row's radiance
+  // build, n_passes passes of the uniforms' samples and depth into the pass slabs, frame_ctr at the zero cell, neither roulette
+  // nor the overlay; the staged rays travel in PtKernelArgs::uuid and the batch's first pass is `first_pass`
+  bool radiance = false;
+  uint32_t first_pass = 0;
 };
 
 // (what fill_uniforms zeroed and nothing here sets stays zero: wave_log and cell_hist, which only a measuring twin gets)
@@ -1131,19 +1151,20 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   }
   const LaunchKnobs knobs = read_launch_knobs();
   if (knobs.carry_lanes) A.carry_lanes = *knobs.carry_lanes;
-  const bool query = use.query;
+  const bool query = use.query, rad = use.radiance;
   const bool feat = use.features || query;
-  if (c->geom.policy == PT_GEOM_AUTO && !feat) try_finish_tuning(c);
-  const bool rr = !feat && c->rr_min_depth > 0, dbg = !feat && c->dbg_enable;
+  const bool door = feat || rad;  // no render launch: a variant row's build, no trial, nothing of the path or the order moves
+  if (c->geom.policy == PT_GEOM_AUTO && !door) try_finish_tuning(c);
+  const bool rr = !door && c->rr_min_depth > 0, dbg = !door && c->dbg_enable;
   if (rr && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and PT_OPT_RUSSIAN_ROULETTE exclude each other");
   if (dbg && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and the debug overlay exclude each other");
   if (dbg && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "debug overlay: the uuid arrays are not in place (pt_set_debug_overlay after a failed upload?)");
   // (the overlay builds exist for the ways to read the list that have a roulette build: the same steering away from the LDS walk)
   if (feat && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "%s: the uuid arrays are not in place (%s after a failed upload?)", query ? "ray queries" : "feature planes",
                                              query ? "PT_OPT_RAY_QUERIES" : "PT_OPT_FEATURES");
-  const PathChoice choice = c->geom.choose(path_scene(c), use.allow_trials && !feat, rr || dbg || feat);
+  const PathChoice choice = c->geom.choose(path_scene(c), use.allow_trials && !door, rr || dbg || door);
   const int path = choice.path;
-  if (!feat) c->geom.last = path;
+  if (!door) c->geom.last = path;
 
   // the kernel, its workgroup size and its dynamic LDS (staged scene + the parked path state of every
   // lane of a walk kernel's workgroup)
@@ -1160,7 +1181,7 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
     scene = c->list.n <= PT_MAX_SPHERES_LDS ? (size_t)PT_LDS_ENTRIES(c->list.n) * 16 : 0;
   }
   const int row = trace_row(path, c->list.n, st.kind, c->grid.head.n[1]);
-  const int build = trace_build(feat, dbg, rr, c->count_work);
+  const int build = trace_build(door, dbg, rr, c->count_work);  // (a radiance launch: the row's feature CELL names its build, see below)
   if (feat) {  // one deterministic segment per pixel into the planes; the overlay and roulette do not act
     A.uuid = c->list.uuid.get();
     A.slot_uuid = path == PT_GEOM_BVH ? c->bvh.uuid.get() : (path == PT_GEOM_GRID ? c->grid.uuid.get() : nullptr);
@@ -1168,14 +1189,21 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
     A.spp = 1; A.max_depth = 1; A.rr_min_depth = 0;
     if (query) A.dbg_selected = (int32_t)use.query_rays;  // (the overlay's field: no build but the overlay's reads it as that)
   }
+  if (rad) {  // the plain estimator on the caller's rays: the uniforms' samples and depth, the pass slabs fill_uniforms bound
+    A.uuid = reinterpret_cast<const int32_t*>(c->d_query.get());  // (the staged rays: pt_kernel_args.h says why there)
+    A.slot_uuid = nullptr;
+    A.dbg_selected = (int32_t)use.query_rays;
+    A.first_pass = use.first_pass;
+    A.rr_min_depth = 0;
+  }
   // the two-axis walk reads the ring layout; it is what `scene` was sized for (staged_cells)
   if (reads_ring_layout(row, build)) {
     A.grid_cells = c->grid.ring.get();
     A.n_cells = (uint32_t)ptrec::ring_cells(c->grid.head.n[0], c->grid.head.n[2]);
   }
   const TraceCell& tk = kTraceKernels[row][build];
-  const void* kfn = query ? query_kernel(c->device, tk) : cell_kernel(c->device, tk);
-  if (!query) c->last_build = build;
+  const void* kfn = rad ? radiance_kernel(c->device, tk) : (query ? query_kernel(c->device, tk) : cell_kernel(c->device, tk));
+  if (!query && !rad) c->last_build = build;
   const uint32_t block = walk ? walk_block_threads(kfn, tk.waves, scene, kWalkLdsMax, knobs.bvh_block) : list_block_threads(scene);
   const size_t lds = walk ? scene + (size_t)PT_PARK_STRIDE * 4 * block : scene;
   A.block_threads = block;
@@ -1187,7 +1215,7 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   A.queue_chunk = P.queue_chunk; A.queue_static = (uint32_t)P.deal; A.queue_groups = P.queue_groups;
   A.n_waves = P.n_waves; A.coop_max_live = P.coop_max_live; A.refill_ahead = P.refill_ahead;
   A.cost_feedback = use.feedback == LaunchUse::PLANNED ? P.cost_feedback : (use.feedback == LaunchUse::ON ? 1u : 0u);
-  if (feat) A.cost_feedback = 0u;
+  if (door) A.cost_feedback = 0u;
   L->kfn = kfn; L->grid = P.grid; L->block = block; L->lds = lds; L->path = path; L->trial = choice.trial;
   return PT_OK;
 }
@@ -2330,6 +2358,73 @@ PT_API int pt_query_rays(pt_ctx* c, const PtRay* rays, uint32_t n, PtRayHit* hit
       for (uint32_t i = 0; i < m; i++)
         hits[first + i] = ptq::unpack_hit(h_out[(size_t)PT_FEAT_ALBEDO * m + i], h_out[(size_t)PT_FEAT_NORMAL * m + i], h_out[(size_t)PT_FEAT_POINT * m + i], ids[i]);
     }
+  }
+  return PT_OK;
+}
+
+// ---- radiance queries (needs PT_OPT_RAY_QUERIES; include/ptrace.h has the contract) ---------------------------
+// n rays in batches of the local pixel count, as pt_query_rays deals them; a batch: stage the rays into the point and normal
+// planes of the query planes (pt_query_rays' own staging), ONE launch of the row's radiance build over the tile rows the rays
+// occupy — n_passes passes of the batch's own into the pass slabs — and ONE fold of those slabs into the records
+// (pt_radiance_fold_kernel): straight into a device `out`, or into the query planes' first plane (a record is a texel) and
+// copied from there.  Nothing is allocated per call but the host vector of a host batch's staging.
+PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out) {
+  if (!c) return PT_ERR_INVALID;
+  if (n == 0) return PT_OK;
+  if (!rays || !out) return fail(c, PT_ERR_INVALID, "pt_query_radiance: NULL argument");
+  if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_query_radiance: not with PT_OPT_COUNT_WORK (the measuring twins have no radiance build)");
+  if (!c->query_on) return fail(c, PT_ERR_NOT_READY, "pt_query_radiance: ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)");
+  if (!c->have_spheres || !c->have_params)
+    return fail(c, PT_ERR_NOT_READY, "pt_query_radiance: pt_set_spheres and pt_set_params must come first");
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_query_radiance: synchronises; not inside a stream capture");
+  if (c->local_rows == 0) return fail(c, PT_ERR_NOT_READY, "pt_query_radiance: this band owns no rows, so it has no work items to decode rays against");
+  if (!query_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "pt_query_radiance: the planes are not allocated for the rows in place (an earlier allocation failed)");
+  if (n_passes == 0) return fail(c, PT_ERR_INVALID, "pt_query_radiance: n_passes == 0");
+  if (n_passes > c->reserved_passes)
+    return fail(c, PT_ERR_CAPACITY, "pt_query_radiance: %u passes > %u reserved (pt_reserve_passes)", n_passes, c->reserved_passes);
+  static_assert(sizeof(PtRayRadiance) == sizeof(ptq::F4), "a record is a texel: the fold's scratch is a plane");
+  const uint32_t plane = (uint32_t)n_pixels(c);
+  const bool rays_on_device = device_pointer(rays), out_on_device = device_pointer(out);
+  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->d_query.get());
+  std::vector<ptq::F4> h_in;  // host rays only: the two planes going up
+  const uint32_t batches = ptq::n_batches(n, plane);
+  for (uint32_t k = 0; k < batches; k++) {
+    const size_t first = (size_t)k * plane;
+    uint32_t m = ptq::batch_rays(n, plane, k);
+    if (rays_on_device) {
+      const PtRay* src = rays + first;
+      uint32_t pl = plane;
+      void* kargs[] = {&src, &m, &planes, &pl};
+      PT_HIP(c, hipLaunchKernel(pt_query_pack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+    } else {
+      h_in.resize(2 * (size_t)m);
+      for (uint32_t i = 0; i < m; i++) ptq::pack_ray(rays[first + i], &h_in[i], &h_in[(size_t)m + i]);
+      PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_POINT * plane, h_in.data(), (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
+      PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_NORMAL * plane, h_in.data() + m, (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
+    }
+    Launch L;
+    LaunchUse use;
+    use.radiance = true;
+    use.query_rays = m;
+    use.first_pass = ptr::batch_first_pass(c->params.first_pass, k, n_passes);
+    use.feedback = LaunchUse::OFF;
+    use.n_first_tiles = ptq::tiles_covered(m, c->width);
+    use.table = c->d_query_order.get();
+    if (int rc = prepare_launch(c, n_passes, use, &L); rc != PT_OK) return rc;
+    PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
+    if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
+    {
+      const ptq::F4* slab = reinterpret_cast<const ptq::F4*>(c->d_slab.get());
+      const ptq::F4* staged = planes;
+      PtRayRadiance* dst = out_on_device ? out + first : reinterpret_cast<PtRayRadiance*>(planes + (size_t)PT_FEAT_ALBEDO * plane);
+      uint32_t pl = plane, np = n_passes;
+      void* kargs[] = {&slab, &pl, &np, &staged, &m, &dst};
+      PT_HIP(c, hipLaunchKernel(pt_radiance_fold_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+      if (!out_on_device) PT_HIP(c, hipMemcpyAsync(out + first, dst, (size_t)m * sizeof(PtRayRadiance), hipMemcpyDeviceToHost, c->stream));
+    }
+    // (the next batch stages into the planes this one's fold reads, and a host batch's vector is packed again)
+    PT_HIP(c, hipStreamSynchronize(c->stream));
   }
   return PT_OK;
 }

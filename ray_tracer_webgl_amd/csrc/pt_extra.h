@@ -1,7 +1,8 @@
 // pt_extra.h — THE LIST of the trace kernel's builds, and how pt_api.hip reaches the kernels of every code object.
 //
 // Each of the 55 trace kernels of the host's table is stated once, below (the twelve ray-query builds of a sixth code object,
-// pt_kernels_query.hip, come from the same variant rows and stand outside the table: see the end of this file): its symbol, the waves per SIMD it is built for (PT_BUILT_FOR,
+// pt_kernels_query.hip, and the twelve radiance-query builds of a seventh, pt_kernels_radiance.hip, come from the same variant
+// rows and stand outside the table: see the end of this file): its symbol, the waves per SIMD it is built for (PT_BUILT_FOR,
 // pt_kernel_args.h) and its build type (pt_trace_body.hpp).  From an entry come the kernel's definition and the `case` of its
 // object's accessor (pt_trace_body.hpp PT_TRACE_KERNEL...), its id, and its cell of the host's table with the same wave count
 // and the symbol as a string (pt_trace_table.hpp).  Plain preprocessor and enums: the device units and the host-only table
@@ -73,7 +74,7 @@ enum { PT_SMALL_KERNELS(PT_KERNEL_ID_ENTRY) PT_SMALL_COUNT };
 enum { PT_VARIANT_ROWS(PT_VARIANT_ID_ENTRY, ) PT_VARIANT_COUNT };
 enum { PT_ROULETTE_LAST = PT_VARIANT_COUNT - 1, PT_TWIN_KERNELS(PT_KERNEL_ID_ENTRY) PT_EXTRA_COUNT };
 
-// The five code objects that hold the table's trace kernels (of the library's eight) and the accessor of each: the kernel's host-side handle (what hipLaunchKernel
+// The five code objects that hold the table's trace kernels (of the library's nine) and the accessor of each: the kernel's host-side handle (what hipLaunchKernel
 // takes) by id, NULL for an id the object does not have.  Asking for a handle loads nothing yet; the HIP runtime loads a code
 // object when one of its kernels is first used.  X(object, accessor, number of ids)
 #define PT_TRACE_OBJECTS(X)                             \
@@ -102,3 +103,8 @@ extern "C" const void* pt_reproject_estimate_kernel_handle(void);
 extern "C" const void* pt_query_kernel(int id);
 extern "C" const void* pt_query_pack_kernel_handle(void);
 extern "C" const void* pt_query_unpack_kernel_handle(void);
+// pt_kernels_radiance.hip (a code object of its own): the radiance-query builds of the variant rows (pt_query_radiance), by the
+// row's variant id as above and outside the table for the same reasons, and the kernel that folds a batch's pass slabs into
+// its records.
+extern "C" const void* pt_radiance_kernel(int id);
+extern "C" const void* pt_radiance_fold_kernel_handle(void);

@@ -101,6 +101,8 @@ struct PtKernelArgs {
   // debug overlay (pt_set_debug_overlay; read by the overlay builds of pt_kernels_debug.hip only, at the point of use: pt_shade.hpp).
   // Behind everything else for the same reason as mat_r0.
   const int32_t* uuid;             // n_spheres: PtSphere.uuid in list order (the caller's values, not indices)
+                                   // (the radiance-query builds, which shade as the plain builds do and never read a uuid, find the
+                                   // base of the query planes here — their staged rays: pt_refill.hpp RAD; the ray count in dbg_selected)
   const int32_t* slot_uuid;        // n_slots: the slot's sphere's uuid (walk kernels, like slot_mat)
   float dbg_cursor[3];             // u_cursor_point, static/shader.frag:102
   int32_t dbg_selected;            // u_selected_object, :101

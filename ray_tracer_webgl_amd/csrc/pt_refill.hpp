@@ -36,9 +36,22 @@ __device__ __forceinline__ PixelDiv pixel_div() {
 // lane's work item: the origin from PT_FEAT_POINT's plane and the direction from PT_FEAT_NORMAL's, where the host staged them.
 // A lane reads its own two texels here and overwrites them in shade_segment, so nobody else touches them.  Only admitted items
 // come here (query_admit below): the ray is valid and within the launch's count.
-template <bool FEAT = false, bool QRY = false>
+// RAD: the radiance-query build's ray (include/ptrace.h pt_query_radiance) — the caller's again, for EVERY sample of the item:
+// A.slab is the pass slabs here, so the query planes the host staged the rays in arrive behind K.uuid (pt_kernel_args.h), and
+// the item's place in them — its local pixel, whatever its pass — is carried in st_s as bits (the decode below puts it there:
+// these builds have no other use for st_s and st_t).  The seed is the item's own, set at the decode as in every plain build,
+// and stays untouched: no jitter draw and no lens draws precede ray_color.  Only admitted items come here (radiance_admit).
+template <bool FEAT = false, bool QRY = false, bool RAD = false>
 __device__ __forceinline__ void start_sample(Path& p, const PixelDiv& pd) {
   karg_t& K = *kargs();
+  if constexpr (RAD) {
+    const uint32_t j = f2u(p.st_s), plane = K.local_rows * K.width;
+    const float4* rays = reinterpret_cast<const float4*>(K.uuid);
+    const float4 qo = rays[2u * plane + j], qd = rays[plane + j];
+    const V3 o = mk(qo.x, qo.y, qo.z), d = mk(qd.x, qd.y, qd.z);
+    p.o = o; p.d = d; p.a = dot3(d, d); p.col = mk(1.0f, 1.0f, 1.0f); p.depth = 0;
+    return;
+  }
   if constexpr (QRY) {
     const uint32_t i = p.slab_index, plane = K.local_rows * K.width;
     const float4* planes = reinterpret_cast<const float4*>(K.slab);
@@ -133,6 +146,19 @@ __device__ __forceinline__ bool query_admit(uint32_t i) {
   return false;
 }
 
+// RAD: does the work item at place j (its local pixel; the passes of a place share its ray) carry a ray to walk?  Decided at the
+// decode for query_admit's reason.  An item at or beyond the launch's ray count (dbg_selected, as above) or with an invalid ray
+// is dropped WITHOUT a store: its slab texels stay stale, and the fold kernel (pt_radiance.hpp fold_at) decides validity again
+// by the same predicate and writes the zero record.  The rays lie in the query planes behind K.uuid (start_sample RAD).
+__device__ __forceinline__ bool radiance_admit(uint32_t j) {
+  karg_t& K = *kargs();
+  if (j >= (uint32_t)K.dbg_selected) return false;
+  const uint32_t plane = K.local_rows * K.width;
+  const float4* rays = reinterpret_cast<const float4*>(K.uuid);
+  const float4 qo = rays[2u * plane + j], qd = rays[plane + j];
+  return ptq::ray_valid(qo.x, qo.y, qo.z, qd.x, qd.y, qd.z);
+}
+
 // ---- refill: the wave pulls work items for the lanes that will need one ----------------------------
 // The wave reserves A.queue_chunk consecutive items from the global queue with ONE atomic
 // (a memory-side atomic moves 64 B, so per-item atomics would dominate the kernel's HBM
@@ -149,7 +175,8 @@ __device__ __forceinline__ bool query_admit(uint32_t i) {
 // an item or finds the queue dry; a wave leaves when every lane is dead after promote(), i.e. every
 // slot is empty too, which the loop below lets happen only on a dry queue.
 // QRY: items that carry no ray to walk are dropped at the decode (query_admit above).
-template <bool COUNT, bool QRY = false>
+// RAD: likewise (radiance_admit above); the item's place goes to start_sample in nx_s, as bits.
+template <bool COUNT, bool QRY = false, bool RAD = false>
 __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q, const PixelDiv& pd, Tally<COUNT>& tally) {
   karg_t& K = *kargs();
   // (local copies, written back at the end: see pt_grid_walk.hpp)
@@ -234,6 +261,7 @@ __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q,
       uint32_t px = tx * 8u + (l & 7u), ly = ty * 8u + (l >> 3);
       bool inside = px < K.width && ly < K.local_rows;
       if constexpr (QRY) { if (inside) inside = query_admit((pass * K.local_rows + ly) * K.width + px); }
+      if constexpr (RAD) { if (inside) inside = radiance_admit(ly * K.width + px); }
       if (inside) {
         uint32_t y = ly;
         if (K.band_count > 1u) {
@@ -252,6 +280,7 @@ __device__ __forceinline__ void refill(const PtKernelArgs& A, Path& p, Queue& q,
         nx_seed = (float)base_hash(f2u(vx), f2u(vy)) * (1.0f / 4294967296.0f) + u_time;
         nx_s = (vx + 1.0f) * 0.5f; // :410
         nx_t = (vy + 1.0f) * 0.5f;
+        if constexpr (RAD) nx_s = u2f(ly * K.width + px);  // the item's place in the staged rays, for start_sample (bits, never computed with)
         nx_slab = (pass * K.local_rows + ly) * K.width + px;
         // only the launch's first pass reports its cost (atomicMax per pixel: the tile's
         // heaviest item): plenty for ordering tiles, and a memory-side atomic moves 64 B.  Launches of

@@ -1,9 +1,9 @@
-// pt_trace_body.hpp — the path-tracing kernel body shared by the six device translation units that trace (each a gfx950
+// pt_trace_body.hpp — the path-tracing kernel body shared by the seven device translation units that trace (each a gfx950
 // code object of its own, loaded when one of its kernels is first asked for): pt_kernels.hip (list and walk
 // kernels), pt_kernels_small.hip (the small-list kernels, one per list length modulo four),
 // pt_kernels_extra.hip (the opt-in builds: the Russian-roulette kernels and the measuring twins),
-// pt_kernels_debug.hip (the opt-in debug-overlay builds), pt_kernels_features.hip (the opt-in first-hit feature builds) and
-// pt_kernels_query.hip (the opt-in ray-query builds).
+// pt_kernels_debug.hip (the opt-in debug-overlay builds), pt_kernels_features.hip (the opt-in first-hit feature builds),
+// pt_kernels_query.hip (the opt-in ray-query builds) and pt_kernels_radiance.hip (the radiance-query builds).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,11 +33,14 @@ using namespace ptd;
 //            planes, no scatter; pt_refill.hpp start_sample, pt_shade.hpp)
 //   QRY      the opt-in ray-query build (pt_query_rays): the feature build with the CALLER's ray, read from the query planes at the
 //            lane's work item, in the pixel-centre ray's place (pt_refill.hpp start_sample); set together with FEAT (adaptor Qry)
+//   RAD      the radiance-query build (pt_query_radiance): the plain build with the CALLER's ray in the camera ray's place — QRY
+//            without FEAT: every sample of an item starts from the ray staged at the item's place, the seed is the item's own,
+//            and the shade, the sample loop and the slab store are the plain build's (pt_refill.hpp start_sample, radiance_admit)
 // Which kernel is which row under which adaptor is stated once, in the lists of pt_extra.h.
 // --------------------------------------------------------------------------------------------
 namespace ptb {
 struct Defaults {
-  static constexpr bool SCAN_LDS = false, HAVE_LDS = false, COUNT = false, RR = false, FLAT_Y = false, DBG = false, FEAT = false, QRY = false;
+  static constexpr bool SCAN_LDS = false, HAVE_LDS = false, COUNT = false, RR = false, FLAT_Y = false, DBG = false, FEAT = false, QRY = false, RAD = false;
   static constexpr int WALK = 0, TAIL = -1;
 };
 struct ListLds : Defaults { static constexpr bool SCAN_LDS = true, HAVE_LDS = true; };
@@ -56,6 +59,7 @@ template <class Row> struct Rr : Row { static constexpr bool RR = true; };
 template <class Row> struct Dbg : Row { static constexpr bool DBG = true; };
 template <class Row> struct Feat : Row { static constexpr bool FEAT = true; };
 template <class Row> struct Qry : Row { static constexpr bool FEAT = true, QRY = true; };
+template <class Row> struct Rad : Row { static constexpr bool RAD = true; };
 }  // namespace ptb
 
 // One entry of a kernel list (pt_extra.h) as the kernel's definition and as the `case` of its object's accessor; a row of
@@ -70,7 +74,7 @@ template <class Row> struct Qry : Row { static constexpr bool FEAT = true, QRY =
 template <class B>
 __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
   using namespace ptk;
-  constexpr bool SCAN_LDS = B::SCAN_LDS, HAVE_LDS = B::HAVE_LDS, COUNT = B::COUNT, RR = B::RR, FLAT_Y = B::FLAT_Y, DBG = B::DBG, FEAT = B::FEAT, QRY = B::QRY;
+  constexpr bool SCAN_LDS = B::SCAN_LDS, HAVE_LDS = B::HAVE_LDS, COUNT = B::COUNT, RR = B::RR, FLAT_Y = B::FLAT_Y, DBG = B::DBG, FEAT = B::FEAT, QRY = B::QRY, RAD = B::RAD;
   constexpr int WALK = B::WALK, TAIL = B::TAIL;
   using S = Scene<SCAN_LDS, HAVE_LDS, WALK, TAIL, FLAT_Y>;
   S::stage(A);
@@ -86,14 +90,14 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
   tally.start();
 
   for (;;) {
-    refill<COUNT, QRY>(A, p, q, pd, tally);
+    refill<COUNT, QRY, RAD>(A, p, q, pd, tally);
     promote<COUNT>(p, tally);
     tally.phase(0);
     // one copy of the camera-ray code per step serves both kinds of lanes: those that just
     // pulled an item and those whose previous path ended in the last step
     if (p.alive && p.new_path) {
       tally.flag(PT_REG_CAMERA_RAY);
-      start_sample<FEAT, QRY>(p, pd);
+      start_sample<FEAT, QRY, RAD>(p, pd);
       p.new_path = false;
     }
     tally.phase(1);

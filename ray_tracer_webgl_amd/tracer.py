@@ -472,6 +472,45 @@ class PathTracer:
             out[name] = col if b - a > 1 else col[:, 0]
         return out
 
+    def query_radiance(self, origins, directions, passes=1):
+        """The path-traced radiance along each of the caller's rays (pt_query_radiance; needs ray_queries(True)): `passes`
+        passes (at most those reserved) of the uniforms' samples_per_pixel samples per ray by the plain estimator.  Two (n, 3)
+        float32 arrays in (directions are not normalised), a dict out — "sum": (n, 3) float32, "samples": (n,) float32, "mean":
+        (n, 3) float32 = sum / samples, 0 where samples is 0 (an invalid ray).  numpy arrays give numpy arrays; under
+        use_torch, torch device tensors give torch device tensors.  Synchronous; nothing else of the context moves, first_pass
+        included."""
+        on_device = self.use_torch and self._torch.is_tensor(origins) and origins.is_cuda
+        if on_device:
+            torch = self._torch
+            o = origins.to(torch.float32).reshape(-1, 3)
+            d = directions.to(device=o.device, dtype=torch.float32).reshape(-1, 3)
+            if o.shape != d.shape:
+                raise ValueError("query_radiance: %d origins, %d directions" % (o.shape[0], d.shape[0]))
+            n = int(o.shape[0])
+            rays = torch.zeros((n, 8), dtype=torch.float32, device=o.device)
+            rays[:, 0:3] = o
+            rays[:, 4:7] = d
+            rec = torch.zeros((n, 4), dtype=torch.float32, device=o.device)
+            if n:
+                self._check(self.lib.pt_query_radiance(self._ctx, C.c_void_p(rays.data_ptr()), n, int(passes), C.c_void_p(rec.data_ptr())))
+            samples = rec[:, 3]
+            mean = torch.where(samples[:, None] > 0, rec[:, 0:3] / torch.clamp(samples, min=1.0)[:, None], torch.zeros_like(rec[:, 0:3]))
+        else:
+            o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+            d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+            if o.shape != d.shape:
+                raise ValueError("query_radiance: %d origins, %d directions" % (o.shape[0], d.shape[0]))
+            n = int(o.shape[0])
+            rays = np.zeros((n, 8), np.float32)
+            rays[:, 0:3] = o
+            rays[:, 4:7] = d
+            rec = np.zeros((n, 4), np.float32)
+            if n:
+                self._check(self.lib.pt_query_radiance(self._ctx, rays.ctypes.data_as(C.c_void_p), n, int(passes), rec.ctypes.data_as(C.c_void_p)))
+            samples = rec[:, 3]
+            mean = np.where(samples[:, None] > 0, rec[:, 0:3] / np.maximum(samples, np.float32(1.0))[:, None], np.float32(0.0)).astype(np.float32)
+        return {"sum": rec[:, 0:3], "samples": samples, "mean": mean}
+
     # -- temporal reprojection (include/ptrace.h PT_OPT_REPROJECT) ---------------------------------
     def reproject_option(self, on=True):
         """Allocate (or release) the history planes of temporal reprojection; needs feature_planes(True) first.  Off by
