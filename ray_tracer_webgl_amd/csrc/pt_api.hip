@@ -310,6 +310,13 @@ uint32_t count_local_rows(uint32_t height, const PtParams& p) {
   return pt_local_rows(height, p.band_rows, p.band_index, p.band_count);
 }
 
+// every tile exactly once, in order: what a tile order holds before any cost has sorted it (a blocking copy)
+hipError_t fill_identity_order(DevBuf<uint32_t>& order, size_t tiles) {
+  std::vector<uint32_t> ident(tiles);
+  for (size_t i = 0; i < tiles; i++) ident[i] = (uint32_t)i;
+  return hipMemcpy(order.get(), ident.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice);
+}
+
 int ensure_buffers(pt_ctx* c) {
   size_t pix = n_pixels(c);
   if (pix == 0) pix = 1;
@@ -332,13 +339,9 @@ int ensure_buffers(pt_ctx* c) {
     PT_HIP(c, c->d_tile_cost.reserve(tiles));
     PT_HIP(c, c->d_tile_order.reserve(tiles));
     PT_HIP(c, hipMemsetAsync(c->d_tile_cost.get(), 0, tiles * sizeof(uint32_t), c->stream));
-    {
-      // the identity order from the start: a launch that skips the order kernel (because an earlier one was only
-      // CAPTURED into a caller's hipGraph and has not run yet) must still find every tile exactly once
-      std::vector<uint32_t> ident(tiles);
-      for (size_t i = 0; i < tiles; i++) ident[i] = (uint32_t)i;
-      PT_HIP(c, hipMemcpy(c->d_tile_order.get(), ident.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    // the identity order from the start: a launch that skips the order kernel (because an earlier one was only
+    // CAPTURED into a caller's hipGraph and has not run yet) must still find every tile exactly once
+    PT_HIP(c, fill_identity_order(c->d_tile_order, tiles));
     c->order.reseeded();
     c->adapt_valid = false;
   }
@@ -371,9 +374,7 @@ int ensure_buffers(pt_ctx* c) {
     PT_HIP(c, hipStreamSynchronize(c->stream));
     c->d_query = DevBuf<float4>();  // (what pt_query_rays tests: both in place, or neither)
     PT_HIP(c, c->d_query_order.reserve(tiles));
-    std::vector<uint32_t> ident(tiles);
-    for (size_t i = 0; i < tiles; i++) ident[i] = (uint32_t)i;
-    PT_HIP(c, hipMemcpy(c->d_query_order.get(), ident.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+    PT_HIP(c, fill_identity_order(c->d_query_order, tiles));
     PT_HIP(c, c->d_query.reserve(PT_FEAT_PLANES * pix));
   }
   if (c->reproj_on && c->d_hist.capacity() != 2 * pix) {  // (likewise: the ids plane, then the point plane at pix)
@@ -487,9 +488,9 @@ Staging grid_build(const pt_ctx* c) {
   return grid_staging(ptscene::staged_cells(g), g.n_entries, walk_lds_room(), c->grid_cells_build, fit_state(c));
 }
 
-// The handle of a table cell's kernel (pt_trace_table.hpp), from its object's accessor.  The first use of a kernel of the three
-// opt-in objects (roulette builds and twins, overlay builds, feature builds) loads that code object and lifts the kernel's
-// dynamic-LDS limit, once per device and id; the main kernels' limit is lifted at pt_create, the small-list kernels need none.
+// The handle of a table cell's kernel (pt_trace_table.hpp), from its object's accessor.  The first use of a kernel of the five
+// opt-in objects (roulette builds and twins, overlay, feature, query and radiance builds) loads that code object and lifts the
+// kernel's dynamic-LDS limit, once per device and id; the main kernels' limit is lifted at pt_create, the small-list kernels need none.
 const void* cell_kernel(int device, const TraceCell& k) {
 #define PT_TRACE_ACCESSOR_OF(object, accessor, n_ids) accessor,
   static const void* (*const accessors[OBJ_COUNT])(int) = {PT_TRACE_OBJECTS(PT_TRACE_ACCESSOR_OF)};
@@ -500,33 +501,6 @@ const void* cell_kernel(int device, const TraceCell& k) {
     std::call_once(once[device & 63][k.object][k.id], [fn] {  // (every caller returns with the attribute set: no launch can overtake it)
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
       (void)hipGetLastError();  // a refused attribute only limits that kernel to the default 64 KiB; the launch code checks sizes
-    });
-  return fn;
-}
-
-// The query build that serves a row: the handle pt_query_kernel gives for the id of the row's feature cell (a cell of the
-// table's BUILD_FEAT column: the query builds share its variant rows, wave counts and launch shapes, and are no column
-// themselves).  Its dynamic-LDS limit is lifted on first use, like cell_kernel's.
-const void* query_kernel(int device, const TraceCell& feat_cell) {
-  static std::once_flag once[64][PT_VARIANT_COUNT];
-  const void* fn = pt_query_kernel(feat_cell.id);
-  if (fn)
-    std::call_once(once[device & 63][feat_cell.id], [fn] {
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
-      (void)hipGetLastError();
-    });
-  return fn;
-}
-
-// The radiance build that serves a row, likewise: the handle pt_radiance_kernel gives for the id of the row's feature cell.
-// Asking for it the first time is what loads the radiance builds' code object.
-const void* radiance_kernel(int device, const TraceCell& feat_cell) {
-  static std::once_flag once[64][PT_VARIANT_COUNT];
-  const void* fn = pt_radiance_kernel(feat_cell.id);
-  if (fn)
-    std::call_once(once[device & 63][feat_cell.id], [fn] {
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLdsMax);
-      (void)hipGetLastError();
     });
   return fn;
 }
@@ -1123,18 +1097,17 @@ struct LaunchUse {
   // full permutation of the tiles, and is planned for that many items; tiles_x, tiles_y and div_per_tile stay the frame's
   uint32_t n_first_tiles = 0;
   const uint32_t* table = nullptr;
-  // pt_render_features' launch: the feature build of the path forced or settled (the cold path while PT_GEOM_AUTO measures),
-  // one pass into the planes; it is no trial, settles nothing and leaves `geom` as it finds it
-  bool features = false;
-  // pt_query_rays' launch: as `features` in everything but the kernel (the row's query build), the planes (the query planes), the
-  // ray count (query_rays: the first that many work items carry a ray) and c->last_build, which it does not store
-  bool query = false;
+  // Which entry point's launch, where it is no render launch (pt_trace_table.hpp Door).  Every door takes its own column of the
+  // row of the path forced or settled (the cold path while PT_GEOM_AUTO measures); it is no trial, settles nothing, reports no
+  // tile costs and leaves `geom` as it finds it; the overlay and roulette do not act.
+  //   DOOR_FEATURES  pt_render_features: one deterministic segment per pixel, one pass, into the feature planes
+  //   DOOR_QUERY     pt_query_rays: the same estimator on the caller's rays (the first query_rays work items carry one), into the
+  //                  query planes; c->last_build is not stored
+  //   DOOR_RADIANCE  pt_query_radiance: the PLAIN estimator on the caller's query_rays rays — n_passes passes of the uniforms'
+  //                  samples and depth into the pass slabs, frame_ctr at the zero cell; the staged rays travel in
+  //                  PtKernelArgs::uuid and the batch's first pass is `first_pass`; c->last_build is not stored
+  Door door = DOOR_NONE;
   uint32_t query_rays = 0;
-  // pt_query_radiance's launch: the door of `query` (the row's variant through the path forced or settled, no trial, nothing
-  // settled, no cost feedback, c->last_build not stored, query_rays rays) in front of the PLAIN estimator — the row's radiance
-  // build, n_passes passes of the uniforms' samples and depth into the pass slabs, frame_ctr at the zero cell, neither roulette
-  // nor the overlay; the staged rays travel in PtKernelArgs::uuid and the batch's first pass is `first_pass`
-  bool radiance = false;
   uint32_t first_pass = 0;
 };
 
@@ -1151,9 +1124,10 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   }
   const LaunchKnobs knobs = read_launch_knobs();
   if (knobs.carry_lanes) A.carry_lanes = *knobs.carry_lanes;
-  const bool query = use.query, rad = use.radiance;
-  const bool feat = use.features || query;
-  const bool door = feat || rad;  // no render launch: a variant row's build, no trial, nothing of the path or the order moves
+  // all that follows reads of the door: is there one (no render launch: a variant row's build, no trial, nothing of the path or
+  // the order moves), does it write first-hit records (`feat`), and which of the two query calls is it
+  const bool door = use.door != DOOR_NONE, query = use.door == DOOR_QUERY, rad = use.door == DOOR_RADIANCE;
+  const bool feat = use.door == DOOR_FEATURES || query;
   if (c->geom.policy == PT_GEOM_AUTO && !door) try_finish_tuning(c);
   const bool rr = !door && c->rr_min_depth > 0, dbg = !door && c->dbg_enable;
   if (rr && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and PT_OPT_RUSSIAN_ROULETTE exclude each other");
@@ -1181,7 +1155,7 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
     scene = c->list.n <= PT_MAX_SPHERES_LDS ? (size_t)PT_LDS_ENTRIES(c->list.n) * 16 : 0;
   }
   const int row = trace_row(path, c->list.n, st.kind, c->grid.head.n[1]);
-  const int build = trace_build(door, dbg, rr, c->count_work);  // (a radiance launch: the row's feature CELL names its build, see below)
+  const int build = door ? door_build(use.door) : trace_build(false, dbg, rr, c->count_work);
   if (feat) {  // one deterministic segment per pixel into the planes; the overlay and roulette do not act
     A.uuid = c->list.uuid.get();
     A.slot_uuid = path == PT_GEOM_BVH ? c->bvh.uuid.get() : (path == PT_GEOM_GRID ? c->grid.uuid.get() : nullptr);
@@ -1202,8 +1176,8 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
     A.n_cells = (uint32_t)ptrec::ring_cells(c->grid.head.n[0], c->grid.head.n[2]);
   }
   const TraceCell& tk = kTraceKernels[row][build];
-  const void* kfn = rad ? radiance_kernel(c->device, tk) : (query ? query_kernel(c->device, tk) : cell_kernel(c->device, tk));
-  if (!query && !rad) c->last_build = build;
+  const void* kfn = cell_kernel(c->device, tk);
+  if (!query && !rad) c->last_build = build;  // (what pt_last_trace_build reports: a render or feature launch's column)
   const uint32_t block = walk ? walk_block_threads(kfn, tk.waves, scene, kWalkLdsMax, knobs.bvh_block) : list_block_threads(scene);
   const size_t lds = walk ? scene + (size_t)PT_PARK_STRIDE * 4 * block : scene;
   A.block_threads = block;
@@ -1225,6 +1199,20 @@ static int launch_trace(pt_ctx* c, const Launch& L) {
   void* kargs[] = {const_cast<PtKernelArgs*>(&L.A)};
   PT_HIP(c, hipLaunchKernel(L.kfn, dim3(L.grid), dim3(L.block), kargs, L.lds, c->stream));
   return PT_OK;
+}
+
+// A whole trace launch with nothing of the caller's between its steps: prepared, the queue's heads zeroed, enqueued; timed where
+// the caller keeps a span (taken once the launch is prepared, around the kernel alone).
+static int trace_once(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, TimedSpan* span = nullptr) {
+  Launch L;
+  if (int rc = prepare_launch(c, n_passes, use, &L); rc != PT_OK) return rc;
+  if (span)
+    if (int rc = span->take(c); rc != PT_OK) return rc;
+  PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
+  if (span)
+    if (int rc = span->begin(c); rc != PT_OK) return rc;
+  if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
+  return span ? span->end(c) : PT_OK;
 }
 
 PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
@@ -1913,18 +1901,12 @@ int partial_round(pt_ctx* c, uint32_t k, uint32_t tiles, uint32_t n_active, uint
     void* kargs[] = {&order, &fl, &part, &base, &n};
     PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_PARTITION), dim3(1), dim3(1024), kargs, 0, c->stream));
   }
-  Launch L;
   LaunchUse use;
   use.feedback = LaunchUse::OFF;  // a partial launch keeps the order it finds, as a frame does
   use.n_first_tiles = n_active;
   use.table = part;
-  if (int rc = prepare_launch(c, k, use, &L); rc != PT_OK) return rc;
   TimedSpan span;
-  if (int rc = span.take(c); rc != PT_OK) return rc;
-  PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
-  if (int rc = span.begin(c); rc != PT_OK) return rc;
-  if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
-  if (int rc = span.end(c); rc != PT_OK) return rc;
+  if (int rc = trace_once(c, k, use, &span); rc != PT_OK) return rc;
   {
     float4* accum = c->accum;
     float4* est = c->d_err.get();
@@ -2224,7 +2206,7 @@ static bool feature_planes_in_place(const pt_ctx* c) {
 }
 
 // ONE launch of the feature build of whichever kernel the context renders with, into the planes.  Nothing else of the context
-// moves: no fold, no timing events, no tile costs, no order kernel, no trial of PT_GEOM_AUTO (prepare_launch, LaunchUse::features);
+// moves: no fold, no timing events, no tile costs, no order kernel, no trial of PT_GEOM_AUTO (prepare_launch, DOOR_FEATURES);
 // the kernel adds its segments to the device counter like every trace launch.
 PT_API int pt_render_features(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
@@ -2236,13 +2218,9 @@ PT_API int pt_render_features(pt_ctx* c) {
   if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_render_features: not inside a stream capture");
   if (!feature_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "pt_render_features: the planes are not allocated for the rows in place (an earlier allocation failed)");
   if (c->local_rows == 0) { c->feat_valid = true; return PT_OK; }  // this band owns no rows: nothing to do, and its (empty) planes speak
-  Launch L;
   LaunchUse use;
-  use.features = true;
-  use.feedback = LaunchUse::OFF;
-  if (int rc = prepare_launch(c, 1, use, &L); rc != PT_OK) return rc;
-  PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
-  if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
+  use.door = DOOR_FEATURES;
+  if (int rc = trace_once(c, 1, use); rc != PT_OK) return rc;
   c->feat_valid = true;
   return PT_OK;
 }
@@ -2295,51 +2273,64 @@ PT_API uint32_t pt_query_batch(pt_ctx* c) {
   return (uint32_t)n_pixels(c);
 }
 
-// n rays in batches of the local pixel count; a batch: stage the rays into the point and normal planes (device arrays: the pack
-// kernel; host arrays: packed on the host, two copies), ONE launch of the query build over the tile rows the rays occupy, the
-// records out of the four planes (the unpack kernel, or four copies and the host's unpack).  Nothing else of the context moves:
-// prepare_launch's LaunchUse::query is LaunchUse::features with another kernel, other planes and no c->last_build.
+// What pt_query_rays and pt_query_radiance (`who`; `build`: its word for the kernels the measuring twins lack) both ask of their
+// arguments and the context before anything is enqueued.
+static int query_ready(pt_ctx* c, const char* who, const char* build, const void* rays, const void* out) {
+  if (!rays || !out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
+  if (c->count_work) return fail(c, PT_ERR_INVALID, "%s: not with PT_OPT_COUNT_WORK (the measuring twins have no %s build)", who, build);
+  if (!c->query_on) return fail(c, PT_ERR_NOT_READY, "%s: ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)", who);
+  if (!c->have_spheres || !c->have_params) return fail(c, PT_ERR_NOT_READY, "%s: pt_set_spheres and pt_set_params must come first", who);
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "%s: synchronises; not inside a stream capture", who);
+  if (c->local_rows == 0) return fail(c, PT_ERR_NOT_READY, "%s: this band owns no rows, so it has no work items to decode rays against", who);
+  if (!query_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "%s: the planes are not allocated for the rows in place (an earlier allocation failed)", who);
+  return PT_OK;
+}
+
+// One batch of m rays into the point and normal planes of the query planes: a device array through the pack kernel, a host array
+// packed into h_in (the caller's, so that nothing is allocated per batch) and copied plane by plane.
+static int stage_rays(pt_ctx* c, const PtRay* rays, bool on_device, uint32_t m, std::vector<ptq::F4>& h_in) {
+  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->d_query.get());
+  uint32_t plane = (uint32_t)n_pixels(c);
+  if (on_device) {
+    void* kargs[] = {&rays, &m, &planes, &plane};
+    PT_HIP(c, hipLaunchKernel(pt_query_pack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+    return PT_OK;
+  }
+  h_in.resize(2 * (size_t)m);
+  for (uint32_t i = 0; i < m; i++) ptq::pack_ray(rays[i], &h_in[i], &h_in[(size_t)m + i]);
+  PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_POINT * plane, h_in.data(), (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
+  PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_NORMAL * plane, h_in.data() + m, (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
+  return PT_OK;
+}
+
+// The launch of a batch of m staged rays through `door`: over the tile rows the rays occupy, in the query planes' own tile order.
+static LaunchUse batch_use(const pt_ctx* c, Door door, uint32_t m) {
+  LaunchUse use;
+  use.door = door;
+  use.query_rays = m;
+  use.n_first_tiles = ptq::tiles_covered(m, c->width);
+  use.table = c->d_query_order.get();
+  return use;
+}
+
+// n rays in batches of the local pixel count; a batch: stage the rays into the point and normal planes (stage_rays), ONE launch
+// of the query build over the tile rows the rays occupy, the records out of the four planes (the unpack kernel, or four copies
+// and the host's unpack).  Nothing else of the context moves (prepare_launch, DOOR_QUERY).
 PT_API int pt_query_rays(pt_ctx* c, const PtRay* rays, uint32_t n, PtRayHit* hits) {
   if (!c) return PT_ERR_INVALID;
   if (n == 0) return PT_OK;
-  if (!rays || !hits) return fail(c, PT_ERR_INVALID, "pt_query_rays: NULL argument");
-  if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_query_rays: not with PT_OPT_COUNT_WORK (the measuring twins have no query build)");
-  if (!c->query_on) return fail(c, PT_ERR_NOT_READY, "pt_query_rays: ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)");
-  if (!c->have_spheres || !c->have_params)
-    return fail(c, PT_ERR_NOT_READY, "pt_query_rays: pt_set_spheres and pt_set_params must come first");
-  PT_HIP(c, hipSetDevice(c->device));
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_query_rays: synchronises; not inside a stream capture");
-  if (c->local_rows == 0) return fail(c, PT_ERR_NOT_READY, "pt_query_rays: this band owns no rows, so it has no work items to decode rays against");
-  if (!query_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "pt_query_rays: the planes are not allocated for the rows in place (an earlier allocation failed)");
+  if (int rc = query_ready(c, "pt_query_rays", "query", rays, hits); rc != PT_OK) return rc;
   const uint32_t plane = (uint32_t)n_pixels(c);
   const bool rays_on_device = device_pointer(rays), hits_on_device = device_pointer(hits);
-  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->d_query.get());
+  const ptq::F4* planes = reinterpret_cast<const ptq::F4*>(c->d_query.get());
   std::vector<ptq::F4> h_in, h_out;  // host arrays only: the two planes going up, the four coming down
   const uint32_t batches = ptq::n_batches(n, plane);
   for (uint32_t k = 0; k < batches; k++) {
     const size_t first = (size_t)k * plane;
     uint32_t m = ptq::batch_rays(n, plane, k);
-    if (rays_on_device) {
-      const PtRay* src = rays + first;
-      uint32_t pl = plane;
-      void* kargs[] = {&src, &m, &planes, &pl};
-      PT_HIP(c, hipLaunchKernel(pt_query_pack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
-    } else {
-      h_in.resize(2 * (size_t)m);
-      for (uint32_t i = 0; i < m; i++) ptq::pack_ray(rays[first + i], &h_in[i], &h_in[(size_t)m + i]);
-      PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_POINT * plane, h_in.data(), (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
-      PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_NORMAL * plane, h_in.data() + m, (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
-    }
-    Launch L;
-    LaunchUse use;
-    use.query = true;
-    use.query_rays = m;
-    use.feedback = LaunchUse::OFF;
-    use.n_first_tiles = ptq::tiles_covered(m, c->width);
-    use.table = c->d_query_order.get();
-    if (int rc = prepare_launch(c, 1, use, &L); rc != PT_OK) return rc;
-    PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
-    if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
+    if (int rc = stage_rays(c, rays + first, rays_on_device, m, h_in); rc != PT_OK) return rc;
+    if (int rc = trace_once(c, 1, batch_use(c, DOOR_QUERY, m)); rc != PT_OK) return rc;
     if (hits_on_device) {
       const ptq::F4* src = planes;
       PtRayHit* dst = hits + first;
@@ -2371,15 +2362,7 @@ PT_API int pt_query_rays(pt_ctx* c, const PtRay* rays, uint32_t n, PtRayHit* hit
 PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out) {
   if (!c) return PT_ERR_INVALID;
   if (n == 0) return PT_OK;
-  if (!rays || !out) return fail(c, PT_ERR_INVALID, "pt_query_radiance: NULL argument");
-  if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_query_radiance: not with PT_OPT_COUNT_WORK (the measuring twins have no radiance build)");
-  if (!c->query_on) return fail(c, PT_ERR_NOT_READY, "pt_query_radiance: ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)");
-  if (!c->have_spheres || !c->have_params)
-    return fail(c, PT_ERR_NOT_READY, "pt_query_radiance: pt_set_spheres and pt_set_params must come first");
-  PT_HIP(c, hipSetDevice(c->device));
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_query_radiance: synchronises; not inside a stream capture");
-  if (c->local_rows == 0) return fail(c, PT_ERR_NOT_READY, "pt_query_radiance: this band owns no rows, so it has no work items to decode rays against");
-  if (!query_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "pt_query_radiance: the planes are not allocated for the rows in place (an earlier allocation failed)");
+  if (int rc = query_ready(c, "pt_query_radiance", "radiance", rays, out); rc != PT_OK) return rc;
   if (n_passes == 0) return fail(c, PT_ERR_INVALID, "pt_query_radiance: n_passes == 0");
   if (n_passes > c->reserved_passes)
     return fail(c, PT_ERR_CAPACITY, "pt_query_radiance: %u passes > %u reserved (pt_reserve_passes)", n_passes, c->reserved_passes);
@@ -2392,28 +2375,10 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
   for (uint32_t k = 0; k < batches; k++) {
     const size_t first = (size_t)k * plane;
     uint32_t m = ptq::batch_rays(n, plane, k);
-    if (rays_on_device) {
-      const PtRay* src = rays + first;
-      uint32_t pl = plane;
-      void* kargs[] = {&src, &m, &planes, &pl};
-      PT_HIP(c, hipLaunchKernel(pt_query_pack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
-    } else {
-      h_in.resize(2 * (size_t)m);
-      for (uint32_t i = 0; i < m; i++) ptq::pack_ray(rays[first + i], &h_in[i], &h_in[(size_t)m + i]);
-      PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_POINT * plane, h_in.data(), (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
-      PT_HIP(c, hipMemcpyAsync(planes + (size_t)PT_FEAT_NORMAL * plane, h_in.data() + m, (size_t)m * sizeof(ptq::F4), hipMemcpyHostToDevice, c->stream));
-    }
-    Launch L;
-    LaunchUse use;
-    use.radiance = true;
-    use.query_rays = m;
+    if (int rc = stage_rays(c, rays + first, rays_on_device, m, h_in); rc != PT_OK) return rc;
+    LaunchUse use = batch_use(c, DOOR_RADIANCE, m);
     use.first_pass = ptr::batch_first_pass(c->params.first_pass, k, n_passes);
-    use.feedback = LaunchUse::OFF;
-    use.n_first_tiles = ptq::tiles_covered(m, c->width);
-    use.table = c->d_query_order.get();
-    if (int rc = prepare_launch(c, n_passes, use, &L); rc != PT_OK) return rc;
-    PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
-    if (int rc = launch_trace(c, L); rc != PT_OK) return rc;
+    if (int rc = trace_once(c, n_passes, use); rc != PT_OK) return rc;
     {
       const ptq::F4* slab = reinterpret_cast<const ptq::F4*>(c->d_slab.get());
       const ptq::F4* staged = planes;

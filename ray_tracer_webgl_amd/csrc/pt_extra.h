@@ -1,18 +1,16 @@
 // pt_extra.h — THE LIST of the trace kernel's builds, and how pt_api.hip reaches the kernels of every code object.
 //
-// Each of the 55 trace kernels of the host's table is stated once, below (the twelve ray-query builds of a sixth code object,
-// pt_kernels_query.hip, and the twelve radiance-query builds of a seventh, pt_kernels_radiance.hip, come from the same variant
-// rows and stand outside the table: see the end of this file): its symbol, the waves per SIMD it is built for (PT_BUILT_FOR,
+// Each of the 79 trace kernels is stated once, below: its symbol, the waves per SIMD it is built for (PT_BUILT_FOR,
 // pt_kernel_args.h) and its build type (pt_trace_body.hpp).  From an entry come the kernel's definition and the `case` of its
 // object's accessor (pt_trace_body.hpp PT_TRACE_KERNEL...), its id, and its cell of the host's table with the same wave count
-// and the symbol as a string (pt_trace_table.hpp).  Plain preprocessor and enums: the device units and the host-only table
-// header read the same text.  A list's order is the order of the definitions in its translation unit.
+// and the symbol as a string (pt_trace_table.hpp).  Plain preprocessor and enums: the seven device units that trace and the
+// host-only table header read the same text.  A list's order is the order of the definitions in its translation unit.
 //
 // HOW TO ADD A COLUMN of builds (one more flag on every variant row): the flag and its adaptor in pt_trace_body.hpp; a new
-// pt_kernels_<name>.hip that is its header comment, PT_VARIANT_ROWS(PT_TRACE_VARIANT, _<suffix>, <Adaptor>) and an accessor
-// over PT_VARIANT_ROWS(PT_TRACE_VARIANT_CASE, ...), added to the Makefile's SRCS; one entry in PT_TRACE_OBJECTS here; and
-// in pt_trace_table.hpp one value of TraceBuild, one cell expansion, one suffix in PT_TABLE_ROW and the option's place in
-// trace_build().
+// pt_kernels_<name>.hip that is its header comment, PT_VARIANT_ROWS(PT_TRACE_VARIANT, _<suffix>, <Adaptor>) and
+// PT_VARIANT_ACCESSOR(pt_<name>_kernel, _<suffix>, <Adaptor>), added to the Makefile's SRCS; one entry in PT_TRACE_OBJECTS
+// here; and in pt_trace_table.hpp one value of TraceBuild, one cell expansion, one suffix in PT_TABLE_ROW and who names the
+// column: the option's place in trace_build() for a render launch's, a Door and its line in door_build() for an entry point's.
 #pragma once
 
 // pt_kernels.hip (compiled into pt_api.hip's object): the list and walk kernels
@@ -44,10 +42,11 @@
   X(pt_trace_kernel_small_count,       PT_WAVES_SMALL,      Count<Small<-1>>)
 
 // The VARIANT ROWS: the twelve ways to read the list that have a Russian-roulette build (pt_kernels_extra.hip, suffix _rr), a
-// debug-overlay build (pt_kernels_debug.hip, _dbg) and a first-hit feature build (pt_kernels_features.hip, _feat), each the
-// row's build under one adaptor with the same launch shape as its namesake.  The LDS list walk has none (pt_geom_plan.hpp
-// steers those launches to the scalar row), and a one-layer grid is walked along three axes by the ..._grid_<suffix> build —
-// right on any grid, and not measured: one build each serves the rows `grid` and `grid_layers`.
+// debug-overlay build (pt_kernels_debug.hip, _dbg), a first-hit feature build (pt_kernels_features.hip, _feat), a ray-query
+// build (pt_kernels_query.hip, _qry) and a radiance-query build (pt_kernels_radiance.hip, _rad), each the row's build under one
+// adaptor with the same launch shape as its namesake.  The LDS list walk has none (pt_geom_plan.hpp steers those launches to the
+// scalar row), and a one-layer grid is walked along three axes by the ..._grid_<suffix> build — right on any grid, and not
+// measured: one build each serves the rows `grid` and `grid_layers`.
 // X(stem, waves, row type, what the expansion passes on: suffix, adaptor)
 #define PT_VARIANT_ROWS(X, ...)                                                \
   X(pt_trace_kernel_small_t0,     PT_WAVES_SMALL, Small<0>,    __VA_ARGS__)    \
@@ -63,7 +62,7 @@
   X(pt_trace_kernel_grid_cells,   PT_WAVES_WALK,  GridCells,   __VA_ARGS__)    \
   X(pt_trace_kernel_grid_gmem,    PT_WAVES_WALK,  GridGmem,    __VA_ARGS__)
 
-// The ids an accessor takes.  A variant's id is its row, in each of the three objects that hold variants; the twins of
+// The ids an accessor takes.  A variant's id is its row, in each of the five objects that hold variants; the twins of
 // pt_kernels_extra.hip follow its roulette builds.
 #define PT_KERNEL_ID(sym) PT_ID_##sym
 #define PT_VARIANT_ID(stem) PT_VARIANT_##stem
@@ -74,15 +73,17 @@ enum { PT_SMALL_KERNELS(PT_KERNEL_ID_ENTRY) PT_SMALL_COUNT };
 enum { PT_VARIANT_ROWS(PT_VARIANT_ID_ENTRY, ) PT_VARIANT_COUNT };
 enum { PT_ROULETTE_LAST = PT_VARIANT_COUNT - 1, PT_TWIN_KERNELS(PT_KERNEL_ID_ENTRY) PT_EXTRA_COUNT };
 
-// The five code objects that hold the table's trace kernels (of the library's nine) and the accessor of each: the kernel's host-side handle (what hipLaunchKernel
-// takes) by id, NULL for an id the object does not have.  Asking for a handle loads nothing yet; the HIP runtime loads a code
-// object when one of its kernels is first used.  X(object, accessor, number of ids)
+// The seven code objects that hold the trace kernels (of the library's nine) and the accessor of each: the kernel's host-side
+// handle (what hipLaunchKernel takes) by id, NULL for an id the object does not have.  Asking for a handle loads nothing yet; the
+// HIP runtime loads a code object when one of its kernels is first used.  X(object, accessor, number of ids)
 #define PT_TRACE_OBJECTS(X)                             \
-  X(MAIN,    pt_main_kernel,    PT_MAIN_COUNT)          \
-  X(SMALL,   pt_small_kernel,   PT_SMALL_COUNT)         \
-  X(EXTRA,   pt_extra_kernel,   PT_EXTRA_COUNT)         \
-  X(DEBUG,   pt_debug_kernel,   PT_VARIANT_COUNT)       \
-  X(FEATURE, pt_feature_kernel, PT_VARIANT_COUNT)
+  X(MAIN,     pt_main_kernel,     PT_MAIN_COUNT)        \
+  X(SMALL,    pt_small_kernel,    PT_SMALL_COUNT)       \
+  X(EXTRA,    pt_extra_kernel,    PT_EXTRA_COUNT)       \
+  X(DEBUG,    pt_debug_kernel,    PT_VARIANT_COUNT)     \
+  X(FEATURE,  pt_feature_kernel,  PT_VARIANT_COUNT)     \
+  X(QUERY,    pt_query_kernel,    PT_VARIANT_COUNT)     \
+  X(RADIANCE, pt_radiance_kernel, PT_VARIANT_COUNT)
 #define PT_TRACE_ACCESSOR_DECL(object, accessor, n_ids) extern "C" const void* accessor(int id);
 PT_TRACE_OBJECTS(PT_TRACE_ACCESSOR_DECL)
 
@@ -95,16 +96,10 @@ extern "C" const void* pt_error_kernel(int id);
 // pt_reproject_estimate's, which gathers the error estimate's state in the same pass
 extern "C" const void* pt_reproject_kernel_handle(void);
 extern "C" const void* pt_reproject_estimate_kernel_handle(void);
-// pt_kernels_query.hip (a code object of its own): the ray-query builds of the variant rows (PT_OPT_RAY_QUERIES, pt_query_rays),
-// by the row's variant id — the id of its _feat cell, whose wave count and launch shape they share.  Deliberately neither an
-// entry of PT_TRACE_OBJECTS nor a column of the host's table: a query is no render launch, pt_last_trace_build never reports
-// one, and the table's five columns and 55 kernels stay what they are.  And the two kernels that move a batch of rays and
-// records between the caller's device arrays and the query planes.
-extern "C" const void* pt_query_kernel(int id);
+// pt_kernels_query.hip, beside its ray-query builds (PT_OPT_RAY_QUERIES, pt_query_rays): the two kernels that move a batch of
+// rays and records between the caller's device arrays and the query planes
 extern "C" const void* pt_query_pack_kernel_handle(void);
 extern "C" const void* pt_query_unpack_kernel_handle(void);
-// pt_kernels_radiance.hip (a code object of its own): the radiance-query builds of the variant rows (pt_query_radiance), by the
-// row's variant id as above and outside the table for the same reasons, and the kernel that folds a batch's pass slabs into
-// its records.
-extern "C" const void* pt_radiance_kernel(int id);
+// pt_kernels_radiance.hip, beside its radiance-query builds (pt_query_radiance): the kernel that folds a batch's pass slabs into
+// its records
 extern "C" const void* pt_radiance_fold_kernel_handle(void);

@@ -3,15 +3,9 @@
 // their own: the HIP runtime loads it when one of these kernels is first asked for, so a context that never turns the
 // overlay on pays nothing for the twelve kernels in here, and pt_kernels_extra.hip loads as fast as before.  They are
 // the variant rows of pt_extra.h (PT_VARIANT_ROWS: one per launch that has a Russian-roulette build, with the same launch
-// shapes as their namesakes) under the adaptor Dbg and the suffix _dbg; pt_api.hip reaches them through pt_debug_kernel() only.
-// (How to add such a column: pt_extra.h.)
+// shapes as their namesakes) under the adaptor Dbg and the suffix _dbg; pt_api.hip reaches them through pt_debug_kernel() only,
+// the accessor PT_VARIANT_ACCESSOR makes of the same rows.  (How to add such a column: pt_extra.h.)
 #include "pt_trace_body.hpp"
 
 PT_VARIANT_ROWS(PT_TRACE_VARIANT, _dbg, Dbg)
-
-extern "C" const void* pt_debug_kernel(int id) {
-  switch (id) {
-    PT_VARIANT_ROWS(PT_TRACE_VARIANT_CASE, _dbg, Dbg)
-    default: return nullptr;
-  }
-}
+PT_VARIANT_ACCESSOR(pt_debug_kernel, _dbg, Dbg)

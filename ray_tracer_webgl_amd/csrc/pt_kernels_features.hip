@@ -4,14 +4,8 @@
 // one of these kernels is first asked for, so a context that never renders features pays nothing for the twelve kernels in
 // here.  They are the variant rows of pt_extra.h (PT_VARIANT_ROWS: one per launch that has a Russian-roulette build, with the
 // same launch shapes as their namesakes) under the adaptor Feat and the suffix _feat; pt_api.hip reaches them through
-// pt_feature_kernel() only.  (How to add such a column: pt_extra.h.)
+// pt_feature_kernel() only, the accessor PT_VARIANT_ACCESSOR makes of the same rows.  (How to add such a column: pt_extra.h.)
 #include "pt_trace_body.hpp"
 
 PT_VARIANT_ROWS(PT_TRACE_VARIANT, _feat, Feat)
-
-extern "C" const void* pt_feature_kernel(int id) {
-  switch (id) {
-    PT_VARIANT_ROWS(PT_TRACE_VARIANT_CASE, _feat, Feat)
-    default: return nullptr;
-  }
-}
+PT_VARIANT_ACCESSOR(pt_feature_kernel, _feat, Feat)

@@ -3,8 +3,8 @@
 // gfx950 code object of their own: the HIP runtime loads it when the option is turned on, so a context that never asks about a
 // ray pays nothing for the fourteen kernels in here.  The twelve trace kernels are the variant rows of pt_extra.h
 // (PT_VARIANT_ROWS, the same launch shapes as their namesakes) under the adaptor Qry and the suffix _qry; pt_api.hip reaches
-// them through pt_query_kernel() only, with the id of the row's _feat cell.  They are NOT a column of the host's trace table
-// (pt_trace_table.hpp; why: DESIGN.md Round 23).
+// them through pt_query_kernel() only, the accessor PT_VARIANT_ACCESSOR makes of the same rows: the column BUILD_QRY of the
+// host's trace table (pt_trace_table.hpp).
 // The other two move a batch between the caller's DEVICE arrays and the planes, one thread per ray, the statements of
 // pt_query.hpp (for host arrays pt_api.hip runs the same statements on the host and copies plane by plane):
 //   pt_query_pack_kernel     PtRay[m] -> origins into PT_FEAT_POINT's plane, directions into PT_FEAT_NORMAL's
@@ -12,13 +12,7 @@
 #include "pt_trace_body.hpp"
 
 PT_VARIANT_ROWS(PT_TRACE_VARIANT, _qry, Qry)
-
-extern "C" const void* pt_query_kernel(int id) {
-  switch (id) {
-    PT_VARIANT_ROWS(PT_TRACE_VARIANT_CASE, _qry, Qry)
-    default: return nullptr;
-  }
-}
+PT_VARIANT_ACCESSOR(pt_query_kernel, _qry, Qry)
 
 // grid = ceil(m / 256) workgroups of 256 threads; m <= plane, the texels of one plane
 extern "C" __global__ __launch_bounds__(256) void pt_query_pack_kernel(const PtRay* rays, uint32_t m, ptq::F4* planes, uint32_t plane) {

@@ -4,21 +4,15 @@
 // in here.  The twelve trace kernels are the variant rows of pt_extra.h (PT_VARIANT_ROWS, the same launch shapes as their
 // namesakes) under the adaptor Rad and the suffix _rad: the plain build of the row with every sample's ray read from the query
 // planes (behind PtKernelArgs::uuid) at the item's place; the seed, the shade, the sample loop and the item's slab store are the
-// plain build's.  pt_api.hip reaches them through pt_radiance_kernel() only, with the id of the row's _feat cell.  Like the _qry
-// builds they are NOT a column of the host's trace table (pt_trace_table.hpp; why: DESIGN.md Round 23).
+// plain build's.  pt_api.hip reaches them through pt_radiance_kernel() only, the accessor PT_VARIANT_ACCESSOR makes of the same
+// rows: the column BUILD_RAD of the host's trace table (pt_trace_table.hpp).
 // The thirteenth folds a batch, one thread per ray, by the statements of pt_radiance.hpp:
 //   pt_radiance_fold_kernel   n_passes slab texels of place i -> PtRayRadiance out[i]; the zero record where the staged ray is invalid
 #include "pt_trace_body.hpp"
 #include "pt_radiance.hpp"
 
 PT_VARIANT_ROWS(PT_TRACE_VARIANT, _rad, Rad)
-
-extern "C" const void* pt_radiance_kernel(int id) {
-  switch (id) {
-    PT_VARIANT_ROWS(PT_TRACE_VARIANT_CASE, _rad, Rad)
-    default: return nullptr;
-  }
-}
+PT_VARIANT_ACCESSOR(pt_radiance_kernel, _rad, Rad)
 
 // grid = ceil(m / 256) workgroups of 256 threads; m <= plane, the texels of one plane; out holds m records
 extern "C" __global__ __launch_bounds__(256) void pt_radiance_fold_kernel(const ptq::F4* slab, uint32_t plane, uint32_t n_passes, const ptq::F4* rays,

@@ -69,6 +69,14 @@ template <class Row> struct Rad : Row { static constexpr bool RAD = true; };
 #define PT_TRACE_KERNEL_CASE(sym, waves, Build) case PT_KERNEL_ID(sym): return reinterpret_cast<const void*>(sym);
 #define PT_TRACE_VARIANT(stem, waves, Row, suffix, Adaptor) PT_TRACE_KERNEL(stem##suffix, waves, Adaptor<Row>)
 #define PT_TRACE_VARIANT_CASE(stem, waves, Row, suffix, Adaptor) case PT_VARIANT_ID(stem): return reinterpret_cast<const void*>(stem##suffix);
+// The accessor of an object whose ids are the variant rows: the row's build of this column by its variant id.
+#define PT_VARIANT_ACCESSOR(name, suffix, Adaptor)             \
+  extern "C" const void* name(int id) {                        \
+    switch (id) {                                              \
+      PT_VARIANT_ROWS(PT_TRACE_VARIANT_CASE, suffix, Adaptor)  \
+      default: return nullptr;                                 \
+    }                                                          \
+  }
 
 // The path-tracing kernel body: one persistent wave working through (pixel, pass) items.
 template <class B>

@@ -33,6 +33,8 @@ PT_TWIN_KERNELS(PT_TWIN_CELL)
 PT_VARIANT_ROWS(PT_VARIANT_CELL, _rr, OBJ_EXTRA)
 PT_VARIANT_ROWS(PT_VARIANT_CELL, _dbg, OBJ_DEBUG)
 PT_VARIANT_ROWS(PT_VARIANT_CELL, _feat, OBJ_FEATURE)
+PT_VARIANT_ROWS(PT_VARIANT_CELL, _qry, OBJ_QUERY)
+PT_VARIANT_ROWS(PT_VARIANT_CELL, _rad, OBJ_RADIANCE)
 }  // namespace trace_cells
 
 // ROW_SMALL + list length % 4; ROW_BVH + what the hierarchy stages in the LDS (hierarchy_staging's kind: 0 / 1 / 2); ROW_GRID +
@@ -40,17 +42,18 @@ PT_VARIANT_ROWS(PT_VARIANT_CELL, _feat, OBJ_FEATURE)
 // along y and ROW_GRID_LAYERS the same build on any other grid (grid_walk_flat)
 enum TraceRow { ROW_LIST_LDS, ROW_SCALAR, ROW_SCALAR_NOLDS, ROW_SMALL, ROW_BVH = ROW_SMALL + 4, ROW_GRID = ROW_BVH + 3, ROW_GRID_LAYERS = ROW_GRID + 3,
                 ROW_COUNT };
-// (the values pt_last_trace_build reports: abi.py BUILD_*)
-enum TraceBuild { BUILD_PLAIN, BUILD_RR, BUILD_TWIN, BUILD_DBG, BUILD_FEAT, BUILD_COUNT };
+// (the first five are the values pt_last_trace_build reports: abi.py BUILD_*; a query or radiance launch is no render launch and
+// its column is never stored in c->last_build)
+enum TraceBuild { BUILD_PLAIN, BUILD_RR, BUILD_TWIN, BUILD_DBG, BUILD_FEAT, BUILD_QRY, BUILD_RAD, BUILD_COUNT };
 
-// A row: its plain kernel, its measuring twin, and the variant row (pt_extra.h) whose roulette, overlay and feature builds
-// serve it.  Where a way to read the list has no twin, the column holds the plain build, which then runs; the LDS list walk has
-// no variants either (pt_geom_plan.hpp steers roulette, overlay and feature launches to the scalar row).
+// A row: its plain kernel, its measuring twin, and the variant row (pt_extra.h) whose roulette, overlay, feature, query and
+// radiance builds serve it.  Where a way to read the list has no twin, the column holds the plain build, which then runs; the
+// LDS list walk has no variants either (pt_geom_plan.hpp steers roulette, overlay and door launches to the scalar row).
 #define PT_K(stem) trace_cells::cell_pt_trace_kernel##stem
-//                                    plain     roulette    measuring twin  debug overlay  first-hit features
-#define PT_TABLE_ROW(plain, twin, v) {PT_K(plain), PT_K(v##_rr), PT_K(twin), PT_K(v##_dbg), PT_K(v##_feat)}
+//                                    plain     roulette    measuring twin  debug overlay  first-hit features  ray queries  radiance queries
+#define PT_TABLE_ROW(plain, twin, v) {PT_K(plain), PT_K(v##_rr), PT_K(twin), PT_K(v##_dbg), PT_K(v##_feat), PT_K(v##_qry), PT_K(v##_rad)}
 constexpr TraceCell kTraceKernels[ROW_COUNT][BUILD_COUNT] = {
-    {PT_K(), PT_K(), PT_K(), PT_K(), PT_K()},
+    {PT_K(), PT_K(), PT_K(), PT_K(), PT_K(), PT_K(), PT_K()},
     PT_TABLE_ROW(_scalar, _scalar, _scalar),
     PT_TABLE_ROW(_scalar_nolds, _scalar_nolds, _scalar_nolds),
     PT_TABLE_ROW(_small_t0, _small_count, _small_t0),
@@ -77,11 +80,19 @@ inline int trace_row(int path, uint32_t n_spheres, int staging_kind, uint32_t gr
   return n_spheres <= PT_MAX_SPHERES_LDS ? ROW_SCALAR : ROW_SCALAR_NOLDS;  // (the LDS copy exists whenever the list fits)
 }
 
-// The column: features before the overlay before roulette before the measuring twin.
+// The column of a render or feature launch: features before the overlay before roulette before the measuring twin.
 inline int trace_build(bool features, bool overlay, bool roulette, bool count_work) {
   return features ? BUILD_FEAT : (overlay ? BUILD_DBG : (roulette ? BUILD_RR : (count_work ? BUILD_TWIN : BUILD_PLAIN)));
 }
 
+// The entry points that are no render launch, each a door to a column of its own: pt_render_features, pt_query_rays,
+// pt_query_radiance.  A door launch takes a variant row's build through the path forced or settled; the overlay, roulette and
+// the measuring twins do not act on it.
+enum Door { DOOR_NONE, DOOR_FEATURES, DOOR_QUERY, DOOR_RADIANCE };
+inline int door_build(Door door) {
+  return door == DOOR_FEATURES ? BUILD_FEAT : (door == DOOR_QUERY ? BUILD_QRY : (door == DOOR_RADIANCE ? BUILD_RAD : BUILD_PLAIN));
+}
+
 // Does the kernel of this cell read the grid's ring layout?  The two-axis walk does: pt_trace_kernel_grid and its twin (the
-// roulette, overlay and feature builds of that row walk three axes).
+// roulette, overlay, feature, query and radiance builds of that row walk three axes).
 inline bool reads_ring_layout(int row, int build) { return row == ROW_GRID && (build == BUILD_PLAIN || build == BUILD_TWIN); }

@@ -86,7 +86,7 @@ def assert_records_equal(got, ref, what):
 
 
 def kernel_of(t, path):
-    """the query kernel a launch through the forced `path` is: the row's feature cell by name, suffix _qry"""
+    """the query kernel a launch through the forced `path` is: the row's cell of the table's query column (pinned on the CPU: test_trace_builds.py)"""
     st = t.stats()
     return build_of(st, "_qry", path=abi.PT_GEOM_SCALAR if path == abi.PT_GEOM_LDS else path)
 
@@ -548,6 +548,12 @@ def test_torch_device_tensors_in_and_out_give_the_same_bytes():
         mixed = np.full((n, 16), GUARD, np.uint32)
         t._check(t.lib.pt_query_rays(t._ctx, C.c_void_p(rays.data_ptr()), n, mixed.ctypes.data_as(C.c_void_p)))
         assert np.array_equal(mixed, host)
+        # ... and the other way round: host rays (three batches, the last of five rays), device records
+        hits.fill_(0x5a5a5a5a)
+        host_rays = pack(oo, dd)
+        t._check(t.lib.pt_query_rays(t._ctx, host_rays.ctypes.data_as(C.c_void_p), n, C.c_void_p(hits.data_ptr())))
+        dev = hits.cpu().numpy().view(np.uint32)
+        assert (dev[n:] == 0x5a5a5a5a).all() and np.array_equal(dev[:n], host)
         # the Python door: tensors in, tensors out; arrays in, arrays out
         got = t.query_rays(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda())
         assert all(v.is_cuda for v in got.values()) and got["index"].dtype == torch.int32 and got["t"].dtype == torch.float32

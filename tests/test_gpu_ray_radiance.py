@@ -99,7 +99,7 @@ def check(t, sph, p, o, d, what, n_passes=PASSES):
 
 
 def kernel_of(t, path):
-    """the radiance kernel a launch through the forced `path` is: the row's feature cell by name, suffix _rad"""
+    """the radiance kernel a launch through the forced `path` is: the row's cell of the table's radiance column (pinned on the CPU: test_trace_builds.py)"""
     return build_of(t.stats(), "_rad", path=abi.PT_GEOM_SCALAR if path == abi.PT_GEOM_LDS else path)
 
 
@@ -549,6 +549,12 @@ def test_torch_device_tensors_in_and_out_give_the_same_bytes():
         mixed = np.full((n, 4), GUARD, np.uint32)
         t._check(t.lib.pt_query_radiance(t._ctx, C.c_void_p(rays.data_ptr()), n, PASSES, mixed.ctypes.data_as(C.c_void_p)))
         assert np.array_equal(mixed, host)
+        # ... and the other way round: host rays (three batches, the last of five rays), device records
+        out.fill_(0x5a5a5a5a)
+        host_rays = pack(o, d)
+        t._check(t.lib.pt_query_radiance(t._ctx, host_rays.ctypes.data_as(C.c_void_p), n, PASSES, C.c_void_p(out.data_ptr())))
+        dev = out.cpu().numpy().view(np.uint32)
+        assert (dev[n:] == 0x5a5a5a5a).all() and np.array_equal(dev[:n], host)
         # the Python door: tensors in, tensors out; arrays in, arrays out; the mean is sum / samples, 0 for an invalid ray
         oo, dd = o[:100].copy(), d[:100].copy()
         dd[7] = 0.0

@@ -145,7 +145,11 @@ def test_rows_twins_and_the_columns_with_one_grid_build():
 # ---- how many waves, and the row, the column and the ring layout of a launch
 
 TABLE_SHIM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "trace_table_shim.cpp")
-COLUMNS = (abi.BUILD_PLAIN, abi.BUILD_ROULETTE, abi.BUILD_TWIN, abi.BUILD_DEBUG_OVERLAY, abi.BUILD_FEATURES)
+REPORTED = (abi.BUILD_PLAIN, abi.BUILD_ROULETTE, abi.BUILD_TWIN, abi.BUILD_DEBUG_OVERLAY, abi.BUILD_FEATURES)
+# the ray-query and radiance-query builds: columns of the table, not values pt_last_trace_build ever reports (no abi constant)
+BUILD_QRY, BUILD_RAD = 5, 6
+COLUMNS = REPORTED + (BUILD_QRY, BUILD_RAD)
+DOORS = (0, 1, 2, 3)  # csrc/pt_trace_table.hpp Door: none, pt_render_features, pt_query_rays, pt_query_radiance
 
 
 @pytest.fixture(scope="module")
@@ -159,6 +163,7 @@ def table():
     lib.tt_cell.restype, lib.tt_cell.argtypes = C.c_char_p, [C.c_int, C.c_int, IP]
     lib.tt_row.restype, lib.tt_row.argtypes = C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_uint32]
     lib.tt_build.restype, lib.tt_build.argtypes = C.c_int, [C.c_int] * 4
+    lib.tt_door_build.restype, lib.tt_door_build.argtypes = C.c_int, [C.c_int]
     lib.tt_reads_ring_layout.restype, lib.tt_reads_ring_layout.argtypes = C.c_int, [C.c_int, C.c_int]
     return lib
 
@@ -192,8 +197,10 @@ def test_every_case_names_the_librarys_cell_in_every_column(table):
             abi.BUILD_ROULETTE: "_" + tb.build_of(st, "_rr"),
             abi.BUILD_DEBUG_OVERLAY: "_" + tb.build_of(st, "_dbg"),
             abi.BUILD_FEATURES: "_" + tb.build_of(st, "_feat"),
+            BUILD_QRY: "_" + tb.build_of(st, "_qry"),
+            BUILD_RAD: "_" + tb.build_of(st, "_rad"),
         }
-        if row == "list_lds":  # no roulette, overlay or feature build: the plain kernel in every column
+        if row == "list_lds":  # no roulette, overlay, feature, query or radiance build: the plain kernel in every column
             want = dict.fromkeys(COLUMNS, "")
         for col in COLUMNS:
             assert lib_cell(table, r, col)[0] == "pt_trace_kernel" + want[col], (row, col)
@@ -212,24 +219,24 @@ def waves_of(name):
 def test_the_whole_table(table):
     shape = (C.c_int * 2)()
     table.tt_shape(shape)
-    assert tuple(shape) == (14, 5) == (len(tb.ROWS), len(COLUMNS))
+    assert tuple(shape) == (14, 7) == (len(tb.ROWS), len(COLUMNS))
     ids = (C.c_int * 16)()
     n_objects = table.tt_objects(ids)
-    assert n_objects == 5 and list(ids[:5]) == [10, 4, 17, 12, 12]  # main, small, extra, debug, features
+    assert n_objects == 7 and list(ids[:7]) == [10, 4, 17, 12, 12, 12, 12]  # main, small, extra, debug, features, query, radiance
     cells = {(r, c): lib_cell(table, r, c) for r in range(14) for c in COLUMNS}
     by_name = {}
     for name, obj, kid, waves in cells.values():
         assert name.startswith("pt_trace_kernel") and waves == waves_of(name), (name, waves)
         assert by_name.setdefault(name, (obj, kid)) == (obj, kid), name   # one kernel, one object and id
-    assert len(by_name) == 55 == 10 + 4 + 17 + 12 + 12
-    assert len(set(by_name.values())) == 55                                # ... and one id, one kernel
+    assert len(by_name) == 79 == 55 + 12 + 12 == sum(ids[:7])
+    assert len(set(by_name.values())) == 79                                # ... and one id, one kernel
     # every id of every object is used by some cell
-    assert set(by_name.values()) == {(obj, kid) for obj in range(5) for kid in range(ids[obj])}
+    assert set(by_name.values()) == {(obj, kid) for obj in range(7) for kid in range(ids[obj])}
     assert {n for n, _, _, w in cells.values() if w == 4} == {"pt_trace_kernel_grid_cells_count"}
     # the names are the tests' names: every plain row, twin and variant of tests/trace_builds.py, nothing else
     variants = sorted({"grid" if r == "grid_layers" else r for r in tb.ROWS if r != "list_lds"})
     want = {"pt_trace_kernel"} | {"pt_trace_kernel_" + r for r in tb.ROWS if r != "list_lds"} | {"pt_trace_kernel_" + t for t in tb.TWINS}
-    want |= {"pt_trace_kernel_%s%s" % (v, s) for v in variants for s in ("_rr", "_dbg", "_feat")}
+    want |= {"pt_trace_kernel_%s%s" % (v, s) for v in variants for s in ("_rr", "_dbg", "_feat", "_qry", "_rad")}
     assert set(by_name) == want and len(variants) == 12
     # the ring layout: the two-axis walk's two kernels
     ring = [(r, c) for r in range(14) for c in COLUMNS if table.tt_reads_ring_layout(r, c)]
@@ -243,4 +250,10 @@ def test_column_precedence(table):
         want = (abi.BUILD_FEATURES if feat else abi.BUILD_DEBUG_OVERLAY if dbg else abi.BUILD_ROULETTE if rr
                 else abi.BUILD_TWIN if count else abi.BUILD_PLAIN)
         assert table.tt_build(feat, dbg, rr, count) == want, (feat, dbg, rr, count)
-    assert COLUMNS == (0, 1, 2, 3, 4)
+    assert REPORTED == (0, 1, 2, 3, 4)
+
+
+def test_a_door_names_its_own_column(table):
+    """no door: the plain column (a render launch's comes from its options, above); each entry point's door: its own"""
+    assert [table.tt_door_build(d) for d in DOORS] == [abi.BUILD_PLAIN, abi.BUILD_FEATURES, BUILD_QRY, BUILD_RAD]
+    assert COLUMNS == (0, 1, 2, 3, 4, 5, 6)

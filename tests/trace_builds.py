@@ -81,6 +81,7 @@ def twin_of(row):
 
 
 def build_of(st, suffix, path=None):
-    """the kernel of a column that has ONE grid build for the rows `grid` and `grid_layers` (roulette, overlay, features)"""
+    """the kernel of a column that has ONE grid build for the rows `grid` and `grid_layers` (roulette, overlay, features, ray queries, radiance
+    queries)"""
     row = row_of(st, path)
     return ("grid" if row == "grid_layers" else row) + suffix

@@ -34,4 +34,7 @@ TT_API int tt_build(int features, int overlay, int roulette, int count_work) {
   return trace_build(features != 0, overlay != 0, roulette != 0, count_work != 0);
 }
 
+// the column of a door launch; door: 0 none / 1 pt_render_features / 2 pt_query_rays / 3 pt_query_radiance
+TT_API int tt_door_build(int door) { return door_build((Door)door); }
+
 TT_API int tt_reads_ring_layout(int row, int build) { return reads_ring_layout(row, build); }
