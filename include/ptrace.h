@@ -299,7 +299,9 @@ int pt_render(pt_ctx* ctx);
 int pt_render_passes(pt_ctx* ctx, uint32_t n_passes);
 /* Pre-sizes the per-pass workspace so pt_render_passes(n <= max_passes) never allocates.  The reservation only grows: a smaller
  * max_passes leaves it as it is.  pt_render_passes with more passes than the largest reservation so far returns PT_ERR_CAPACITY
- * and enqueues nothing. */
+ * and enqueues nothing.  A refused reservation (PT_ERR_HIP) leaves the count as it was; the context's buffers are then not in place
+ * after a failed allocation: the render and read-out calls return PT_ERR_CAPACITY until a sizing call (pt_reserve_passes, a
+ * repartitioning pt_set_params, pt_resize) succeeds. */
 int pt_reserve_passes(pt_ctx* ctx, uint32_t max_passes);
 /* render_count = 0 (src/state.rs:343-346): clears accumulation, spp counter and statistics */
 int pt_reset_accum(pt_ctx* ctx);

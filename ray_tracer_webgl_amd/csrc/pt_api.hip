@@ -37,6 +37,7 @@
 #include "pt_reproject.hpp"
 #include "pt_query.hpp"
 #include "pt_radiance.hpp"
+#include "pt_buffers.hpp"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -48,34 +49,15 @@
 
 static thread_local std::string g_create_error;
 
-// A device buffer and its capacity in elements; the one owner of every allocation the library makes, freed with it.
-template <class T>
-struct DevBuf {
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
-  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
-  ~DevBuf() { if (p_) (void)hipFree(p_); }
-  // room for exactly n elements, contents undefined: the old buffer is freed BEFORE the new one is allocated (the two need
-  // not fit on the device together); on failure it holds nothing and has capacity 0
-  hipError_t reserve(size_t n) {
-    hipError_t e = hipSuccess;
-    if (p_) e = hipFree(p_);
-    p_ = nullptr;
-    cap_ = 0;
-    if (e == hipSuccess) e = hipMalloc(&p_, n * sizeof(T));
-    if (e != hipSuccess) { p_ = nullptr; return e; }
-    cap_ = n;
-    return hipSuccess;
-  }
-  T* get() const { return p_; }
-  size_t capacity() const { return cap_; }
-
- private:
-  T* p_ = nullptr;
-  size_t cap_ = 0;
-};
+// the allocator of pt_buffers.hpp's DevBuf; its codes are hipError_t values.  A refused allocation is reported by the call that
+// asked for it and leaves no error pending for the hipGetLastError() of a later, good launch.
+int ptbuf::dev_malloc(void** p, size_t bytes) {
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) (void)hipGetLastError();
+  return (int)e;
+}
+int ptbuf::dev_free(void* p) { return (int)hipFree(p); }
+using ptbuf::DevBuf;
 
 // Everything a trace-kernel launch needs, decided from the context's scene and uniforms: the
 // argument block, which kernel walks the sphere list, launch geometry.  No HIP call in here that
@@ -138,26 +120,23 @@ struct pt_ctx {
   bool have_spheres = false, have_params = false;  // have_spheres: list, bvh and grid are one scene's, wholly installed
   PtParams params{};
   uint32_t local_rows = 0;
-  // accumulation
-  DevBuf<float4> own_accum;
-  float4* accum = nullptr; // own_accum or caller-bound (never freed here)
-  size_t accum_pixels = 0;
-  bool accum_bound = false;
+  // The buffers sized for the row partition, in five sets (pt_buffers.hpp: what each holds, how it is sized, what a failed
+  // allocation leaves; ensure_buffers fits them).  frame: what every context has — the accumulation (own or caller-bound), the
+  // per-pass slabs, the work queue's per-tile cost and order (with `order` below), the reference's frame (two RGBA8 textures +
+  // canvas) and the read-out staging.  The opt-in sets hold their `on` flag and validity beside their buffers: est
+  // (PT_OPT_ERROR_ESTIMATE; pt_kernels_error.hip: the state folded by pt_fold_error_kernel in pt_accumulate_kernel's place, the
+  // tile records then their tallies), feat (PT_OPT_FEATURES; pt_kernels_features.hip: written by pt_render_features, which also
+  // needs the uuid arrays below), query (PT_OPT_RAY_QUERIES; pt_kernels_query.hip: rays staged into the point and normal planes,
+  // records read back from all four; the frame's own tile order belongs to the render launches; pt_query_rays also needs the
+  // uuid arrays) and hist (PT_OPT_REPROJECT; pt_kernels_reproject.hip: pt_keep_history / pt_load_history).
+  ptbuf::FrameSet<float4> frame;
+  ptbuf::EstimateSet<float4> est;
+  ptbuf::FeatureSet<float4> feat;
+  ptbuf::QuerySet<float4> query;
+  ptbuf::HistorySet<float4> hist;
+  uint32_t reserved_passes = 1;
   uint32_t total_spp = 0;   // enqueued directly (not through graph replays)
   bool captured = false;    // some launch was captured into a hipGraph: only the device knows the spp
-  // per-pass slabs (passes * local pixels)
-  DevBuf<float4> d_slab;
-  uint32_t reserved_passes = 1;
-  // read-out staging
-  DevBuf<float4> d_resolve;
-  // per-pixel error estimate (PT_OPT_ERROR_ESTIMATE; pt_kernels_error.hip): two float4 per local pixel, A = {mean.rgb, n} and
-  // B = {M2.rgb, k}, folded by pt_fold_error_kernel in pt_accumulate_kernel's place; the tile records and their tallies
-  bool err_on = false;
-  bool err_paused = false;          // pt_tune's measuring launches fold the plain way (it clears everything afterwards)
-  int err_spp = 0;                  // samples_per_pixel of the passes folded since the last clear (0 = none yet)
-  DevBuf<float4> d_err;
-  DevBuf<float4> d_err_tiles;       // tiles records, then tiles tallies (pt_error_tiles_kernel)
-  DevBuf<float4> d_err_stage;       // pt_reproject_estimate's staging of the state, 2 x local pixels: while PT_OPT_REPROJECT is on too
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   PathTuner geom;
   hipEvent_t trial_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // begin/end per trial
@@ -178,29 +157,8 @@ struct pt_ctx {
   float dbg_cursor[3] = {0.f, 0.f, 0.f};
   bool uuid_valid = false;          // the three uuid arrays match the scene and structures in place
   int last_build = 0;               // which build the most recent trace launch was (pt_last_trace_build)
-  // first-hit feature planes (PT_OPT_FEATURES; pt_kernels_features.hip): four planes of one 16-byte texel per local pixel in one
-  // allocation, plane k at k * local pixels; written by pt_render_features, which also needs the uuid arrays above
-  bool feat_on = false;
-  bool feat_valid = false;          // the planes speak for the scene, uniforms and partition in place (pt_read_features)
-  DevBuf<float4> d_feat;
-  // ray queries (PT_OPT_RAY_QUERIES; pt_kernels_query.hip): the query planes — the feature planes' layout, rays staged into the
-  // point and normal planes, records read back from all four — and the identity tile order a query launch is dealt by (the
-  // frame's own order belongs to the render launches); pt_query_rays also needs the uuid arrays above
-  bool query_on = false;
-  DevBuf<float4> d_query;
-  DevBuf<uint32_t> d_query_order;
-  // temporal reprojection (PT_OPT_REPROJECT; pt_kernels_reproject.hip): the history planes — the ids plane, then the point plane,
-  // of an earlier view (pt_keep_history / pt_load_history) — the uniforms they were rendered with, and the last call's tallies
-  bool reproj_on = false;
-  bool hist_valid = false;          // the history speaks for the scene and partition in place, and no pt_reproject has used it
-  PtParams hist_params{};
-  DevBuf<float4> d_hist;
-  DevBuf<unsigned long long> d_reproj_tally;  // {pixels_hit, pixels_kept, samples_kept}
-  bool reproj_ran = false;          // the tallies are those of a pt_reproject (pt_reproject_stats)
-  // work-queue ordering feedback, one entry per tile
-  DevBuf<uint32_t> d_tile_cost;
-  DevBuf<uint32_t> d_tile_order;
-  TileOrder order;  // what the host knows of the two (pt_tile_order.hpp): when the order kernel runs, when the frames' order is probed
+  // work-queue ordering feedback, one entry per tile: what the host knows of frame.tile_cost and frame.tile_order
+  TileOrder order;  // (pt_tile_order.hpp): when the order kernel runs, when the frames' order is probed
   // adaptive sampling (pt_render_adaptive): a partial round's tables — 3 x tiles words: the flags as uploaded, the partition the
   // trace launch and the masked fold read, the cost order it was made from — and the host's copy of the flags
   DevBuf<uint32_t> d_adapt;
@@ -208,10 +166,8 @@ struct pt_ctx {
   bool adapt_valid = false;       // the tables are those of a partial round of the scene and partition in place (pt_adaptive_tiles)
   uint32_t adapt_tiles = 0, adapt_active = 0;
   uint64_t scene_gen = 0;  // counts pt_set_spheres: the frames' cost-sorted tile order is probed per scene (ensure_cost_order)
-  // the reference's frame (pt_render_frame / pt_render_frames): two RGBA8 textures + canvas, the
-  // device-side frame counter ([0] frames replayed since the series began, [1] a cell that stays 0)
-  DevBuf<uint32_t> d_tex[2];
-  DevBuf<uint32_t> d_canvas;
+  // the reference's frame (pt_render_frame / pt_render_frames): the device-side frame counter ([0] frames replayed since the
+  // series began, [1] a cell that stays 0)
   DevBuf<uint32_t> d_frame_ctr;
   // captured frames, one graph per group size (kFrameGroups: 64, 16, 4, 1 frames — a group is ONE trace launch of that many passes,
   // one kernel for their blends, one advance; a single frame is trace + blend + advance), each captured once per plan
@@ -282,7 +238,7 @@ int fail(pt_ctx* c, int code, const char* fmt, ...) {
 
 #define PT_HIP(c, call)                                                                     \
   do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
+    hipError_t e_ = static_cast<hipError_t>(call); /* (DevBuf::reserve hands the code on as an int) */ \
     if (e_ != hipSuccess)                                                                   \
       return fail((c), PT_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_),   \
                   __FILE__, __LINE__);                                                      \
@@ -317,79 +273,82 @@ hipError_t fill_identity_order(DevBuf<uint32_t>& order, size_t tiles) {
   return hipMemcpy(order.get(), ident.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice);
 }
 
+// what the context's buffers are sized for: the partition in place
+ptbuf::Extent extent_of(const pt_ctx* c) { return {n_pixels(c), n_tiles(c), c->reserved_passes}; }
+
+// a set's fit was refused (`what` names the set): above the planes' index cap nothing was freed, after a failed allocation the
+// set is not in place until a later fit succeeds
+int fit_refused(pt_ctx* c, const char* what, const ptbuf::Fit& f, const ptbuf::Extent& e) {
+  if (f.capped) return fail(c, PT_ERR_CAPACITY, "%s: %zu local pixels exceed the kernels' 32-bit texel index", what, e.pix);
+  return fail(c, PT_ERR_HIP, "%s: a device allocation for %zu local pixels failed: %s", what, e.pix, hipGetErrorString((hipError_t)f.err));
+}
+
+// The five sets fitted to the partition in place, in their order; what a fit reallocated is zeroed or filled here — also when a
+// later buffer of the same set was refused: what is in place is defined.
 int ensure_buffers(pt_ctx* c) {
-  size_t pix = n_pixels(c);
-  if (pix == 0) pix = 1;
-  if (!c->accum_bound) {
-    if (c->own_accum.capacity() < pix) {
-      PT_HIP(c, c->own_accum.reserve(pix));
-      PT_HIP(c, hipMemsetAsync(c->own_accum.get(), 0, pix * sizeof(float4), c->stream));
+  const ptbuf::Extent e = extent_of(c);
+  auto zero = [c](auto& buf, size_t n) { return hipMemsetAsync(buf.get(), 0, n * sizeof(*buf.get()), c->stream); };
+  {
+    auto& s = c->frame;
+    const ptbuf::Fit f = s.fit(e);
+    if (f.fresh & s.ACCUM) {
+      PT_HIP(c, zero(s.own_accum, e.pix));
       c->total_spp = 0;
     }
-    c->accum = c->own_accum.get();
-    c->accum_pixels = c->own_accum.capacity();
-  }
-  const size_t need = pix * (size_t)c->reserved_passes;
-  if (c->d_slab.capacity() < need) PT_HIP(c, c->d_slab.reserve(need));
-  size_t tiles = (size_t)tiles_x(c) * tiles_y(c);
-  if (tiles == 0) tiles = 1;
-  // reallocated and re-seeded whenever the tile count CHANGES, not only when it grows: an order left from another count would
-  // name tiles that do not exist, or miss some
-  if (c->d_tile_cost.capacity() != tiles || c->d_tile_order.capacity() != tiles) {
-    PT_HIP(c, c->d_tile_cost.reserve(tiles));
-    PT_HIP(c, c->d_tile_order.reserve(tiles));
-    PT_HIP(c, hipMemsetAsync(c->d_tile_cost.get(), 0, tiles * sizeof(uint32_t), c->stream));
-    // the identity order from the start: a launch that skips the order kernel (because an earlier one was only
-    // CAPTURED into a caller's hipGraph and has not run yet) must still find every tile exactly once
-    PT_HIP(c, fill_identity_order(c->d_tile_order, tiles));
-    c->order.reseeded();
-    c->adapt_valid = false;
-  }
-  if (c->d_canvas.capacity() < pix) {  // create_texture x2 (src/webgl.rs:82-123), cleared: alpha 0 = "no data" (shader.frag:391)
-    for (int k = 0; k < 2; k++) {
-      PT_HIP(c, c->d_tex[k].reserve(pix));
-      PT_HIP(c, hipMemsetAsync(c->d_tex[k].get(), 0, pix * sizeof(uint32_t), c->stream));
+    if (f.fresh & s.COST) PT_HIP(c, zero(s.tile_cost, e.tiles));
+    if (f.fresh & s.ORDER) {
+      // the identity order from the start: a launch that skips the order kernel (because an earlier one was only
+      // CAPTURED into a caller's hipGraph and has not run yet) must still find every tile exactly once
+      PT_HIP(c, fill_identity_order(s.tile_order, e.tiles));
+      c->order.reseeded();
+      c->adapt_valid = false;
     }
-    PT_HIP(c, c->d_canvas.reserve(pix));  // (last: its capacity says all three are in place)
-    PT_HIP(c, hipMemsetAsync(c->d_canvas.get(), 0, pix * sizeof(uint32_t), c->stream));
+    // create_texture x2 (src/webgl.rs:82-123), cleared: alpha 0 = "no data" (shader.frag:391)
+    if (f.fresh & s.TEX0) PT_HIP(c, zero(s.tex[0], e.pix));
+    if (f.fresh & s.TEX1) PT_HIP(c, zero(s.tex[1], e.pix));
+    if (f.fresh & s.CANVAS) PT_HIP(c, zero(s.canvas, e.pix));
+    if (!f.ok()) return fit_refused(c, "the context's buffers", f, e);
   }
-  if (c->d_resolve.capacity() < pix) PT_HIP(c, c->d_resolve.reserve(pix));
-  if (c->err_on) {
-    if (c->d_err.capacity() < 2 * pix) {
-      PT_HIP(c, c->d_err.reserve(2 * pix));
-      PT_HIP(c, hipMemsetAsync(c->d_err.get(), 0, 2 * pix * sizeof(float4), c->stream));
-      c->err_spp = 0;
-    }
-    if (c->d_err_tiles.capacity() < 2 * tiles) PT_HIP(c, c->d_err_tiles.reserve(2 * tiles));
-    // (pt_reproject_estimate gathers the state from other pixels' places: it cannot write in place, and it does not allocate)
-    if (c->reproj_on && c->d_err_stage.capacity() < 2 * pix) PT_HIP(c, c->d_err_stage.reserve(2 * pix));
+  {
+    // (the stage: pt_reproject_estimate gathers the state from other pixels' places: it cannot write in place, and it does not allocate)
+    const ptbuf::Fit f = c->est.fit(e, c->hist.on);
+    if (f.fresh & c->est.STATE) PT_HIP(c, zero(c->est.state, 2 * e.pix));
+    if (!f.ok()) return fit_refused(c, "error estimate", f, e);
   }
-  if (c->feat_on && c->d_feat.capacity() != PT_FEAT_PLANES * pix) {  // (sized for the local rows in place: plane k begins at k * pix)
-    c->feat_valid = false;
-    if (pix > 0x3fffffffu / PT_FEAT_PLANES) return fail(c, PT_ERR_CAPACITY, "feature planes: %zu local pixels exceed the kernels' 32-bit texel index", pix);
-    PT_HIP(c, c->d_feat.reserve(PT_FEAT_PLANES * pix));
+  if (const ptbuf::Fit f = c->feat.fit(e); !f.ok()) return fit_refused(c, "feature planes", f, e);
+  {
+    if (c->query.on && !c->query.fits(e)) PT_HIP(c, hipStreamSynchronize(c->stream));  // (a query in flight uses what the fit frees)
+    const ptbuf::Fit f = c->query.fit(e);
+    if (f.fresh & c->query.ORDER) PT_HIP(c, fill_identity_order(c->query.order, e.tiles));
+    if (!f.ok()) return fit_refused(c, "query planes", f, e);
   }
-  if (c->query_on && (c->d_query.capacity() != PT_FEAT_PLANES * pix || c->d_query_order.capacity() != tiles)) {  // (likewise)
-    if (pix > 0x3fffffffu / PT_FEAT_PLANES) return fail(c, PT_ERR_CAPACITY, "query planes: %zu local pixels exceed the kernels' 32-bit texel index", pix);
-    PT_HIP(c, hipStreamSynchronize(c->stream));
-    c->d_query = DevBuf<float4>();  // (what pt_query_rays tests: both in place, or neither)
-    PT_HIP(c, c->d_query_order.reserve(tiles));
-    PT_HIP(c, fill_identity_order(c->d_query_order, tiles));
-    PT_HIP(c, c->d_query.reserve(PT_FEAT_PLANES * pix));
-  }
-  if (c->reproj_on && c->d_hist.capacity() != 2 * pix) {  // (likewise: the ids plane, then the point plane at pix)
-    c->hist_valid = false;
-    PT_HIP(c, c->d_hist.reserve(2 * pix));
-  }
+  if (const ptbuf::Fit f = c->hist.fit(e); !f.ok()) return fit_refused(c, "history planes", f, e);
   return PT_OK;
+}
+
+// The contract of the frame set, as the planes have it: in place for the rows in place, or the call is refused.  Asked by every
+// trace launch (prepare_launch) and by the entry points that hand the staging, the textures or the canvas to a copy or a kernel
+// without one; with the estimate on its state belongs to every render and read-out, and is asked with them.  Host compares only.
+int frame_buffers_ready(pt_ctx* c, const char* who) {
+  const ptbuf::Extent e = extent_of(c);
+  if (c->frame.in_place(e) && (!c->est.on || c->est.in_place(e, c->hist.on))) return PT_OK;
+  return fail(c, PT_ERR_CAPACITY, "%s: the context's buffers are not allocated for the rows in place (an earlier allocation failed)", who);
+}
+
+// an entry point (`who`) of an opt-in set that is off
+enum OptInSet { SET_ESTIMATE, SET_FEATURES, SET_QUERIES, SET_REPROJECT };
+int option_off(pt_ctx* c, const char* who, OptInSet set, int code = PT_ERR_NOT_READY) {
+  static const char* const what[] = {"the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", "the feature planes are off (pt_set_option PT_OPT_FEATURES)",
+                                     "ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)", "reprojection is off (pt_set_option PT_OPT_REPROJECT)"};
+  return fail(c, code, "%s: %s", who, what[set]);
 }
 
 // the error estimate speaks for the passes folded since its last clear: cleared wherever the accumulation is cleared or replaced
 int clear_error(pt_ctx* c) {
-  if (!c->err_on) return PT_OK;
+  if (!c->est.on) return PT_OK;
   const size_t pix = n_pixels(c);
-  if (pix) PT_HIP(c, hipMemsetAsync(c->d_err.get(), 0, 2 * pix * sizeof(float4), c->stream));
-  c->err_spp = 0;
+  if (pix) PT_HIP(c, hipMemsetAsync(c->est.state.get(), 0, 2 * pix * sizeof(float4), c->stream));
+  c->est.spp = 0;
   return PT_OK;
 }
 
@@ -447,7 +406,7 @@ bool is_capturing(const pt_ctx* c) {
 
 // the queue order of the tiles from their costs (the identity while every cost is zero)
 int launch_tile_order(pt_ctx* c) {
-  hipLaunchKernelGGL(pt_tile_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_tile_cost.get(), c->d_tile_order.get(),
+  hipLaunchKernelGGL(pt_tile_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->frame.tile_cost.get(), c->frame.tile_order.get(),
                      n_tiles(c));
   PT_HIP(c, hipGetLastError());
   return PT_OK;
@@ -556,12 +515,12 @@ static int create_common(pt_ctx** out, int device, uint32_t width, uint32_t heig
     c->stream = c->own_stream;
   }
   const double t_stream = host_ms();
-  if ((e = c->d_counters.reserve(PT_CTR_ALLOC)) != hipSuccess) return bail(e, "hipMalloc(counters)");
+  if ((e = (hipError_t)c->d_counters.reserve(PT_CTR_ALLOC)) != hipSuccess) return bail(e, "hipMalloc(counters)");
   const double t_first_malloc = host_ms();
   if ((e = hipMemsetAsync(c->d_counters.get(), 0, PT_CTR_ALLOC * sizeof(unsigned long long), c->stream)) != hipSuccess)
     return bail(e, "hipMemsetAsync(counters)");
   const double t_first_memset = host_ms();
-  if ((e = c->d_frame_ctr.reserve(2)) != hipSuccess) return bail(e, "hipMalloc(frame counter)");
+  if ((e = (hipError_t)c->d_frame_ctr.reserve(2)) != hipSuccess) return bail(e, "hipMalloc(frame counter)");
   if ((e = hipMemsetAsync(c->d_frame_ctr.get(), 0, 2 * sizeof(uint32_t), c->stream)) != hipSuccess)
     return bail(e, "hipMemsetAsync(frame counter)");
   const double t_small_allocs = host_ms();
@@ -632,7 +591,7 @@ template <class T>
 void release(std::vector<T>& v) { std::vector<T>().swap(v); }
 
 // no scene is in place (until an install has wholly succeeded: the render calls answer PT_ERR_NOT_READY meanwhile)
-void drop_scene(pt_ctx* c) { c->have_spheres = c->bvh.present = c->grid.present = c->uuid_valid = c->feat_valid = false; }
+void drop_scene(pt_ctx* c) { c->have_spheres = c->bvh.present = c->grid.present = c->uuid_valid = c->feat.valid = false; }
 
 // (list.n and list.host follow when the whole scene is in place: pt_set_spheres)
 int install_list(pt_ctx* c, const ptscene::Split& sp, size_t n) {
@@ -685,7 +644,7 @@ int install_grid(pt_ctx* c, ptgrid::Grid& grid, const ptscene::Split& sp) {
 // The uuid arrays of the debug overlay, of the feature planes and of ray queries: PtSphere.uuid in list order and per slot of the structures in
 // place (the walk kernels shade from a slot, like slot_mat).  Made when one of them is turned on and again whenever the scene or the
 // grid changes while one is on (wants_uuids); a context that never enables one never allocates them.  Synchronises: a set-up call's work.
-inline bool wants_uuids(const pt_ctx* c) { return c->dbg_enable || c->feat_on || c->query_on; }
+inline bool wants_uuids(const pt_ctx* c) { return c->dbg_enable || c->feat.on || c->query.on; }
 int upload_uuids(pt_ctx* c, const std::vector<int32_t>& uuid) {
   PT_HIP(c, hipSetDevice(c->device));
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight may read the arrays in place
@@ -731,7 +690,7 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
   PT_HIP(c, hipStreamSynchronize(c->stream));
   // validate first, commit afterwards: from the first device write until everything is in place the context has no scene
   drop_scene(c);
-  c->hist_valid = false;  // (the history's list indices would name other spheres)
+  c->hist.valid = false;  // (the history's list indices would name other spheres)
   if (int rc = install_scene(c, sp, n, have_bvh ? &bvh : nullptr, have_grid ? &grid : nullptr); rc != PT_OK) return drop_scene(c), rc;
   c->list.n = n;
   c->list.host = std::move(sp);
@@ -769,15 +728,17 @@ PT_API int pt_set_params(pt_ctx* c, const PtParams* p) {
   bool repartition = rows != c->local_rows;
   for (uint32_t k = 0; k < 3; k++) repartition |= eff(*p, k) != eff(c->params, k);
   // validate first, commit afterwards: a refused call leaves the context as it was
-  if (repartition && c->accum_bound && (size_t)rows * c->width > c->accum_pixels)
+  if (repartition && c->frame.accum_bound && (size_t)rows * c->width > c->frame.accum_pixels)
     return fail(c, PT_ERR_CAPACITY, "pt_set_params: bound accumulation buffer too small for %u rows", rows);
-  c->feat_valid = false;  // the feature planes speak for the uniforms they were rendered with
+  c->feat.valid = false;  // the feature planes speak for the uniforms they were rendered with
   if (repartition) {
-    c->hist_valid = false;  // (the history planes held other rows; an ordinary pt_set_params leaves them alone)
+    c->hist.valid = false;  // (the history planes held other rows; an ordinary pt_set_params leaves them alone)
     const uint32_t old_rows = c->local_rows;
     c->local_rows = rows;
     int rc = ensure_buffers(c);
-    if (rc != PT_OK) { // allocation failed: keep the previous partition renderable
+    if (rc != PT_OK) {
+      // allocation failed: the previous partition and uniforms stay the context's.  A buffer the failure freed is no longer in
+      // place for them either: the render and read-out calls answer PT_ERR_CAPACITY until a sizing call succeeds
       c->local_rows = old_rows;
       return rc;
     }
@@ -790,7 +751,7 @@ PT_API int pt_set_params(pt_ctx* c, const PtParams* p) {
     c->captured = false;  // whatever a replayed graph accumulated is gone with the old partition
     c->adapt_valid = false;
     // a different set of rows: the accumulated image no longer applies, and neither do the frame textures
-    PT_HIP(c, hipMemsetAsync(c->accum, 0, n_pixels(c) * sizeof(float4), c->stream));
+    PT_HIP(c, hipMemsetAsync(c->frame.accum, 0, n_pixels(c) * sizeof(float4), c->stream));
     if (int rc = clear_error(c); rc != PT_OK) return rc;
     return pt_clear_textures(c);
   }
@@ -807,11 +768,11 @@ PT_API int pt_resize(pt_ctx* c, uint32_t width, uint32_t height) {
   c->height = height;
   c->have_params = false; // uniforms must be re-uploaded for the new size
   c->adapt_valid = false;
-  c->feat_valid = false;
-  c->hist_valid = false;
+  c->feat.valid = false;
+  c->hist.valid = false;
   c->params.band_count = 0;
   c->local_rows = height;
-  if (c->accum_bound) { c->accum_bound = false; c->accum = nullptr; }
+  if (c->frame.accum_bound) { c->frame.accum_bound = false; c->frame.accum = nullptr; }
   int rc = ensure_buffers(c);
   if (rc != PT_OK) return rc;
   // update_render_dimensions_to_match_window re-specifies both textures as empty on EVERY resize
@@ -825,11 +786,15 @@ PT_API int pt_reserve_passes(pt_ctx* c, uint32_t max_passes) {
   if (!c || max_passes == 0) return fail(c, PT_ERR_INVALID, "pt_reserve_passes: bad argument");
   PT_HIP(c, hipSetDevice(c->device));
   const double t_begin = host_ms();
-  if (max_passes > c->reserved_passes) {
+  const uint32_t reserved = c->reserved_passes;
+  if (max_passes > reserved) {
     PT_HIP(c, hipStreamSynchronize(c->stream));
     c->reserved_passes = max_passes;
   }
   const int rc = ensure_buffers(c);
+  // a refused reservation leaves the count as it was.  The slab it freed comes back with the next sizing call that succeeds
+  // (this one, a repartition, pt_resize); until then the render and read-out calls are refused (frame_buffers_ready).
+  if (rc != PT_OK) c->reserved_passes = reserved;
   c->setup_ms[PT_SETUP_RESERVE_TOTAL] = host_ms() - t_begin;
   return rc;
 }
@@ -837,8 +802,8 @@ PT_API int pt_reserve_passes(pt_ctx* c, uint32_t max_passes) {
 PT_API int pt_reset_accum(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   PT_HIP(c, hipSetDevice(c->device));
-  if (c->accum)
-    PT_HIP(c, hipMemsetAsync(c->accum, 0, n_pixels(c) * sizeof(float4), c->stream));
+  if (c->frame.accum)
+    PT_HIP(c, hipMemsetAsync(c->frame.accum, 0, n_pixels(c) * sizeof(float4), c->stream));
   PT_HIP(c, hipMemsetAsync(c->d_counters.get(), 0, PT_CTR_COUNT * sizeof(unsigned long long), c->stream));
   if (int rc = clear_error(c); rc != PT_OK) return rc;
   PT_HIP(c, hipStreamSynchronize(c->stream));
@@ -856,29 +821,29 @@ PT_API int pt_bind_accum(pt_ctx* c, void* dev_ptr, size_t bytes) {
   PT_HIP(c, hipSetDevice(c->device));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   if (!dev_ptr) {
-    c->accum_bound = false;
-    c->accum = nullptr;
+    c->frame.accum_bound = false;
+    c->frame.accum = nullptr;
     int rc = ensure_buffers(c);
     c->total_spp = 0;
     if (rc != PT_OK) return rc;
     // the own buffer comes back EMPTY: what it held when the caller's buffer took its place belongs to another frame — possibly to
     // another row partition, set while it was out of use — and the sample count above has just restarted
-    if (const size_t pix = n_pixels(c)) PT_HIP(c, hipMemsetAsync(c->accum, 0, pix * sizeof(float4), c->stream));
+    if (const size_t pix = n_pixels(c)) PT_HIP(c, hipMemsetAsync(c->frame.accum, 0, pix * sizeof(float4), c->stream));
     return clear_error(c);
   }
   size_t need = n_pixels(c) * sizeof(float4);
   if (bytes < need) return fail(c, PT_ERR_CAPACITY, "pt_bind_accum: %zu bytes < %zu needed", bytes, need);
   if (((uintptr_t)dev_ptr & 15u) != 0) return fail(c, PT_ERR_INVALID, "pt_bind_accum: pointer not 16-byte aligned");
-  c->accum = (float4*)dev_ptr;
-  c->accum_pixels = bytes / sizeof(float4);
-  c->accum_bound = true;
+  c->frame.accum = (float4*)dev_ptr;
+  c->frame.accum_pixels = bytes / sizeof(float4);
+  c->frame.accum_bound = true;
   c->total_spp = 0; // the caller owns the contents; spp counting restarts
   return clear_error(c);  // (and so does the estimate: it knows nothing of what the caller's buffer holds)
 }
 
 PT_API int pt_accum_ptr(pt_ctx* c, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr) return PT_ERR_INVALID;
-  *dev_ptr = c->accum;
+  *dev_ptr = c->frame.accum;
   if (bytes) *bytes = n_pixels(c) * sizeof(float4);
   return PT_OK;
 }
@@ -891,7 +856,7 @@ PT_API int pt_read_accum(pt_ctx* c, float* dst, size_t bytes) {
   const size_t need = n_pixels(c) * sizeof(float4);
   if (bytes < need) return fail(c, PT_ERR_CAPACITY, "pt_read_accum: %zu bytes < %zu needed", bytes, need);
   PT_HIP(c, hipSetDevice(c->device));
-  if (need) PT_HIP(c, hipMemcpyAsync(dst, c->accum, need, hipMemcpyDefault, c->stream));
+  if (need) PT_HIP(c, hipMemcpyAsync(dst, c->frame.accum, need, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
@@ -901,6 +866,7 @@ PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
   const size_t need = n_pixels(c) * sizeof(float4);
   if (bytes != need)
     return fail(c, PT_ERR_INVALID, "pt_load_accum: %zu bytes, the current row partition holds %zu", bytes, need);
+  if (int rc = frame_buffers_ready(c, "pt_load_accum"); rc != PT_OK) return rc;
   PT_HIP(c, hipSetDevice(c->device));
   if (need == 0) return PT_OK;
   // validate first, commit afterwards (like pt_set_params): the checkpoint is staged in the read-out
@@ -908,10 +874,10 @@ PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
   // the first and the last pixel must agree — is checked there, and only then does it replace the
   // accumulation.  A refused checkpoint leaves the context as it was.
   const size_t n_pix = n_pixels(c);
-  PT_HIP(c, hipMemcpyAsync(c->d_resolve.get(), src, need, hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipMemcpyAsync(c->frame.resolve.get(), src, need, hipMemcpyDefault, c->stream));
   float4 ends[2];
-  PT_HIP(c, hipMemcpyAsync(&ends[0], c->d_resolve.get(), sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  PT_HIP(c, hipMemcpyAsync(&ends[1], c->d_resolve.get() + (n_pix - 1), sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipMemcpyAsync(&ends[0], c->frame.resolve.get(), sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipMemcpyAsync(&ends[1], c->frame.resolve.get() + (n_pix - 1), sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   const float w = ends[0].w;
   if (!(w >= 0.0f) || w >= 16777216.0f || w != std::floor(w))
@@ -919,7 +885,7 @@ PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
   if (ends[1].w != w)
     return fail(c, PT_ERR_INVALID, "pt_load_accum: sample counts differ across the buffer (%g ... %g): not an accumulation of whole passes",
                 (double)w, (double)ends[1].w);
-  PT_HIP(c, hipMemcpyAsync(c->accum, c->d_resolve.get(), need, hipMemcpyDeviceToDevice, c->stream));
+  PT_HIP(c, hipMemcpyAsync(c->frame.accum, c->frame.resolve.get(), need, hipMemcpyDeviceToDevice, c->stream));
   if (int rc = clear_error(c); rc != PT_OK) return rc;  // (a checkpoint carries sums, not the passes they came from)
   PT_HIP(c, hipStreamSynchronize(c->stream));
   // the host-side mirrors follow the loaded state
@@ -981,10 +947,10 @@ static int fill_uniforms(pt_ctx* c, uint32_t n_passes, PtKernelArgs& A) {
   A.geom = c->list.geom.get();
   A.mat = c->list.mat.get();
   A.mat_r0 = c->list.r0.get();
-  A.slab = reinterpret_cast<float*>(c->d_slab.get());
+  A.slab = reinterpret_cast<float*>(c->frame.slab.get());
   A.counters = c->d_counters.get();
-  A.tile_order = c->d_tile_order.get();
-  A.tile_cost = c->d_tile_cost.get();
+  A.tile_order = c->frame.tile_order.get();
+  A.tile_cost = c->frame.tile_cost.get();
   A.carry_lanes = c->carry_lanes;
   A.refill_min = c->refill_min;
   A.frame_ctr = c->d_frame_ctr.get() + 1;  // the cell that stays 0 (pt_render_frames points at [0])
@@ -1109,11 +1075,15 @@ struct LaunchUse {
   Door door = DOOR_NONE;
   uint32_t query_rays = 0;
   uint32_t first_pass = 0;
+  // the entry point, for a refusal of prepare_launch's own (the frames' launches were asked under their names: frame_ready)
+  const char* who = "pt_render";
 };
 
 // (what fill_uniforms zeroed and nothing here sets stays zero: wave_log and cell_hist, which only a measuring twin gets)
 static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, Launch* L) {
   PtKernelArgs& A = L->A;
+  // no trace launch gets a pointer into a buffer that is not in place: after a failed allocation the call is refused
+  if (int rc = frame_buffers_ready(c, use.who); rc != PT_OK) return rc;
   {
     int rc = fill_uniforms(c, n_passes, A);
     if (rc != PT_OK) return rc;
@@ -1159,12 +1129,12 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   if (feat) {  // one deterministic segment per pixel into the planes; the overlay and roulette do not act
     A.uuid = c->list.uuid.get();
     A.slot_uuid = path == PT_GEOM_BVH ? c->bvh.uuid.get() : (path == PT_GEOM_GRID ? c->grid.uuid.get() : nullptr);
-    A.slab = reinterpret_cast<float*>(query ? c->d_query.get() : c->d_feat.get());
+    A.slab = reinterpret_cast<float*>(query ? c->query.planes.get() : c->feat.planes.get());
     A.spp = 1; A.max_depth = 1; A.rr_min_depth = 0;
     if (query) A.dbg_selected = (int32_t)use.query_rays;  // (the overlay's field: no build but the overlay's reads it as that)
   }
   if (rad) {  // the plain estimator on the caller's rays: the uniforms' samples and depth, the pass slabs fill_uniforms bound
-    A.uuid = reinterpret_cast<const int32_t*>(c->d_query.get());  // (the staged rays: pt_kernel_args.h says why there)
+    A.uuid = reinterpret_cast<const int32_t*>(c->query.planes.get());  // (the staged rays: pt_kernel_args.h says why there)
     A.slot_uuid = nullptr;
     A.dbg_selected = (int32_t)use.query_rays;
     A.first_pass = use.first_pass;
@@ -1224,17 +1194,18 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
     return fail(c, PT_ERR_CAPACITY, "pt_render_passes: %u passes > %u reserved (pt_reserve_passes)",
                 n_passes, c->reserved_passes);
   if (c->local_rows == 0) return PT_OK; // this band owns no rows
-  const bool estimate = c->err_on && !c->err_paused;
+  const bool estimate = c->est.on && !c->est.paused;
   // the estimate folds pass SUMS: every pass since its last clear must hold the same number of samples
-  if (estimate && c->err_spp != 0 && c->err_spp != c->params.samples_per_pixel)
+  if (estimate && c->est.spp != 0 && c->est.spp != c->params.samples_per_pixel)
     return fail(c, PT_ERR_INVALID, "pt_render_passes: %d samples per pixel while the error estimate holds passes of %d: clear first "
-                                   "(pt_reset_accum)", c->params.samples_per_pixel, c->err_spp);
+                                   "(pt_reset_accum)", c->params.samples_per_pixel, c->est.spp);
   PT_HIP(c, hipSetDevice(c->device));
 
   Launch L;
   {
     LaunchUse use;
     use.allow_trials = true;
+    use.who = "pt_render_passes";
     int rc = prepare_launch(c, n_passes, use, &L);
     if (rc != PT_OK) return rc;
   }
@@ -1292,16 +1263,16 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
 
   uint32_t n_pix = (uint32_t)n_pixels(c);
   if (estimate) {  // the same adds into accum, and the estimate's update beside them (pt_kernels_error.hip)
-    float4* accum = c->accum;
-    float4* est = c->d_err.get();
-    const float4* slab = c->d_slab.get();
+    float4* accum = c->frame.accum;
+    float4* est = c->est.state.get();
+    const float4* slab = c->frame.slab.get();
     uint32_t passes = n_passes;
     void* kargs[] = {&accum, &est, &slab, &n_pix, &passes};
     PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
-    c->err_spp = p.samples_per_pixel;
+    c->est.spp = p.samples_per_pixel;
   } else {
     hipLaunchKernelGGL(pt_accumulate_kernel, dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream,
-                       c->accum, c->d_slab.get(), n_pix, n_passes);
+                       c->frame.accum, c->frame.slab.get(), n_pix, n_passes);
     PT_HIP(c, hipGetLastError());
   }
 
@@ -1345,7 +1316,7 @@ int plan_frame(pt_ctx* c, const uint32_t* ctr, uint32_t even_odd0, int max_rende
   F->last_frame_weight = c->params.last_frame_weight;
   F->L.A.slab = reinterpret_cast<float*>(slab);
   F->stream = c->stream; F->slab = slab;
-  F->tex0 = c->d_tex[0].get(); F->tex1 = c->d_tex[1].get(); F->canvas = c->d_canvas.get();
+  F->tex0 = c->frame.tex[0].get(); F->tex1 = c->frame.tex[1].get(); F->canvas = c->frame.canvas.get();
   F->n_frames = n_frames;
   return PT_OK;
 }
@@ -1358,13 +1329,13 @@ int enqueue_frame(pt_ctx* c, FramePlan& F, bool advance) {
   const uint32_t n_pix = (uint32_t)n_pixels(c);
   if (F.n_frames > 1u) {  // a group: its blends as one pass over the pixels
     hipLaunchKernelGGL(pt_frames_blend_kernel, dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream, F.slab, F.n_frames,
-                       c->d_tex[0].get(), c->d_tex[1].get(), c->d_canvas.get(), n_pix, F.ctr, F.render_count0, F.even_odd0, F.max_render_count,
+                       c->frame.tex[0].get(), c->frame.tex[1].get(), c->frame.canvas.get(), n_pix, F.ctr, F.render_count0, F.even_odd0, F.max_render_count,
                        F.should_average, F.last_frame_weight);
     PT_HIP(c, hipGetLastError());
   }
   for (uint32_t f = 0; f < (F.n_frames > 1u ? 0u : 1u); f++) {
     hipLaunchKernelGGL(pt_frame_blend_kernel, dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream, F.slab + (size_t)f * n_pix,
-                       c->d_tex[0].get(), c->d_tex[1].get(), c->d_canvas.get(), n_pix, F.ctr, f, F.render_count0, F.even_odd0, F.max_render_count,
+                       c->frame.tex[0].get(), c->frame.tex[1].get(), c->frame.canvas.get(), n_pix, F.ctr, f, F.render_count0, F.even_odd0, F.max_render_count,
                        F.should_average, F.last_frame_weight);
     PT_HIP(c, hipGetLastError());
   }
@@ -1394,7 +1365,7 @@ int enqueue_frame(pt_ctx* c, FramePlan& F, bool advance) {
 int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
   const TileOrder::FrameStep step = c->order.frames(c->params.samples_per_pixel, c->params, c->scene_gen, n_frames, [c] { return is_capturing(c); });
   if (step.zero_costs)  // back to the identity order: what the order kernel writes when every cost is zero
-    PT_HIP(c, hipMemsetAsync(c->d_tile_cost.get(), 0, c->d_tile_cost.capacity() * sizeof(uint32_t), c->stream));
+    PT_HIP(c, hipMemsetAsync(c->frame.tile_cost.get(), 0, c->frame.tile_cost.capacity() * sizeof(uint32_t), c->stream));
   if (step.order_kernel) {
     int rc = launch_tile_order(c);
     if (rc != PT_OK) return rc;
@@ -1406,7 +1377,7 @@ int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
   use.feedback = LaunchUse::ON;
   int rc = prepare_launch(c, 1, use, &L);
   if (rc != PT_OK) return rc;
-  L.A.slab = reinterpret_cast<float*>(c->d_slab.get());  // scratch: a frame's own slab is written before it is read
+  L.A.slab = reinterpret_cast<float*>(c->frame.slab.get());  // scratch: a frame's own slab is written before it is read
   unsigned long long* seg = c->d_counters.get() + PT_CTR_SEGMENTS;
   PT_HIP(c, hipMemcpyAsync(c->d_counters.get() + PT_CTR_SCRATCH, seg, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
   PT_HIP(c, zero_queue_heads(c, L.A.queue_static));
@@ -1424,18 +1395,19 @@ int frame_ready(pt_ctx* c, const char* who) {
   if (!c->have_spheres || !c->have_params)
     return fail(c, PT_ERR_NOT_READY, "%s: pt_set_spheres and pt_set_params must come first", who);
   if (c->count_work) return fail(c, PT_ERR_INVALID, "%s: not with PT_OPT_COUNT_WORK (the measuring twins are not frame kernels)", who);
-  return PT_OK;
+  return frame_buffers_ready(c, who);
 }
 
 } // namespace
 
 PT_API int pt_clear_textures(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
+  if (int rc = frame_buffers_ready(c, "pt_clear_textures"); rc != PT_OK) return rc;
   PT_HIP(c, hipSetDevice(c->device));
   const size_t bytes = n_pixels(c) * sizeof(uint32_t);
   if (bytes == 0) return PT_OK;
-  for (int k = 0; k < 2; k++) PT_HIP(c, hipMemsetAsync(c->d_tex[k].get(), 0, bytes, c->stream));
-  PT_HIP(c, hipMemsetAsync(c->d_canvas.get(), 0, bytes, c->stream));
+  for (int k = 0; k < 2; k++) PT_HIP(c, hipMemsetAsync(c->frame.tex[k].get(), 0, bytes, c->stream));
+  PT_HIP(c, hipMemsetAsync(c->frame.canvas.get(), 0, bytes, c->stream));
   return PT_OK;
 }
 
@@ -1445,7 +1417,7 @@ PT_API int pt_render_frame(pt_ctx* c, uint32_t even_odd_count) {
   if (c->local_rows == 0) return PT_OK;
   PT_HIP(c, hipSetDevice(c->device));
   FramePlan F;
-  rc = plan_frame(c, c->d_frame_ctr.get() + 1, even_odd_count, 0x7fffffff, 1, c->d_slab.get(), &F);  // frame 0 of a series of one
+  rc = plan_frame(c, c->d_frame_ctr.get() + 1, even_odd_count, 0x7fffffff, 1, c->frame.slab.get(), &F);  // frame 0 of a series of one
   if (rc != PT_OK) return rc;
   rc = ensure_cost_order(c, 1);
   if (rc != PT_OK) return rc;
@@ -1507,7 +1479,7 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
     hipGraphExec_t* exec = &c->frame_exec[g];
     FramePlan* plan_store = &c->frame_plan[g];
     FramePlan F;
-    int r = plan_frame(c, c->d_frame_ctr.get(), even_odd_count, (int)max_render_count, frames, frames > 1u ? c->d_frame_slab.get() : c->d_slab.get(), &F);
+    int r = plan_frame(c, c->d_frame_ctr.get(), even_odd_count, (int)max_render_count, frames, frames > 1u ? c->d_frame_slab.get() : c->frame.slab.get(), &F);
     if (r != PT_OK) return r;
     if (*exec && memcmp(&F, plan_store, sizeof F) == 0) return PT_OK;  // (bytewise, padding included: plan_frame zeroed it)
     if (*exec) { (void)hipGraphExecDestroy(*exec); *exec = nullptr; }
@@ -1542,23 +1514,25 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
 
 static int read_rgba8(pt_ctx* c, const uint32_t* src, uint8_t* out, const char* who) {
   if (!c || !out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
+  if (int rc = frame_buffers_ready(c, who); rc != PT_OK) return rc;
   PT_HIP(c, hipSetDevice(c->device));
   const size_t bytes = n_pixels(c) * 4;
   if (bytes) PT_HIP(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
-PT_API int pt_read_canvas(pt_ctx* c, uint8_t* rgba_out) { return read_rgba8(c, c ? c->d_canvas.get() : nullptr, rgba_out, "pt_read_canvas"); }
+PT_API int pt_read_canvas(pt_ctx* c, uint8_t* rgba_out) { return read_rgba8(c, c ? c->frame.canvas.get() : nullptr, rgba_out, "pt_read_canvas"); }
 PT_API int pt_read_texture(pt_ctx* c, int index, uint8_t* rgba_out) {
   if (c && (index < 0 || index > 1)) return fail(c, PT_ERR_INVALID, "pt_read_texture: index %d", index);
-  return read_rgba8(c, c ? c->d_tex[index].get() : nullptr, rgba_out, "pt_read_texture");
+  return read_rgba8(c, c ? c->frame.tex[index].get() : nullptr, rgba_out, "pt_read_texture");
 }
 PT_API int pt_write_texture(pt_ctx* c, int index, const uint8_t* rgba_in) {
   if (!c || !rgba_in) return fail(c, PT_ERR_INVALID, "pt_write_texture: NULL argument");
   if (index < 0 || index > 1) return fail(c, PT_ERR_INVALID, "pt_write_texture: index %d", index);
+  if (int rc = frame_buffers_ready(c, "pt_write_texture"); rc != PT_OK) return rc;
   PT_HIP(c, hipSetDevice(c->device));
   const size_t bytes = n_pixels(c) * 4;
-  if (bytes) PT_HIP(c, hipMemcpyAsync(c->d_tex[index].get(), rgba_in, bytes, hipMemcpyDefault, c->stream));
+  if (bytes) PT_HIP(c, hipMemcpyAsync(c->frame.tex[index].get(), rgba_in, bytes, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
@@ -1678,6 +1652,7 @@ PT_API int pt_synchronize(pt_ctx* c) {
 static int resolve_common(pt_ctx* c, void* out, int gamma, int mode, const uint8_t* prev) {
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_resolve: NULL argument");
   if (c->total_spp == 0 && !c->captured) return fail(c, PT_ERR_NOT_READY, "pt_resolve: nothing rendered yet");
+  if (int rc = frame_buffers_ready(c, "pt_resolve"); rc != PT_OK) return rc;
   PT_HIP(c, hipSetDevice(c->device));
   uint32_t n_pix = (uint32_t)n_pixels(c);
   if (n_pix == 0) return PT_OK;
@@ -1685,25 +1660,25 @@ static int resolve_common(pt_ctx* c, void* out, int gamma, int mode, const uint8
   uint32_t grid = pixel_grid(n_pix);
   size_t bytes;
   if (mode == 0) {
-    hipLaunchKernelGGL(pt_resolve_kernel, dim3(grid), dim3(256), 0, c->stream, c->accum, c->d_resolve.get(),
+    hipLaunchKernelGGL(pt_resolve_kernel, dim3(grid), dim3(256), 0, c->stream, c->frame.accum, c->frame.resolve.get(),
                        n_pix, gamma);
     bytes = (size_t)n_pix * sizeof(float4);
   } else if (mode == 1) {
-    hipLaunchKernelGGL(pt_resolve_rgba8_kernel, dim3(grid), dim3(256), 0, c->stream, c->accum,
-                       reinterpret_cast<uint32_t*>(c->d_resolve.get()), n_pix, gamma);
+    hipLaunchKernelGGL(pt_resolve_rgba8_kernel, dim3(grid), dim3(256), 0, c->stream, c->frame.accum,
+                       reinterpret_cast<uint32_t*>(c->frame.resolve.get()), n_pix, gamma);
     bytes = (size_t)n_pix * 4;
   } else {
     // stage prev into the upper half of the resolve buffer (16 B/pixel holds 4 B in + 4 B out)
-    uint32_t* d_out = reinterpret_cast<uint32_t*>(c->d_resolve.get());
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(c->frame.resolve.get());
     uint32_t* d_prev = d_out + n_pix;
     PT_HIP(c, hipMemcpyAsync(d_prev, prev, (size_t)n_pix * 4, hipMemcpyDefault, c->stream));
-    hipLaunchKernelGGL(pt_blend_rgba8_kernel, dim3(grid), dim3(256), 0, c->stream, c->accum, d_prev, d_out,
+    hipLaunchKernelGGL(pt_blend_rgba8_kernel, dim3(grid), dim3(256), 0, c->stream, c->frame.accum, d_prev, d_out,
                        n_pix, c->params.render_count, c->params.should_average,
                        c->params.last_frame_weight);
     bytes = (size_t)n_pix * 4;
   }
   PT_HIP(c, hipGetLastError());
-  PT_HIP(c, hipMemcpyAsync(out, c->d_resolve.get(), bytes, hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipMemcpyAsync(out, c->frame.resolve.get(), bytes, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
@@ -1718,23 +1693,24 @@ PT_API int pt_blend_rgba8(pt_ctx* c, const uint8_t* prev, uint8_t* out) {
 // ---- the error estimate's read-out (include/ptrace.h; kernels: pt_kernels_error.hip) ------------------------------------
 PT_API int pt_error_ptr(pt_ctx* c, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr) return fail(c, PT_ERR_INVALID, "pt_error_ptr: NULL argument");
-  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_ptr: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
-  *dev_ptr = c->d_err.get();
+  if (!c->est.on) return option_off(c, "pt_error_ptr", SET_ESTIMATE);
+  *dev_ptr = c->est.state.get();
   if (bytes) *bytes = n_pixels(c) * 2 * sizeof(float4);
   return PT_OK;
 }
 
 PT_API int pt_resolve_error(pt_ctx* c, float* rgba_out) {
   if (!c || !rgba_out) return fail(c, PT_ERR_INVALID, "pt_resolve_error: NULL argument");
-  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_resolve_error: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+  if (!c->est.on) return option_off(c, "pt_resolve_error", SET_ESTIMATE);
+  PT_TRY(frame_buffers_ready(c, "pt_resolve_error"));
   PT_HIP(c, hipSetDevice(c->device));
   uint32_t n_pix = (uint32_t)n_pixels(c);
   if (n_pix == 0) return PT_OK;
-  const float4* est = c->d_err.get();
-  float4* out = c->d_resolve.get();
+  const float4* est = c->est.state.get();
+  float4* out = c->frame.resolve.get();
   void* kargs[] = {&est, &out, &n_pix};
   PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_RESOLVE), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
-  PT_HIP(c, hipMemcpyAsync(rgba_out, c->d_resolve.get(), (size_t)n_pix * sizeof(float4), hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipMemcpyAsync(rgba_out, c->frame.resolve.get(), (size_t)n_pix * sizeof(float4), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
@@ -1746,12 +1722,13 @@ static int resolve_filtered(pt_ctx* c, const char* who, float* rgba_out, uint32_
   if (radius > PT_FILTER_MAX_RADIUS) return fail(c, PT_ERR_INVALID, "%s: radius %u > PT_FILTER_MAX_RADIUS", who, radius);
   if (patch && *patch > PT_FILTER_MAX_PATCH) return fail(c, PT_ERR_INVALID, "%s: patch %u > PT_FILTER_MAX_PATCH", who, *patch);
   if (!std::isfinite(kappa) || kappa < 0.0f) return fail(c, PT_ERR_INVALID, "%s: kappa must be finite and >= 0", who);
-  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "%s: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", who);
+  if (!c->est.on) return option_off(c, who, SET_ESTIMATE);
+  PT_TRY(frame_buffers_ready(c, who));
   PT_HIP(c, hipSetDevice(c->device));
   uint32_t n_pix = (uint32_t)n_pixels(c);
   if (n_pix == 0) return PT_OK;
-  const float4* est = c->d_err.get();
-  float4* out = c->d_resolve.get();
+  const float4* est = c->est.state.get();
+  float4* out = c->frame.resolve.get();
   uint32_t width = c->width, rows = c->local_rows;
   uint32_t band_rows = c->params.band_count > 1 ? c->params.band_rows : 0u;  // (0: no band, every local row is a neighbour)
   const dim3 grid((width + 31u) / 32u, (rows + 7u) / 8u);
@@ -1763,7 +1740,7 @@ static int resolve_filtered(pt_ctx* c, const char* who, float* rgba_out, uint32_
     void* kargs[] = {&est, &out, &width, &rows, &band_rows, &radius, &kappa, &gamma};
     PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FILTER), grid, dim3(256), kargs, 0, c->stream));
   }
-  PT_HIP(c, hipMemcpyAsync(rgba_out, c->d_resolve.get(), (size_t)n_pix * sizeof(float4), hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipMemcpyAsync(rgba_out, c->frame.resolve.get(), (size_t)n_pix * sizeof(float4), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
@@ -1776,12 +1753,12 @@ PT_API int pt_resolve_filtered_patch(pt_ctx* c, float* rgba_out, uint32_t radius
   return resolve_filtered(c, "pt_resolve_filtered_patch", rgba_out, radius, &patch, kappa, gamma);
 }
 
-// the tile kernel over the current state: records into d_err_tiles[0, n), tallies into [n, 2 n); enqueued, not awaited
+// the tile kernel over the current state: records into est.tiles[0, n), tallies into [n, 2 n); enqueued, not awaited
 static int launch_error_tiles(pt_ctx* c) {
   uint32_t tiles_n = n_tiles(c);
   if (tiles_n == 0) return PT_OK;
-  const float4* est = c->d_err.get();
-  float4* tiles = c->d_err_tiles.get();
+  const float4* est = c->est.state.get();
+  float4* tiles = c->est.tiles.get();
   float4* aux = tiles + tiles_n;
   uint32_t width = c->width, rows = c->local_rows, tx = tiles_x(c);
   void* kargs[] = {&est, &tiles, &aux, &width, &rows, &tx, &tiles_n};
@@ -1791,13 +1768,14 @@ static int launch_error_tiles(pt_ctx* c) {
 
 PT_API int pt_error_tiles(pt_ctx* c, float* tiles_out, uint32_t* tx_out, uint32_t* ty_out) {
   if (!c) return PT_ERR_INVALID;
-  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_tiles: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+  if (!c->est.on) return option_off(c, "pt_error_tiles", SET_ESTIMATE);
+  PT_TRY(frame_buffers_ready(c, "pt_error_tiles"));
   if (tx_out) *tx_out = tiles_x(c);
   if (ty_out) *ty_out = tiles_y(c);
   if (!tiles_out || n_tiles(c) == 0) return PT_OK;
   PT_HIP(c, hipSetDevice(c->device));
   if (int rc = launch_error_tiles(c); rc != PT_OK) return rc;
-  PT_HIP(c, hipMemcpyAsync(tiles_out, c->d_err_tiles.get(), (size_t)tiles_x(c) * tiles_y(c) * sizeof(float4), hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipMemcpyAsync(tiles_out, c->est.tiles.get(), (size_t)tiles_x(c) * tiles_y(c) * sizeof(float4), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
@@ -1807,7 +1785,8 @@ PT_API int pt_error_tiles(pt_ctx* c, float* tiles_out, uint32_t* tx_out, uint32_
 static int error_stats(pt_ctx* c, PtErrorStats* out, std::vector<float>& h) {
   h.clear();
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_error_stats: NULL argument");
-  if (!c->err_on) return fail(c, PT_ERR_NOT_READY, "pt_error_stats: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)");
+  if (!c->est.on) return option_off(c, "pt_error_stats", SET_ESTIMATE);
+  PT_TRY(frame_buffers_ready(c, "pt_error_stats"));
   memset(out, 0, sizeof *out);
   out->pixels = (uint64_t)n_pixels(c);
   PT_HIP(c, hipSetDevice(c->device));
@@ -1815,7 +1794,7 @@ static int error_stats(pt_ctx* c, PtErrorStats* out, std::vector<float>& h) {
   const size_t tiles = (size_t)tiles_x(c) * tiles_y(c);
   if (tiles == 0) return PT_OK;
   h.resize(8 * tiles);
-  PT_HIP(c, hipMemcpyAsync(h.data(), c->d_err_tiles.get(), 2 * tiles * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipMemcpyAsync(h.data(), c->est.tiles.get(), 2 * tiles * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   pterr::sum_tiles(h.data(), tiles, out->pixels, out);
   return PT_OK;
@@ -1832,7 +1811,7 @@ namespace {
 // what both entry points ask of their arguments (`who`: the entry point; `per`: what it calls the passes of one launch)
 int noise_target_args(pt_ctx* c, const char* who, const char* per, float target, uint32_t passes_per, uint32_t max_passes, const PtErrorStats* out) {
   if (!c || !out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
-  if (!c->err_on) return fail(c, PT_ERR_INVALID, "%s: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", who);
+  if (!c->est.on) return option_off(c, who, SET_ESTIMATE, PT_ERR_INVALID);
   if (!(target > 0.0f) || !std::isfinite(target)) return fail(c, PT_ERR_INVALID, "%s: the target must be finite and positive", who);
   if (passes_per == 0 || max_passes == 0) return fail(c, PT_ERR_INVALID, "%s: no passes to render", who);
   if (passes_per > c->reserved_passes)
@@ -1895,7 +1874,7 @@ int partial_round(pt_ctx* c, uint32_t k, uint32_t tiles, uint32_t n_active, uint
   }
   PT_HIP(c, hipMemcpyAsync(flags, c->h_adapt_flags.data(), (size_t)tiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   {
-    const uint32_t* order = c->d_tile_order.get();
+    const uint32_t* order = c->frame.tile_order.get();
     const uint32_t* fl = flags;
     uint32_t n = tiles;
     void* kargs[] = {&order, &fl, &part, &base, &n};
@@ -1905,18 +1884,19 @@ int partial_round(pt_ctx* c, uint32_t k, uint32_t tiles, uint32_t n_active, uint
   use.feedback = LaunchUse::OFF;  // a partial launch keeps the order it finds, as a frame does
   use.n_first_tiles = n_active;
   use.table = part;
+  use.who = "pt_render_adaptive";
   TimedSpan span;
   if (int rc = trace_once(c, k, use, &span); rc != PT_OK) return rc;
   {
-    float4* accum = c->accum;
-    float4* est = c->d_err.get();
-    const float4* slab = c->d_slab.get();
+    float4* accum = c->frame.accum;
+    float4* est = c->est.state.get();
+    const float4* slab = c->frame.slab.get();
     const uint32_t* order = part;
     uint32_t na = n_active, width = c->width, rows = c->local_rows, tx = tiles_x(c), passes = k;
     void* kargs[] = {&accum, &est, &slab, &order, &na, &width, &rows, &tx, &passes};
     PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD_TILES), dim3(tile_grid(n_active)), dim3(256), kargs, 0, c->stream));
   }
-  c->err_spp = p.samples_per_pixel;
+  c->est.spp = p.samples_per_pixel;
   c->adapt_valid = true;
   c->adapt_tiles = tiles;
   c->adapt_active = n_active;
@@ -1933,9 +1913,9 @@ PT_API int pt_render_adaptive(pt_ctx* c, float target_rel_error, uint32_t passes
   if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: not with PT_OPT_COUNT_WORK (the measuring twins log whole launches)");
   if (int rc = not_capturing(c, "pt_render_adaptive"); rc != PT_OK) return rc;
   // (refused before the first look: a call must not answer for an estimate it could not continue)
-  if (c->have_params && c->err_spp != 0 && c->err_spp != c->params.samples_per_pixel)
+  if (c->have_params && c->est.spp != 0 && c->est.spp != c->params.samples_per_pixel)
     return fail(c, PT_ERR_INVALID, "pt_render_adaptive: %d samples per pixel while the error estimate holds passes of %d: clear first "
-                                   "(pt_reset_accum)", c->params.samples_per_pixel, c->err_spp);
+                                   "(pt_reset_accum)", c->params.samples_per_pixel, c->est.spp);
   const uint32_t tiles = n_tiles(c);
   PtAdaptiveStats ad;
   memset(&ad, 0, sizeof ad);
@@ -2008,9 +1988,9 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
   out->render_kernel_ms = c->kernel_ms;
   out->render_launches = c->launches;
   out->total_spp = c->total_spp;
-  if (c->accum && c->local_rows) { // what the device has really accumulated (graph replays included)
+  if (c->frame.accum && c->local_rows) { // what the device has really accumulated (graph replays included)
     float4 px0;
-    PT_HIP(c, hipMemcpy(&px0, c->accum, sizeof px0, hipMemcpyDeviceToHost));
+    PT_HIP(c, hipMemcpy(&px0, c->frame.accum, sizeof px0, hipMemcpyDeviceToHost));
     if (px0.w >= 0.0f && px0.w < 4294967040.0f) out->total_spp = (uint32_t)px0.w;
   }
   out->n_spheres = c->list.n;
@@ -2039,12 +2019,25 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
   return PT_OK;
 }
 
-// PT_OPT_REPROJECT off: the history planes, the tallies and the history itself go (the caller has drained the stream)
-static void release_reproject(pt_ctx* c) {
-  c->reproj_on = c->hist_valid = c->reproj_ran = false;
-  c->d_hist = DevBuf<float4>();
-  c->d_err_stage = DevBuf<float4>();
-  c->d_reproj_tally = DevBuf<unsigned long long>();
+// An option that owns a set of buffers (`name`: the option's words in pt_set_option's messages).  The image does not depend on
+// any of them; the set is allocated here and released when the option is turned off.  Drains the stream first: work in flight
+// may use the set.  `off` releases the set and what hangs on it; `kernel` is one of the option's code object — asking for its
+// attributes loads that object now: a set-up call's work, not a render call's —; `extra` is what the option needs beyond its
+// buffers once they are in place.  Whatever fails, the option stays off with everything released.
+template <class Set, class Off, class Extra>
+static int set_buffer_option(pt_ctx* c, int value, const char* name, Set& set, Off off, const void* kernel, Extra extra) {
+  if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: %s %d", name, value);
+  PT_HIP(c, hipSetDevice(c->device));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  if (!value) { off(); return PT_OK; }
+  if (set.on) return PT_OK;
+  hipFuncAttributes attr;
+  PT_HIP(c, hipFuncGetAttributes(&attr, kernel));
+  set.on = true;
+  int rc = ensure_buffers(c);
+  if (rc == PT_OK) rc = extra();
+  if (rc != PT_OK) off();
+  return rc;
 }
 
 PT_API int pt_set_option(pt_ctx* c, int key, int value) {
@@ -2083,86 +2076,19 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     c->grid_fit_mode = value;
     return PT_OK;
   }
-  if (key == PT_OPT_ERROR_ESTIMATE) { // the image does not depend on it; the state is allocated and zeroed here, released when turned off
-    if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: error estimate %d", value);
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipStreamSynchronize(c->stream));  // (a fold in flight reads the state)
-    if (!value) {
-      c->err_on = false;
-      c->err_spp = 0;
-      c->d_err = DevBuf<float4>();
-      c->d_err_tiles = DevBuf<float4>();
-      c->d_err_stage = DevBuf<float4>();
-      return PT_OK;
-    }
-    if (c->err_on) return PT_OK;
-    // (asking for a kernel's attributes loads the estimate's code object now: a set-up call's work, not a captured launch's)
-    hipFuncAttributes attr;
-    PT_HIP(c, hipFuncGetAttributes(&attr, pt_error_kernel(PT_E_FOLD)));
-    c->err_on = true;
-    int rc = ensure_buffers(c);
-    if (rc == PT_OK) rc = clear_error(c);
-    if (rc != PT_OK) { c->err_on = false; c->d_err = DevBuf<float4>(); c->d_err_tiles = DevBuf<float4>(); c->d_err_stage = DevBuf<float4>(); }
-    return rc;
-  }
-  if (key == PT_OPT_FEATURES) { // the image does not depend on it; the planes are allocated here, released when turned off
-    if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: feature planes %d", value);
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipStreamSynchronize(c->stream));  // (a feature launch in flight writes the planes)
-    if (!value) {
-      c->feat_on = c->feat_valid = false;
-      c->d_feat = DevBuf<float4>();
-      release_reproject(c);  // (it reads the planes: off with them)
-      return PT_OK;
-    }
-    if (c->feat_on) return PT_OK;
-    // (asking for a kernel's attributes loads the feature builds' code object now: a set-up call's work, not a render call's)
-    hipFuncAttributes attr;
-    PT_HIP(c, hipFuncGetAttributes(&attr, pt_feature_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar))));
-    c->feat_on = true;
-    int rc = ensure_buffers(c);
-    if (rc == PT_OK && !c->uuid_valid && c->have_spheres) rc = upload_uuids(c, c->list.host.uuid);  // the scene in place
-    if (rc != PT_OK) { c->feat_on = false; c->d_feat = DevBuf<float4>(); }
-    return rc;
-  }
-  if (key == PT_OPT_RAY_QUERIES) { // the image does not depend on it; the query planes are allocated here, released when turned off
-    if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: ray queries %d", value);
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipStreamSynchronize(c->stream));
-    if (!value) {
-      c->query_on = false;
-      c->d_query = DevBuf<float4>();
-      c->d_query_order = DevBuf<uint32_t>();
-      return PT_OK;
-    }
-    if (c->query_on) return PT_OK;
-    // (asking for a kernel's attributes loads the query builds' code object now: a set-up call's work, not a query's)
-    hipFuncAttributes attr;
-    PT_HIP(c, hipFuncGetAttributes(&attr, pt_query_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar))));
-    c->query_on = true;
-    int rc = ensure_buffers(c);
-    if (rc == PT_OK && !c->uuid_valid && c->have_spheres) rc = upload_uuids(c, c->list.host.uuid);  // the scene in place
-    if (rc != PT_OK) { c->query_on = false; c->d_query = DevBuf<float4>(); c->d_query_order = DevBuf<uint32_t>(); }
-    return rc;
-  }
-  if (key == PT_OPT_REPROJECT) { // the image does not depend on it; the history planes are allocated here, released when turned off
-    if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: reprojection %d", value);
-    if (value && !c->feat_on) return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_REPROJECT needs PT_OPT_FEATURES on (it reads the feature planes)");
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipStreamSynchronize(c->stream));  // (a copy or a gather in flight uses the history planes)
-    if (!value) { release_reproject(c); return PT_OK; }
-    if (c->reproj_on) return PT_OK;
-    // (asking for the kernel's attributes loads its code object now: a set-up call's work, not pt_reproject's)
-    hipFuncAttributes attr;
-    PT_HIP(c, hipFuncGetAttributes(&attr, pt_reproject_kernel_handle()));
-    c->reproj_on = true;
-    int rc = ensure_buffers(c);
-    if (rc == PT_OK && c->d_reproj_tally.capacity() < 3) {
-      hipError_t e = c->d_reproj_tally.reserve(3);
-      if (e != hipSuccess) rc = fail(c, PT_ERR_HIP, "pt_set_option: the reprojection tallies: %s", hipGetErrorString(e));
-    }
-    if (rc != PT_OK) release_reproject(c);
-    return rc;
+  // (reprojection reads the feature planes and stages the estimate's state: off with the former, and the stage with it)
+  auto reproject_off = [c] { c->hist.release(); c->est.stage.release(); };
+  auto uuids = [c] { return !c->uuid_valid && c->have_spheres ? upload_uuids(c, c->list.host.uuid) : PT_OK; };  // the scene in place
+  if (key == PT_OPT_ERROR_ESTIMATE)
+    return set_buffer_option(c, value, "error estimate", c->est, [c] { c->est.release(); }, pt_error_kernel(PT_E_FOLD), [c] { return clear_error(c); });
+  if (key == PT_OPT_FEATURES)
+    return set_buffer_option(c, value, "feature planes", c->feat, [&] { c->feat.release(); reproject_off(); },
+                             pt_feature_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar)), uuids);
+  if (key == PT_OPT_RAY_QUERIES)
+    return set_buffer_option(c, value, "ray queries", c->query, [c] { c->query.release(); }, pt_query_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar)), uuids);
+  if (key == PT_OPT_REPROJECT) {
+    if (value == 1 && !c->feat.on) return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_REPROJECT needs PT_OPT_FEATURES on (it reads the feature planes)");
+    return set_buffer_option(c, value, "reprojection", c->hist, reproject_off, pt_reproject_kernel_handle(), [] { return PT_OK; });
   }
   return fail(c, PT_ERR_INVALID, "pt_set_option: unknown key %d", key);
 }
@@ -2198,13 +2124,7 @@ PT_API int pt_last_trace_build(pt_ctx* c) {
 }
 
 // ---- first-hit feature planes (PT_OPT_FEATURES; include/ptrace.h has the record) ---------------------------------------------
-// are the planes allocated for the local rows in place?  (They are unless an allocation failed: ensure_buffers sizes them wherever
-// the rows change.)
-static bool feature_planes_in_place(const pt_ctx* c) {
-  const size_t pix = n_pixels(c) ? n_pixels(c) : 1;
-  return c->feat_on && c->d_feat.get() && c->d_feat.capacity() == PT_FEAT_PLANES * pix;
-}
-
+// (the planes are in place for the local rows unless an allocation failed: ensure_buffers sizes them wherever the rows change)
 // ONE launch of the feature build of whichever kernel the context renders with, into the planes.  Nothing else of the context
 // moves: no fold, no timing events, no tile costs, no order kernel, no trial of PT_GEOM_AUTO (prepare_launch, DOOR_FEATURES);
 // the kernel adds its segments to the device counter like every trace launch.
@@ -2213,24 +2133,25 @@ PT_API int pt_render_features(pt_ctx* c) {
   if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_render_features: not with PT_OPT_COUNT_WORK (the measuring twins have no feature build)");
   if (!c->have_spheres || !c->have_params)
     return fail(c, PT_ERR_NOT_READY, "pt_render_features: pt_set_spheres and pt_set_params must come first");
-  if (!c->feat_on) return fail(c, PT_ERR_NOT_READY, "pt_render_features: the feature planes are off (pt_set_option PT_OPT_FEATURES)");
+  if (!c->feat.on) return option_off(c, "pt_render_features", SET_FEATURES);
   PT_HIP(c, hipSetDevice(c->device));
   if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_render_features: not inside a stream capture");
-  if (!feature_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "pt_render_features: the planes are not allocated for the rows in place (an earlier allocation failed)");
-  if (c->local_rows == 0) { c->feat_valid = true; return PT_OK; }  // this band owns no rows: nothing to do, and its (empty) planes speak
+  if (!c->feat.in_place(extent_of(c))) return fail(c, PT_ERR_CAPACITY, "pt_render_features: the planes are not allocated for the rows in place (an earlier allocation failed)");
+  if (c->local_rows == 0) { c->feat.valid = true; return PT_OK; }  // this band owns no rows: nothing to do, and its (empty) planes speak
   LaunchUse use;
   use.door = DOOR_FEATURES;
+  use.who = "pt_render_features";
   if (int rc = trace_once(c, 1, use); rc != PT_OK) return rc;
-  c->feat_valid = true;
+  c->feat.valid = true;
   return PT_OK;
 }
 
 PT_API int pt_features_ptr(pt_ctx* c, int plane, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr) return fail(c, PT_ERR_INVALID, "pt_features_ptr: NULL argument");
   if (plane < 0 || plane >= PT_FEAT_PLANES) return fail(c, PT_ERR_INVALID, "pt_features_ptr: plane %d out of range", plane);
-  if (!c->feat_on) return fail(c, PT_ERR_NOT_READY, "pt_features_ptr: the feature planes are off (pt_set_option PT_OPT_FEATURES)");
-  if (!feature_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "pt_features_ptr: the planes are not allocated for the rows in place (an earlier allocation failed)");
-  *dev_ptr = c->d_feat.get() + (size_t)plane * n_pixels(c);
+  if (!c->feat.on) return option_off(c, "pt_features_ptr", SET_FEATURES);
+  if (!c->feat.in_place(extent_of(c))) return fail(c, PT_ERR_CAPACITY, "pt_features_ptr: the planes are not allocated for the rows in place (an earlier allocation failed)");
+  *dev_ptr = c->feat.planes.get() + (size_t)plane * n_pixels(c);
   if (bytes) *bytes = n_pixels(c) * sizeof(float4);
   return PT_OK;
 }
@@ -2239,25 +2160,18 @@ PT_API int pt_read_features(pt_ctx* c, int plane, void* out) {
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_read_features: NULL argument");
   if (plane < 0 || plane >= PT_FEAT_PLANES) return fail(c, PT_ERR_INVALID, "pt_read_features: plane %d out of range", plane);
   if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_read_features: not with PT_OPT_COUNT_WORK");
-  if (!c->feat_on) return fail(c, PT_ERR_NOT_READY, "pt_read_features: the feature planes are off (pt_set_option PT_OPT_FEATURES)");
-  if (!c->feat_valid)
+  if (!c->feat.on) return option_off(c, "pt_read_features", SET_FEATURES);
+  if (!c->feat.valid)
     return fail(c, PT_ERR_NOT_READY, "pt_read_features: no pt_render_features since the scene, the uniforms or the size last changed");
   PT_HIP(c, hipSetDevice(c->device));
   if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_read_features: not inside a stream capture (a read-out synchronises)");
   const size_t need = n_pixels(c) * sizeof(float4);
-  if (need) PT_HIP(c, hipMemcpyAsync(out, c->d_feat.get() + (size_t)plane * n_pixels(c), need, hipMemcpyDefault, c->stream));
+  if (need) PT_HIP(c, hipMemcpyAsync(out, c->feat.planes.get() + (size_t)plane * n_pixels(c), need, hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
 }
 
 // ---- ray queries (PT_OPT_RAY_QUERIES; include/ptrace.h has the contract) --------------------------------------
-// are the query planes and their tile order allocated for the local rows in place?  (As with the feature planes.)
-static bool query_planes_in_place(const pt_ctx* c) {
-  const size_t pix = n_pixels(c) ? n_pixels(c) : 1, tiles = n_tiles(c) ? n_tiles(c) : 1;
-  return c->query_on && c->d_query.get() && c->d_query.capacity() == PT_FEAT_PLANES * pix && c->d_query_order.get() &&
-         c->d_query_order.capacity() == tiles;
-}
-
 // can the device read (and write) this pointer of the caller's?  A pointer the runtime does not know is the host's.
 static bool device_pointer(const void* p) {
   hipPointerAttribute_t attr;
@@ -2269,7 +2183,7 @@ static bool device_pointer(const void* p) {
 }
 
 PT_API uint32_t pt_query_batch(pt_ctx* c) {
-  if (!c || !c->query_on || !c->have_spheres || !c->have_params || c->local_rows == 0 || !query_planes_in_place(c)) return 0u;
+  if (!c || !c->query.on || !c->have_spheres || !c->have_params || c->local_rows == 0 || !c->query.in_place(extent_of(c))) return 0u;
   return (uint32_t)n_pixels(c);
 }
 
@@ -2278,19 +2192,19 @@ PT_API uint32_t pt_query_batch(pt_ctx* c) {
 static int query_ready(pt_ctx* c, const char* who, const char* build, const void* rays, const void* out) {
   if (!rays || !out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
   if (c->count_work) return fail(c, PT_ERR_INVALID, "%s: not with PT_OPT_COUNT_WORK (the measuring twins have no %s build)", who, build);
-  if (!c->query_on) return fail(c, PT_ERR_NOT_READY, "%s: ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)", who);
+  if (!c->query.on) return option_off(c, who, SET_QUERIES);
   if (!c->have_spheres || !c->have_params) return fail(c, PT_ERR_NOT_READY, "%s: pt_set_spheres and pt_set_params must come first", who);
   PT_HIP(c, hipSetDevice(c->device));
   if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "%s: synchronises; not inside a stream capture", who);
   if (c->local_rows == 0) return fail(c, PT_ERR_NOT_READY, "%s: this band owns no rows, so it has no work items to decode rays against", who);
-  if (!query_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "%s: the planes are not allocated for the rows in place (an earlier allocation failed)", who);
-  return PT_OK;
+  if (!c->query.in_place(extent_of(c))) return fail(c, PT_ERR_CAPACITY, "%s: the planes are not allocated for the rows in place (an earlier allocation failed)", who);
+  return frame_buffers_ready(c, who);  // (before the first ray is staged, not only at the launch)
 }
 
 // One batch of m rays into the point and normal planes of the query planes: a device array through the pack kernel, a host array
 // packed into h_in (the caller's, so that nothing is allocated per batch) and copied plane by plane.
 static int stage_rays(pt_ctx* c, const PtRay* rays, bool on_device, uint32_t m, std::vector<ptq::F4>& h_in) {
-  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->d_query.get());
+  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->query.planes.get());
   uint32_t plane = (uint32_t)n_pixels(c);
   if (on_device) {
     void* kargs[] = {&rays, &m, &planes, &plane};
@@ -2308,9 +2222,10 @@ static int stage_rays(pt_ctx* c, const PtRay* rays, bool on_device, uint32_t m, 
 static LaunchUse batch_use(const pt_ctx* c, Door door, uint32_t m) {
   LaunchUse use;
   use.door = door;
+  use.who = door == DOOR_QUERY ? "pt_query_rays" : "pt_query_radiance";
   use.query_rays = m;
   use.n_first_tiles = ptq::tiles_covered(m, c->width);
-  use.table = c->d_query_order.get();
+  use.table = c->query.order.get();
   return use;
 }
 
@@ -2323,7 +2238,7 @@ PT_API int pt_query_rays(pt_ctx* c, const PtRay* rays, uint32_t n, PtRayHit* hit
   if (int rc = query_ready(c, "pt_query_rays", "query", rays, hits); rc != PT_OK) return rc;
   const uint32_t plane = (uint32_t)n_pixels(c);
   const bool rays_on_device = device_pointer(rays), hits_on_device = device_pointer(hits);
-  const ptq::F4* planes = reinterpret_cast<const ptq::F4*>(c->d_query.get());
+  const ptq::F4* planes = reinterpret_cast<const ptq::F4*>(c->query.planes.get());
   std::vector<ptq::F4> h_in, h_out;  // host arrays only: the two planes going up, the four coming down
   const uint32_t batches = ptq::n_batches(n, plane);
   for (uint32_t k = 0; k < batches; k++) {
@@ -2369,7 +2284,7 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
   static_assert(sizeof(PtRayRadiance) == sizeof(ptq::F4), "a record is a texel: the fold's scratch is a plane");
   const uint32_t plane = (uint32_t)n_pixels(c);
   const bool rays_on_device = device_pointer(rays), out_on_device = device_pointer(out);
-  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->d_query.get());
+  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->query.planes.get());
   std::vector<ptq::F4> h_in;  // host rays only: the two planes going up
   const uint32_t batches = ptq::n_batches(n, plane);
   for (uint32_t k = 0; k < batches; k++) {
@@ -2380,7 +2295,7 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
     use.first_pass = ptr::batch_first_pass(c->params.first_pass, k, n_passes);
     if (int rc = trace_once(c, n_passes, use); rc != PT_OK) return rc;
     {
-      const ptq::F4* slab = reinterpret_cast<const ptq::F4*>(c->d_slab.get());
+      const ptq::F4* slab = reinterpret_cast<const ptq::F4*>(c->frame.slab.get());
       const ptq::F4* staged = planes;
       PtRayRadiance* dst = out_on_device ? out + first : reinterpret_cast<PtRayRadiance*>(planes + (size_t)PT_FEAT_ALBEDO * plane);
       uint32_t pl = plane, np = n_passes;
@@ -2395,12 +2310,6 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
 }
 
 // ---- temporal reprojection (PT_OPT_REPROJECT; include/ptrace.h has the contract) ------------------------------
-// are the history planes allocated for the local rows in place?  (As with the feature planes: unless an allocation failed.)
-static bool history_planes_in_place(const pt_ctx* c) {
-  const size_t pix = n_pixels(c) ? n_pixels(c) : 1;
-  return c->reproj_on && c->d_hist.get() && c->d_hist.capacity() == 2 * pix;
-}
-
 // the row partition a set of uniforms names, as pt_set_params compares it (band_count <= 1: "all rows" whatever the rest holds)
 static bool same_partition(const PtParams& a, const PtParams& b) {
   const bool band_a = a.band_count > 1 && a.band_rows != 0, band_b = b.band_count > 1 && b.band_rows != 0;
@@ -2409,24 +2318,24 @@ static bool same_partition(const PtParams& a, const PtParams& b) {
 }
 
 static int reproject_ready(pt_ctx* c, const char* who) {
-  if (!c->reproj_on) return fail(c, PT_ERR_NOT_READY, "%s: reprojection is off (pt_set_option PT_OPT_REPROJECT)", who);
-  if (!history_planes_in_place(c)) return fail(c, PT_ERR_CAPACITY, "%s: the history planes are not allocated for the rows in place (an earlier allocation failed)", who);
+  if (!c->hist.on) return option_off(c, who, SET_REPROJECT);
+  if (!c->hist.in_place(extent_of(c))) return fail(c, PT_ERR_CAPACITY, "%s: the history planes are not allocated for the rows in place (an earlier allocation failed)", who);
   return PT_OK;
 }
 
 PT_API int pt_keep_history(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   if (int rc = reproject_ready(c, "pt_keep_history"); rc != PT_OK) return rc;
-  if (!c->feat_on || !c->feat_valid || !feature_planes_in_place(c))
+  if (!c->feat.on || !c->feat.valid || !c->feat.in_place(extent_of(c)))
     return fail(c, PT_ERR_NOT_READY, "pt_keep_history: no pt_render_features since the scene, the uniforms or the size last changed");
   PT_HIP(c, hipSetDevice(c->device));
   if (const size_t pix = n_pixels(c)) {
     const size_t bytes = pix * sizeof(float4);
-    PT_HIP(c, hipMemcpyAsync(c->d_hist.get(), c->d_feat.get() + (size_t)PT_FEAT_IDS * pix, bytes, hipMemcpyDeviceToDevice, c->stream));
-    PT_HIP(c, hipMemcpyAsync(c->d_hist.get() + pix, c->d_feat.get() + (size_t)PT_FEAT_POINT * pix, bytes, hipMemcpyDeviceToDevice, c->stream));
+    PT_HIP(c, hipMemcpyAsync(c->hist.planes.get(), c->feat.planes.get() + (size_t)PT_FEAT_IDS * pix, bytes, hipMemcpyDeviceToDevice, c->stream));
+    PT_HIP(c, hipMemcpyAsync(c->hist.planes.get() + pix, c->feat.planes.get() + (size_t)PT_FEAT_POINT * pix, bytes, hipMemcpyDeviceToDevice, c->stream));
   }
-  c->hist_params = c->params;
-  c->hist_valid = true;
+  c->hist.params = c->params;
+  c->hist.valid = true;
   return PT_OK;
 }
 
@@ -2439,12 +2348,12 @@ PT_API int pt_load_history(pt_ctx* c, const PtParams* prev, const void* ids, con
   if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_load_history: synchronises; not inside a stream capture");
   if (const size_t pix = n_pixels(c)) {
     const size_t bytes = pix * sizeof(float4);
-    PT_HIP(c, hipMemcpyAsync(c->d_hist.get(), ids, bytes, hipMemcpyDefault, c->stream));
-    PT_HIP(c, hipMemcpyAsync(c->d_hist.get() + pix, point, bytes, hipMemcpyDefault, c->stream));
+    PT_HIP(c, hipMemcpyAsync(c->hist.planes.get(), ids, bytes, hipMemcpyDefault, c->stream));
+    PT_HIP(c, hipMemcpyAsync(c->hist.planes.get() + pix, point, bytes, hipMemcpyDefault, c->stream));
   }
   PT_HIP(c, hipStreamSynchronize(c->stream));
-  c->hist_params = *prev;
-  c->hist_valid = true;
+  c->hist.params = *prev;
+  c->hist.valid = true;
   return PT_OK;
 }
 
@@ -2465,23 +2374,22 @@ static int reproject_call(pt_ctx* c, const PtReprojectOptions* opt, const char* 
   if (!std::isfinite(opt->tolerance_px) || opt->tolerance_px < 0.0f)
     return fail(c, PT_ERR_INVALID, "%s: tolerance_px must be finite and >= 0", who);
   if (int rc = reproject_ready(c, who); rc != PT_OK) return rc;
-  if (carry && !c->err_on) return fail(c, PT_ERR_NOT_READY, "%s: the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", who);
+  if (carry && !c->est.on) return option_off(c, who, SET_ESTIMATE);
+  PT_TRY(frame_buffers_ready(c, who));  // (the gather goes through the read-out staging)
   PT_HIP(c, hipSetDevice(c->device));
   if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "%s: not inside a stream capture", who);
-  if (!c->hist_valid) return fail(c, PT_ERR_NOT_READY, "%s: no history (pt_keep_history / pt_load_history; one pt_reproject uses it up)", who);
-  if (!c->feat_on || !c->feat_valid || !feature_planes_in_place(c))
+  if (!c->hist.valid) return fail(c, PT_ERR_NOT_READY, "%s: no history (pt_keep_history / pt_load_history; one pt_reproject uses it up)", who);
+  if (!c->feat.on || !c->feat.valid || !c->feat.in_place(extent_of(c)))
     return fail(c, PT_ERR_NOT_READY, "%s: no pt_render_features since the uniforms of the new view went up", who);
   // (nothing folded since the last clear: the state is zero and there is nothing to carry — the call is pt_reproject)
-  carry = carry && c->err_spp != 0;
-  const size_t pix = n_pixels(c);
-  if (carry && pix && c->d_err_stage.capacity() < 2 * pix)
-    return fail(c, PT_ERR_CAPACITY, "%s: the state's staging buffer is not allocated for the rows in place (an earlier allocation failed)", who);
+  carry = carry && c->est.spp != 0;
+  const size_t pix = n_pixels(c);  // (the state's staging buffer is in place with the estimate: frame_buffers_ready above)
   float k16[ptrep::K_COUNT];
-  if (pt_reproject_constants(&c->hist_params, opt->tolerance_px, k16) != PT_OK)
+  if (pt_reproject_constants(&c->hist.params, opt->tolerance_px, k16) != PT_OK)
     return fail(c, PT_ERR_INVALID, "%s: the history view's camera is degenerate", who);
-  c->hist_valid = false;  // one-shot: from here on the accumulation belongs to the new view
-  c->reproj_ran = true;
-  PT_HIP(c, hipMemsetAsync(c->d_reproj_tally.get(), 0, 3 * sizeof(unsigned long long), c->stream));
+  c->hist.valid = false;  // one-shot: from here on the accumulation belongs to the new view
+  c->hist.ran = true;
+  PT_HIP(c, hipMemsetAsync(c->hist.tally.get(), 0, 3 * sizeof(unsigned long long), c->stream));
   if (pix == 0) return PT_OK;  // this band owns no rows
   ptrep::Consts K;
   for (int k = 0; k < 3; k++) {
@@ -2498,28 +2406,28 @@ static int reproject_call(pt_ctx* c, const PtReprojectOptions* opt, const char* 
   const bool band = c->params.band_count > 1 && c->params.band_rows != 0;
   ptrep::Frame F = {c->width, c->height, c->local_rows, band ? c->params.band_rows : 0u, band ? c->params.band_index : 0u,
                     band ? c->params.band_count : 1u};
-  const float4* cur_ids = c->d_feat.get() + (size_t)PT_FEAT_IDS * pix;
-  const float4* cur_pnt = c->d_feat.get() + (size_t)PT_FEAT_POINT * pix;
-  const float4* hist_ids = c->d_hist.get();
-  const float4* hist_pnt = c->d_hist.get() + pix;
-  const float4* accum = c->accum;
-  float4* out = c->d_resolve.get();  // (the staging buffer pt_load_accum uses: the gather reads accum at other pixels' places)
-  unsigned long long* tally = c->d_reproj_tally.get();
+  const float4* cur_ids = c->feat.planes.get() + (size_t)PT_FEAT_IDS * pix;
+  const float4* cur_pnt = c->feat.planes.get() + (size_t)PT_FEAT_POINT * pix;
+  const float4* hist_ids = c->hist.planes.get();
+  const float4* hist_pnt = c->hist.planes.get() + pix;
+  const float4* accum = c->frame.accum;
+  float4* out = c->frame.resolve.get();  // (the staging buffer pt_load_accum uses: the gather reads accum at other pixels' places)
+  unsigned long long* tally = c->hist.tally.get();
   const dim3 grid((c->width + 31u) / 32u, (c->local_rows + 7u) / 8u);
   if (!carry) {
     void* kargs[] = {&cur_ids, &cur_pnt, &hist_ids, &hist_pnt, &accum, &out, &K, &F, &tally};
     PT_HIP(c, hipLaunchKernel(pt_reproject_kernel_handle(), grid, dim3(256), kargs, 0, c->stream));
-    PT_HIP(c, hipMemcpyAsync(c->accum, out, pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    PT_HIP(c, hipMemcpyAsync(c->frame.accum, out, pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     return clear_error(c);  // (history is sums, not the passes they came from: as pt_load_accum)
   }
   // the estimate's constants: the caps in passes of err_spp samples; err_spp stays, so the next fold must use the same value
-  const ptrep::EstConsts E = ptrep::est_consts(c->err_spp, opt->cap_diffuse, opt->cap_other);
-  const float4* err = c->d_err.get();
-  float4* out_err = c->d_err_stage.get();
+  const ptrep::EstConsts E = ptrep::est_consts(c->est.spp, opt->cap_diffuse, opt->cap_other);
+  const float4* err = c->est.state.get();
+  float4* out_err = c->est.stage.get();
   void* kargs[] = {&cur_ids, &cur_pnt, &hist_ids, &hist_pnt, &accum, &err, &out, &out_err, &K, (void*)&E, &F, &tally};
   PT_HIP(c, hipLaunchKernel(pt_reproject_estimate_kernel_handle(), grid, dim3(256), kargs, 0, c->stream));
-  PT_HIP(c, hipMemcpyAsync(c->accum, out, pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-  PT_HIP(c, hipMemcpyAsync(c->d_err.get(), out_err, 2 * pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  PT_HIP(c, hipMemcpyAsync(c->frame.accum, out, pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  PT_HIP(c, hipMemcpyAsync(c->est.state.get(), out_err, 2 * pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
   return PT_OK;
 }
 
@@ -2529,12 +2437,12 @@ PT_API int pt_reproject_estimate(pt_ctx* c, const PtReprojectOptions* opt) { ret
 
 PT_API int pt_reproject_stats(pt_ctx* c, PtReprojectStats* out) {
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_reproject_stats: NULL argument");
-  if (!c->reproj_on) return fail(c, PT_ERR_NOT_READY, "pt_reproject_stats: reprojection is off (pt_set_option PT_OPT_REPROJECT)");
-  if (!c->reproj_ran) return fail(c, PT_ERR_NOT_READY, "pt_reproject_stats: no pt_reproject yet");
+  if (!c->hist.on) return option_off(c, "pt_reproject_stats", SET_REPROJECT);
+  if (!c->hist.ran) return fail(c, PT_ERR_NOT_READY, "pt_reproject_stats: no pt_reproject yet");
   PT_HIP(c, hipSetDevice(c->device));
   if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_reproject_stats: synchronises; not inside a stream capture");
   unsigned long long h[3] = {0, 0, 0};
-  PT_HIP(c, hipMemcpyAsync(h, c->d_reproj_tally.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipMemcpyAsync(h, c->hist.tally.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   out->pixels = (uint64_t)n_pixels(c);
   out->pixels_hit = h[0];
@@ -2577,7 +2485,7 @@ int rebuild_grid(pt_ctx* c, double factor, bool keep_tuned) {
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight read the grid in place
   const int tuned = c->geom.tuned;
   int rc = install_grid(c, grid, sp);
-  c->feat_valid = false;
+  c->feat.valid = false;
   if (rc == PT_OK && wants_uuids(c)) rc = upload_uuids(c, sp.uuid);
   c->geom.list_paths(path_scene(c));  // (which kernels the grid can feed, and whether PT_GEOM_AUTO has anything to measure, follow its size — or its absence, had the upload failed)
   if (keep_tuned && rc == PT_OK && tuned == PT_GEOM_GRID && c->grid.present) c->geom.tuned = tuned;  // a refit keeps the settled choice
@@ -2669,8 +2577,8 @@ PT_API int pt_grid_fit(pt_ctx* c) {
 PT_API int pt_tune(pt_ctx* c, uint32_t n_passes) {
   if (!c || n_passes == 0) return fail(c, PT_ERR_INVALID, "pt_tune: bad argument");
   // measuring launches are not part of any frame: they fold the plain way, and whatever they launched is cleared below
-  struct Pause { pt_ctx* c; ~Pause() { c->err_paused = false; } } pause{c};
-  c->err_paused = true;
+  struct Pause { pt_ctx* c; ~Pause() { c->est.paused = false; } } pause{c};
+  c->est.paused = true;
   bool launched = false;
   if (c->have_spheres) {
     int rc = tune_grid_to_view(c, n_passes, &launched);

@@ -1,0 +1,240 @@
+// pt_buffers.hpp — the device buffers a context owns, in sets: which buffers a set holds, how they are sized for the row
+// partition in place, and what a failed allocation leaves.  Host-only and HIP-free: tests/buffers_shim.cpp compiles it with
+// g++ against a stand-in allocator.  The includer defines the two functions below (pt_api.hip: hipMalloc / hipFree).
+//
+// The contract of every set: IN PLACE FOR THE ROWS IN PLACE, OR REFUSED.  fit(extent) sizes the set's buffers; in_place(extent)
+// says whether every one of them is allocated for that extent.  A buffer is freed before its successor is asked for (the two
+// need not fit on the device together), so a refused allocation leaves that buffer empty and the set not in place: the calls
+// that would hand the set to a kernel or a copy answer PT_ERR_CAPACITY until a later fit succeeds.  fit makes no device call
+// but the allocator's; it returns which buffers are FRESH — reallocated, contents undefined — and the caller (ensure_buffers in
+// pt_api.hip) zeroes or fills exactly those.  Validity that belongs to a set alone ends where the set reallocates.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <utility>
+
+#include "../../include/ptrace.h"
+
+namespace ptbuf {
+
+// the device allocator, defined by the includer: 0 = done, anything else = the runtime's error code (pt_api.hip: a hipError_t).
+// A refused dev_malloc must leave no error pending in the runtime: the next good launch's error check must not find it.
+int dev_malloc(void** p, size_t bytes);
+int dev_free(void* p);
+
+// A device buffer and its capacity in elements; the one owner of every allocation the library makes, freed with it.
+template <class T>
+struct DevBuf {
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
+  ~DevBuf() { if (p_) (void)dev_free(p_); }
+  // room for exactly n elements, contents undefined: the old buffer is freed BEFORE the new one is allocated (the two need
+  // not fit on the device together); on failure it holds nothing and has capacity 0
+  int reserve(size_t n) {
+    int e = 0;
+    if (p_) e = dev_free(p_);
+    p_ = nullptr;
+    cap_ = 0;
+    void* q = nullptr;
+    if (e == 0) e = dev_malloc(&q, n * sizeof(T));
+    if (e != 0) return e;
+    p_ = static_cast<T*>(q);
+    cap_ = n;
+    return 0;
+  }
+  void release() { *this = DevBuf(); }
+  T* get() const { return p_; }
+  size_t capacity() const { return cap_; }
+  // allocated, for exactly n elements / for at least n
+  bool holds(size_t n) const { return p_ && cap_ == n; }
+  bool holds_at_least(size_t n) const { return p_ && cap_ >= n; }
+
+ private:
+  T* p_ = nullptr;
+  size_t cap_ = 0;
+};
+
+// What the buffers are sized for: the local pixels, the work queue's 8x8 tiles over them and the reserved passes of the
+// partition in place.  A band without rows is sized as one pixel and one tile: 0 counts as 1, here and nowhere else.
+struct Extent {
+  size_t pix, tiles, passes;
+  Extent(size_t pix_, size_t tiles_, size_t passes_) : pix(pix_ ? pix_ : 1), tiles(tiles_ ? tiles_ : 1), passes(passes_ ? passes_ : 1) {}
+};
+
+// What a fit did.
+struct Fit {
+  int err = 0;         // the allocator's code of the allocation that was refused (0: none was)
+  bool capped = false; // refused before anything was freed: the extent is beyond the kernels' 32-bit texel index
+  uint32_t fresh = 0;  // the set's bit of every buffer that was reallocated and is in place: its contents are undefined
+  bool ok() const { return err == 0 && !capped; }
+};
+
+// the planes of PT_FEAT_PLANES texels per pixel are indexed with 32 bits by the kernels
+inline bool planes_indexable(size_t pix) { return pix <= 0x3fffffffu / PT_FEAT_PLANES; }
+inline size_t plane_texels(size_t pix) { return (size_t)PT_FEAT_PLANES * pix; }
+
+// reserve `n` elements of `buf` inside a fit: false when refused (f.err says why), else the buffer's bit is fresh
+template <class T>
+inline bool refit(Fit& f, DevBuf<T>& buf, size_t n, uint32_t bit) {
+  if ((f.err = buf.reserve(n)) != 0) return false;
+  f.fresh |= bit;
+  return true;
+}
+
+// ---- the buffers every context has --------------------------------------------------------------------------------------
+// the own accumulation (>= pix; `accum` names it, or the caller's bound buffer, and never freed memory), the per-pass slabs
+// (>= pix * passes), the work queue's per-tile cost and order (== tiles: an order left from another count would name tiles that
+// do not exist, or miss some), the reference's two RGBA8 textures and canvas (>= pix) and the read-out staging (>= pix)
+template <class Texel>
+struct FrameSet {
+  enum : uint32_t { ACCUM = 1, SLAB = 2, COST = 4, ORDER = 8, TEX0 = 16, TEX1 = 32, CANVAS = 64, RESOLVE = 128 };
+  DevBuf<Texel> own_accum;
+  Texel* accum = nullptr;  // own_accum or caller-bound (never freed here)
+  size_t accum_pixels = 0;
+  bool accum_bound = false;
+  DevBuf<Texel> slab;
+  DevBuf<uint32_t> tile_cost, tile_order;
+  DevBuf<uint32_t> tex[2], canvas;
+  DevBuf<Texel> resolve;
+
+  Fit fit(const Extent& e) {
+    Fit f;
+    if (!accum_bound) {
+      if (own_accum.capacity() < e.pix) {
+        accum = nullptr;  // (before the buffer it names is freed)
+        accum_pixels = 0;
+        if (!refit(f, own_accum, e.pix, ACCUM)) return f;
+      }
+      accum = own_accum.get();
+      accum_pixels = own_accum.capacity();
+    }
+    if (slab.capacity() < e.pix * e.passes && !refit(f, slab, e.pix * e.passes, SLAB)) return f;
+    if (tile_cost.capacity() != e.tiles || tile_order.capacity() != e.tiles)
+      if (!refit(f, tile_cost, e.tiles, COST) || !refit(f, tile_order, e.tiles, ORDER)) return f;
+    if (canvas.capacity() < e.pix)  // (the canvas last: its capacity says all three are in place)
+      if (!refit(f, tex[0], e.pix, TEX0) || !refit(f, tex[1], e.pix, TEX1) || !refit(f, canvas, e.pix, CANVAS)) return f;
+    if (resolve.capacity() < e.pix) refit(f, resolve, e.pix, RESOLVE);
+    return f;
+  }
+  bool in_place(const Extent& e) const {
+    return accum && (accum_bound || own_accum.holds_at_least(e.pix)) && slab.holds_at_least(e.pix * e.passes) &&
+           tile_cost.holds(e.tiles) && tile_order.holds(e.tiles) && tex[0].holds_at_least(e.pix) && tex[1].holds_at_least(e.pix) &&
+           canvas.holds_at_least(e.pix) && resolve.holds_at_least(e.pix);
+  }
+};
+
+// ---- the opt-in sets: nothing is held while `on` is false ---------------------------------------------------------------
+// PT_OPT_ERROR_ESTIMATE: the state — two texels per local pixel, A = {mean.rgb, n} and B = {M2.rgb, k} (>= 2 pix; fresh state
+// holds no passes: spp restarts) —, the tile records and their tallies (>= 2 tiles), and pt_reproject_estimate's staging of the
+// state (>= 2 pix), which is held only while PT_OPT_REPROJECT is on too
+template <class Texel>
+struct EstimateSet {
+  enum : uint32_t { STATE = 1, TILES = 2, STAGE = 4 };
+  bool on = false;
+  bool paused = false;  // pt_tune's measuring launches fold the plain way (it clears everything afterwards)
+  int spp = 0;          // samples_per_pixel of the passes folded since the last clear (0 = none yet)
+  DevBuf<Texel> state, tiles, stage;
+
+  Fit fit(const Extent& e, bool reprojecting) {
+    Fit f;
+    if (!on || !reprojecting) stage.release();
+    if (!on) return f;
+    if (state.capacity() < 2 * e.pix) {
+      spp = 0;
+      if (!refit(f, state, 2 * e.pix, STATE)) return f;
+    }
+    if (tiles.capacity() < 2 * e.tiles && !refit(f, tiles, 2 * e.tiles, TILES)) return f;
+    if (reprojecting && stage.capacity() < 2 * e.pix) refit(f, stage, 2 * e.pix, STAGE);
+    return f;
+  }
+  bool in_place(const Extent& e, bool reprojecting) const {
+    return on && state.holds_at_least(2 * e.pix) && tiles.holds_at_least(2 * e.tiles) && (!reprojecting || stage.holds_at_least(2 * e.pix));
+  }
+  void release() {
+    on = false;
+    spp = 0;
+    state.release(); tiles.release(); stage.release();
+  }
+};
+
+// PT_OPT_FEATURES: four planes of one texel per local pixel in one allocation, plane k at k * pix — hence sized exactly
+template <class Texel>
+struct FeatureSet {
+  enum : uint32_t { PLANES = 1 };
+  bool on = false;
+  bool valid = false;  // the planes speak for the scene, uniforms and partition in place (pt_read_features)
+  DevBuf<Texel> planes;
+
+  Fit fit(const Extent& e) {
+    Fit f;
+    if (!on || planes.capacity() == plane_texels(e.pix)) return f;
+    valid = false;
+    if (!planes_indexable(e.pix)) { f.capped = true; return f; }
+    refit(f, planes, plane_texels(e.pix), PLANES);
+    return f;
+  }
+  bool in_place(const Extent& e) const { return on && planes.holds(plane_texels(e.pix)); }
+  void release() {
+    on = valid = false;
+    planes.release();
+  }
+};
+
+// PT_OPT_RAY_QUERIES: the query planes — the feature planes' layout — and the identity tile order a query launch is dealt by
+// (== tiles).  Both in place or neither: the planes go before the order is touched.
+template <class Texel>
+struct QuerySet {
+  enum : uint32_t { PLANES = 1, ORDER = 2 };
+  bool on = false;
+  DevBuf<Texel> planes;
+  DevBuf<uint32_t> order;
+
+  bool fits(const Extent& e) const { return planes.capacity() == plane_texels(e.pix) && order.capacity() == e.tiles; }
+  Fit fit(const Extent& e) {
+    Fit f;
+    if (!on || fits(e)) return f;
+    if (!planes_indexable(e.pix)) { f.capped = true; return f; }
+    planes.release();
+    if (refit(f, order, e.tiles, ORDER)) refit(f, planes, plane_texels(e.pix), PLANES);
+    return f;
+  }
+  bool in_place(const Extent& e) const { return on && planes.holds(plane_texels(e.pix)) && order.holds(e.tiles); }
+  void release() {
+    on = false;
+    planes.release(); order.release();
+  }
+};
+
+// PT_OPT_REPROJECT: the history planes — the ids plane, then the point plane at pix, of an earlier view (== 2 pix) —, the
+// uniforms they were rendered with, and the last call's three tallies {pixels_hit, pixels_kept, samples_kept}
+template <class Texel>
+struct HistorySet {
+  enum : uint32_t { PLANES = 1, TALLY = 2 };
+  bool on = false;
+  bool valid = false;  // the history speaks for the scene and partition in place, and no pt_reproject has used it
+  bool ran = false;    // the tallies are those of a pt_reproject (pt_reproject_stats)
+  PtParams params{};
+  DevBuf<Texel> planes;
+  DevBuf<unsigned long long> tally;
+
+  Fit fit(const Extent& e) {
+    Fit f;
+    if (!on) return f;
+    if (planes.capacity() != 2 * e.pix) {
+      valid = false;
+      if (!refit(f, planes, 2 * e.pix, PLANES)) return f;
+    }
+    if (tally.capacity() < 3) refit(f, tally, 3, TALLY);
+    return f;
+  }
+  bool in_place(const Extent& e) const { return on && planes.holds(2 * e.pix) && tally.holds_at_least(3); }
+  void release() {
+    on = valid = ran = false;
+    planes.release(); tally.release();
+  }
+};
+
+}  // namespace ptbuf
