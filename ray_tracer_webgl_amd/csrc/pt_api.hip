@@ -38,6 +38,7 @@
 #include "pt_query.hpp"
 #include "pt_radiance.hpp"
 #include "pt_buffers.hpp"
+#include "pt_ctx_state.hpp"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -117,7 +118,10 @@ struct pt_ctx {
   SceneList list;
   SceneBvh bvh;
   SceneGrid grid;
-  bool have_spheres = false, have_params = false;  // have_spheres: list, bvh and grid are one scene's, wholly installed
+  // what the context knows of its derived products and of its accumulation (pt_ctx_state.hpp: the plain flags with the table
+  // of what each change drops — applied with changed(*c, ...) —, and the host tallies with their named transitions)
+  ptstate::Flags state;
+  ptstate::AccumTally tally;
   PtParams params{};
   uint32_t local_rows = 0;
   // The buffers sized for the row partition, in five sets (pt_buffers.hpp: what each holds, how it is sized, what a failed
@@ -135,12 +139,9 @@ struct pt_ctx {
   ptbuf::QuerySet<float4> query;
   ptbuf::HistorySet<float4> hist;
   uint32_t reserved_passes = 1;
-  uint32_t total_spp = 0;   // enqueued directly (not through graph replays)
-  bool captured = false;    // some launch was captured into a hipGraph: only the device knows the spp
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   PathTuner geom;
   hipEvent_t trial_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // begin/end per trial
-  bool grid_cells_build = false;  // pt_tune measured the build that gathers its entries from L2 faster than the LDS-staged one on this scene and view (grid_staging)
   int grid_fit_mode = 0;  // PT_OPT_GRID_FIT: 0 pt_tune measures the margin classes, 1 it takes the one the camera needs unmeasured
   int count_work = 0; // PT_OPT_COUNT_WORK: launch the measuring twin of the walk kernel
   DevBuf<uint32_t> d_cell_hist;           // grid twins: leaf-round lanes per entry run + coherence bins (pt_debug_cell_hist)
@@ -155,17 +156,14 @@ struct pt_ctx {
   bool dbg_enable = false;
   int32_t dbg_selected = 0;
   float dbg_cursor[3] = {0.f, 0.f, 0.f};
-  bool uuid_valid = false;          // the three uuid arrays match the scene and structures in place
-  int last_build = 0;               // which build the most recent trace launch was (pt_last_trace_build)
+  int last_build = 0;              // which build the most recent trace launch was (pt_last_trace_build)
   // work-queue ordering feedback, one entry per tile: what the host knows of frame.tile_cost and frame.tile_order
   TileOrder order;  // (pt_tile_order.hpp): when the order kernel runs, when the frames' order is probed
   // adaptive sampling (pt_render_adaptive): a partial round's tables — 3 x tiles words: the flags as uploaded, the partition the
   // trace launch and the masked fold read, the cost order it was made from — and the host's copy of the flags
   DevBuf<uint32_t> d_adapt;
   std::vector<uint32_t> h_adapt_flags;
-  bool adapt_valid = false;       // the tables are those of a partial round of the scene and partition in place (pt_adaptive_tiles)
-  uint32_t adapt_tiles = 0, adapt_active = 0;
-  uint64_t scene_gen = 0;  // counts pt_set_spheres: the frames' cost-sorted tile order is probed per scene (ensure_cost_order)
+  uint32_t adapt_tiles = 0, adapt_active = 0;  // (while state.adapt_valid: pt_adaptive_tiles)
   // the reference's frame (pt_render_frame / pt_render_frames): the device-side frame counter ([0] frames replayed since the
   // series began, [1] a cell that stays 0)
   DevBuf<uint32_t> d_frame_ctr;
@@ -179,8 +177,6 @@ struct pt_ctx {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events; // pool
   size_t events_used = 0;
   double kernel_ms = 0.0;
-  uint32_t launches = 0;
-  uint64_t samples = 0;
   // device properties
   int num_cus = 256;
   // host-clock durations of the set-up calls, ms (include/ptrace_dev.h pt_debug_setup_times: where a first frame's time goes)
@@ -293,7 +289,7 @@ int ensure_buffers(pt_ctx* c) {
     const ptbuf::Fit f = s.fit(e);
     if (f.fresh & s.ACCUM) {
       PT_HIP(c, zero(s.own_accum, e.pix));
-      c->total_spp = 0;
+      c->tally.own_fresh();
     }
     if (f.fresh & s.COST) PT_HIP(c, zero(s.tile_cost, e.tiles));
     if (f.fresh & s.ORDER) {
@@ -301,7 +297,7 @@ int ensure_buffers(pt_ctx* c) {
       // CAPTURED into a caller's hipGraph and has not run yet) must still find every tile exactly once
       PT_HIP(c, fill_identity_order(s.tile_order, e.tiles));
       c->order.reseeded();
-      c->adapt_valid = false;
+      changed(*c, ptstate::TILE_COUNT_CHANGED);
     }
     // create_texture x2 (src/webgl.rs:82-123), cleared: alpha 0 = "no data" (shader.frag:391)
     if (f.fresh & s.TEX0) PT_HIP(c, zero(s.tex[0], e.pix));
@@ -350,6 +346,15 @@ int clear_error(pt_ctx* c) {
   if (pix) PT_HIP(c, hipMemsetAsync(c->est.state.get(), 0, 2 * pix * sizeof(float4), c->stream));
   c->est.spp = 0;
   return PT_OK;
+}
+
+// The accumulation emptied in place and the estimate with it: what pt_reset_accum, a repartition and an unbind share (a bound
+// buffer and a checkpoint bring their own texels: pt_bind_accum and pt_load_accum clear the estimate alone).  The tallies'
+// transition stays with each caller: some commit it before these fallible clears, others after their last synchronise.
+int empty_accum(pt_ctx* c) {
+  const size_t pix = n_pixels(c);
+  if (c->frame.accum && pix) PT_HIP(c, hipMemsetAsync(c->frame.accum, 0, pix * sizeof(float4), c->stream));
+  return clear_error(c);
 }
 
 int fold_events(pt_ctx* c) {
@@ -403,6 +408,15 @@ bool is_capturing(const pt_ctx* c) {
   (void)hipStreamIsCapturing(c->stream, &cap);
   return cap != hipStreamCaptureStatusNone;
 }
+int not_capturing(pt_ctx* c, const char* who) {
+  return is_capturing(c) ? fail(c, PT_ERR_INVALID, "%s: synchronises; not inside a stream capture", who) : PT_OK;
+}
+
+// every call that launches needs a scene and uniforms
+int scene_and_uniforms(pt_ctx* c, const char* who) {
+  if (c->state.have_spheres && c->state.have_params) return PT_OK;
+  return fail(c, PT_ERR_NOT_READY, "%s: pt_set_spheres and pt_set_params must come first", who);
+}
 
 // the queue order of the tiles from their costs (the identity while every cost is zero)
 int launch_tile_order(pt_ctx* c) {
@@ -433,7 +447,7 @@ PathScene path_scene(const pt_ctx* c) {
 
 // the margin class the current uniforms need of the grid (pt_geom_plan.hpp); 0 = no grid / no uniforms / a camera that is not finite
 double need_factor(const pt_ctx* c) {
-  return c->grid.present && c->have_params ? view_need_factor(c->params, c->grid.head.c0, c->grid.head.s0) : 0.0;
+  return c->grid.present && c->state.have_params ? view_need_factor(c->params, c->grid.head.c0, c->grid.head.s0) : 0.0;
 }
 
 // does the grid in place fit the view (PtStats.grid_fit_stale, pt_grid_fit)?
@@ -444,7 +458,7 @@ int fit_state(const pt_ctx* c) {
 // the build of the grid kernel the next launch gets and the bytes it stages (with a grid)
 Staging grid_build(const pt_ctx* c) {
   const ptgrid::Grid& g = c->grid.head;
-  return grid_staging(ptscene::staged_cells(g), g.n_entries, walk_lds_room(), c->grid_cells_build, fit_state(c));
+  return grid_staging(ptscene::staged_cells(g), g.n_entries, walk_lds_room(), c->state.grid_cells_build, fit_state(c));
 }
 
 // The handle of a table cell's kernel (pt_trace_table.hpp), from its object's accessor.  The first use of a kernel of the five
@@ -591,7 +605,10 @@ template <class T>
 void release(std::vector<T>& v) { std::vector<T>().swap(v); }
 
 // no scene is in place (until an install has wholly succeeded: the render calls answer PT_ERR_NOT_READY meanwhile)
-void drop_scene(pt_ctx* c) { c->have_spheres = c->bvh.present = c->grid.present = c->uuid_valid = c->feat.valid = false; }
+void drop_scene(pt_ctx* c) {
+  c->bvh.present = c->grid.present = false;
+  changed(*c, ptstate::SCENE_DROPPED);
+}
 
 // (list.n and list.host follow when the whole scene is in place: pt_set_spheres)
 int install_list(pt_ctx* c, const ptscene::Split& sp, size_t n) {
@@ -600,10 +617,10 @@ int install_list(pt_ctx* c, const ptscene::Split& sp, size_t n) {
   return upload(c, c->list.r0, sp.r0.data(), 2 * n, n ? 2 * n : 2u, 0);
 }
 
-// a structure's index (padding: 0xff, no sphere) and per-slot materials (padding: 0); its uuids follow when the overlay is on
+// a structure's index (padding: 0xff, no sphere) and per-slot materials (padding: 0); its uuids follow when the overlay is on (the
+// caller has reported the change that ends the uuid arrays' validity: SCENE_DROPPED or GRID_REBUILT)
 int install_slots(pt_ctx* c, SceneSlots& s, const std::vector<uint32_t>& index, size_t n, size_t n_pad, const ptscene::Split& sp) {
   s.present = false;  // (until the caller's install has succeeded: a failed allocation must not leave a structure that points nowhere)
-  c->uuid_valid = false;
   PT_TRY(upload(c, s.index, index.data(), n, n_pad, 0xff));
   s.index_n = n_pad;
   return upload(c, s.mat, ptscene::per_slot(index.data(), n, sp.mat.data(), sp.mat.size()).data(), n, n_pad, 0);
@@ -655,7 +672,7 @@ int upload_uuids(pt_ctx* c, const std::vector<int32_t>& uuid) {
     PT_HIP(c, hipMemcpy(index.data(), s->index.get(), index.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     PT_TRY(upload(c, s->uuid, ptscene::per_slot(index.data(), index.size(), uuid.data(), uuid.size())));  // (padding slots are never hit)
   }
-  c->uuid_valid = true;
+  changed(*c, ptstate::UUIDS_UPLOADED);
   return PT_OK;
 }
 
@@ -690,15 +707,11 @@ PT_API int pt_set_spheres(pt_ctx* c, const PtSphere* s, uint32_t n) {
   PT_HIP(c, hipStreamSynchronize(c->stream));
   // validate first, commit afterwards: from the first device write until everything is in place the context has no scene
   drop_scene(c);
-  c->hist.valid = false;  // (the history's list indices would name other spheres)
   if (int rc = install_scene(c, sp, n, have_bvh ? &bvh : nullptr, have_grid ? &grid : nullptr); rc != PT_OK) return drop_scene(c), rc;
   c->list.n = n;
   c->list.host = std::move(sp);
-  c->grid_cells_build = false;  // (a measurement of the previous scene)
-  c->scene_gen++;
-  c->adapt_valid = false;
+  changed(*c, ptstate::SCENE_INSTALLED);
   c->geom.reset();  // a new scene: PT_GEOM_AUTO measures again
-  c->have_spheres = true;
   c->geom.list_paths(path_scene(c));
   const double t_end = host_ms();
   c->setup_ms[PT_SETUP_SPHERES_SPLIT] = t_split - t_begin;
@@ -721,18 +734,12 @@ PT_API int pt_set_params(pt_ctx* c, const PtParams* p) {
                 p->band_rows, p->band_index, p->band_count);
   PT_HIP(c, hipSetDevice(c->device));
   uint32_t rows = count_local_rows(c->height, *p);
-  auto eff = [](const PtParams& q, uint32_t k) -> uint32_t {
-    if (q.band_count <= 1 || q.band_rows == 0) return k == 2 ? 1u : 0u;
-    return k == 0 ? q.band_rows : (k == 1 ? q.band_index : q.band_count);
-  };
-  bool repartition = rows != c->local_rows;
-  for (uint32_t k = 0; k < 3; k++) repartition |= eff(*p, k) != eff(c->params, k);
+  const bool repartition = rows != c->local_rows || ptstate::Partition(*p) != ptstate::Partition(c->params);
   // validate first, commit afterwards: a refused call leaves the context as it was
   if (repartition && c->frame.accum_bound && (size_t)rows * c->width > c->frame.accum_pixels)
     return fail(c, PT_ERR_CAPACITY, "pt_set_params: bound accumulation buffer too small for %u rows", rows);
-  c->feat.valid = false;  // the feature planes speak for the uniforms they were rendered with
   if (repartition) {
-    c->hist.valid = false;  // (the history planes held other rows; an ordinary pt_set_params leaves them alone)
+    changed(*c, ptstate::ROWS_ASKED);
     const uint32_t old_rows = c->local_rows;
     c->local_rows = rows;
     int rc = ensure_buffers(c);
@@ -746,17 +753,14 @@ PT_API int pt_set_params(pt_ctx* c, const PtParams* p) {
     // clears below: whatever they return, local_rows, params.band_* and the sample count agree with each other
     // (a refused clear leaves a self-consistent context whose old image is gone, never a new partition with old uniforms).
     c->params = *p;
-    c->have_params = true;
-    c->total_spp = 0;
-    c->captured = false;  // whatever a replayed graph accumulated is gone with the old partition
-    c->adapt_valid = false;
+    changed(*c, ptstate::UNIFORMS_OTHER_ROWS);
+    c->tally.repartitioned();
     // a different set of rows: the accumulated image no longer applies, and neither do the frame textures
-    PT_HIP(c, hipMemsetAsync(c->frame.accum, 0, n_pixels(c) * sizeof(float4), c->stream));
-    if (int rc = clear_error(c); rc != PT_OK) return rc;
+    if (int rc = empty_accum(c); rc != PT_OK) return rc;
     return pt_clear_textures(c);
   }
   c->params = *p;
-  c->have_params = true;
+  changed(*c, ptstate::UNIFORMS_SAME_ROWS);
   return PT_OK;
 }
 
@@ -766,10 +770,7 @@ PT_API int pt_resize(pt_ctx* c, uint32_t width, uint32_t height) {
   PT_HIP(c, hipStreamSynchronize(c->stream));
   c->width = width;
   c->height = height;
-  c->have_params = false; // uniforms must be re-uploaded for the new size
-  c->adapt_valid = false;
-  c->feat.valid = false;
-  c->hist.valid = false;
+  changed(*c, ptstate::RESIZED);  // (uniforms must be re-uploaded for the new size)
   c->params.band_count = 0;
   c->local_rows = height;
   if (c->frame.accum_bound) { c->frame.accum_bound = false; c->frame.accum = nullptr; }
@@ -802,17 +803,12 @@ PT_API int pt_reserve_passes(pt_ctx* c, uint32_t max_passes) {
 PT_API int pt_reset_accum(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   PT_HIP(c, hipSetDevice(c->device));
-  if (c->frame.accum)
-    PT_HIP(c, hipMemsetAsync(c->frame.accum, 0, n_pixels(c) * sizeof(float4), c->stream));
   PT_HIP(c, hipMemsetAsync(c->d_counters.get(), 0, PT_CTR_COUNT * sizeof(unsigned long long), c->stream));
-  if (int rc = clear_error(c); rc != PT_OK) return rc;
+  if (int rc = empty_accum(c); rc != PT_OK) return rc;
   PT_HIP(c, hipStreamSynchronize(c->stream));
   c->events_used = 0;
   c->kernel_ms = 0.0;
-  c->launches = 0;
-  c->total_spp = 0;
-  c->captured = false;
-  c->samples = 0;
+  c->tally.emptied();
   return PT_OK;
 }
 
@@ -823,13 +819,11 @@ PT_API int pt_bind_accum(pt_ctx* c, void* dev_ptr, size_t bytes) {
   if (!dev_ptr) {
     c->frame.accum_bound = false;
     c->frame.accum = nullptr;
-    int rc = ensure_buffers(c);
-    c->total_spp = 0;
-    if (rc != PT_OK) return rc;
+    c->tally.rebound();  // (whatever ensure_buffers answers)
+    if (int rc = ensure_buffers(c); rc != PT_OK) return rc;
     // the own buffer comes back EMPTY: what it held when the caller's buffer took its place belongs to another frame — possibly to
     // another row partition, set while it was out of use — and the sample count above has just restarted
-    if (const size_t pix = n_pixels(c)) PT_HIP(c, hipMemsetAsync(c->frame.accum, 0, pix * sizeof(float4), c->stream));
-    return clear_error(c);
+    return empty_accum(c);
   }
   size_t need = n_pixels(c) * sizeof(float4);
   if (bytes < need) return fail(c, PT_ERR_CAPACITY, "pt_bind_accum: %zu bytes < %zu needed", bytes, need);
@@ -837,7 +831,7 @@ PT_API int pt_bind_accum(pt_ctx* c, void* dev_ptr, size_t bytes) {
   c->frame.accum = (float4*)dev_ptr;
   c->frame.accum_pixels = bytes / sizeof(float4);
   c->frame.accum_bound = true;
-  c->total_spp = 0; // the caller owns the contents; spp counting restarts
+  c->tally.rebound();  // the caller owns the contents; spp counting restarts
   return clear_error(c);  // (and so does the estimate: it knows nothing of what the caller's buffer holds)
 }
 
@@ -888,10 +882,7 @@ PT_API int pt_load_accum(pt_ctx* c, const float* src, size_t bytes) {
   PT_HIP(c, hipMemcpyAsync(c->frame.accum, c->frame.resolve.get(), need, hipMemcpyDeviceToDevice, c->stream));
   if (int rc = clear_error(c); rc != PT_OK) return rc;  // (a checkpoint carries sums, not the passes they came from)
   PT_HIP(c, hipStreamSynchronize(c->stream));
-  // the host-side mirrors follow the loaded state
-  c->total_spp = (uint32_t)w;
-  c->samples = (uint64_t)w * (uint64_t)n_pix;
-  c->captured = false;
+  c->tally.loaded((uint32_t)w, n_pix);  // the host-side mirrors follow the loaded state
   return PT_OK;
 }
 
@@ -1102,9 +1093,9 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   const bool rr = !door && c->rr_min_depth > 0, dbg = !door && c->dbg_enable;
   if (rr && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and PT_OPT_RUSSIAN_ROULETTE exclude each other");
   if (dbg && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and the debug overlay exclude each other");
-  if (dbg && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "debug overlay: the uuid arrays are not in place (pt_set_debug_overlay after a failed upload?)");
+  if (dbg && !c->state.uuid_valid) return fail(c, PT_ERR_NOT_READY, "debug overlay: the uuid arrays are not in place (pt_set_debug_overlay after a failed upload?)");
   // (the overlay builds exist for the ways to read the list that have a roulette build: the same steering away from the LDS walk)
-  if (feat && !c->uuid_valid) return fail(c, PT_ERR_NOT_READY, "%s: the uuid arrays are not in place (%s after a failed upload?)", query ? "ray queries" : "feature planes",
+  if (feat && !c->state.uuid_valid) return fail(c, PT_ERR_NOT_READY, "%s: the uuid arrays are not in place (%s after a failed upload?)", query ? "ray queries" : "feature planes",
                                              query ? "PT_OPT_RAY_QUERIES" : "PT_OPT_FEATURES");
   const PathChoice choice = c->geom.choose(path_scene(c), use.allow_trials && !door, rr || dbg || door);
   const int path = choice.path;
@@ -1187,8 +1178,7 @@ static int trace_once(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, TimedS
 
 PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
   if (!c) return PT_ERR_INVALID;
-  if (!c->have_spheres || !c->have_params)
-    return fail(c, PT_ERR_NOT_READY, "pt_render: pt_set_spheres and pt_set_params must come first");
+  if (int rc = scene_and_uniforms(c, "pt_render"); rc != PT_OK) return rc;
   if (n_passes == 0) return fail(c, PT_ERR_INVALID, "pt_render_passes: n_passes == 0");
   if (n_passes > c->reserved_passes)
     return fail(c, PT_ERR_CAPACITY, "pt_render_passes: %u passes > %u reserved (pt_reserve_passes)",
@@ -1279,13 +1269,7 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
   // Host-side tallies describe work enqueued directly.  A captured launch runs as often as its
   // graph is replayed, which the host cannot see: read-out takes its divisor from the device
   // (accum.w, see pixel_scale), and pt_get_stats reads the accumulated spp back from there.
-  if (capturing) {
-    c->captured = true;
-  } else {
-    c->launches++;
-    c->total_spp += n_passes * (uint32_t)p.samples_per_pixel;
-    c->samples += (uint64_t)n_pix * n_passes * (uint64_t)p.samples_per_pixel;
-  }
+  c->tally.uniform_launch(capturing, n_pix, n_passes, (uint32_t)p.samples_per_pixel);
   return PT_OK;
 }
 
@@ -1363,7 +1347,7 @@ int enqueue_frame(pt_ctx* c, FramePlan& F, bool advance) {
 // of the statistics.
 // (When which of it happens: TileOrder::frames, pt_tile_order.hpp.)
 int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
-  const TileOrder::FrameStep step = c->order.frames(c->params.samples_per_pixel, c->params, c->scene_gen, n_frames, [c] { return is_capturing(c); });
+  const TileOrder::FrameStep step = c->order.frames(c->params.samples_per_pixel, c->params, c->state.scene_gen, n_frames, [c] { return is_capturing(c); });
   if (step.zero_costs)  // back to the identity order: what the order kernel writes when every cost is zero
     PT_HIP(c, hipMemsetAsync(c->frame.tile_cost.get(), 0, c->frame.tile_cost.capacity() * sizeof(uint32_t), c->stream));
   if (step.order_kernel) {
@@ -1386,14 +1370,13 @@ int ensure_cost_order(pt_ctx* c, uint32_t n_frames) {
   rc = launch_tile_order(c);
   if (rc != PT_OK) return rc;
   PT_HIP(c, hipMemcpyAsync(seg, c->d_counters.get() + PT_CTR_SCRATCH, sizeof *seg, hipMemcpyDeviceToDevice, c->stream));
-  c->order.probed_for(c->params, c->scene_gen);
+  c->order.probed_for(c->params, c->state.scene_gen);
   return PT_OK;
 }
 
 int frame_ready(pt_ctx* c, const char* who) {
   if (!c) return PT_ERR_INVALID;
-  if (!c->have_spheres || !c->have_params)
-    return fail(c, PT_ERR_NOT_READY, "%s: pt_set_spheres and pt_set_params must come first", who);
+  if (int rc = scene_and_uniforms(c, who); rc != PT_OK) return rc;
   if (c->count_work) return fail(c, PT_ERR_INVALID, "%s: not with PT_OPT_COUNT_WORK (the measuring twins are not frame kernels)", who);
   return frame_buffers_ready(c, who);
 }
@@ -1424,8 +1407,7 @@ PT_API int pt_render_frame(pt_ctx* c, uint32_t even_odd_count) {
   PT_HIP(c, zero_queue_heads(c, F.L.A.queue_static));  // (the shared head, the groups' heads, or — statically dealt — none)
   rc = enqueue_frame(c, F, false);
   if (rc != PT_OK) return rc;
-  c->launches++;
-  c->samples += (uint64_t)n_pixels(c) * (uint64_t)c->params.samples_per_pixel;
+  c->tally.frames(1, n_pixels(c), (uint32_t)c->params.samples_per_pixel);
   return PT_OK;
 }
 
@@ -1507,8 +1489,7 @@ PT_API int pt_render_frames(pt_ctx* c, uint32_t even_odd_count, uint32_t max_ren
   for (int g = 0; g < kFrameLevels; g++)
     for (uint32_t k = 0; k < counts[g]; k++) PT_HIP(c, hipGraphLaunch(c->frame_exec[g], c->stream));
   if (rc = span.end(c); rc != PT_OK) return rc;
-  c->launches += n_frames;
-  c->samples += (uint64_t)n_frames * n_pixels(c) * (uint64_t)c->params.samples_per_pixel;
+  c->tally.frames(n_frames, n_pixels(c), (uint32_t)c->params.samples_per_pixel);
   return PT_OK;
 }
 
@@ -1598,7 +1579,7 @@ PT_API int pt_debug_wait(pt_ctx* c, unsigned timeout_ms) {
 // first, the launch the product makes — one workgroup of 1024 threads on the context's stream.
 PT_API int pt_debug_tile_order(pt_ctx* c, const uint32_t* cost, uint32_t n, uint32_t* order_out, uint32_t* cost_out) {
   if (!c || !cost || !order_out || !cost_out || n == 0) return fail(c, PT_ERR_INVALID, "pt_debug_tile_order: NULL argument or no tiles");
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_debug_tile_order: synchronises; not inside a stream capture");
+  PT_TRY(not_capturing(c, "pt_debug_tile_order"));
   PT_HIP(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)n * sizeof(uint32_t);
   DevBuf<uint32_t> d_cost, d_order;
@@ -1618,7 +1599,7 @@ PT_API int pt_debug_partition_order(pt_ctx* c, const uint32_t* order, const uint
                                     uint32_t* base_out) {
   if (!c || !order || !flags || !part_out || !base_out || n == 0)
     return fail(c, PT_ERR_INVALID, "pt_debug_partition_order: NULL argument or no tiles");
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_debug_partition_order: synchronises; not inside a stream capture");
+  PT_TRY(not_capturing(c, "pt_debug_partition_order"));
   PT_HIP(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)n * sizeof(uint32_t);
   DevBuf<uint32_t> d_in, d_out;  // {order, flags} and {part, base}
@@ -1651,7 +1632,7 @@ PT_API int pt_synchronize(pt_ctx* c) {
 
 static int resolve_common(pt_ctx* c, void* out, int gamma, int mode, const uint8_t* prev) {
   if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_resolve: NULL argument");
-  if (c->total_spp == 0 && !c->captured) return fail(c, PT_ERR_NOT_READY, "pt_resolve: nothing rendered yet");
+  if (c->tally.nothing_rendered()) return fail(c, PT_ERR_NOT_READY, "pt_resolve: nothing rendered yet");
   if (int rc = frame_buffers_ready(c, "pt_resolve"); rc != PT_OK) return rc;
   PT_HIP(c, hipSetDevice(c->device));
   uint32_t n_pix = (uint32_t)n_pixels(c);
@@ -1730,7 +1711,7 @@ static int resolve_filtered(pt_ctx* c, const char* who, float* rgba_out, uint32_
   const float4* est = c->est.state.get();
   float4* out = c->frame.resolve.get();
   uint32_t width = c->width, rows = c->local_rows;
-  uint32_t band_rows = c->params.band_count > 1 ? c->params.band_rows : 0u;  // (0: no band, every local row is a neighbour)
+  uint32_t band_rows = ptstate::Partition(c->params).rows;  // (0: no band, every local row is a neighbour)
   const dim3 grid((width + 31u) / 32u, (rows + 7u) / 8u);
   if (patch) {
     uint32_t P = *patch;
@@ -1818,9 +1799,6 @@ int noise_target_args(pt_ctx* c, const char* who, const char* per, float target,
     return fail(c, PT_ERR_CAPACITY, "%s: %u passes per %s > %u reserved (pt_reserve_passes)", who, passes_per, per, c->reserved_passes);
   return PT_OK;
 }
-int not_capturing(pt_ctx* c, const char* who) {
-  return is_capturing(c) ? fail(c, PT_ERR_INVALID, "%s: synchronises; not inside a stream capture", who) : PT_OK;
-}
 
 // the frame is the frame one uninterrupted call would give: the next launch goes on where this one ended (pass indices are
 // frame-wide: the step does not depend on how many tiles ran)
@@ -1855,8 +1833,7 @@ namespace {
 // One partial round: k passes over the tiles flagged in c->h_adapt_flags (n_active of `tiles`, 0 < n_active < tiles).
 int partial_round(pt_ctx* c, uint32_t k, uint32_t tiles, uint32_t n_active, uint64_t pixels_active) {
   const PtParams& p = c->params;
-  if (!c->have_spheres || !c->have_params)
-    return fail(c, PT_ERR_NOT_READY, "pt_render_adaptive: pt_set_spheres and pt_set_params must come first");
+  PT_TRY(scene_and_uniforms(c, "pt_render_adaptive"));
   PT_HIP(c, hipSetDevice(c->device));
   if (c->d_adapt.capacity() != 3 * (size_t)tiles) {
     PT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1865,7 +1842,7 @@ int partial_round(pt_ctx* c, uint32_t k, uint32_t tiles, uint32_t n_active, uint
   uint32_t* flags = c->d_adapt.get();
   uint32_t* part = flags + tiles;
   uint32_t* base = part + tiles;
-  c->adapt_valid = false;
+  changed(*c, ptstate::PARTIAL_ROUND_BEGINS);
   // the cost order up to date, as the next pt_render_passes would bring it — and never from costs that are all zero: the order
   // kernel would write the identity over a sorted order
   if (c->order.partial_wants_order_kernel()) {
@@ -1897,11 +1874,10 @@ int partial_round(pt_ctx* c, uint32_t k, uint32_t tiles, uint32_t n_active, uint
     PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD_TILES), dim3(tile_grid(n_active)), dim3(256), kargs, 0, c->stream));
   }
   c->est.spp = p.samples_per_pixel;
-  c->adapt_valid = true;
+  changed(*c, ptstate::PARTIAL_ROUND_DONE);
   c->adapt_tiles = tiles;
   c->adapt_active = n_active;
-  c->launches++;
-  c->samples += pixels_active * k * (uint64_t)p.samples_per_pixel;
+  c->tally.partial_round(pixels_active, k, (uint32_t)p.samples_per_pixel);
   return PT_OK;
 }
 
@@ -1913,7 +1889,7 @@ PT_API int pt_render_adaptive(pt_ctx* c, float target_rel_error, uint32_t passes
   if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_render_adaptive: not with PT_OPT_COUNT_WORK (the measuring twins log whole launches)");
   if (int rc = not_capturing(c, "pt_render_adaptive"); rc != PT_OK) return rc;
   // (refused before the first look: a call must not answer for an estimate it could not continue)
-  if (c->have_params && c->est.spp != 0 && c->est.spp != c->params.samples_per_pixel)
+  if (c->state.have_params && c->est.spp != 0 && c->est.spp != c->params.samples_per_pixel)
     return fail(c, PT_ERR_INVALID, "pt_render_adaptive: %d samples per pixel while the error estimate holds passes of %d: clear first "
                                    "(pt_reset_accum)", c->params.samples_per_pixel, c->est.spp);
   const uint32_t tiles = n_tiles(c);
@@ -1960,7 +1936,7 @@ PT_API int pt_render_adaptive(pt_ctx* c, float target_rel_error, uint32_t passes
 
 PT_API int pt_adaptive_tiles(pt_ctx* c, uint32_t* base_out, uint32_t* order_out, uint32_t* n_tiles, uint32_t* n_active) {
   if (!c) return PT_ERR_INVALID;
-  if (!c->adapt_valid) return fail(c, PT_ERR_NOT_READY, "pt_adaptive_tiles: no partial round yet (pt_render_adaptive)");
+  if (!c->state.adapt_valid) return fail(c, PT_ERR_NOT_READY, "pt_adaptive_tiles: no partial round yet (pt_render_adaptive)");
   if (n_tiles) *n_tiles = c->adapt_tiles;
   if (n_active) *n_active = c->adapt_active;
   if (!base_out && !order_out) return PT_OK;
@@ -1983,11 +1959,11 @@ PT_API int pt_get_stats(pt_ctx* c, PtStats* out) {
   PT_HIP(c, hipMemcpy(ctr, c->d_counters.get(), sizeof ctr, hipMemcpyDeviceToHost));
   memset(out, 0, sizeof *out);
   out->segments = ctr[PT_CTR_SEGMENTS];
-  out->samples = c->samples;
+  out->samples = c->tally.samples;
   out->sphere_tests = ctr[PT_CTR_SEGMENTS] * (uint64_t)c->list.n;
   out->render_kernel_ms = c->kernel_ms;
-  out->render_launches = c->launches;
-  out->total_spp = c->total_spp;
+  out->render_launches = c->tally.launches;
+  out->total_spp = c->tally.total_spp;
   if (c->frame.accum && c->local_rows) { // what the device has really accumulated (graph replays included)
     float4 px0;
     PT_HIP(c, hipMemcpy(&px0, c->frame.accum, sizeof px0, hipMemcpyDeviceToHost));
@@ -2078,7 +2054,7 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
   }
   // (reprojection reads the feature planes and stages the estimate's state: off with the former, and the stage with it)
   auto reproject_off = [c] { c->hist.release(); c->est.stage.release(); };
-  auto uuids = [c] { return !c->uuid_valid && c->have_spheres ? upload_uuids(c, c->list.host.uuid) : PT_OK; };  // the scene in place
+  auto uuids = [c] { return !c->state.uuid_valid && c->state.have_spheres ? upload_uuids(c, c->list.host.uuid) : PT_OK; };  // the scene in place
   if (key == PT_OPT_ERROR_ESTIMATE)
     return set_buffer_option(c, value, "error estimate", c->est, [c] { c->est.release(); }, pt_error_kernel(PT_E_FOLD), [c] { return clear_error(c); });
   if (key == PT_OPT_FEATURES)
@@ -2106,7 +2082,7 @@ PT_API int pt_set_debug_overlay(pt_ctx* c, int enable, int32_t selected_object, 
     c->dbg_enable = false;
     return PT_OK;
   }
-  if (!c->uuid_valid && c->have_spheres) {
+  if (!c->state.uuid_valid && c->state.have_spheres) {
     int rc = upload_uuids(c, c->list.host.uuid);
     if (rc != PT_OK) return rc;
   }
@@ -2131,8 +2107,7 @@ PT_API int pt_last_trace_build(pt_ctx* c) {
 PT_API int pt_render_features(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   if (c->count_work) return fail(c, PT_ERR_INVALID, "pt_render_features: not with PT_OPT_COUNT_WORK (the measuring twins have no feature build)");
-  if (!c->have_spheres || !c->have_params)
-    return fail(c, PT_ERR_NOT_READY, "pt_render_features: pt_set_spheres and pt_set_params must come first");
+  PT_TRY(scene_and_uniforms(c, "pt_render_features"));
   if (!c->feat.on) return option_off(c, "pt_render_features", SET_FEATURES);
   PT_HIP(c, hipSetDevice(c->device));
   if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_render_features: not inside a stream capture");
@@ -2183,7 +2158,7 @@ static bool device_pointer(const void* p) {
 }
 
 PT_API uint32_t pt_query_batch(pt_ctx* c) {
-  if (!c || !c->query.on || !c->have_spheres || !c->have_params || c->local_rows == 0 || !c->query.in_place(extent_of(c))) return 0u;
+  if (!c || !c->query.on || !c->state.have_spheres || !c->state.have_params || c->local_rows == 0 || !c->query.in_place(extent_of(c))) return 0u;
   return (uint32_t)n_pixels(c);
 }
 
@@ -2193,9 +2168,9 @@ static int query_ready(pt_ctx* c, const char* who, const char* build, const void
   if (!rays || !out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
   if (c->count_work) return fail(c, PT_ERR_INVALID, "%s: not with PT_OPT_COUNT_WORK (the measuring twins have no %s build)", who, build);
   if (!c->query.on) return option_off(c, who, SET_QUERIES);
-  if (!c->have_spheres || !c->have_params) return fail(c, PT_ERR_NOT_READY, "%s: pt_set_spheres and pt_set_params must come first", who);
+  PT_TRY(scene_and_uniforms(c, who));
   PT_HIP(c, hipSetDevice(c->device));
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "%s: synchronises; not inside a stream capture", who);
+  PT_TRY(not_capturing(c, who));
   if (c->local_rows == 0) return fail(c, PT_ERR_NOT_READY, "%s: this band owns no rows, so it has no work items to decode rays against", who);
   if (!c->query.in_place(extent_of(c))) return fail(c, PT_ERR_CAPACITY, "%s: the planes are not allocated for the rows in place (an earlier allocation failed)", who);
   return frame_buffers_ready(c, who);  // (before the first ray is staged, not only at the launch)
@@ -2310,13 +2285,6 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
 }
 
 // ---- temporal reprojection (PT_OPT_REPROJECT; include/ptrace.h has the contract) ------------------------------
-// the row partition a set of uniforms names, as pt_set_params compares it (band_count <= 1: "all rows" whatever the rest holds)
-static bool same_partition(const PtParams& a, const PtParams& b) {
-  const bool band_a = a.band_count > 1 && a.band_rows != 0, band_b = b.band_count > 1 && b.band_rows != 0;
-  if (!band_a || !band_b) return band_a == band_b;
-  return a.band_rows == b.band_rows && a.band_index == b.band_index && a.band_count == b.band_count;
-}
-
 static int reproject_ready(pt_ctx* c, const char* who) {
   if (!c->hist.on) return option_off(c, who, SET_REPROJECT);
   if (!c->hist.in_place(extent_of(c))) return fail(c, PT_ERR_CAPACITY, "%s: the history planes are not allocated for the rows in place (an earlier allocation failed)", who);
@@ -2342,10 +2310,10 @@ PT_API int pt_keep_history(pt_ctx* c) {
 PT_API int pt_load_history(pt_ctx* c, const PtParams* prev, const void* ids, const void* point) {
   if (!c || !prev || !ids || !point) return fail(c, PT_ERR_INVALID, "pt_load_history: NULL argument");
   if (int rc = reproject_ready(c, "pt_load_history"); rc != PT_OK) return rc;
-  if (prev->width != c->width || prev->height != c->height || !same_partition(*prev, c->params))
+  if (prev->width != c->width || prev->height != c->height || ptstate::Partition(*prev) != ptstate::Partition(c->params))
     return fail(c, PT_ERR_INVALID, "pt_load_history: the history view's size or row partition is not the context's");
   PT_HIP(c, hipSetDevice(c->device));
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_load_history: synchronises; not inside a stream capture");
+  PT_TRY(not_capturing(c, "pt_load_history"));
   if (const size_t pix = n_pixels(c)) {
     const size_t bytes = pix * sizeof(float4);
     PT_HIP(c, hipMemcpyAsync(c->hist.planes.get(), ids, bytes, hipMemcpyDefault, c->stream));
@@ -2387,7 +2355,7 @@ static int reproject_call(pt_ctx* c, const PtReprojectOptions* opt, const char* 
   float k16[ptrep::K_COUNT];
   if (pt_reproject_constants(&c->hist.params, opt->tolerance_px, k16) != PT_OK)
     return fail(c, PT_ERR_INVALID, "%s: the history view's camera is degenerate", who);
-  c->hist.valid = false;  // one-shot: from here on the accumulation belongs to the new view
+  changed(*c, ptstate::REPROJECTED);  // one-shot: from here on the accumulation belongs to the new view
   c->hist.ran = true;
   PT_HIP(c, hipMemsetAsync(c->hist.tally.get(), 0, 3 * sizeof(unsigned long long), c->stream));
   if (pix == 0) return PT_OK;  // this band owns no rows
@@ -2403,9 +2371,8 @@ static int reproject_call(pt_ctx* c, const PtReprojectOptions* opt, const char* 
   K.k = k16[ptrep::K_K];
   K.cap_diffuse = opt->cap_diffuse;
   K.cap_other = opt->cap_other;
-  const bool band = c->params.band_count > 1 && c->params.band_rows != 0;
-  ptrep::Frame F = {c->width, c->height, c->local_rows, band ? c->params.band_rows : 0u, band ? c->params.band_index : 0u,
-                    band ? c->params.band_count : 1u};
+  const ptstate::Partition part(c->params);
+  ptrep::Frame F = {c->width, c->height, c->local_rows, part.rows, part.index, part.count};
   const float4* cur_ids = c->feat.planes.get() + (size_t)PT_FEAT_IDS * pix;
   const float4* cur_pnt = c->feat.planes.get() + (size_t)PT_FEAT_POINT * pix;
   const float4* hist_ids = c->hist.planes.get();
@@ -2440,7 +2407,7 @@ PT_API int pt_reproject_stats(pt_ctx* c, PtReprojectStats* out) {
   if (!c->hist.on) return option_off(c, "pt_reproject_stats", SET_REPROJECT);
   if (!c->hist.ran) return fail(c, PT_ERR_NOT_READY, "pt_reproject_stats: no pt_reproject yet");
   PT_HIP(c, hipSetDevice(c->device));
-  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_reproject_stats: synchronises; not inside a stream capture");
+  PT_TRY(not_capturing(c, "pt_reproject_stats"));
   unsigned long long h[3] = {0, 0, 0};
   PT_HIP(c, hipMemcpyAsync(h, c->hist.tally.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
@@ -2469,7 +2436,7 @@ namespace {
 // captured into a caller's hipGraph holds its numbers, and no A/B build fixes its factor (PT_GRID_DNEAR, PT_DEV_KNOBS builds only:
 // pt_grid.hpp builds every grid for it)?
 bool grid_refittable(const pt_ctx* c) {
-  if (!c->grid.present || !c->have_params || c->captured) return false;
+  if (!c->grid.present || !c->state.have_params || c->tally.captured) return false;
 #ifdef PT_DEV_KNOBS
   if (getenv("PT_GRID_DNEAR")) return false;  // (the A/B build's own factor stands)
 #endif
@@ -2484,8 +2451,8 @@ int rebuild_grid(pt_ctx* c, double factor, bool keep_tuned) {
   PT_HIP(c, hipSetDevice(c->device));
   PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight read the grid in place
   const int tuned = c->geom.tuned;
+  changed(*c, ptstate::GRID_REBUILT);
   int rc = install_grid(c, grid, sp);
-  c->feat.valid = false;
   if (rc == PT_OK && wants_uuids(c)) rc = upload_uuids(c, sp.uuid);
   c->geom.list_paths(path_scene(c));  // (which kernels the grid can feed, and whether PT_GEOM_AUTO has anything to measure, follow its size — or its absence, had the upload failed)
   if (keep_tuned && rc == PT_OK && tuned == PT_GEOM_GRID && c->grid.present) c->geom.tuned = tuned;  // a refit keeps the settled choice
@@ -2551,12 +2518,13 @@ int tune_grid_to_view(pt_ctx* c, uint32_t n_passes, bool* launched) {
   if (!search.kept()) return PT_OK;
   const double keep = search.keep();
   if (!at(keep)) { int rc = rebuild_grid(c, keep, false); if (rc != PT_OK) return rc; }
-  c->grid_cells_build = false;
+  changed(*c, ptstate::CELLS_BUILD_UNMEASURED);
   if (c->grid.present && at(keep) && cells_build_worth_timing(c->grid.head.n_entries, grid_build(c).kind)) {
-    c->grid_cells_build = true;
+    changed(*c, ptstate::CELLS_BUILD_CHOSEN);  // (on trial: the launch below is the build's)
     std::optional<ClassProbe> probe;
-    if (int rc = measure(keep, true, false, &probe); rc != PT_OK) { c->grid_cells_build = false; return rc; }
-    c->grid_cells_build = keep_cells_build(probe, search.keep_ms());
+    const int rc = measure(keep, true, false, &probe);
+    if (rc != PT_OK || !keep_cells_build(probe, search.keep_ms())) changed(*c, ptstate::CELLS_BUILD_UNMEASURED);
+    return rc;
   }
   return PT_OK;
 }
@@ -2565,7 +2533,7 @@ int tune_grid_to_view(pt_ctx* c, uint32_t n_passes, bool* launched) {
 
 PT_API int pt_refit_grid(pt_ctx* c, int only_if_stale) {
   if (!c) return PT_ERR_INVALID;
-  if (!c->have_spheres || !c->have_params) return PT_OK;
+  if (!c->state.have_spheres || !c->state.have_params) return PT_OK;
   return fit_grid_to_view(c, only_if_stale ? 1 : 0);
 }
 
@@ -2580,11 +2548,11 @@ PT_API int pt_tune(pt_ctx* c, uint32_t n_passes) {
   struct Pause { pt_ctx* c; ~Pause() { c->est.paused = false; } } pause{c};
   c->est.paused = true;
   bool launched = false;
-  if (c->have_spheres) {
+  if (c->state.have_spheres) {
     int rc = tune_grid_to_view(c, n_passes, &launched);
     if (rc != PT_OK) return rc;
   }
-  if (!c->have_spheres || !c->geom.has_path_to_decide())
+  if (!c->state.have_spheres || !c->geom.has_path_to_decide())
     return launched ? pt_reset_accum(c) : PT_OK;
   c->geom.reset();
   for (int k = 0; k < 1 + c->geom.n_paths; k++) {

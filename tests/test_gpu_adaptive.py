@@ -474,4 +474,23 @@ def test_error_paths_leave_the_context_usable(ora):
     assert t.lib.pt_adaptive_tiles(t._ctx, None, None, C.byref(n), C.byref(na)) == abi.PT_ERR_NOT_READY
     with pytest.raises(PtError):
         t.adaptive_tiles()
+    # ... and so do another row partition and a resize, while new uniforms for the same rows leave them (csrc/pt_ctx_state.hpp)
+    def tables():
+        return t.lib.pt_adaptive_tiles(t._ctx, None, None, C.byref(n), C.byref(na))
+
+    for change in ("band", "resize"):
+        t.reset()
+        t.set_params(p)
+        t.render_adaptive(TARGET, PER_ROUND, CAP)
+        assert tables() == abi.PT_OK and n.value == 40
+        q = t.params.copy()
+        q.time += 1.0
+        t.set_params(q)
+        assert tables() == abi.PT_OK
+        if change == "band":
+            q.band_rows, q.band_index, q.band_count = 8, 1, 3
+            t.set_params(q)
+        else:
+            assert t.lib.pt_resize(t._ctx, 33, 19) == abi.PT_OK
+        assert tables() == abi.PT_ERR_NOT_READY, change
     t.close()
