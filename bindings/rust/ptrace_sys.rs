@@ -68,6 +68,28 @@ pub struct PtRayRadiance {       // the record of one ray of pt_query_radiance, 
     pub sum: [f32; 3], pub samples: f32,
 }
 
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct PtMeterOptions {      // the rule of one pt_meter, 48 bytes; the window is in image coordinates, w == 0 or h == 0: the whole frame
+    pub key: f32, pub key_permille: u32, pub high_permille: u32, pub e_min: f32, pub e_max: f32, pub white_min: f32, pub rate: f32,
+    pub x0: u32, pub y0: u32, pub w: u32, pub h: u32, pub _pad: u32,
+}
+impl Default for PtMeterOptions {  // PT_METER_OPTIONS_DEFAULT
+    fn default() -> Self {
+        PtMeterOptions { key: 0.18, key_permille: 500, high_permille: 990, e_min: 0.00390625, e_max: 256.0, white_min: 1.0, rate: 1.0,
+                         x0: 0, y0: 0, w: 0, h: 0, _pad: 0 }
+    }
+}
+
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtExposure {          // the exposure record pt_meter keeps on the device, 32 bytes
+    pub exposure: f32, pub white: f32, pub y_key: f32, pub y_high: f32, pub lit: u64, pub below: u32, pub meterings: u32,
+}
+
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtToneOptions {       // curve PT_TONE_*, gamma, exposure (0: the device record's exposure and white), white; 16 bytes
+    pub curve: i32, pub gamma: i32, pub exposure: f32, pub white: f32,
+}
+
 #[repr(C)] pub struct PtCtx { _private: [u8; 0] }
 
 #[link(name = "ptrace")]
@@ -135,6 +157,15 @@ extern "C" {
     // view — by the plain estimator, n_passes passes (at most those reserved) of samples_per_pixel samples per ray; host or device
     // pointers, synchronous; the camera, the accumulation and first_pass do not move
     pub fn pt_query_radiance(ctx: *mut PtCtx, rays: *const PtRay, n: u32, n_passes: u32, out: *mut PtRayRadiance) -> c_int;
+    // exposure metering and the toned read-outs (pt_set_option PT_OPT_TONEMAP 1): meter the frame on the device (src NULL: the
+    // accumulation; else host or device linear RGBA f32 texels), keep the exposure record there, read the frame out through a tone
+    // curve; pt_exposure_solve is the metering's second kernel on the host (ranks add their histograms, solve, pt_meter_set)
+    pub fn pt_meter(ctx: *mut PtCtx, src: *const f32, options: *const PtMeterOptions) -> c_int;
+    pub fn pt_meter_read(ctx: *mut PtCtx, out: *mut PtExposure, hist256: *mut u32) -> c_int;
+    pub fn pt_meter_set(ctx: *mut PtCtx, record: *const PtExposure) -> c_int;
+    pub fn pt_exposure_solve(hist256: *const u32, below: u32, options: *const PtMeterOptions, prev_or_null: *const PtExposure, out: *mut PtExposure) -> c_int;
+    pub fn pt_resolve_toned(ctx: *mut PtCtx, src: *const f32, options: *const PtToneOptions, rgba_out: *mut f32) -> c_int;
+    pub fn pt_resolve_toned_rgba8(ctx: *mut PtCtx, src: *const f32, options: *const PtToneOptions, rgba_out: *mut u8) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;
@@ -159,6 +190,10 @@ pub const PT_OPT_ERROR_ESTIMATE: c_int = 7;     // opt-in, 0 = off; the image bi
 pub const PT_OPT_FEATURES: c_int = 8;           // opt-in, 0 = off; the image bits do not depend on it
 pub const PT_OPT_REPROJECT: c_int = 9;          // opt-in, 0 = off; needs PT_OPT_FEATURES on
 pub const PT_OPT_RAY_QUERIES: c_int = 10;       // opt-in, 0 = off; the image bits do not depend on it
+pub const PT_OPT_TONEMAP: c_int = 11;           // opt-in, 0 = off; the image bits do not depend on it
+pub const PT_TONE_CLAMP: i32 = 0;
+pub const PT_TONE_REINHARD: i32 = 1;
+pub const PT_TONE_FILMIC: i32 = 2;
 pub const PT_RAY_INVALID: i32 = -2;             // PtRayHit.index / uuid / type of an invalid ray
 pub const PT_REPROJECT_TOLERANCE_DEFAULT: f32 = 2.0;
 pub const PT_REPROJECT_CAP_DIFFUSE_DEFAULT: f32 = 32.0;

@@ -115,6 +115,9 @@ enum {
   PT_OPT_RAY_QUERIES = 10, /* 1: allocate the query planes of pt_query_rays (see below; 64 bytes per local pixel), keep the uuid
                              arrays on the device and load the query builds' code object.  0 (default): release the planes.
                              The image bits of a context are the same either way. */
+  PT_OPT_TONEMAP = 11,     /* 1: put the exposure state in place (see pt_meter below; 258 tallies and one PtExposure record, about
+                             1 KB whatever the size of the frame) and load the display kernels' code object.  0 (default): release
+                             it; the exposure is forgotten.  The image bits of a context are the same either way. */
 };
 
 /* ---- background modes ----------------------------------------------------------------------- */
@@ -810,6 +813,110 @@ typedef struct PtRayRadiance {
   float samples;
 } PtRayRadiance; /* 16 bytes: an accumulation texel */
 int pt_query_radiance(pt_ctx* ctx, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out);
+
+/* ---- exposure metering and tone-mapped read-out (build extension, opt-in: PT_OPT_TONEMAP) --------------------------------------
+ * Every other read-out ends in sqrt and a clamp at 1: the reference's framebuffer.  A frame lit by PT_EMISSIVE spheres holds far
+ * more range than that; these calls meter the frame on the device, keep an EXPOSURE there and read the frame out through a tone
+ * curve.  No existing read-out changes.  The kernels are a code object of their own (loaded when the option is turned on, or at
+ * the first toned read-out with an explicit exposure); the arithmetic is csrc/pt_tone.hpp, shared with pt_exposure_solve.
+ * THE OPTION puts one fixed-size device buffer in place: 256 + 2 uint32 tallies and one PtExposure record.  The record is VALID
+ * once it was metered or set since the option came on.  An exposure is the viewer's adaptation, not a product of the scene: it
+ * survives pt_set_spheres, pt_set_params, pt_resize and pt_reset_accum and ends only when the option is turned off.
+ * THE SOURCE IMAGE, `src`: NULL is the context's accumulation, per pixel x.c = v.c * scale with scale = v.w > 0 ? 1 / v.w : 0 —
+ * pt_resolve with gamma = 0, bit for bit.  Otherwise a host or device pointer to local_rows*width linear RGBA fp32 texels (what
+ * pt_resolve_filtered_patch(..., gamma = 0) wrote, for instance): x = src.rgb, its .a is not read.  A device src is read in place;
+ * a host src is copied into the pass slabs first (free between calls, as pt_query_radiance uses them).
+ * pt_meter: asynchronous on the context's stream, no allocation, and no synchronisation for a NULL or device src (a call with a
+ * host src synchronises).  Two kernels behind a clear of the tallies.
+ * KERNEL 1, per local pixel inside the window, fp32, ONE IEEE operation per statement, nothing fused:
+ *     Y = 0.2126f*x.r ;  t = 0.7152f*x.g ;  Y = Y + t ;  t = 0.0722f*x.b ;  Y = Y + t
+ *     if !(Y >= 2^-16): below += 1                     (zero, negative, NaN, subnormal, too dark)
+ *     else: k = (bits(Y) >> 20) - 888 ;  if k > 255: k = 255 ;  hist[k] += 1
+ * 888 is bits(2^-16) >> 20: the 256 bins are eight per octave over [2^-16, 2^16), everything at or above 2^16, +inf included,
+ * lands in bin 255, and the lower edge of bin k is the float whose bits are (k + 888) << 20.  The counts are integers, summed per
+ * workgroup in the LDS and added with integer atomics: exact in any order.
+ * THE WINDOW {x0, y0, w, h} is in IMAGE coordinates, row 0 at the bottom; w == 0 or h == 0 means the whole frame.  Local pixel
+ * (px, ly) is metered when x0 <= px < x0 + w and its image row y = pt_band_row(band_rows, band_index, band_count, ly) lies in
+ * [y0, y0 + h); the sums cannot wrap: a window that reaches past the frame ends at the frame.  A band context meters its rows.
+ * KERNEL 2, one workgroup, from the tallies and the record before (`/` correctly rounded; N, rank and the cumulative counts uint64):
+ *     N = sum hist
+ *     if N == 0: the record keeps exposure, white, y_key and y_high (1, white_min, 0, 0 when it was never valid);
+ *                lit = 0, below is stored, meterings += 1; done
+ *     rank(p) = min(N - 1, (N * p) / 1000)
+ *     bin(p)  = the smallest k whose cumulative count exceeds rank(p)
+ *     y_key = edge(bin(key_permille)) ;  y_high = edge(bin(high_permille))
+ *     e_t = key / y_key
+ *     if (e_t < e_min) e_t = e_min ;  if (e_t > e_max) e_t = e_max
+ *     if the record was valid and rate < 1:
+ *         if !(rate > 0): e = e_prev
+ *         else: d = e_t - e_prev ;  d = d * rate ;  e = e_prev + d
+ *     else: e = e_t
+ *     white = y_high * e ;  if !(white >= white_min) white = white_min
+ *     record = {exposure e, white, y_key, y_high, lit = N, below, meterings + 1}
+ * pt_meter: PT_ERR_INVALID for a NULL ctx or options, a key, e_min, e_max or white_min that is not finite and positive,
+ * e_min > e_max, a permille above 1000, key_permille > high_permille, a rate that is NaN; then PT_ERR_NOT_READY while the option
+ * is off; then PT_ERR_INVALID inside a stream capture; then, for src == NULL, what pt_resolve would answer (PT_ERR_NOT_READY
+ * before anything was rendered), and PT_ERR_CAPACITY while the buffers are not in place.
+ * pt_meter_read: synchronises; the record and the tallies of the last metering (all zero while a pt_meter_set is all there was);
+ * either out pointer may be NULL.  PT_ERR_NOT_READY while the option is off or the record is not valid.
+ * pt_meter_set: loads a record as it is (meterings included) and makes the state valid; exposure and white must be finite and
+ * positive (PT_ERR_INVALID); PT_ERR_NOT_READY while the option is off; synchronises, not inside a stream capture.
+ * pt_exposure_solve: kernel 2's statements on the host, no device and no context: the same header, the same bits.  The window of
+ * `options` is not read; prev NULL means "never valid".  PT_ERR_INVALID for a NULL hist256, options or out and for the option
+ * values pt_meter refuses.  It is what makes an N-rank frame equal the single-GPU one: the ranks add their histograms and their
+ * `below` (integers, any order), each solves with the same prev, each calls pt_meter_set.
+ * THE TONED READ-OUTS follow pt_resolve: rgba_out is a host or device pointer to local_rows*width texels, the call synchronises.
+ * PtToneOptions.exposure == 0 reads exposure and white from the device record, with no host round trip — a pt_meter enqueued just
+ * before is enough — and answers PT_ERR_NOT_READY while the option is off or the record is not valid.  exposure > 0 (finite) uses
+ * the caller's exposure and white and needs neither record nor option.  Per channel, fp32, one operation per statement:
+ *     x = x * e
+ *     PT_TONE_CLAMP     y = x
+ *     PT_TONE_REINHARD  w2 = white*white  (once)
+ *                       a = x / w2 ;  a = a + 1 ;  n = x * a ;  d = x + 1 ;  y = n / d
+ *     PT_TONE_FILMIC    a = 2.51f*x ;  a = a + 0.03f ;  n = x * a ;
+ *                       b = 2.43f*x ;  b = b + 0.59f ;  d = x * b ;  d = d + 0.14f ;  y = n / d
+ *     gamma != 0:       y = sqrtf(y)
+ * The float form writes {y.rgb, 1}; the byte form writes unorm8(y) with alpha 255, unorm8 as pt_resolve_rgba8 has it
+ * (!(y > 0) -> 0; y >= 1 -> 255; else truncate (y * 255 + 0.5), two statements).  Non-finite and negative operands go through the
+ * statements as they are.  PT_TONE_CLAMP with exposure 1 IS pt_resolve / pt_resolve_rgba8, bit for bit.
+ * PT_ERR_INVALID: NULL ctx, options or rgba_out, a curve that is none of the three, an exposure that is neither 0 nor finite and
+ * positive, PT_TONE_REINHARD with a caller's white that is not above 0 (+inf is allowed: plain x / (1 + x)); then, for
+ * exposure == 0, PT_ERR_NOT_READY as above; then PT_ERR_INVALID inside a stream capture; then, for src == NULL, what pt_resolve
+ * would answer.
+ * WHAT THESE CALLS LEAVE ALONE is what pt_resolve leaves alone: the accumulation, the estimate, the planes and their validity, the
+ * textures and the canvas, first_pass, the tile order, PtStats and pt_last_trace_build. */
+enum { PT_TONE_CLAMP = 0, PT_TONE_REINHARD = 1, PT_TONE_FILMIC = 2 };
+typedef struct PtMeterOptions {
+  float key;              /* the luminance the key percentile is exposed to          default 0.18  */
+  uint32_t key_permille;  /* the percentile of the lit pixels that is the key        default 500   */
+  uint32_t high_permille; /* ... and the one that becomes `white`                    default 990   */
+  float e_min, e_max;     /* the range of the exposure                               default 2^-8, 2^8 */
+  float white_min;        /* the least `white`                                       default 1     */
+  float rate;             /* the share of the way to the target one metering goes    default 1     */
+  uint32_t x0, y0, w, h;  /* the window, image coordinates; w == 0 or h == 0: the whole frame */
+  uint32_t _pad;
+} PtMeterOptions; /* 48 bytes */
+#define PT_METER_OPTIONS_DEFAULT {0.18f, 500u, 990u, 0.00390625f, 256.0f, 1.0f, 1.0f, 0u, 0u, 0u, 0u, 0u}
+typedef struct PtExposure {
+  float exposure, white; /* what the toned read-outs multiply by, and Reinhard's white point (exposed luminance) */
+  float y_key, y_high;   /* the lower edges of the bins the two percentiles fell in (linear luminance)          */
+  uint64_t lit;          /* N: the metered pixels that fell in a bin                                            */
+  uint32_t below;        /* ... and those that did not                                                          */
+  uint32_t meterings;    /* meterings since the record became valid                                             */
+} PtExposure; /* 32 bytes */
+typedef struct PtToneOptions {
+  int32_t curve;  /* PT_TONE_*                                             */
+  int32_t gamma;  /* != 0: the square root after the curve                 */
+  float exposure; /* 0: the device record's exposure and white; > 0: these */
+  float white;
+} PtToneOptions; /* 16 bytes */
+int pt_meter(pt_ctx* ctx, const float* src, const PtMeterOptions* options);
+int pt_meter_read(pt_ctx* ctx, PtExposure* out, uint32_t hist256[256]);
+int pt_meter_set(pt_ctx* ctx, const PtExposure* record);
+int pt_exposure_solve(const uint32_t hist256[256], uint32_t below, const PtMeterOptions* options, const PtExposure* prev_or_NULL,
+                      PtExposure* out);
+int pt_resolve_toned(pt_ctx* ctx, const float* src, const PtToneOptions* options, float* rgba_out);
+int pt_resolve_toned_rgba8(pt_ctx* ctx, const float* src, const PtToneOptions* options, uint8_t* rgba_out);
 
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)

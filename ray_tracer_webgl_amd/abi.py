@@ -35,6 +35,13 @@ PT_FEAT_ALBEDO, PT_FEAT_NORMAL, PT_FEAT_POINT, PT_FEAT_IDS, PT_FEAT_PLANES = 0, 
 PT_OPT_ERROR_ESTIMATE = 7  # the per-pixel error estimate (pt_error_ptr, pt_resolve_error, pt_error_tiles, pt_error_stats, pt_render_until)
 PT_OPT_REPROJECT = 9  # temporal reprojection's history planes (pt_keep_history, pt_load_history, pt_reproject, pt_reproject_estimate, pt_reproject_stats)
 PT_OPT_RAY_QUERIES = 10  # the query planes of pt_query_rays (closest hits for the caller's rays), pt_query_batch
+PT_OPT_TONEMAP = 11  # the exposure state of pt_meter and the toned read-outs (pt_meter_read, pt_meter_set, pt_resolve_toned, pt_resolve_toned_rgba8)
+PT_TONE_CLAMP, PT_TONE_REINHARD, PT_TONE_FILMIC = 0, 1, 2  # PtToneOptions.curve
+PT_METER_KEY_DEFAULT = 0.18            # PtMeterOptions: the luminance the key percentile is exposed to
+PT_METER_KEY_PERMILLE_DEFAULT = 500    # ... the percentile that is the key
+PT_METER_HIGH_PERMILLE_DEFAULT = 990   # ... and the one that becomes white
+PT_METER_E_MIN_DEFAULT = 2.0 ** -8     # ... the exposure's range
+PT_METER_E_MAX_DEFAULT = 2.0 ** 8
 PT_RAY_INVALID = -2  # PtRayHit.index, .uuid and .type of an invalid ray (a non-finite component, or a direction of three zeros)
 PT_REPROJECT_TOLERANCE_DEFAULT = 2.0     # pt_reproject: the distance test, in pixel footprints at the history camera's depth
 PT_REPROJECT_CAP_DIFFUSE_DEFAULT = 32.0   # ... the most samples a kept diffuse pixel carries over
@@ -262,6 +269,69 @@ class PtRayRadiance(C.Structure):
         ("sum", C.c_float * 3),
         ("samples", C.c_float),
     ]
+
+
+class PtMeterOptions(C.Structure):
+    """include/ptrace.h PtMeterOptions: the rule of one pt_meter (and of pt_exposure_solve, which does not read the window),
+    48 bytes.  The window {x0, y0, w, h} is in image coordinates, row 0 at the bottom; w == 0 or h == 0 is the whole frame."""
+
+    _fields_ = [
+        ("key", C.c_float),
+        ("key_permille", C.c_uint32),
+        ("high_permille", C.c_uint32),
+        ("e_min", C.c_float),
+        ("e_max", C.c_float),
+        ("white_min", C.c_float),
+        ("rate", C.c_float),
+        ("x0", C.c_uint32),
+        ("y0", C.c_uint32),
+        ("w", C.c_uint32),
+        ("h", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+    def __init__(self, key=PT_METER_KEY_DEFAULT, key_permille=PT_METER_KEY_PERMILLE_DEFAULT, high_permille=PT_METER_HIGH_PERMILLE_DEFAULT,
+                 e_min=PT_METER_E_MIN_DEFAULT, e_max=PT_METER_E_MAX_DEFAULT, white_min=1.0, rate=1.0, window=(0, 0, 0, 0)):
+        super().__init__(key, key_permille, high_permille, e_min, e_max, white_min, rate, window[0], window[1], window[2], window[3], 0)
+
+    def copy(self):
+        out = PtMeterOptions()
+        C.memmove(C.byref(out), C.byref(self), C.sizeof(self))
+        return out
+
+
+class PtExposure(C.Structure):
+    """include/ptrace.h PtExposure: the exposure record pt_meter keeps on the device, 32 bytes."""
+
+    _fields_ = [
+        ("exposure", C.c_float),
+        ("white", C.c_float),
+        ("y_key", C.c_float),
+        ("y_high", C.c_float),
+        ("lit", C.c_uint64),
+        ("below", C.c_uint32),
+        ("meterings", C.c_uint32),
+    ]
+
+    def copy(self):
+        out = PtExposure()
+        C.memmove(C.byref(out), C.byref(self), C.sizeof(self))
+        return out
+
+
+class PtToneOptions(C.Structure):
+    """include/ptrace.h PtToneOptions: curve (PT_TONE_*), gamma, and the exposure — 0 reads exposure and white from the device
+    record, a positive value uses these —, 16 bytes."""
+
+    _fields_ = [
+        ("curve", C.c_int32),
+        ("gamma", C.c_int32),
+        ("exposure", C.c_float),
+        ("white", C.c_float),
+    ]
+
+    def __init__(self, curve=PT_TONE_REINHARD, gamma=1, exposure=0.0, white=1.0):
+        super().__init__(curve, gamma, exposure, white)
 
 
 class PtHostSphere(C.Structure):

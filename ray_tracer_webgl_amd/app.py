@@ -13,7 +13,9 @@ run_setters -> render -> (save).  Two display modes:
     src/state.rs:343-346) clears the accumulation — or, with `reproject` options given, carries it over
     into the new view (temporal reprojection, include/ptrace.h pt_reproject); with `carry_estimate` the
     per-pixel error estimate is kept and carried too (pt_reproject_estimate), so the filtered read-outs of the
-    tracer know of the history while the camera moves.
+    tracer know of the history while the camera moves.  With `tone=(abi.PtMeterOptions, abi.PtToneOptions)` every
+    rendered tick meters the accumulation on the device (pt_meter) and the canvas is drawn through the tone curve
+    (pt_resolve_toned_rgba8) instead of the clamp of pt_resolve_rgba8; `tone=None` draws the canvas as ever.
 """
 import time
 
@@ -29,14 +31,16 @@ class FrameLoop:
     LOOSE_FRAMES = 32
 
     def __init__(self, width, height, device=0, mode="reference", host_spheres=None, debugging=False, reproject=None,
-                 carry_estimate=False):
+                 carry_estimate=False, tone=None):
         assert mode in ("reference", "linear")
+        assert tone is None or mode == "linear", "the toned canvas reads the fp32 accumulation: linear mode only"
         assert reproject is None or mode == "linear", "temporal reprojection carries the fp32 accumulation: linear mode only"
         assert not carry_estimate or reproject is not None, "carry_estimate needs `reproject` options"
         self.mode = mode
         self.reproject = reproject  # abi.PtReprojectOptions, or None: a camera change clears the accumulation
         self.carry_estimate = bool(carry_estimate)  # keep the error estimate and carry it with the accumulation
         self._estimate_spp = 0  # samples_per_pixel of the ticks the estimate holds (0: none): a fold needs the same value
+        self.tone = tone  # (abi.PtMeterOptions, abi.PtToneOptions), or None: the canvas is resolve_rgba8's
         self.debugging = bool(debugging)
         self.state = State(width, height)
         if self.debugging:  # State.enable_debugging (src/state.rs:87): the shader's cursor dot and selected-object outline
@@ -50,6 +54,8 @@ class FrameLoop:
             self.tracer.reproject_option(True)
             if self.carry_estimate:
                 self.tracer.error_estimate(True)
+        if self.tone is not None:
+            self.tracer.tone_mapping(True)
         self.grid_refits = 0
         self._loose = 0
         # two RGBA8 textures cleared to 0 (alpha 0 = "no data", shader.frag:391): in HBM, owned by the context
@@ -138,7 +144,13 @@ class FrameLoop:
                 self.tracer.reset()  # the view stands still but the tick's samples_per_pixel changed: the estimate cannot follow
             self.tracer.render()
             self._estimate_spp = p.samples_per_pixel
-            self._canvas = self.tracer.resolve_rgba8(True)
+            if self.tone is not None:
+                # meter, then read out with the record the metering leaves on the device (PtToneOptions.exposure == 0: no
+                # host round trip between the two); the exposure adapts from tick to tick at the meter options' rate
+                self.tracer.meter(self.tone[0])
+                self._canvas = self.tracer.toned_rgba8(self.tone[1])
+            else:
+                self._canvas = self.tracer.resolve_rgba8(True)
         self.frames_rendered += 1
         return True
 

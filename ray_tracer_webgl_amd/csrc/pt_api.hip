@@ -37,6 +37,7 @@
 #include "pt_reproject.hpp"
 #include "pt_query.hpp"
 #include "pt_radiance.hpp"
+#include "pt_tone.hpp"
 #include "pt_buffers.hpp"
 #include "pt_ctx_state.hpp"
 
@@ -124,7 +125,7 @@ struct pt_ctx {
   ptstate::AccumTally tally;
   PtParams params{};
   uint32_t local_rows = 0;
-  // The buffers sized for the row partition, in five sets (pt_buffers.hpp: what each holds, how it is sized, what a failed
+  // The buffers sized for the row partition, in five sets, and a sixth of a fixed size (pt_buffers.hpp: what each holds, how it is sized, what a failed
   // allocation leaves; ensure_buffers fits them).  frame: what every context has — the accumulation (own or caller-bound), the
   // per-pass slabs, the work queue's per-tile cost and order (with `order` below), the reference's frame (two RGBA8 textures +
   // canvas) and the read-out staging.  The opt-in sets hold their `on` flag and validity beside their buffers: est
@@ -132,12 +133,14 @@ struct pt_ctx {
   // tile records then their tallies), feat (PT_OPT_FEATURES; pt_kernels_features.hip: written by pt_render_features, which also
   // needs the uuid arrays below), query (PT_OPT_RAY_QUERIES; pt_kernels_query.hip: rays staged into the point and normal planes,
   // records read back from all four; the frame's own tile order belongs to the render launches; pt_query_rays also needs the
-  // uuid arrays) and hist (PT_OPT_REPROJECT; pt_kernels_reproject.hip: pt_keep_history / pt_load_history).
+  // uuid arrays) and hist (PT_OPT_REPROJECT; pt_kernels_reproject.hip: pt_keep_history / pt_load_history).  expo (PT_OPT_TONEMAP;
+  // pt_kernels_display.hip: pt_meter's tallies and the exposure record) is the one set no extent sizes: resizes leave it alone.
   ptbuf::FrameSet<float4> frame;
   ptbuf::EstimateSet<float4> est;
   ptbuf::FeatureSet<float4> feat;
   ptbuf::QuerySet<float4> query;
   ptbuf::HistorySet<float4> hist;
+  ptbuf::ExposureSet expo;
   uint32_t reserved_passes = 1;
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   PathTuner geom;
@@ -319,6 +322,12 @@ int ensure_buffers(pt_ctx* c) {
     if (!f.ok()) return fit_refused(c, "query planes", f, e);
   }
   if (const ptbuf::Fit f = c->hist.fit(e); !f.ok()) return fit_refused(c, "history planes", f, e);
+  {
+    // (fixed size: fresh once, when the option comes on — or again after a refused allocation; no tallies, no record yet)
+    const ptbuf::Fit f = c->expo.fit();
+    if (f.fresh & c->expo.STATE) PT_HIP(c, zero(c->expo.state, c->expo.kWords));
+    if (!f.ok()) return fit_refused(c, "exposure state", f, e);
+  }
   return PT_OK;
 }
 
@@ -332,10 +341,11 @@ int frame_buffers_ready(pt_ctx* c, const char* who) {
 }
 
 // an entry point (`who`) of an opt-in set that is off
-enum OptInSet { SET_ESTIMATE, SET_FEATURES, SET_QUERIES, SET_REPROJECT };
+enum OptInSet { SET_ESTIMATE, SET_FEATURES, SET_QUERIES, SET_REPROJECT, SET_TONEMAP };
 int option_off(pt_ctx* c, const char* who, OptInSet set, int code = PT_ERR_NOT_READY) {
   static const char* const what[] = {"the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", "the feature planes are off (pt_set_option PT_OPT_FEATURES)",
-                                     "ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)", "reprojection is off (pt_set_option PT_OPT_REPROJECT)"};
+                                     "ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)", "reprojection is off (pt_set_option PT_OPT_REPROJECT)",
+                                     "tone mapping is off (pt_set_option PT_OPT_TONEMAP)"};
   return fail(c, code, "%s: %s", who, what[set]);
 }
 
@@ -2066,6 +2076,8 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     if (value == 1 && !c->feat.on) return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_REPROJECT needs PT_OPT_FEATURES on (it reads the feature planes)");
     return set_buffer_option(c, value, "reprojection", c->hist, reproject_off, pt_reproject_kernel_handle(), [] { return PT_OK; });
   }
+  if (key == PT_OPT_TONEMAP)
+    return set_buffer_option(c, value, "tone mapping", c->expo, [c] { c->expo.release(); }, pt_display_kernel(PT_D_METER), [] { return PT_OK; });
   return fail(c, PT_ERR_INVALID, "pt_set_option: unknown key %d", key);
 }
 
@@ -2282,6 +2294,133 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
     PT_HIP(c, hipStreamSynchronize(c->stream));
   }
   return PT_OK;
+}
+
+// ---- exposure metering and the toned read-out (PT_OPT_TONEMAP; include/ptrace.h has the contract) -------------
+// The source image of pt_meter and the toned read-outs, ready for a kernel: the accumulation (src NULL: what pt_resolve asks of
+// the context is asked here), the caller's device texels in place, or the caller's host texels copied into the pass slabs (free
+// between calls, as pt_query_radiance uses them: the read-outs' own staging holds the result).
+struct ToneSource {
+  const pttone::F4* texels = nullptr;
+  int from_accum = 0;
+  bool staged = false;  // a host source: the call synchronises before it returns
+};
+static int tone_source(pt_ctx* c, const char* who, const float* src, ToneSource& s) {
+  if (!src && c->tally.nothing_rendered()) return fail(c, PT_ERR_NOT_READY, "%s: nothing rendered yet", who);
+  PT_TRY(frame_buffers_ready(c, who));
+  const size_t n_pix = n_pixels(c);
+  if (!src) {
+    s.texels = reinterpret_cast<const pttone::F4*>(c->frame.accum);
+    s.from_accum = 1;
+  } else if (device_pointer(src)) {
+    s.texels = reinterpret_cast<const pttone::F4*>(src);
+  } else {
+    if (n_pix) PT_HIP(c, hipMemcpyAsync(c->frame.slab.get(), src, n_pix * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    s.texels = reinterpret_cast<const pttone::F4*>(c->frame.slab.get());
+    s.staged = true;
+  }
+  return PT_OK;
+}
+
+PT_API int pt_meter(pt_ctx* c, const float* src, const PtMeterOptions* opt) {
+  if (!c || !opt) return fail(c, PT_ERR_INVALID, "pt_meter: NULL argument");
+  if (!pttone::meter_options_valid(*opt))
+    return fail(c, PT_ERR_INVALID, "pt_meter: key, e_min <= e_max and white_min must be finite and positive, key_permille <= high_permille <= 1000, rate no NaN");
+  if (!c->expo.on) return option_off(c, "pt_meter", SET_TONEMAP);
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_meter: not inside a stream capture");
+  ToneSource s;
+  PT_TRY(tone_source(c, "pt_meter", src, s));
+  if (!c->expo.in_place()) return fail(c, PT_ERR_CAPACITY, "pt_meter: the exposure state is not allocated (an earlier allocation failed)");
+  uint32_t* state = c->expo.state.get();
+  uint32_t n_pix = (uint32_t)n_pixels(c), width = c->width;
+  const ptstate::Partition part(c->params);
+  pttone::Window win = {opt->x0, opt->y0, opt->w, opt->h, part.rows, part.index, part.count};
+  PT_HIP(c, hipMemsetAsync(state, 0, pttone::kTallies * sizeof(uint32_t), c->stream));
+  if (n_pix) {  // (a band without rows: N == 0 on the device)
+    void* kargs[] = {&s.texels, &s.from_accum, &n_pix, &width, &win, &state};
+    PT_HIP(c, hipLaunchKernel(pt_display_kernel(PT_D_METER), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
+  }
+  PtMeterOptions rule = *opt;
+  int was_valid = c->expo.valid ? 1 : 0;
+  void* kargs[] = {&state, &rule, &was_valid};
+  PT_HIP(c, hipLaunchKernel(pt_display_kernel(PT_D_EXPOSURE), dim3(1), dim3(256), kargs, 0, c->stream));
+  c->expo.valid = true;
+  if (s.staged) PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+PT_API int pt_meter_read(pt_ctx* c, PtExposure* out, uint32_t hist256[256]) {
+  if (!c) return PT_ERR_INVALID;
+  if (!c->expo.on) return option_off(c, "pt_meter_read", SET_TONEMAP);
+  if (!c->expo.valid || !c->expo.in_place()) return fail(c, PT_ERR_NOT_READY, "pt_meter_read: no exposure yet (pt_meter or pt_meter_set come first)");
+  PT_HIP(c, hipSetDevice(c->device));
+  PT_TRY(not_capturing(c, "pt_meter_read"));
+  const uint32_t* state = c->expo.state.get();
+  if (hist256) PT_HIP(c, hipMemcpyAsync(hist256, state, pttone::kBins * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (out) PT_HIP(c, hipMemcpyAsync(out, state + pttone::kTallies, sizeof(PtExposure), hipMemcpyDeviceToHost, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+PT_API int pt_meter_set(pt_ctx* c, const PtExposure* rec) {
+  if (!c || !rec) return fail(c, PT_ERR_INVALID, "pt_meter_set: NULL argument");
+  if (!pttone::finite_positive(rec->exposure) || !pttone::finite_positive(rec->white))
+    return fail(c, PT_ERR_INVALID, "pt_meter_set: exposure and white must be finite and positive");
+  if (!c->expo.on) return option_off(c, "pt_meter_set", SET_TONEMAP);
+  PT_HIP(c, hipSetDevice(c->device));
+  PT_TRY(not_capturing(c, "pt_meter_set"));
+  if (!c->expo.in_place()) return fail(c, PT_ERR_CAPACITY, "pt_meter_set: the exposure state is not allocated (an earlier allocation failed)");
+  PT_HIP(c, hipMemcpyAsync(c->expo.state.get() + pttone::kTallies, rec, sizeof(PtExposure), hipMemcpyHostToDevice, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  c->expo.valid = true;
+  return PT_OK;
+}
+
+PT_API int pt_exposure_solve(const uint32_t hist256[256], uint32_t below, const PtMeterOptions* opt, const PtExposure* prev, PtExposure* out) {
+  if (!hist256 || !opt || !out || !pttone::meter_options_valid(*opt)) return PT_ERR_INVALID;
+  const PtExposure none{};
+  *out = pttone::solve(hist256, below, *opt, prev != nullptr, prev ? *prev : none);
+  return PT_OK;
+}
+
+// the two toned read-outs: `bytes` 0 float texels, 1 RGBA8
+static int resolve_toned(pt_ctx* c, const char* who, const float* src, const PtToneOptions* opt, void* rgba_out, int bytes) {
+  if (!c || !opt || !rgba_out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
+  if (opt->curve != PT_TONE_CLAMP && opt->curve != PT_TONE_REINHARD && opt->curve != PT_TONE_FILMIC)
+    return fail(c, PT_ERR_INVALID, "%s: curve %d is none of PT_TONE_CLAMP, PT_TONE_REINHARD, PT_TONE_FILMIC", who, (int)opt->curve);
+  const bool from_record = opt->exposure == 0.0f;
+  if (!from_record && !pttone::finite_positive(opt->exposure))
+    return fail(c, PT_ERR_INVALID, "%s: exposure must be 0 (the device record's) or finite and positive", who);
+  if (!from_record && opt->curve == PT_TONE_REINHARD && !(opt->white > 0.0f))
+    return fail(c, PT_ERR_INVALID, "%s: PT_TONE_REINHARD needs a white above 0", who);
+  if (from_record) {
+    if (!c->expo.on) return option_off(c, who, SET_TONEMAP);
+    if (!c->expo.valid || !c->expo.in_place()) return fail(c, PT_ERR_NOT_READY, "%s: no exposure yet (pt_meter or pt_meter_set come first)", who);
+  }
+  PT_HIP(c, hipSetDevice(c->device));
+  PT_TRY(not_capturing(c, who));
+  ToneSource s;
+  PT_TRY(tone_source(c, who, src, s));
+  uint32_t n_pix = (uint32_t)n_pixels(c);
+  if (n_pix == 0) return PT_OK;
+  void* out = c->frame.resolve.get();
+  int32_t curve = opt->curve;
+  int gamma = opt->gamma;
+  float exposure = opt->exposure, white = opt->white;
+  const PtExposure* record = from_record ? reinterpret_cast<const PtExposure*>(c->expo.state.get() + pttone::kTallies) : nullptr;
+  void* kargs[] = {&s.texels, &s.from_accum, &out, &bytes, &n_pix, &curve, &gamma, &exposure, &white, &record};
+  PT_HIP(c, hipLaunchKernel(pt_display_kernel(PT_D_TONE), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, hipMemcpyAsync(rgba_out, out, (size_t)n_pix * (bytes ? 4 : sizeof(float4)), hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+PT_API int pt_resolve_toned(pt_ctx* c, const float* src, const PtToneOptions* opt, float* rgba_out) {
+  return resolve_toned(c, "pt_resolve_toned", src, opt, rgba_out, 0);
+}
+PT_API int pt_resolve_toned_rgba8(pt_ctx* c, const float* src, const PtToneOptions* opt, uint8_t* rgba_out) {
+  return resolve_toned(c, "pt_resolve_toned_rgba8", src, opt, rgba_out, 1);
 }
 
 // ---- temporal reprojection (PT_OPT_REPROJECT; include/ptrace.h has the contract) ------------------------------

@@ -237,4 +237,29 @@ struct HistorySet {
   }
 };
 
+// PT_OPT_TONEMAP: the metering's tallies — 256 bins, `below`, the pixels looked at — and behind them the PtExposure record, in one
+// allocation of a FIXED size: the only set whose fit does not read the extent, so no resize and no repartition touches it.  The
+// record is the viewer's adaptation, not a product of the scene: `valid` (metered or set since the option came on) has no row in
+// the change table of pt_ctx_state.hpp and ends only where the set is released, or reallocated after a refused allocation.
+struct ExposureSet {
+  enum : uint32_t { STATE = 1 };
+  static constexpr size_t kTallies = 258, kWords = kTallies + sizeof(PtExposure) / sizeof(uint32_t);
+  bool on = false;
+  bool valid = false;
+  DevBuf<uint32_t> state;
+
+  Fit fit() {
+    Fit f;
+    if (!on || state.holds(kWords)) return f;
+    valid = false;
+    refit(f, state, kWords, STATE);
+    return f;
+  }
+  bool in_place() const { return on && state.holds(kWords); }
+  void release() {
+    on = valid = false;
+    state.release();
+  }
+};
+
 }  // namespace ptbuf

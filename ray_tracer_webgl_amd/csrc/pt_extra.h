@@ -96,6 +96,9 @@ extern "C" const void* pt_error_kernel(int id);
 // pt_reproject_estimate's, which gathers the error estimate's state in the same pass
 extern "C" const void* pt_reproject_kernel_handle(void);
 extern "C" const void* pt_reproject_estimate_kernel_handle(void);
+// pt_kernels_display.hip (a code object of its own): exposure metering's two kernels and the toned read-out's (PT_OPT_TONEMAP)
+enum { PT_D_METER = 0, PT_D_EXPOSURE, PT_D_TONE, PT_D_COUNT };
+extern "C" const void* pt_display_kernel(int id);
 // pt_kernels_query.hip, beside its ray-query builds (PT_OPT_RAY_QUERIES, pt_query_rays): the two kernels that move a batch of
 // rays and records between the caller's device arrays and the query planes
 extern "C" const void* pt_query_pack_kernel_handle(void);

@@ -58,6 +58,14 @@ def main(argv=None):
                     help="also write the first-hit feature planes of the frame's camera (pt_render_features: one pinhole ray per "
                          "pixel) as PREFIX_albedo.npy, PREFIX_normal.npy, PREFIX_point.npy (float32) and PREFIX_ids.npy (int32: list "
                          "index, uuid, type, front_face), each (rows, width, 4), row 0 = the image's lowest row")
+    ap.add_argument("--tone", choices=["clamp", "reinhard", "filmic"],
+                    help="read the frame out through a tone curve (pt_resolve_toned) instead of the reference's sqrt-and-clamp: for "
+                         "frames with more range than a display (config4's light).  Composes with --denoise / --denoise-patch: the "
+                         "filtered linear frame is what is metered and toned")
+    ap.add_argument("--exposure", default="auto", metavar="auto|VALUE",
+                    help="with --tone: auto meters the frame on the device (pt_meter: the median lit pixel is exposed to 0.18) and "
+                         "reads out with that record; VALUE multiplies the radiance by VALUE (Reinhard's white is then the "
+                         "metered 99th percentile exposed by VALUE, at least 1).  Default auto")
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--checkpoint", help="also save the fp32 accumulation buffer (.npz)")
     args = ap.parse_args(argv)
@@ -109,6 +117,14 @@ def main(argv=None):
             denoise_patch = parse_denoise(args.denoise_patch, abi.PT_FILTER_PATCH_KAPPA_DEFAULT)
         except ValueError as e:
             ap.error("--denoise-patch: %s" % e)
+    exposure = None
+    if args.tone is not None and args.exposure != "auto":
+        try:
+            exposure = float(args.exposure)
+        except ValueError:
+            exposure = float("nan")
+        if not (0.0 < exposure < float("inf")):
+            ap.error("--exposure: auto, or a finite positive value")
     if args.noise_target is not None or args.error_out:
         if overlay is not None:
             ap.error("--noise-target / --error-out measure the frame's noise: not with --debug-overlay")
@@ -118,17 +134,33 @@ def main(argv=None):
         pt, acc = render_scene(sc, device=args.device, passes_per_launch=per, geometry_path=geom, tune=min(per, 8), overlay=overlay)
     dt = time.perf_counter() - t0
     st = pt.stats()
+    toned = args.tone is not None  # (the filters then hand over a LINEAR frame: the tone curve and the sqrt come after them)
     if denoise is not None:
-        frame = pt.filtered_image(denoise[0], denoise[1], gamma=True)
+        frame = pt.filtered_image(denoise[0], denoise[1], gamma=not toned)
         print("denoise: radius %d, kappa %g, %.2f accepted taps per pixel" % (denoise[0], denoise[1], float(frame[..., 3].mean())))
         frame[..., 3] = 1.0   # (the taps are no alpha)
     elif denoise_patch is not None:
-        frame = pt.patch_filtered_image(denoise_patch[0], abi.PT_FILTER_MAX_PATCH, denoise_patch[1], gamma=True)
+        frame = pt.patch_filtered_image(denoise_patch[0], abi.PT_FILTER_MAX_PATCH, denoise_patch[1], gamma=not toned)
         print("denoise: radius %d, patch %d, kappa %g, %.2f accepted taps per pixel" % (
             denoise_patch[0], abi.PT_FILTER_MAX_PATCH, denoise_patch[1], float(frame[..., 3].mean())))
         frame[..., 3] = 1.0
-    else:
+    elif not toned:
         frame = pt.resolve(gamma=True)
+    else:
+        frame = None  # (the accumulation itself)
+    if toned:
+        curve = {"clamp": abi.PT_TONE_CLAMP, "reinhard": abi.PT_TONE_REINHARD, "filmic": abi.PT_TONE_FILMIC}[args.tone]
+        pt.tone_mapping(True)
+        pt.meter(abi.PtMeterOptions(), src=frame)
+        rec, _ = pt.exposure()
+        opt = abi.PtToneOptions(curve, 1, 0.0, 1.0)
+        if exposure is not None:
+            opt = abi.PtToneOptions(curve, 1, exposure, max(rec.y_high * exposure, 1.0))
+        clipped = int((pt.resolve_rgba8(True)[..., :3] == 255).sum())
+        frame = pt.toned_image(opt, src=frame)
+        print("tone: %s, exposure %g (%s), white %g; key luminance %g, %d lit pixels, %d below 2^-16; %d channel values at 255, %d without the curve" % (
+            args.tone, opt.exposure or rec.exposure, "given" if exposure is not None else "metered", opt.white if exposure is not None else rec.white,
+            rec.y_key, rec.lit, rec.below, int((frame[..., :3] >= 1.0).sum()), clipped))
     image_io.write_png(args.out, frame)
     if args.error_out:
         err = pt.error_image()

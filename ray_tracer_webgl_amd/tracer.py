@@ -511,6 +511,88 @@ class PathTracer:
             mean = np.where(samples[:, None] > 0, rec[:, 0:3] / np.maximum(samples, np.float32(1.0))[:, None], np.float32(0.0)).astype(np.float32)
         return {"sum": rec[:, 0:3], "samples": samples, "mean": mean}
 
+    # -- exposure metering and the toned read-outs (include/ptrace.h PT_OPT_TONEMAP) -----------------
+    def tone_mapping(self, on=True):
+        """Put the exposure state in place (or release it: the exposure is forgotten).  Off by default; the image bits are the
+        same either way.  The exposure survives set_spheres, set_params, resize and reset."""
+        self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_TONEMAP, 1 if on else 0))
+
+    def _tone_src(self, src):
+        """(pointer, object to keep alive) of a source image: None is the accumulation; a (local_rows, width, 4) float32 numpy
+        array is read from the host; under use_torch a torch device tensor is read in place."""
+        if src is None:
+            return None, None
+        shape = (self.local_rows, self.width, 4)
+        if self.use_torch and self._torch.is_tensor(src) and src.is_cuda:
+            t = src.to(self._torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError("source image is %s, this context holds %s" % (tuple(t.shape), shape))
+            return C.c_void_p(t.data_ptr()), t  # (the context runs on torch's current stream: the tensor's writes come first)
+        a = np.ascontiguousarray(src, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError("source image is %s, this context holds %s" % (a.shape, shape))
+        return a.ctypes.data_as(C.c_void_p), a
+
+    def meter(self, options=None, src=None):
+        """Meter the frame on the device (pt_meter): the luminance histogram of the window's pixels, then the exposure record
+        from it and the record before.  `options`: abi.PtMeterOptions (default: the header's).  `src`: None for the
+        accumulation, or linear RGBA float32 texels (see _tone_src).  Asynchronous unless `src` is a host array."""
+        opt = options if options is not None else abi.PtMeterOptions()
+        ptr, keep = self._tone_src(src)
+        self._check(self.lib.pt_meter(self._ctx, ptr, C.byref(opt)))
+        del keep
+
+    def exposure(self):
+        """(abi.PtExposure, histogram (256,) uint32) of the last metering (pt_meter_read).  Synchronises."""
+        rec = abi.PtExposure()
+        hist = np.zeros(256, np.uint32)
+        self._check(self.lib.pt_meter_read(self._ctx, C.byref(rec), hist.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return rec, hist
+
+    def set_exposure(self, rec):
+        """Load an exposure record (pt_meter_set): what a rank does with the record solved from the ranks' summed histograms."""
+        r = rec.copy()
+        self._check(self.lib.pt_meter_set(self._ctx, C.byref(r)))
+
+    @staticmethod
+    def solve_exposure(hist, below, options=None, prev=None):
+        """Kernel 2 on the host (pt_exposure_solve; no device and no context): the record of a histogram (256 counts) and `below` under
+        `options`, after the record `prev` (None: never valid)."""
+        opt = options if options is not None else abi.PtMeterOptions()
+        h = np.ascontiguousarray(hist, dtype=np.uint32)
+        if h.shape != (256,):
+            raise ValueError("solve_exposure: the histogram has 256 bins, not %s" % (h.shape,))
+        out = abi.PtExposure()
+        p = C.byref(prev) if prev is not None else None
+        rc = load().pt_exposure_solve(h.ctypes.data_as(C.POINTER(C.c_uint32)), int(below), C.byref(opt), p, C.byref(out))
+        if rc != abi.PT_OK:
+            raise PtError(rc, "pt_exposure_solve: invalid options")
+        return out
+
+    def _toned(self, fn, dtype, options, src):
+        opt = options if options is not None else abi.PtToneOptions()
+        ptr, keep = self._tone_src(src)
+        if keep is not None and not isinstance(keep, np.ndarray):
+            out = self._torch.empty((self.local_rows, self.width, 4), dtype=self._torch.float32 if dtype == np.float32 else self._torch.uint8,
+                                    device=keep.device)
+            if out.numel():
+                self._check(fn(self._ctx, ptr, C.byref(opt), C.c_void_p(out.data_ptr())))
+            return out
+        out = np.empty((self.local_rows, self.width, 4), dtype=dtype)
+        if out.size:
+            self._check(fn(self._ctx, ptr, C.byref(opt), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def toned_image(self, options=None, src=None):
+        """(local_rows, width, 4) fp32: the frame exposed, through the curve, optionally square-rooted (pt_resolve_toned);
+        a = 1.  `options`: abi.PtToneOptions — exposure 0 uses the device record of the last meter() or set_exposure().  A
+        numpy or no `src` gives a numpy array; a torch device tensor gives a torch device tensor."""
+        return self._toned(self.lib.pt_resolve_toned, np.float32, options, src)
+
+    def toned_rgba8(self, options=None, src=None):
+        """The same as bytes, alpha 255 (pt_resolve_toned_rgba8)."""
+        return self._toned(self.lib.pt_resolve_toned_rgba8, np.uint8, options, src)
+
     # -- temporal reprojection (include/ptrace.h PT_OPT_REPROJECT) ---------------------------------
     def reproject_option(self, on=True):
         """Allocate (or release) the history planes of temporal reprojection; needs feature_planes(True) first.  Off by
