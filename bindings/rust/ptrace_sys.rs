@@ -90,6 +90,17 @@ pub struct PtToneOptions {       // curve PT_TONE_*, gamma, exposure (0: the dev
     pub curve: i32, pub gamma: i32, pub exposure: f32, pub white: f32,
 }
 
+pub const PT_GLARE_MAX_LEVELS: usize = 8;
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct PtGlareOptions {      // the rule of one pt_glare, 48 bytes; weight[k - 1] is the weight of level k, the first `levels` are read
+    pub strength: f32, pub threshold: f32, pub levels: u32, pub _pad: u32, pub weight: [f32; PT_GLARE_MAX_LEVELS],
+}
+impl Default for PtGlareOptions {  // PT_GLARE_OPTIONS_DEFAULT
+    fn default() -> Self {
+        PtGlareOptions { strength: 0.15, threshold: 0.0, levels: 6, _pad: 0, weight: [0.35, 0.25, 0.18, 0.12, 0.06, 0.04, 0.0, 0.0] }
+    }
+}
+
 #[repr(C)] pub struct PtCtx { _private: [u8; 0] }
 
 #[link(name = "ptrace")]
@@ -166,6 +177,10 @@ extern "C" {
     pub fn pt_exposure_solve(hist256: *const u32, below: u32, options: *const PtMeterOptions, prev_or_null: *const PtExposure, out: *mut PtExposure) -> c_int;
     pub fn pt_resolve_toned(ctx: *mut PtCtx, src: *const f32, options: *const PtToneOptions, rgba_out: *mut f32) -> c_int;
     pub fn pt_resolve_toned_rgba8(ctx: *mut PtCtx, src: *const f32, options: *const PtToneOptions, rgba_out: *mut u8) -> c_int;
+    // glare (pt_set_option PT_OPT_GLARE 1): a share of the frame's light spread over a bloom pyramid and added back, energy
+    // conserved; src as above, rgba_out linear RGBA f32 on the host or the device (may be a device src): what pt_meter and
+    // pt_resolve_toned take next; synchronous
+    pub fn pt_glare(ctx: *mut PtCtx, src: *const f32, options: *const PtGlareOptions, rgba_out: *mut f32) -> c_int;
     // the camera moves every tick (State::update_position, src/state.rs:411-441): does the grid of a large scene still fit
     // it (0 yes / 1 no: refit now / 2 looser than needed), and the rebuild for the margin class the camera needs
     pub fn pt_grid_fit(ctx: *mut PtCtx) -> c_int;
@@ -191,6 +206,7 @@ pub const PT_OPT_FEATURES: c_int = 8;           // opt-in, 0 = off; the image bi
 pub const PT_OPT_REPROJECT: c_int = 9;          // opt-in, 0 = off; needs PT_OPT_FEATURES on
 pub const PT_OPT_RAY_QUERIES: c_int = 10;       // opt-in, 0 = off; the image bits do not depend on it
 pub const PT_OPT_TONEMAP: c_int = 11;           // opt-in, 0 = off; the image bits do not depend on it
+pub const PT_OPT_GLARE: c_int = 12;             // opt-in, 0 = off; scratch only, the image bits do not depend on it
 pub const PT_TONE_CLAMP: i32 = 0;
 pub const PT_TONE_REINHARD: i32 = 1;
 pub const PT_TONE_FILMIC: i32 = 2;

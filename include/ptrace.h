@@ -118,6 +118,9 @@ enum {
   PT_OPT_TONEMAP = 11,     /* 1: put the exposure state in place (see pt_meter below; 258 tallies and one PtExposure record, about
                              1 KB whatever the size of the frame) and load the display kernels' code object.  0 (default): release
                              it; the exposure is forgotten.  The image bits of a context are the same either way. */
+  PT_OPT_GLARE = 12,       /* 1: allocate the glare pyramid of pt_glare (see below; one float4 per texel of the eight levels, about a
+                             third of the frame: 5.4 bytes per local pixel; scratch only, no state) and load the glare kernels' code
+                             object.  0 (default): release it.  The image bits of a context are the same either way. */
 };
 
 /* ---- background modes ----------------------------------------------------------------------- */
@@ -917,6 +920,56 @@ int pt_exposure_solve(const uint32_t hist256[256], uint32_t below, const PtMeter
                       PtExposure* out);
 int pt_resolve_toned(pt_ctx* ctx, const float* src, const PtToneOptions* options, float* rgba_out);
 int pt_resolve_toned_rgba8(pt_ctx* ctx, const float* src, const PtToneOptions* options, uint8_t* rgba_out);
+
+/* ---- glare: an energy-conserving bloom pyramid ahead of the toned read-out (build extension, opt-in: PT_OPT_GLARE) -------------
+ * After any tone curve a light is a flat disc at the byte 255; what says "this is fifteen times brighter than the wall" on a
+ * display is the veil a lens or an eye puts around it.  pt_glare spreads a share of the frame's light over a pyramid of levels
+ * and adds it back: accumulation -> [filter] -> GLARE -> meter -> tone.  It touches no existing read-out and composes through
+ * `src`, as pt_meter and pt_resolve_toned do.  Three kernels in a code object of their own (loaded when the option is turned on);
+ * the arithmetic is csrc/pt_glare.hpp, shared with the CPU checks.
+ * THE OPTION puts one float4 buffer in place, the pyramid: levels 1 .. PT_GLARE_MAX_LEVELS of the local frame, refitted by
+ * pt_resize and by a repartition.  It is scratch: nothing in it outlives a call, it has no validity.
+ * `src` and `rgba_out` are pt_resolve_toned's: src NULL is the accumulation (x.c = v.c * scale, scale = v.w > 0 ? 1 / v.w : 0),
+ * otherwise width*local_rows linear RGBA fp32 texels on the host or the device (.a not read; a host src is copied into the pass
+ * slabs first); rgba_out is a host or device pointer and may equal a device src; the call synchronises.  The output is LINEAR
+ * radiance {r, g, b, 1}: what pt_meter(ctx, out, ...) and pt_resolve_toned(ctx, out, ...) take next.
+ * THE STATEMENTS, fp32, ONE IEEE operation per statement, nothing fused.  (w_0, h_0) is the frame, w_k = (w_{k-1} + 1) / 2,
+ * h_k likewise; weight[k] below is the weight of level k, PtGlareOptions.weight[k - 1].  Per channel c:
+ *   bright, per pixel:   x = source colour ;  Y = luminance(x)           (pt_meter's five statements)
+ *                        if !(Y - Y == 0):         b.c = 0               (NaN or infinite: one bad pixel must not veil the frame)
+ *                        else if threshold == 0:   b.c = x.c
+ *                        else: t = Y - threshold ; if !(t > 0) b.c = 0 else { m = t / Y ;  b.c = x.c * m }
+ *   down, D_0 = b, D_k from D_{k-1}, k = 1 .. levels.  First along x, then along y; the x pass's result is rounded to fp32:
+ *                        taps t0..t3 at 2X-1, 2X, 2X+1, 2X+2, each index clamped to [0, w_{k-1} - 1]
+ *                        o = t0 + t3 ;  i = t1 + t2 ;  i = 3 * i ;  s = o + i ;  v = s * 0.125
+ *   up(A) to a (w, h) level from a (W, H) level.  First along x, then along y:
+ *                        p = X >> 1 ;  q = (X odd) ? p + 1 : p - 1 ;  both clamped to [0, W - 1]
+ *                        t = 3 * A[p] ;  t = t + A[q] ;  v = t * 0.25
+ *   gather:              U_levels = weight[levels] * D_levels
+ *                        k = levels - 1 .. 1:  a = weight[k] * D_k ;  U_k = a + up(U_{k+1})
+ *   composite, per pixel: G = up(U_1) at frame size ;  d = G.c - b.c ;  d = d * strength ;  out.c = x.c + d ;  out.w = 1
+ * down's taps are 1 3 3 1 over 8 and up's 3 1 over 4: both sum to one and both are exact on a constant, so with weights that add up
+ * to 1 the glare CONSERVES ENERGY — a constant frame comes back bit for bit, and what the veil gains the light's own pixels
+ * lose (d is negative there).  The bits do not depend on how the kernels tile a level.
+ * REFUSALS, in this order: PT_ERR_INVALID for a NULL ctx, options or rgba_out, a strength that is not finite or outside [0, 1], a
+ * threshold that is not finite or negative, levels outside 1 .. PT_GLARE_MAX_LEVELS, a weight of a used level that is not finite or
+ * negative (the weights past `levels` are not read); PT_ERR_NOT_READY while the option is off; PT_ERR_INVALID on a band context
+ * (a row partition of more than one rank: its rows are interleaved and its neighbours live on other ranks — an N-rank frame is
+ * glared after the gather, on a context of the whole frame, through a non-NULL src); PT_ERR_INVALID inside a stream capture;
+ * for src == NULL what pt_resolve would answer; PT_ERR_CAPACITY while the pyramid is not in place.  A context without rows
+ * launches nothing.
+ * WHAT THE CALL LEAVES ALONE is what pt_resolve_toned leaves alone, and the exposure record. */
+#define PT_GLARE_MAX_LEVELS 8
+typedef struct PtGlareOptions {
+  float strength;    /* share of the spread light that is added back, finite, 0 .. 1          */
+  float threshold;   /* linear luminance above which a pixel spills; 0: every pixel, whole    */
+  uint32_t levels;   /* 1 .. PT_GLARE_MAX_LEVELS                                              */
+  uint32_t _pad;
+  float weight[PT_GLARE_MAX_LEVELS]; /* weight of level 1 .. levels; used as they are; each finite and >= 0;
+                                        the glare conserves energy when they add up to 1      */
+} PtGlareOptions; /* 48 bytes */
+#define PT_GLARE_OPTIONS_DEFAULT {0.15f, 0.0f, 6u, 0u, {0.35f, 0.25f, 0.18f, 0.12f, 0.06f, 0.04f, 0.0f, 0.0f}}
+int pt_glare(pt_ctx* ctx, const float* src, const PtGlareOptions* options, float* rgba_out);
 
 /* ---- temporal blend of the reference, static/shader.frag:387-404 + src/webgl.rs:186-204 --------
  * Blends the current resolved, gamma-encoded frame with `prev_rgba8` (the ping-pong texture)

@@ -37,6 +37,11 @@ PT_OPT_REPROJECT = 9  # temporal reprojection's history planes (pt_keep_history,
 PT_OPT_RAY_QUERIES = 10  # the query planes of pt_query_rays (closest hits for the caller's rays), pt_query_batch
 PT_OPT_TONEMAP = 11  # the exposure state of pt_meter and the toned read-outs (pt_meter_read, pt_meter_set, pt_resolve_toned, pt_resolve_toned_rgba8)
 PT_TONE_CLAMP, PT_TONE_REINHARD, PT_TONE_FILMIC = 0, 1, 2  # PtToneOptions.curve
+PT_OPT_GLARE = 12  # the pyramid of pt_glare (scratch only, no state)
+PT_GLARE_MAX_LEVELS = 8
+PT_GLARE_STRENGTH_DEFAULT = 0.15    # PtGlareOptions: the share of the spread light that is added back
+PT_GLARE_LEVELS_DEFAULT = 6         # ... the levels in use
+PT_GLARE_WEIGHTS_DEFAULT = (0.35, 0.25, 0.18, 0.12, 0.06, 0.04, 0.0, 0.0)  # ... and their weights (they add up to 1)
 PT_METER_KEY_DEFAULT = 0.18            # PtMeterOptions: the luminance the key percentile is exposed to
 PT_METER_KEY_PERMILLE_DEFAULT = 500    # ... the percentile that is the key
 PT_METER_HIGH_PERMILLE_DEFAULT = 990   # ... and the one that becomes white
@@ -332,6 +337,28 @@ class PtToneOptions(C.Structure):
 
     def __init__(self, curve=PT_TONE_REINHARD, gamma=1, exposure=0.0, white=1.0):
         super().__init__(curve, gamma, exposure, white)
+
+
+class PtGlareOptions(C.Structure):
+    """include/ptrace.h PtGlareOptions: the rule of one pt_glare, 48 bytes.  `weights`: the weights of level 1 .. levels (at most
+    PT_GLARE_MAX_LEVELS; the rest are 0); the glare conserves energy when they add up to 1."""
+
+    _fields_ = [
+        ("strength", C.c_float),
+        ("threshold", C.c_float),
+        ("levels", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("weight", C.c_float * PT_GLARE_MAX_LEVELS),
+    ]
+
+    def __init__(self, strength=PT_GLARE_STRENGTH_DEFAULT, threshold=0.0, levels=PT_GLARE_LEVELS_DEFAULT, weights=PT_GLARE_WEIGHTS_DEFAULT):
+        w = tuple(weights) + (0.0,) * (PT_GLARE_MAX_LEVELS - len(tuple(weights)))
+        super().__init__(strength, threshold, levels, 0, (C.c_float * PT_GLARE_MAX_LEVELS)(*w))
+
+    def copy(self):
+        out = PtGlareOptions()
+        C.memmove(C.byref(out), C.byref(self), C.sizeof(self))
+        return out
 
 
 class PtHostSphere(C.Structure):

@@ -15,8 +15,11 @@ run_setters -> render -> (save).  Two display modes:
     per-pixel error estimate is kept and carried too (pt_reproject_estimate), so the filtered read-outs of the
     tracer know of the history while the camera moves.  With `tone=(abi.PtMeterOptions, abi.PtToneOptions)` every
     rendered tick meters the accumulation on the device (pt_meter) and the canvas is drawn through the tone curve
-    (pt_resolve_toned_rgba8) instead of the clamp of pt_resolve_rgba8; `tone=None` draws the canvas as ever.
+    (pt_resolve_toned_rgba8) instead of the clamp of pt_resolve_rgba8; `tone=None` draws the canvas as ever.  With
+    `glare=abi.PtGlareOptions()` beside `tone`, every rendered tick is first glared into a device buffer (pt_glare) and that
+    buffer is what is metered and toned; `glare=None` is the loop without it, byte for byte.
 """
+import ctypes as C
 import time
 
 import numpy as np
@@ -31,9 +34,10 @@ class FrameLoop:
     LOOSE_FRAMES = 32
 
     def __init__(self, width, height, device=0, mode="reference", host_spheres=None, debugging=False, reproject=None,
-                 carry_estimate=False, tone=None):
+                 carry_estimate=False, tone=None, glare=None):
         assert mode in ("reference", "linear")
         assert tone is None or mode == "linear", "the toned canvas reads the fp32 accumulation: linear mode only"
+        assert glare is None or tone is not None, "the glared frame is linear radiance: it is drawn through `tone`"
         assert reproject is None or mode == "linear", "temporal reprojection carries the fp32 accumulation: linear mode only"
         assert not carry_estimate or reproject is not None, "carry_estimate needs `reproject` options"
         self.mode = mode
@@ -41,6 +45,8 @@ class FrameLoop:
         self.carry_estimate = bool(carry_estimate)  # keep the error estimate and carry it with the accumulation
         self._estimate_spp = 0  # samples_per_pixel of the ticks the estimate holds (0: none): a fold needs the same value
         self.tone = tone  # (abi.PtMeterOptions, abi.PtToneOptions), or None: the canvas is resolve_rgba8's
+        self.glare = glare  # abi.PtGlareOptions, or None: the accumulation itself is metered and toned
+        self._glared = None  # the device buffer of the glared frame
         self.debugging = bool(debugging)
         self.state = State(width, height)
         if self.debugging:  # State.enable_debugging (src/state.rs:87): the shader's cursor dot and selected-object outline
@@ -56,6 +62,11 @@ class FrameLoop:
                 self.tracer.error_estimate(True)
         if self.tone is not None:
             self.tracer.tone_mapping(True)
+        if self.glare is not None:
+            import torch  # (plumbing: the device buffer between pt_glare and the metering)
+
+            self.tracer.glare(True)
+            self._glared = torch.empty((height, width, 4), dtype=torch.float32, device="cuda:%d" % device)
         self.grid_refits = 0
         self._loose = 0
         # two RGBA8 textures cleared to 0 (alpha 0 = "no data", shader.frag:391): in HBM, owned by the context
@@ -147,8 +158,12 @@ class FrameLoop:
             if self.tone is not None:
                 # meter, then read out with the record the metering leaves on the device (PtToneOptions.exposure == 0: no
                 # host round trip between the two); the exposure adapts from tick to tick at the meter options' rate
-                self.tracer.meter(self.tone[0])
-                self._canvas = self.tracer.toned_rgba8(self.tone[1])
+                src = None
+                if self.glare is not None:  # accumulation -> glare -> meter -> tone, the linear frame staying on the device
+                    src = C.c_void_p(self._glared.data_ptr())
+                    self.tracer.glare_into(src, options=self.glare)
+                self.tracer.meter(self.tone[0], src=src)
+                self._canvas = self.tracer.toned_rgba8(self.tone[1], src=src)
             else:
                 self._canvas = self.tracer.resolve_rgba8(True)
         self.frames_rendered += 1

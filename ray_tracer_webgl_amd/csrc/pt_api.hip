@@ -38,6 +38,7 @@
 #include "pt_query.hpp"
 #include "pt_radiance.hpp"
 #include "pt_tone.hpp"
+#include "pt_glare.hpp"
 #include "pt_buffers.hpp"
 #include "pt_ctx_state.hpp"
 
@@ -135,12 +136,14 @@ struct pt_ctx {
   // records read back from all four; the frame's own tile order belongs to the render launches; pt_query_rays also needs the
   // uuid arrays) and hist (PT_OPT_REPROJECT; pt_kernels_reproject.hip: pt_keep_history / pt_load_history).  expo (PT_OPT_TONEMAP;
   // pt_kernels_display.hip: pt_meter's tallies and the exposure record) is the one set no extent sizes: resizes leave it alone.
+  // glare (PT_OPT_GLARE; pt_kernels_glare.hip: pt_glare's pyramid) is sized from the width and the rows in place; scratch, no state.
   ptbuf::FrameSet<float4> frame;
   ptbuf::EstimateSet<float4> est;
   ptbuf::FeatureSet<float4> feat;
   ptbuf::QuerySet<float4> query;
   ptbuf::HistorySet<float4> hist;
   ptbuf::ExposureSet expo;
+  ptbuf::GlareSet<float4> glare;
   uint32_t reserved_passes = 1;
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   PathTuner geom;
@@ -328,6 +331,8 @@ int ensure_buffers(pt_ctx* c) {
     if (f.fresh & c->expo.STATE) PT_HIP(c, zero(c->expo.state, c->expo.kWords));
     if (!f.ok()) return fit_refused(c, "exposure state", f, e);
   }
+  // (scratch: a fresh pyramid is not zeroed, every pt_glare writes what it reads)
+  if (const ptbuf::Fit f = c->glare.fit(c->width, c->local_rows); !f.ok()) return fit_refused(c, "glare pyramid", f, e);
   return PT_OK;
 }
 
@@ -341,11 +346,11 @@ int frame_buffers_ready(pt_ctx* c, const char* who) {
 }
 
 // an entry point (`who`) of an opt-in set that is off
-enum OptInSet { SET_ESTIMATE, SET_FEATURES, SET_QUERIES, SET_REPROJECT, SET_TONEMAP };
+enum OptInSet { SET_ESTIMATE, SET_FEATURES, SET_QUERIES, SET_REPROJECT, SET_TONEMAP, SET_GLARE };
 int option_off(pt_ctx* c, const char* who, OptInSet set, int code = PT_ERR_NOT_READY) {
   static const char* const what[] = {"the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", "the feature planes are off (pt_set_option PT_OPT_FEATURES)",
                                      "ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)", "reprojection is off (pt_set_option PT_OPT_REPROJECT)",
-                                     "tone mapping is off (pt_set_option PT_OPT_TONEMAP)"};
+                                     "tone mapping is off (pt_set_option PT_OPT_TONEMAP)", "the glare is off (pt_set_option PT_OPT_GLARE)"};
   return fail(c, code, "%s: %s", who, what[set]);
 }
 
@@ -2078,6 +2083,8 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
   }
   if (key == PT_OPT_TONEMAP)
     return set_buffer_option(c, value, "tone mapping", c->expo, [c] { c->expo.release(); }, pt_display_kernel(PT_D_METER), [] { return PT_OK; });
+  if (key == PT_OPT_GLARE)
+    return set_buffer_option(c, value, "glare", c->glare, [c] { c->glare.release(); }, pt_glare_kernel(PT_G_DOWN), [] { return PT_OK; });
   return fail(c, PT_ERR_INVALID, "pt_set_option: unknown key %d", key);
 }
 
@@ -2421,6 +2428,63 @@ PT_API int pt_resolve_toned(pt_ctx* c, const float* src, const PtToneOptions* op
 }
 PT_API int pt_resolve_toned_rgba8(pt_ctx* c, const float* src, const PtToneOptions* opt, uint8_t* rgba_out) {
   return resolve_toned(c, "pt_resolve_toned_rgba8", src, opt, rgba_out, 1);
+}
+
+// ---- glare: the bloom pyramid ahead of the toned read-out (PT_OPT_GLARE; include/ptrace.h has the contract) ----
+// `levels` downs, `levels` gathers, one composite into the read-outs' staging and one copy to the caller: rgba_out may be a
+// device src, which the composite still reads.
+// the down kernel's grid: a 256-thread workgroup per 16x16 tile of the level, capped — the kernel strides over the tiles
+inline uint32_t glare_tile_grid(uint32_t w, uint32_t h) { return grid_for(((w + 15u) / 16u) * ((h + 15u) / 16u), 1, 2048); }
+
+PT_API int pt_glare(pt_ctx* c, const float* src, const PtGlareOptions* opt, float* rgba_out) {
+  if (!c || !opt || !rgba_out) return fail(c, PT_ERR_INVALID, "pt_glare: NULL argument");
+  if (!ptglare::options_valid(*opt))
+    return fail(c, PT_ERR_INVALID, "pt_glare: strength must be finite and in [0, 1], threshold finite and >= 0, levels 1 .. %d, the weights of the levels in use finite and >= 0",
+                (int)PT_GLARE_MAX_LEVELS);
+  if (!c->glare.on) return option_off(c, "pt_glare", SET_GLARE);
+  if (!ptstate::Partition(c->params).every_row())
+    return fail(c, PT_ERR_INVALID, "pt_glare: a band context holds interleaved rows whose neighbours live on other ranks: glare the gathered frame on a context of "
+                                   "the whole frame, through src");
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "pt_glare: synchronises; not inside a stream capture");
+  ToneSource s;
+  PT_TRY(tone_source(c, "pt_glare", src, s));
+  if (!c->glare.in_place(c->width, c->local_rows))
+    return fail(c, PT_ERR_CAPACITY, "pt_glare: the pyramid is not allocated for the rows in place (an earlier allocation failed)");
+  uint32_t w = c->width, h = c->local_rows;
+  if ((size_t)w * h == 0) return PT_OK;
+  // level k of the pyramid (k = 1 .. levels) behind level k - 1
+  pttone::F4* level[PT_GLARE_MAX_LEVELS + 1] = {nullptr};
+  uint32_t lw[PT_GLARE_MAX_LEVELS + 1], lh[PT_GLARE_MAX_LEVELS + 1];
+  lw[0] = w; lh[0] = h;
+  pttone::F4* next = reinterpret_cast<pttone::F4*>(c->glare.pyramid.get());
+  for (uint32_t k = 1; k <= opt->levels; k++) {
+    lw[k] = ptglare::half_up(lw[k - 1]); lh[k] = ptglare::half_up(lh[k - 1]);
+    level[k] = next;
+    next += (size_t)lw[k] * lh[k];
+  }
+  float threshold = opt->threshold, strength = opt->strength;
+  for (uint32_t k = 1; k <= opt->levels; k++) {
+    const pttone::F4* from = k == 1 ? s.texels : level[k - 1];
+    int mode = k == 1 ? (s.from_accum ? 2 : 1) : 0;
+    void* kargs[] = {&from, &mode, &threshold, &lw[k - 1], &lh[k - 1], &level[k], &lw[k], &lh[k]};
+    PT_HIP(c, hipLaunchKernel(pt_glare_kernel(PT_G_DOWN), dim3(glare_tile_grid(lw[k], lh[k])), dim3(256), kargs, 0, c->stream));
+  }
+  for (uint32_t k = opt->levels; k >= 1; k--) {
+    const bool top = k == opt->levels;
+    const pttone::F4* above = top ? nullptr : level[k + 1];
+    uint32_t W = top ? 0u : lw[k + 1], H = top ? 0u : lh[k + 1];
+    float weight = opt->weight[k - 1];
+    void* kargs[] = {&level[k], &lw[k], &lh[k], &weight, &above, &W, &H};
+    PT_HIP(c, hipLaunchKernel(pt_glare_kernel(PT_G_GATHER), dim3(pixel_grid(lw[k] * lh[k])), dim3(256), kargs, 0, c->stream));
+  }
+  pttone::F4* out = reinterpret_cast<pttone::F4*>(c->frame.resolve.get());
+  const pttone::F4* u1 = level[1];
+  void* kargs[] = {&s.texels, &s.from_accum, &threshold, &strength, &u1, &lw[1], &lh[1], &out, &w, &h};
+  PT_HIP(c, hipLaunchKernel(pt_glare_kernel(PT_G_COMPOSITE), dim3(pixel_grid(w * h)), dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, hipMemcpyAsync(rgba_out, out, (size_t)w * h * sizeof(float4), hipMemcpyDefault, c->stream));
+  PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
 }
 
 // ---- temporal reprojection (PT_OPT_REPROJECT; include/ptrace.h has the contract) ------------------------------

@@ -14,6 +14,7 @@
 #include <utility>
 
 #include "../../include/ptrace.h"
+#include "pt_glare.hpp"
 
 namespace ptbuf {
 
@@ -259,6 +260,34 @@ struct ExposureSet {
   void release() {
     on = valid = false;
     state.release();
+  }
+};
+
+// PT_OPT_GLARE: pt_glare's pyramid — levels 1 .. PT_GLARE_MAX_LEVELS of the local frame, level k behind level k - 1, one texel per
+// level texel (ptglare::pyramid_texels: about a third of the frame) — sized exactly from the width and the rows in place, so a
+// resize and a repartition refit it.  It is SCRATCH: every pt_glare writes all it reads, nothing in it outlives a call, so it
+// carries no validity and has no row in the change table of pt_ctx_state.hpp, and a fresh pyramid is not zeroed.  A frame without
+// rows is sized as one texel (0 counts as 1, as in Extent).
+template <class Texel>
+struct GlareSet {
+  enum : uint32_t { PYRAMID = 1 };
+  bool on = false;
+  DevBuf<Texel> pyramid;
+
+  static size_t texels(uint32_t width, uint32_t rows) {
+    const size_t n = ptglare::pyramid_texels(width, rows, PT_GLARE_MAX_LEVELS);
+    return n ? n : 1;
+  }
+  Fit fit(uint32_t width, uint32_t rows) {
+    Fit f;
+    if (!on || pyramid.holds(texels(width, rows))) return f;
+    refit(f, pyramid, texels(width, rows), PYRAMID);
+    return f;
+  }
+  bool in_place(uint32_t width, uint32_t rows) const { return on && pyramid.holds(texels(width, rows)); }
+  void release() {
+    on = false;
+    pyramid.release();
   }
 };
 

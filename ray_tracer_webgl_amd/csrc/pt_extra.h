@@ -99,6 +99,9 @@ extern "C" const void* pt_reproject_estimate_kernel_handle(void);
 // pt_kernels_display.hip (a code object of its own): exposure metering's two kernels and the toned read-out's (PT_OPT_TONEMAP)
 enum { PT_D_METER = 0, PT_D_EXPOSURE, PT_D_TONE, PT_D_COUNT };
 extern "C" const void* pt_display_kernel(int id);
+// pt_kernels_glare.hip (a code object of its own): the glare pyramid's down, gather and composite kernels (PT_OPT_GLARE)
+enum { PT_G_DOWN = 0, PT_G_GATHER, PT_G_COMPOSITE, PT_G_COUNT };
+extern "C" const void* pt_glare_kernel(int id);
 // pt_kernels_query.hip, beside its ray-query builds (PT_OPT_RAY_QUERIES, pt_query_rays): the two kernels that move a batch of
 // rays and records between the caller's device arrays and the query planes
 extern "C" const void* pt_query_pack_kernel_handle(void);

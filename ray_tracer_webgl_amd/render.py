@@ -19,6 +19,19 @@ from . import abi
 from .tracer import PathTracer, render_scene
 
 
+def glare_options(strength, levels, threshold):
+    """abi.PtGlareOptions of --glare / --glare-levels / --glare-threshold, or None when a value is out of range.  With fewer (or
+    more) levels than the default's six, the default weights of the levels in use are rescaled to add up to 1 (levels 7 and 8
+    take the last default weight before the rescaling)."""
+    if not (0.0 <= strength <= 1.0) or not (1 <= levels <= abi.PT_GLARE_MAX_LEVELS) or not (0.0 <= threshold < float("inf")):
+        return None
+    base = list(abi.PT_GLARE_WEIGHTS_DEFAULT[:abi.PT_GLARE_LEVELS_DEFAULT])
+    base += [base[-1]] * (abi.PT_GLARE_MAX_LEVELS - len(base))
+    used = base[:levels]
+    total = sum(used)
+    return abi.PtGlareOptions(strength, threshold, levels, [w / total for w in used])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--config", default="config2", choices=sorted(scenes.CONFIGS))
@@ -66,6 +79,15 @@ def main(argv=None):
                     help="with --tone: auto meters the frame on the device (pt_meter: the median lit pixel is exposed to 0.18) and "
                          "reads out with that record; VALUE multiplies the radiance by VALUE (Reinhard's white is then the "
                          "metered 99th percentile exposed by VALUE, at least 1).  Default auto")
+    ap.add_argument("--glare", type=float, metavar="STRENGTH",
+                    help="with --tone: spread this share (0 .. 1; the header's default is 0.15) of the frame's light over a bloom "
+                         "pyramid before metering and toning (pt_glare): the veil that tells a light from a white wall once both are at "
+                         "byte 255.  Energy-conserving; composes with --denoise / --denoise-patch")
+    ap.add_argument("--glare-levels", type=int, default=abi.PT_GLARE_LEVELS_DEFAULT, metavar="N",
+                    help="with --glare: pyramid levels in use, 1 .. %d (default %d); the default weights of the levels in use are "
+                         "rescaled to add up to 1" % (abi.PT_GLARE_MAX_LEVELS, abi.PT_GLARE_LEVELS_DEFAULT))
+    ap.add_argument("--glare-threshold", type=float, default=0.0, metavar="T",
+                    help="with --glare: only the luminance above T spills (default 0: every pixel, whole)")
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--checkpoint", help="also save the fp32 accumulation buffer (.npz)")
     args = ap.parse_args(argv)
@@ -125,6 +147,13 @@ def main(argv=None):
             exposure = float("nan")
         if not (0.0 < exposure < float("inf")):
             ap.error("--exposure: auto, or a finite positive value")
+    glare = None
+    if args.glare is not None:
+        if args.tone is None:
+            ap.error("--glare hands over linear radiance: only with --tone")
+        glare = glare_options(args.glare, args.glare_levels, args.glare_threshold)
+        if glare is None:
+            ap.error("--glare: a strength in 0 .. 1, --glare-levels 1 .. %d, --glare-threshold finite and >= 0" % abi.PT_GLARE_MAX_LEVELS)
     if args.noise_target is not None or args.error_out:
         if overlay is not None:
             ap.error("--noise-target / --error-out measure the frame's noise: not with --debug-overlay")
@@ -151,6 +180,12 @@ def main(argv=None):
     if toned:
         curve = {"clamp": abi.PT_TONE_CLAMP, "reinhard": abi.PT_TONE_REINHARD, "filmic": abi.PT_TONE_FILMIC}[args.tone]
         pt.tone_mapping(True)
+        if glare is not None:
+            pt.glare(True)
+            plain = pt.resolve(gamma=False) if frame is None else frame
+            frame = pt.glared_image(src=frame, options=glare)
+            print("glare: strength %g, %d levels, threshold %g; the frame's brightest channel value %g -> %g" % (
+                glare.strength, glare.levels, glare.threshold, float(np.nanmax(plain[..., :3])), float(np.nanmax(frame[..., :3]))))
         pt.meter(abi.PtMeterOptions(), src=frame)
         rec, _ = pt.exposure()
         opt = abi.PtToneOptions(curve, 1, 0.0, 1.0)

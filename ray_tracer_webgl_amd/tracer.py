@@ -519,9 +519,12 @@ class PathTracer:
 
     def _tone_src(self, src):
         """(pointer, object to keep alive) of a source image: None is the accumulation; a (local_rows, width, 4) float32 numpy
-        array is read from the host; under use_torch a torch device tensor is read in place."""
+        array is read from the host; under use_torch a torch device tensor is read in place; a ctypes.c_void_p is taken as
+        a device pointer to such texels (the caller keeps the memory alive)."""
         if src is None:
             return None, None
+        if isinstance(src, C.c_void_p):
+            return src, None
         shape = (self.local_rows, self.width, 4)
         if self.use_torch and self._torch.is_tensor(src) and src.is_cuda:
             t = src.to(self._torch.float32).contiguous()
@@ -592,6 +595,29 @@ class PathTracer:
     def toned_rgba8(self, options=None, src=None):
         """The same as bytes, alpha 255 (pt_resolve_toned_rgba8)."""
         return self._toned(self.lib.pt_resolve_toned_rgba8, np.uint8, options, src)
+
+    # -- glare: the bloom pyramid ahead of the toned read-out (include/ptrace.h PT_OPT_GLARE) --------
+    def glare(self, on=True):
+        """Put the glare pyramid in place (or release it).  Off by default; scratch only: the image bits are the same either
+        way, and resize and set_params refit it."""
+        self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_GLARE, 1 if on else 0))
+
+    def glared_image(self, src=None, options=None):
+        """(local_rows, width, 4) fp32: the LINEAR frame with its glare, a = 1 (pt_glare) — what meter(src=...) and
+        toned_image(src=...) take next.  `options`: abi.PtGlareOptions (default: the header's).  `src`: None for the
+        accumulation, or linear RGBA float32 texels (see _tone_src).  A numpy or no `src` gives a numpy array; a torch device
+        tensor gives a torch device tensor."""
+        opt = options if options is not None else abi.PtGlareOptions()
+        return self._toned(self.lib.pt_glare, np.float32, opt, src)
+
+    def glare_into(self, dst, src=None, options=None):
+        """pt_glare into device memory of the caller's: `dst` is a ctypes.c_void_p to local_rows * width float4 texels, and may
+        be a device `src`.  Synchronises."""
+        opt = options if options is not None else abi.PtGlareOptions()
+        ptr, keep = self._tone_src(src)
+        if self.local_rows * self.width:
+            self._check(self.lib.pt_glare(self._ctx, ptr, C.byref(opt), dst))
+        del keep
 
     # -- temporal reprojection (include/ptrace.h PT_OPT_REPROJECT) ---------------------------------
     def reproject_option(self, on=True):
