@@ -224,6 +224,9 @@ pub const PT_FILTER_KAPPA_DEFAULT: f32 = 2.0;   // ... and the kappa its callers
 pub const PT_FILTER_MAX_PATCH: u32 = 1;               // pt_resolve_filtered_patch: the largest patch radius
 pub const PT_FILTER_PATCH_KAPPA_DEFAULT: f32 = 1.5;   // ... and the kappa its callers start from
 pub const PT_OPT_RUSSIAN_ROULETTE: c_int = 5;   // opt-in, 0 = off: the reference's estimator has none (shader.frag:297-339)
+pub const PT_OPT_NEXT_EVENT: c_int = 13;        // opt-in, 0 = off: the render launches sample the emissive spheres at diffuse hits (same
+                                                // expectation, other samples); excludes roulette, the debug overlay and PT_OPT_COUNT_WORK
+pub const PT_BUILD_NEXT_EVENT: c_int = 16;      // pt_last_trace_build after a next-event launch
 
 // The rAF closure of src/lib.rs:65-104 with webgl::render replaced (one tick):
 //     state::update_render_globals(&mut state);

@@ -121,6 +121,42 @@ enum {
   PT_OPT_GLARE = 12,       /* 1: allocate the glare pyramid of pt_glare (see below; one float4 per texel of the eight levels, about a
                              third of the frame: 5.4 bytes per local pixel; scratch only, no state) and load the glare kernels' code
                              object.  0 (default): release it.  The image bits of a context are the same either way. */
+  PT_OPT_NEXT_EVENT = 13,  /* 1: NEXT-EVENT ESTIMATION — the render launches (pt_render_passes, _frame(s), _until, _adaptive) sample
+                             the emissive spheres at DIFFUSE hits.  NOT the reference's estimator sample for sample: every pixel's
+                             EXPECTATION is the plain estimator's, the samples differ.  0 (default): off, the table is released;
+                             bit-exact against the oracle.  Excludes PT_OPT_RUSSIAN_ROULETTE, the debug overlay and
+                             PT_OPT_COUNT_WORK (PT_ERR_INVALID, whichever comes second).  pt_render_features, pt_query_rays and
+                             pt_query_radiance stay the plain estimator.  The statements (csrc/pt_nee.hpp has each as one fp32
+                             operation; the order below is the contract):
+                               LIGHTS  the spheres of the installed list with type == PT_EMISSIVE, a finite centre, a finite
+                                       non-zero radius and a finite albedo, in list order; L of them.  The device table holds
+                                       {centre, r * r, albedo, list index} per light; it is built when the option is turned on
+                                       over an installed scene and by pt_set_spheres while the option is on, never otherwise.
+                               AT A DIFFUSE HIT x with face-forward normal n:
+                                1. the shader's scatter draw, unchanged;  2. depth++ and the depth test, unchanged (a path that
+                                   has used up its depth adds its throughput and ends);
+                                3. if the path goes on and L > 0: ONE hash3 -> (u0, u1, u2);
+                                4. k = min((int)(u0 * float(L)), L - 1);
+                                5. w = c_k - x (per component), d2 = fma(w.z, w.z, fma(w.y, w.y, w.x * w.x)), r2 = r_k * r_k;
+                                6. P(x, k) := d2 > r2 — the light can be sampled from x;
+                                7. if P: q = r2 / d2; cosmax = sqrt(max(0, 1 - q)); om = 1 - cosmax; cos_t = 1 - u1 * om;
+                                   sin_t = sqrt(max(0, fma(-cos_t, cos_t, 1))); (s, c) = sincos2pi(u2);
+                                8. z = w * (1 / sqrt(d2)); sg = copysign(1, z.z); a = -1 / (sg + z.z); b = (z.x * z.y) * a;
+                                   t = (fma(sg * (z.x * z.x), a, 1), sg * b, -sg * z.x); bt = (b, fma(z.y * z.y, a, sg), -z.y)
+                                   (branch-free, finite for every unit z, (0, 0, -1) included: |sg + z.z| >= 1);
+                                   omega = fma(z, cos_t, fma(bt, sin_t * s, t * (sin_t * c))) per component;
+                                9. cos_s = fma(n.z, omega.z, fma(n.y, omega.y, n.x * omega.x));
+                               10. if cos_s > 0: the next segment is the SHADOW RAY (x, omega) through the unchanged
+                                   intersection (MIN_T, MAX_T, ties as hit_world);
+                               11. if its closest hit is list index k:
+                                   sum.c = sum.c + (throughput.c * albedo_k.c) * ((float(L) * (2 * om)) * cos_s),
+                                   throughput after the hit's albedo;
+                               12. the path goes on along the scattered ray of step 1.
+                             A shadow segment is no bounce; it is one segment in PtStats.segments and in the tile cost.
+                             NO DOUBLE COUNTING: a path that reaches a light j straight from a vertex where steps 3 onward ran
+                             adds j's emission only if !P(o, j), o the segment's origin; every other arrival (from the camera,
+                             after METAL or GLASS, with L == 0, on an emissive sphere that is no light) adds it as always.  With
+                             L == 0 no draw is made and nothing is skipped: the output is the plain build's, bit for bit. */
 };
 
 /* ---- background modes ----------------------------------------------------------------------- */

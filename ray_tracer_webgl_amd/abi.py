@@ -39,6 +39,7 @@ PT_OPT_TONEMAP = 11  # the exposure state of pt_meter and the toned read-outs (p
 PT_TONE_CLAMP, PT_TONE_REINHARD, PT_TONE_FILMIC = 0, 1, 2  # PtToneOptions.curve
 PT_OPT_GLARE = 12  # the pyramid of pt_glare (scratch only, no state)
 PT_GLARE_MAX_LEVELS = 8
+PT_OPT_NEXT_EVENT = 13  # next-event estimation: the render launches sample the emissive spheres at DIFFUSE hits (same expectation, other samples)
 PT_GLARE_STRENGTH_DEFAULT = 0.15    # PtGlareOptions: the share of the spread light that is added back
 PT_GLARE_LEVELS_DEFAULT = 6         # ... the levels in use
 PT_GLARE_WEIGHTS_DEFAULT = (0.35, 0.25, 0.18, 0.12, 0.06, 0.04, 0.0, 0.0)  # ... and their weights (they add up to 1)
@@ -58,6 +59,7 @@ PT_FILTER_MAX_PATCH = 1               # pt_resolve_filtered_patch: the largest p
 PT_FILTER_PATCH_KAPPA_DEFAULT = 1.5   # ... and the kappa its callers start from
 NO_SELECTED_OBJECT_ID = 1000  # src/state.rs:12: State.selected_object while the crosshair is on nothing
 BUILD_PLAIN, BUILD_ROULETTE, BUILD_TWIN, BUILD_DEBUG_OVERLAY, BUILD_FEATURES = 0, 1, 2, 3, 4  # pt_last_trace_build
+BUILD_NEXT_EVENT = 16  # ... and the next-event builds, which are no column of the trace table (csrc/pt_nee_table.hpp)
 PT_STREAM_LEGACY = 1  # include/ptrace.h: hipStreamLegacy, the default (NULL) stream by name
 GEOM_NAMES = {0: "auto", 1: "lds", 2: "scalar", 3: "bvh", 4: "grid", 5: "small"}
 

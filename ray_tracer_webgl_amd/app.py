@@ -17,7 +17,8 @@ run_setters -> render -> (save).  Two display modes:
     rendered tick meters the accumulation on the device (pt_meter) and the canvas is drawn through the tone curve
     (pt_resolve_toned_rgba8) instead of the clamp of pt_resolve_rgba8; `tone=None` draws the canvas as ever.  With
     `glare=abi.PtGlareOptions()` beside `tone`, every rendered tick is first glared into a device buffer (pt_glare) and that
-    buffer is what is metered and toned; `glare=None` is the loop without it, byte for byte.
+    buffer is what is metered and toned; `glare=None` is the loop without it, byte for byte.  With `next_event=True` the
+    ticks are traced by the next-event builds (PathTracer.next_event): the same expectation, other samples.
 """
 import ctypes as C
 import time
@@ -34,12 +35,13 @@ class FrameLoop:
     LOOSE_FRAMES = 32
 
     def __init__(self, width, height, device=0, mode="reference", host_spheres=None, debugging=False, reproject=None,
-                 carry_estimate=False, tone=None, glare=None):
+                 carry_estimate=False, tone=None, glare=None, next_event=False):
         assert mode in ("reference", "linear")
         assert tone is None or mode == "linear", "the toned canvas reads the fp32 accumulation: linear mode only"
         assert glare is None or tone is not None, "the glared frame is linear radiance: it is drawn through `tone`"
         assert reproject is None or mode == "linear", "temporal reprojection carries the fp32 accumulation: linear mode only"
         assert not carry_estimate or reproject is not None, "carry_estimate needs `reproject` options"
+        assert not (next_event and debugging), "next-event estimation and the debug overlay exclude each other"
         self.mode = mode
         self.reproject = reproject  # abi.PtReprojectOptions, or None: a camera change clears the accumulation
         self.carry_estimate = bool(carry_estimate)  # keep the error estimate and carry it with the accumulation
@@ -60,6 +62,9 @@ class FrameLoop:
             self.tracer.reproject_option(True)
             if self.carry_estimate:
                 self.tracer.error_estimate(True)
+        self.next_event = bool(next_event)  # PT_OPT_NEXT_EVENT: the ticks sample the scene's emissive spheres
+        if self.next_event:
+            self.tracer.next_event(True)
         if self.tone is not None:
             self.tracer.tone_mapping(True)
         if self.glare is not None:

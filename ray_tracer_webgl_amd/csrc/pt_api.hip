@@ -31,6 +31,8 @@
 #include "pt_geom_plan.hpp"
 #include "pt_launch_plan.hpp"
 #include "pt_trace_table.hpp"
+#include "pt_nee_table.hpp"
+#include "pt_nee.hpp"
 #include "pt_tile_order.hpp"
 #include "pt_error_plan.hpp"
 #include "pt_reproject_plan.hpp"
@@ -157,6 +159,9 @@ struct pt_ctx {
   uint32_t carry_lanes = 12;
   uint32_t refill_min = 4;
   int rr_min_depth = 0;  // PT_OPT_RUSSIAN_ROULETTE: 0 = off (the reference's estimator, bit-exact against the oracle)
+  // PT_OPT_NEXT_EVENT: the light table of the scene in place (pt_buffers.hpp LightSet: built when the option comes on over a scene
+  // and by pt_set_spheres while it is on, never otherwise)
+  ptbuf::LightSet<ptnee::Light> lights;
   // debug overlay (pt_set_debug_overlay): the shader's u_enable_debugging / u_selected_object / u_cursor_point, and the uuids
   // its outline test compares — uploaded when the overlay is first turned on for a scene (upload_uuids), never before
   bool dbg_enable = false;
@@ -481,8 +486,10 @@ Staging grid_build(const pt_ctx* c) {
 // kernel's dynamic-LDS limit, once per device and id; the main kernels' limit is lifted at pt_create, the small-list kernels need none.
 const void* cell_kernel(int device, const TraceCell& k) {
 #define PT_TRACE_ACCESSOR_OF(object, accessor, n_ids) accessor,
-  static const void* (*const accessors[OBJ_COUNT])(int) = {PT_TRACE_OBJECTS(PT_TRACE_ACCESSOR_OF)};
-  static std::once_flag once[64][OBJ_COUNT][PT_EXTRA_COUNT];  // (function attributes belong to a device: the context's is current here)
+  // (... and behind the table's objects the side table's: the next-event builds, pt_nee_table.hpp)
+  static const void* (*const accessors[OBJ_COUNT + 1])(int) = {PT_TRACE_OBJECTS(PT_TRACE_ACCESSOR_OF) pt_nee_kernel};
+  static_assert(OBJ_NEE == OBJ_COUNT, "the next-event object follows the trace table's");
+  static std::once_flag once[64][OBJ_COUNT + 1][PT_EXTRA_COUNT];  // (function attributes belong to a device: the context's is current here)
   static_assert(PT_EXTRA_COUNT >= PT_VARIANT_COUNT, "the extra object has the most ids");
   const void* fn = accessors[k.object](k.id);
   if (fn && k.object >= OBJ_EXTRA)
@@ -691,11 +698,25 @@ int upload_uuids(pt_ctx* c, const std::vector<int32_t>& uuid) {
   return PT_OK;
 }
 
-// the device half of pt_set_spheres: list, hierarchy, grid, and the uuid arrays when the overlay or the feature planes are on
+// The light table of PT_OPT_NEXT_EVENT for the list `sp` (pt_nee.hpp lights_of).  The caller has made sure that nothing in flight
+// reads the table in place.  A refused allocation leaves the set not in place: render launches are refused until a later build
+// succeeds (prepare_launch).
+int upload_lights(pt_ctx* c, const ptscene::Split& sp, uint32_t n) {
+  std::vector<ptnee::Light> table(n ? n : 1u);
+  const uint32_t L = ptnee::lights_of(sp.geom.data(), sp.mat.data(), n, table.data());
+  const ptbuf::Fit f = c->lights.fit(L);
+  if (!f.ok()) return fail(c, PT_ERR_HIP, "PT_OPT_NEXT_EVENT: no room for the table of %u lights (%s)", L, hipGetErrorString((hipError_t)f.err));
+  if (L) PT_HIP(c, hipMemcpy(c->lights.table.get(), table.data(), (size_t)L * sizeof(ptnee::Light), hipMemcpyHostToDevice));
+  return PT_OK;
+}
+
+// the device half of pt_set_spheres: list, hierarchy, grid, the uuid arrays when the overlay or the feature planes are on, and the
+// light table when next-event estimation is
 int install_scene(pt_ctx* c, const ptscene::Split& sp, uint32_t n, ptbvh::Bvh* bvh, ptgrid::Grid* grid) {
   PT_TRY(install_list(c, sp, n));
   if (bvh) PT_TRY(install_bvh(c, *bvh, sp));
   if (grid) PT_TRY(install_grid(c, *grid, sp));
+  if (c->lights.on) PT_TRY(upload_lights(c, sp, n));
   return wants_uuids(c) ? upload_uuids(c, sp.uuid) : PT_OK;
 }
 
@@ -1106,13 +1127,16 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   const bool feat = use.door == DOOR_FEATURES || query;
   if (c->geom.policy == PT_GEOM_AUTO && !door) try_finish_tuning(c);
   const bool rr = !door && c->rr_min_depth > 0, dbg = !door && c->dbg_enable;
+  // next-event estimation acts on render launches only; the doors stay the plain estimator
+  const bool nee = !door && c->lights.on;
+  if (nee && !c->lights.in_place()) return fail(c, PT_ERR_CAPACITY, "%s: PT_OPT_NEXT_EVENT's light table is not in place (a failed allocation: install the scene or turn the option on again)", use.who);
   if (rr && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and PT_OPT_RUSSIAN_ROULETTE exclude each other");
   if (dbg && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and the debug overlay exclude each other");
   if (dbg && !c->state.uuid_valid) return fail(c, PT_ERR_NOT_READY, "debug overlay: the uuid arrays are not in place (pt_set_debug_overlay after a failed upload?)");
   // (the overlay builds exist for the ways to read the list that have a roulette build: the same steering away from the LDS walk)
   if (feat && !c->state.uuid_valid) return fail(c, PT_ERR_NOT_READY, "%s: the uuid arrays are not in place (%s after a failed upload?)", query ? "ray queries" : "feature planes",
                                              query ? "PT_OPT_RAY_QUERIES" : "PT_OPT_FEATURES");
-  const PathChoice choice = c->geom.choose(path_scene(c), use.allow_trials && !door, rr || dbg || door);
+  const PathChoice choice = c->geom.choose(path_scene(c), use.allow_trials && !door, rr || dbg || door || nee);
   const int path = choice.path;
   if (!door) c->geom.last = path;
 
@@ -1146,14 +1170,24 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
     A.first_pass = use.first_pass;
     A.rr_min_depth = 0;
   }
-  // the two-axis walk reads the ring layout; it is what `scene` was sized for (staged_cells)
-  if (reads_ring_layout(row, build)) {
+  // (the next-event builds: the side table's cell where the column would have been the plain build; their light table and its
+  // length travel where the radiance builds find their rays — pt_kernel_args.h)
+  const bool nee_cell = takes_nee_cell(nee, build);
+  // the two-axis walk reads the ring layout; it is what `scene` was sized for (staged_cells).  The next-event build of that row
+  // walks three axes, like the roulette build: the plain array
+  if (!nee_cell && reads_ring_layout(row, build)) {
     A.grid_cells = c->grid.ring.get();
     A.n_cells = (uint32_t)ptrec::ring_cells(c->grid.head.n[0], c->grid.head.n[2]);
   }
-  const TraceCell& tk = kTraceKernels[row][build];
+  if (nee_cell) {
+    A.uuid = reinterpret_cast<const int32_t*>(c->lights.table.get());
+    A.slot_uuid = nullptr;
+    A.dbg_selected = (int32_t)c->lights.n;
+    A.rr_min_depth = 0;
+  }
+  const TraceCell& tk = nee_cell ? kNeeKernels[row] : kTraceKernels[row][build];
   const void* kfn = cell_kernel(c->device, tk);
-  if (!query && !rad) c->last_build = build;  // (what pt_last_trace_build reports: a render or feature launch's column)
+  if (!query && !rad) c->last_build = nee_cell ? (int)BUILD_NEXT_EVENT : build;  // (what pt_last_trace_build reports: a render or feature launch's column)
   const uint32_t block = walk ? walk_block_threads(kfn, tk.waves, scene, kWalkLdsMax, knobs.bvh_block) : list_block_threads(scene);
   const size_t lds = walk ? scene + (size_t)PT_PARK_STRIDE * 4 * block : scene;
   A.block_threads = block;
@@ -2041,6 +2075,9 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     return PT_OK;
   }
   if (key == PT_OPT_COUNT_WORK) { // measuring twin of the walk kernels (PtStats.work); slower, never timed
+    if (value > 0 && c->lights.on)
+      return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_COUNT_WORK and PT_OPT_NEXT_EVENT exclude each other (turn next-event estimation off first: "
+                                     "pt_set_option(ctx, PT_OPT_NEXT_EVENT, 0))");
     c->count_work = value < 0 ? 0 : (value > 2 ? 2 : value);  // 2 (dev tools only): the grid twins also fill the gather histogram (pt_debug_cell_hist)
     return PT_OK;
   }
@@ -2054,7 +2091,34 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     if (value > 0 && c->dbg_enable)
       return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_RUSSIAN_ROULETTE and the debug overlay exclude each other (turn the overlay off first: "
                                      "pt_set_debug_overlay(ctx, 0, ...))");
+    if (value > 0 && c->lights.on)
+      return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_RUSSIAN_ROULETTE and PT_OPT_NEXT_EVENT exclude each other (turn next-event estimation off first: "
+                                     "pt_set_option(ctx, PT_OPT_NEXT_EVENT, 0))");
     c->rr_min_depth = value;
+    return PT_OK;
+  }
+  if (key == PT_OPT_NEXT_EVENT) { // changes sample values (not expectations): off unless asked for
+    if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: next-event estimation %d", value);
+    if (value && c->rr_min_depth > 0)
+      return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_NEXT_EVENT and PT_OPT_RUSSIAN_ROULETTE exclude each other (turn roulette off first: "
+                                     "pt_set_option(ctx, PT_OPT_RUSSIAN_ROULETTE, 0))");
+    if (value && c->dbg_enable)
+      return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_NEXT_EVENT and the debug overlay exclude each other (turn the overlay off first: "
+                                     "pt_set_debug_overlay(ctx, 0, ...))");
+    if (value && c->count_work)
+      return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_NEXT_EVENT and PT_OPT_COUNT_WORK exclude each other (turn the measuring twins off first: "
+                                     "pt_set_option(ctx, PT_OPT_COUNT_WORK, 0))");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipStreamSynchronize(c->stream));  // launches in flight may read the table in place
+    if (!value) { c->lights.release(); return PT_OK; }
+    if (c->lights.on) return PT_OK;
+    hipFuncAttributes attr;  // (loads the next-event builds' code object now: a set-up call's work, not a render call's)
+    PT_HIP(c, hipFuncGetAttributes(&attr, pt_nee_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar))));
+    c->lights.on = true;
+    if (c->state.have_spheres) {  // over an installed scene: its table, now
+      int rc = upload_lights(c, c->list.host, c->list.n);
+      if (rc != PT_OK) { c->lights.release(); return rc; }
+    }
     return PT_OK;
   }
   if (key == PT_OPT_CARRY_LANES) { // 0 = lockstep to the last lane; scheduling only, never results
@@ -2097,6 +2161,9 @@ PT_API int pt_set_debug_overlay(pt_ctx* c, int enable, int32_t selected_object, 
   if (enable && c->rr_min_depth > 0)
     return fail(c, PT_ERR_INVALID, "pt_set_debug_overlay: the debug overlay and PT_OPT_RUSSIAN_ROULETTE exclude each other (turn roulette off first: "
                                    "pt_set_option(ctx, PT_OPT_RUSSIAN_ROULETTE, 0))");
+  if (enable && c->lights.on)
+    return fail(c, PT_ERR_INVALID, "pt_set_debug_overlay: the debug overlay and PT_OPT_NEXT_EVENT exclude each other (turn next-event estimation off first: "
+                                   "pt_set_option(ctx, PT_OPT_NEXT_EVENT, 0))");
   if (!enable) {
     c->dbg_enable = false;
     return PT_OK;
@@ -2112,7 +2179,7 @@ PT_API int pt_set_debug_overlay(pt_ctx* c, int enable, int32_t selected_object, 
 }
 
 // which build of the trace kernel the most recent launch was: 0 plain, 1 Russian roulette, 2 measuring twin, 3 debug overlay,
-// 4 first-hit features
+// 4 first-hit features, 16 next-event estimation (no column of the trace table: pt_nee_table.hpp)
 PT_API int pt_last_trace_build(pt_ctx* c) {
   if (!c) return PT_ERR_INVALID;
   return c->last_build;

@@ -291,4 +291,32 @@ struct GlareSet {
   }
 };
 
+// PT_OPT_NEXT_EVENT: the light table of the scene in place — n records (pt_nee.hpp Light), one allocation of at least max(n, 1).
+// It is sized by the SCENE, not by the rows: no resize and no repartition touches it; pt_set_spheres rebuilds it while the option
+// is on, and turning the option on over an installed scene builds it.  `n` speaks for the table only while it is in place: a
+// refused allocation leaves n = 0 and the buffer empty, and the render calls answer PT_ERR_CAPACITY until a later fit succeeds.
+template <class Record>
+struct LightSet {
+  enum : uint32_t { TABLE = 1 };
+  bool on = false;
+  uint32_t n = 0;  // lights in the table (0: a scene without lights, or no scene yet)
+  DevBuf<Record> table;
+
+  Fit fit(uint32_t n_lights) {
+    Fit f;
+    n = 0;
+    if (!on) return f;
+    const size_t want = n_lights ? n_lights : 1u;
+    if (table.capacity() < want && !refit(f, table, want, TABLE)) return f;
+    n = n_lights;
+    return f;
+  }
+  bool in_place() const { return on && table.holds_at_least(n ? n : 1u); }
+  void release() {
+    on = false;
+    n = 0;
+    table.release();
+  }
+};
+
 }  // namespace ptbuf

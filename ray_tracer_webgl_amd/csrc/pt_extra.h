@@ -102,6 +102,18 @@ extern "C" const void* pt_display_kernel(int id);
 // pt_kernels_glare.hip (a code object of its own): the glare pyramid's down, gather and composite kernels (PT_OPT_GLARE)
 enum { PT_G_DOWN = 0, PT_G_GATHER, PT_G_COMPOSITE, PT_G_COUNT };
 extern "C" const void* pt_glare_kernel(int id);
+// pt_kernels_nee.hip (a code object of its own): the next-event builds (PT_OPT_NEXT_EVENT), the twelve variant rows under the
+// adaptor Nee with the suffix _nee, by variant id.  No column of the trace table: the host keeps them in the side table
+// kNeeKernels (pt_nee_table.hpp) and takes a cell of it where a render launch's column would have been the plain build.
+// Waves per SIMD a row's _nee build is built for: its namesake's figure, except where the four registers of shadow state that cross
+// a walk (pt_scene.hpp NeeState) do not fit beside it — the nodes-only hierarchy walk and the cells-only grid walk spill at 80
+// VGPRs (8 and 12 bytes of scratch per lane in the cross-compile's resource report) and are built for PT_WAVES_NEE_TIGHT, 96 VGPRs.
+// One statement for the kernels' attribute and the host's side table.
+#define PT_WAVES_NEE_TIGHT 5
+constexpr int pt_nee_waves(int variant_id, int waves) {
+  return variant_id == PT_VARIANT_ID(pt_trace_kernel_bvh_nodes) || variant_id == PT_VARIANT_ID(pt_trace_kernel_grid_cells) ? PT_WAVES_NEE_TIGHT : waves;
+}
+extern "C" const void* pt_nee_kernel(int id);
 // pt_kernels_query.hip, beside its ray-query builds (PT_OPT_RAY_QUERIES, pt_query_rays): the two kernels that move a batch of
 // rays and records between the caller's device arrays and the query planes
 extern "C" const void* pt_query_pack_kernel_handle(void);

@@ -103,6 +103,8 @@ struct PtKernelArgs {
   const int32_t* uuid;             // n_spheres: PtSphere.uuid in list order (the caller's values, not indices)
                                    // (the radiance-query builds, which shade as the plain builds do and never read a uuid, find the
                                    // base of the query planes here — their staged rays: pt_refill.hpp RAD; the ray count in dbg_selected)
+                                   // (the next-event builds, which never read a uuid either, find the LIGHT TABLE here — L records of
+                                   // pt_nee.hpp Light, 32 bytes each — and L in dbg_selected: pt_shade.hpp NEE)
   const int32_t* slot_uuid;        // n_slots: the slot's sphere's uuid (walk kernels, like slot_mat)
   float dbg_cursor[3];             // u_cursor_point, static/shader.frag:102
   int32_t dbg_selected;            // u_selected_object, :101

@@ -57,6 +57,34 @@ struct Path {
   float nx_seed = 0.f, nx_s = 0.f, nx_t = 0.f;
 };
 
+// ---- per-lane state of the next-event builds (PT_OPT_NEXT_EVENT; pt_shade.hpp, pt_nee.hpp) --------
+// Present under NEE only: every other build carries an empty struct.  A lane whose DIFFUSE hit drew a light sample with
+// cos_s > 0 walks the shadow ray (x, omega) as its next segment — `pending` — and keeps what the shade call after it needs:
+// the light, the scalar weight L * 2 (1 - cosmax) * cos_s, and the scattered direction the path then goes on along (the
+// origin is the shadow ray's own: the same bits).  `sampled`: the segment under way starts at a vertex that ran the light
+// sample, so an emissive sphere it reaches adds its emission only where the light could not be sampled from there.
+// Five registers: the two flags and the light share one (bit 0 pending, bit 1 sampled, the light from bit 2); the walk builds
+// keep wgt in the parking area's one spare dword while they walk (park_store / park_load below), so four cross a walk.
+template <bool NEE>
+struct NeeState {};
+template <>
+struct NeeState<true> {
+  uint32_t bits = 0u;
+  float wgt = 0.f;
+  V3 nd = mk(0, 0, 0);
+  __device__ __forceinline__ bool pending() const { return (bits & 1u) != 0u; }
+  __device__ __forceinline__ bool sampled() const { return (bits & 2u) != 0u; }
+  __device__ __forceinline__ int light() const { return (int)(bits >> 2); }
+  __device__ __forceinline__ void set_sampled(bool on) { bits = on ? 2u : 0u; }  // (never while pending)
+  __device__ __forceinline__ void set_pending(int k) { bits = 3u | ((uint32_t)k << 2); }
+  __device__ __forceinline__ void clear_pending() { bits = 2u; }  // the vertex the path goes on from ran the light sample
+};
+
+// how shade_segment takes it: the state by reference under NEE, the empty struct BY VALUE otherwise — a reference to it would be
+// one more address-taken local in every other build, and their code must not move (profiles/r30_kernel_identity.txt)
+template <bool NEE> struct NeeArgOf { typedef NeeState<false> type; };
+template <> struct NeeArgOf<true> { typedef NeeState<true>& type; };
+
 // ---- wave-uniform work-queue state (pt_refill.hpp) ------------------------------------------------
 struct Queue {
   uint32_t pool_next = 0, pool_end = 0;  // this wave's reserved queue items
@@ -241,6 +269,11 @@ __device__ __forceinline__ void park_load(const PtKernelArgs& A, Path& p) {
   p.sample = (int)ps[12]; p.depth = (int)ps[13];
   p.slab_index = ps[9]; p.item_tile = ps[10]; p.item_segs = ps[11];
 }
+
+// (the next-event builds: the shadow ray's weight in the spare dword, PT_PARK_DWORDS .. PT_PARK_STRIDE - 1)
+static_assert(PT_PARK_STRIDE > PT_PARK_DWORDS, "the parking area has a spare dword per lane");
+__device__ __forceinline__ void park_store(const PtKernelArgs& A, const NeeState<true>& ne) { park_of(A)[PT_PARK_DWORDS] = f2u(ne.wgt); }
+__device__ __forceinline__ void park_load(const PtKernelArgs& A, NeeState<true>& ne) { ne.wgt = u2f(park_of(A)[PT_PARK_DWORDS]); }
 
 // ---- executed-work tallies of the COUNT twins (wave-uniform; compiled away in the timed kernels) ----
 // The measuring twin of a kernel is the same body with these counters live: iterations and active

@@ -9,6 +9,7 @@
 // statement.  RNG draws happen exactly where the shader draws them (one random_in_unit_sphere for
 // DIFFUSE :217 and METAL :240 alike — also when fuzz is 0 —, one hash1 for GLASS :267).
 #pragma once
+#include "pt_nee.hpp"
 #include "pt_scene.hpp"
 
 namespace ptk {
@@ -23,8 +24,12 @@ namespace ptk {
 // miss — goes to the four planes behind A.slab and the path ends; no draw, no scatter, no colour store
 // QRY: the opt-in ray-query build (pt_query_rays; pt_kernels_query.hip): FEAT's store IS its store — the planes behind A.slab are
 // the query planes, the work item is the ray's place — and nothing in here differs
-template <typename S, bool RR, bool COUNT, bool DBG = false, bool FEAT = false, bool QRY = false>
-__device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, const Hit& h, const Carry& cw, Tally<COUNT>& tally) {
+// NEE: the opt-in next-event build (PT_OPT_NEXT_EVENT; pt_kernels_nee.hip): one light sample at every DIFFUSE hit whose path goes
+// on, its shadow ray walked as the lane's next segment (pt_scene.hpp NeeState, pt_nee.hpp has the statements); the light table
+// travels in PtKernelArgs::uuid and L in dbg_selected (pt_kernel_args.h), read from the kernarg segment at the point of use
+template <typename S, bool RR, bool COUNT, bool DBG = false, bool FEAT = false, bool QRY = false, bool NEE = false>
+__device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, const Hit& h, const Carry& cw, Tally<COUNT>& tally, typename NeeArgOf<NEE>::type ne) {
+  static_assert(!NEE || (!RR && !DBG && !FEAT && !COUNT), "next-event estimation excludes roulette, the overlay, the doors and the twins");
   tally.flag(PT_REG_SHADE_ANY);
   // local copies, written back at the end (see pt_grid_walk.hpp: references would be memory to the
   // passes that run before inlining)
@@ -35,7 +40,32 @@ __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, co
   const float closest = h.closest; const int hit = h.hit; const uint32_t hit_pos = cw.hit_pos;
   (void)hit_pos;
   item_segs++;
+  if constexpr (NEE) {
+    // THE SHADOW SEGMENT's end: no bounce (no draw, no depth).  The light's term is added when the closest hit along (x, omega)
+    // is the light itself — by list index; a walk's hit by slot through bvh_slot_index, as the feature build reads it —, then the
+    // path goes on from the same origin along the scattered ray its DIFFUSE hit drew.
+    if (ne.pending()) {
+      int index = hit;
+      if constexpr (S::TREE) {
+        if (hit >= 0 && hit_pos != 0xffffffffu) index = (int)A.bvh_slot_index[hit_pos];
+      }
+      karg_t* K = kargs();
+      const float4 l1 = reinterpret_cast<const float4*>(K->uuid)[2 * ne.light() + 1];  // albedo.xyz, list index
+      if (hit >= 0 && index == __float_as_int(l1.w)) {
+        float s3[3] = {sum.x, sum.y, sum.z};
+        const float t3[3] = {col.x, col.y, col.z}, a3[3] = {l1.x, l1.y, l1.z};
+        ptnee::add(s3, t3, a3, ne.wgt);
+        p.sum = mk(s3[0], s3[1], s3[2]);
+      }
+      ne.clear_pending();
+      p.d = ne.nd; p.a = dot3(ne.nd, ne.nd);
+      p.item_segs = item_segs;
+      return;
+    }
+  }
   bool finished = false; // this camera path is over
+  bool nee_skip = false; // NEE: the emissive sphere reached was the light sample's to estimate
+  (void)nee_skip;
   // ONE copy of what several outcomes share.  The lanes of a wave end their segments differently (sky, DIFFUSE,
   // METAL, GLASS ...) and a wave runs every branch some lane takes: the sky and GLASS both want 1 / sqrt(|d|^2), and
   // DIFFUSE, METAL and GLASS all begin their draw with the same seed step + hash.  Both are computed once, in straight
@@ -77,6 +107,17 @@ __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, co
     front = dot3(d, on) < 0.0f; // :137
     n = front ? on : mk(-on.x, -on.y, -on.z);
     alb = mk(m0.x, m0.y, m0.z);
+    if constexpr (NEE) {
+      // NO DOUBLE COUNTING: a segment that starts at a vertex where the light sample ran and ends on a LIGHT adds the emission
+      // only if the light could not be sampled from there, !P(o, j).  A sphere that was hit has a finite centre and r * r; it
+      // is in the table if its radius is not zero and its albedo is finite (ptnee::is_light).
+      if (ne.sampled() && mtype == 3) {
+        const float x3[3] = {o.x, o.y, o.z}, c3[3] = {g.x, g.y, g.z};
+        float w3[3], d2;
+        const bool reached = ptnee::reach(x3, c3, g.w, w3, d2);
+        nee_skip = reached && radius != 0.0f && ptnee::is_finite(m0.x) && ptnee::is_finite(m0.y) && ptnee::is_finite(m0.z);
+      }
+    }
     if constexpr (DBG) {
       // DEBUG OVERLAY — opt-in (pt_set_debug_overlay), static/shader.frag:307-318, on the complete hit record: before the
       // PT_EMISSIVE test and before any scatter draw.  The cursor dot: |hit point - cursor| < 0.1 -> the sample is (0, 0, 1);
@@ -204,7 +245,11 @@ __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, co
       o = p; d = nd;
       col.x *= alb.x; col.y *= alb.y; col.z *= alb.z;
     } else if (mtype == 3) { // EMISSIVE (extension): radiance = throughput * emission
-      sum.x += col.x * alb.x; sum.y += col.y * alb.y; sum.z += col.z * alb.z;
+      if constexpr (NEE) {
+        if (!nee_skip) { sum.x += col.x * alb.x; sum.y += col.y * alb.y; sum.z += col.z * alb.z; }
+      } else {
+        sum.x += col.x * alb.x; sum.y += col.y * alb.y; sum.z += col.z * alb.z;
+      }
       finished = true;
     } else {
       finished = true; // unrecognised material absorbs, :284-285
@@ -235,8 +280,39 @@ __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, co
           col.x *= inv; col.y *= inv; col.z *= inv;
         }
       }
+      if constexpr (NEE) {
+        // THE LIGHT SAMPLE — opt-in (PT_OPT_NEXT_EVENT), after the shader's own scatter draw and depth test, at a DIFFUSE hit whose
+        // path goes on, when there is a light: one hash3, a light, a direction inside the cone the light subtends (pt_nee.hpp).
+        // With cos_s > 0 the lane's next segment is the shadow ray; the scattered direction waits in ne.nd.
+        karg_t* K = kargs();
+        const int n_lights = K->dbg_selected;
+        const bool smp = !finished && mtype == 0 && n_lights > 0;
+        ne.set_sampled(smp);
+        if (smp) {
+          float u0, u1, u2;
+          hash3(seed, u0, u1, u2);
+          const int k = ptnee::choose(u0, n_lights);
+          const float4 l0 = reinterpret_cast<const float4*>(K->uuid)[2 * k];  // centre, r * r
+          const float x3[3] = {o.x, o.y, o.z}, c3[3] = {l0.x, l0.y, l0.z};
+          float w3[3], d2;
+          if (ptnee::reach(x3, c3, l0.w, w3, d2)) {
+            float sp, cp, om3[3], om;
+            sincos2pi(u2, sp, cp);
+            ptnee::sample(w3, d2, l0.w, u1, sp, cp, om3, om);
+            const float n3[3] = {n.x, n.y, n.z};
+            const float cos_s = ptnee::cos_at(n3, om3);
+            if (cos_s > 0.0f) {
+              ne.set_pending(k); ne.wgt = ptnee::weight(n_lights, om, cos_s);
+              ne.nd = d;
+              d = mk(om3[0], om3[1], om3[2]);
+              a = dot3(d, d);
+            }
+          }
+        }
+      }
     }
   }
+  if constexpr (NEE) { if (finished) ne.set_sampled(false); }
 
   if (finished) {
     tally.flag(PT_REG_SHADE_FINISHED);

@@ -1,9 +1,10 @@
-// pt_trace_body.hpp — the path-tracing kernel body shared by the seven device translation units that trace (each a gfx950
+// pt_trace_body.hpp — the path-tracing kernel body shared by the eight device translation units that trace (each a gfx950
 // code object of its own, loaded when one of its kernels is first asked for): pt_kernels.hip (list and walk
 // kernels), pt_kernels_small.hip (the small-list kernels, one per list length modulo four),
 // pt_kernels_extra.hip (the opt-in builds: the Russian-roulette kernels and the measuring twins),
 // pt_kernels_debug.hip (the opt-in debug-overlay builds), pt_kernels_features.hip (the opt-in first-hit feature builds),
-// pt_kernels_query.hip (the opt-in ray-query builds) and pt_kernels_radiance.hip (the radiance-query builds).
+// pt_kernels_query.hip (the opt-in ray-query builds), pt_kernels_radiance.hip (the radiance-query builds) and pt_kernels_nee.hip
+// (the opt-in next-event builds).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,11 +37,13 @@ using namespace ptd;
 //   RAD      the radiance-query build (pt_query_radiance): the plain build with the CALLER's ray in the camera ray's place — QRY
 //            without FEAT: every sample of an item starts from the ray staged at the item's place, the seed is the item's own,
 //            and the shade, the sample loop and the slab store are the plain build's (pt_refill.hpp start_sample, radiance_admit)
+//   NEE      the opt-in next-event build (PT_OPT_NEXT_EVENT): the plain build with one light sample at every DIFFUSE hit whose path
+//            goes on, its shadow ray walked as the lane's next segment (pt_shade.hpp, pt_nee.hpp, pt_scene.hpp NeeState)
 // Which kernel is which row under which adaptor is stated once, in the lists of pt_extra.h.
 // --------------------------------------------------------------------------------------------
 namespace ptb {
 struct Defaults {
-  static constexpr bool SCAN_LDS = false, HAVE_LDS = false, COUNT = false, RR = false, FLAT_Y = false, DBG = false, FEAT = false, QRY = false, RAD = false;
+  static constexpr bool SCAN_LDS = false, HAVE_LDS = false, COUNT = false, RR = false, FLAT_Y = false, DBG = false, FEAT = false, QRY = false, RAD = false, NEE = false;
   static constexpr int WALK = 0, TAIL = -1;
 };
 struct ListLds : Defaults { static constexpr bool SCAN_LDS = true, HAVE_LDS = true; };
@@ -60,6 +63,7 @@ template <class Row> struct Dbg : Row { static constexpr bool DBG = true; };
 template <class Row> struct Feat : Row { static constexpr bool FEAT = true; };
 template <class Row> struct Qry : Row { static constexpr bool FEAT = true, QRY = true; };
 template <class Row> struct Rad : Row { static constexpr bool RAD = true; };
+template <class Row> struct Nee : Row { static constexpr bool NEE = true; };
 }  // namespace ptb
 
 // One entry of a kernel list (pt_extra.h) as the kernel's definition and as the `case` of its object's accessor; a row of
@@ -82,7 +86,7 @@ template <class Row> struct Rad : Row { static constexpr bool RAD = true; };
 template <class B>
 __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
   using namespace ptk;
-  constexpr bool SCAN_LDS = B::SCAN_LDS, HAVE_LDS = B::HAVE_LDS, COUNT = B::COUNT, RR = B::RR, FLAT_Y = B::FLAT_Y, DBG = B::DBG, FEAT = B::FEAT, QRY = B::QRY, RAD = B::RAD;
+  constexpr bool SCAN_LDS = B::SCAN_LDS, HAVE_LDS = B::HAVE_LDS, COUNT = B::COUNT, RR = B::RR, FLAT_Y = B::FLAT_Y, DBG = B::DBG, FEAT = B::FEAT, QRY = B::QRY, RAD = B::RAD, NEE = B::NEE;
   constexpr int WALK = B::WALK, TAIL = B::TAIL;
   using S = Scene<SCAN_LDS, HAVE_LDS, WALK, TAIL, FLAT_Y>;
   S::stage(A);
@@ -96,6 +100,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
   const PixelDiv pd = pixel_div();
   uint32_t seg_count = 0; // wave-uniform tally (samples are derived on the host: pixels * spp * passes)
   tally.start();
+  NeeState<NEE> ne;  // the next-event builds' shadow state (empty unless NEE)
 
   for (;;) {
     refill<COUNT, QRY, RAD>(A, p, q, pd, tally);
@@ -120,6 +125,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
     const bool fast = regular_ray(A, p);
     const int n_live = (int)__popcll(live);
     if constexpr (S::TREE) park_store(A, p);
+    if constexpr (S::TREE && NEE) park_store(A, ne);  // (the shadow ray's weight: the parking area's spare dword)
     // TAIL MODE (pt_list.hpp) is the list kernels' way out of a launch's drain: the last few rays of a wave are looked at
     // by all 64 lanes.  The walk kernels do not have it: a walk costs a wave ~1 500 issue slots whatever its lane count
     // and a turn-around n / 64 x 45 + 70 per ray, so it only ever served waves of <= 3 live rays there (config 2), while
@@ -161,6 +167,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
       if (coop) cw.carried = false;
       cw.closest_w = h.closest;
       park_load(A, p);
+      if constexpr (NEE) park_load(A, ne);
     }
     tally.phase(6);
 
@@ -168,7 +175,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
     const bool shade = p.alive && !cw.carried;
     seg_count += (uint32_t)__popcll(pt_ballot(shade));
     tally.timebin(A, shade);
-    if (shade) shade_segment<S, RR, COUNT, DBG, FEAT, QRY>(A, p, h, cw, tally);
+    if (shade) shade_segment<S, RR, COUNT, DBG, FEAT, QRY, NEE>(A, p, h, cw, tally, ne);
     tally.collect();
     tally.phase(7);
   }

@@ -133,6 +133,14 @@ class PathTracer:
         not with the roulette-free oracle.  A context set to PT_GEOM_LDS renders through the scalar walk meanwhile."""
         self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_RUSSIAN_ROULETTE, int(min_depth)))
 
+    def next_event(self, on=True):
+        """Next-event estimation (PT_OPT_NEXT_EVENT; off by default): at every DIFFUSE hit whose path goes on, the render launches
+        sample one of the scene's emissive spheres through a shadow ray, and a path that then runs into a light it could have
+        sampled adds nothing.  Same expectation per pixel as the plain estimator, different samples: bit-comparable with
+        tests/nee_ref.py, not with the oracle (a scene without lights renders the oracle's bits).  Excludes Russian roulette,
+        the debug overlay and the measuring twins; the feature, query and radiance calls stay the plain estimator."""
+        self._check(self.lib.pt_set_option(self._ctx, abi.PT_OPT_NEXT_EVENT, 1 if on else 0))
+
     def set_debug_overlay(self, enable, selected_object=abi.NO_SELECTED_OBJECT_ID, cursor_point=(0.0, 0.0, 0.0)):
         """The shader's debug overlay (static/shader.frag:307-318; pt_set_debug_overlay): hits within 0.1 of `cursor_point`
         are blue, the silhouette band of the sphere whose uuid is `selected_object` is red, and such a path ends there.
@@ -705,11 +713,12 @@ def _memcpy(dst, src, nbytes, kind):
         raise PtError(abi.PT_ERR_HIP, "hipMemcpy failed with %d" % rc)
 
 
-def render_scene(scene, device=0, use_torch=False, passes_per_launch=None, band=None, geometry_path=None, tune=None, overlay=None):
+def render_scene(scene, device=0, use_torch=False, passes_per_launch=None, band=None, geometry_path=None, tune=None, overlay=None, next_event=False):
     """Render a scenes.Scene completely; returns (PathTracer, accum ndarray).  `tune` = n: pt_tune(n) after scene and
     uniforms are up, as bench.py does before it times anything — the grid is refitted to the camera and PT_GEOM_AUTO
     settled with n-pass launches (the as-benchmarked path: tests that pin what the bench line times pass it).
-    `overlay` = (selected_object, cursor_point): with the debug overlay on (set_debug_overlay)."""
+    `overlay` = (selected_object, cursor_point): with the debug overlay on (set_debug_overlay).  `next_event`: with
+    next-event estimation on (PathTracer.next_event)."""
     p = scene.params.copy()
     if band is not None:
         p.band_rows, p.band_index, p.band_count = band
@@ -719,6 +728,8 @@ def render_scene(scene, device=0, use_torch=False, passes_per_launch=None, band=
     pt.set_spheres(scene.spheres)
     if overlay is not None:
         pt.set_debug_overlay(True, overlay[0], overlay[1])
+    if next_event:
+        pt.next_event(True)
     pt.set_params(p)
     per = passes_per_launch or scene.n_passes
     pt.reserve_passes(max(per, int(tune or 0)))
