@@ -68,6 +68,21 @@ pub struct PtRayRadiance {       // the record of one ray of pt_query_radiance, 
     pub sum: [f32; 3], pub samples: f32,
 }
 
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtGatherPoint {       // one item of pt_gather_irradiance / pt_bake_probes, 32 bytes; a probe's normal and the pads are not read
+    pub position: [f32; 3], pub _pad0: f32, pub normal: [f32; 3], pub _pad1: f32,
+}
+
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtIrradiance {        // the record of one point of pt_gather_irradiance, 16 bytes; samples 0 marks an invalid item
+    pub e: [f32; 3], pub samples: f32,
+}
+
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtProbeSH {           // the record of one probe of pt_bake_probes, 112 bytes: nine real SH coefficients of bands 0 to 2 per channel
+    pub sh: [[f32; 3]; 9], pub samples: f32,
+}
+
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct PtMeterOptions {      // the rule of one pt_meter, 48 bytes; the window is in image coordinates, w == 0 or h == 0: the whole frame
     pub key: f32, pub key_permille: u32, pub high_permille: u32, pub e_min: f32, pub e_max: f32, pub white_min: f32, pub rate: f32,
@@ -168,6 +183,8 @@ extern "C" {
     // view — by the plain estimator, n_passes passes (at most those reserved) of samples_per_pixel samples per ray; host or device
     // pointers, synchronous; the camera, the accumulation and first_pass do not move
     pub fn pt_query_radiance(ctx: *mut PtCtx, rays: *const PtRay, n: u32, n_passes: u32, out: *mut PtRayRadiance) -> c_int;
+    pub fn pt_gather_irradiance(ctx: *mut PtCtx, points: *const PtGatherPoint, n: u32, directions: u32, n_passes: u32, out: *mut PtIrradiance) -> c_int;
+    pub fn pt_bake_probes(ctx: *mut PtCtx, probes: *const PtGatherPoint, n: u32, directions: u32, n_passes: u32, out: *mut PtProbeSH) -> c_int;
     // exposure metering and the toned read-outs (pt_set_option PT_OPT_TONEMAP 1): meter the frame on the device (src NULL: the
     // accumulation; else host or device linear RGBA f32 texels), keep the exposure record there, read the frame out through a tone
     // curve; pt_exposure_solve is the metering's second kernel on the host (ranks add their histograms, solve, pt_meter_set)

@@ -853,6 +853,71 @@ typedef struct PtRayRadiance {
 } PtRayRadiance; /* 16 bytes: an accumulation texel */
 int pt_query_radiance(pt_ctx* ctx, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out);
 
+/* ---- gather queries: the irradiance at points and SH probes, made on the device (needs PT_OPT_RAY_QUERIES on; no option of its own) ----
+ * pt_query_radiance answers a ray; these two answer "how much light arrives HERE": the rays of an item are made on the device,
+ * walked by pt_query_radiance's own launches and folds, and reduced on the device — 32 bytes up and 16 or 112 bytes down per
+ * item instead of 32 up and 16 down per ray.  The kernels are a code object of their own (csrc/pt_kernels_gather.hip, loaded at
+ * the first call); the arithmetic is csrc/pt_gather.hpp, shared with the host.
+ * THE DEFINING SENTENCE: item i of a call with D = directions is exactly what a caller gets who (1) makes the n * D rays below
+ * on the host, ray j of item i at index i * D + j, (2) calls pt_query_radiance(ctx, rays, n * D, n_passes, rec) ONCE — the batch,
+ * place, pass and seed rules above apply unchanged to those indices — and (3) reduces rec[i * D .. i * D + D) by the statement
+ * list below.  What pt_query_radiance leaves alone these calls leave alone; PtStats moves exactly as that one call moves it.
+ * D is a multiple of 64 in [64, 4096], and n * D is at most 2^32 - 1.
+ * THE DIRECTION SET, the same for every item; fp32, one IEEE operation per statement, `/` and sqrt correctly rounded, for j < D:
+ *   a = float(2 j + 1) / float(D)
+ *   u = float(((j * 0x9E3779B97F4A7C15) mod 2^64) >> 40) * 2^-24      (frac(j * 0.61803398875) cut to 24 bits, in integers:
+ *                                                            the constant is 2^64 / the golden ratio, j * 0.618... to 2^-52)
+ *   (s, c) = sincos2pi(u)                                    (sin and cos of 2 pi u: the arithmetic contract's)
+ * pt_bake_probes — the sphere, +y the stratified axis (the axis the sky varies along); `normal` is not read:
+ *   y = 1 - a;  r2 = fma(-y, y, 1);  r = sqrt(r2);  omega = (r * c, y, r * s)
+ * pt_gather_irradiance — the hemisphere about the normal, cosine-weighted:
+ *   h = a * 0.5;  sh = sqrt(h);  lx = sh * c;  ly = sh * s;  m = 1 - h;  lz = sqrt(m)
+ *   g = max(|n.x|, |n.y|, |n.z|);  p = n / g (per component);  d2 = fma(p.z, p.z, fma(p.y, p.y, p.x * p.x));  i = 1 / sqrt(d2);
+ *   z = p * i                                                (the unit normal of ANY finite non-zero normal, however short or long)
+ *   sg = copysign(1, z.z);  q = -1 / (sg + z.z);  b = (z.x * z.y) * q
+ *   t = (fma(sg * (z.x * z.x), q, 1), sg * b, -sg * z.x);  bt = (b, fma(z.y * z.y, q, sg), -z.y)     (csrc/pt_nee.hpp's frame)
+ *   omega.k = fma(z.k, lz, fma(bt.k, ly, t.k * lx))
+ * The ray is {position, omega}; nothing is offset (t_min = 0.001 along a unit direction is the bounce ray's own guard).
+ * THE REDUCTION of an item's records r_j = rec[i * D + j], and ITS ORDER, which is part of the contract: 64 lanes; lane l starts
+ * from accumulators of +0 and takes j = l, l + 64, l + 128, ... in ascending order:
+ *   mean.c = r_j.sum.c / r_j.samples
+ *   irradiance: acc.c = acc.c + mean.c                 probe: acc[k].c = fma(mean.c, Y_k(omega_j), acc[k].c), k = 0 .. 8
+ *   acc.samples = acc.samples + r_j.samples
+ * then the tree: for o = 32, 16, 8, 4, 2, 1: v[l] = v[l] + v[l xor o] for every lane at once, per accumulator; the item's sums
+ * are v[0].  Neither the launch shape nor a batch boundary enters (an item that straddles batches carries its lanes' partial
+ * sums from one to the next: the same adds in the same order), and no floating-point atomic is used.
+ *   irradiance: e.c = v.c * (3.14159265f / float(D))          probe: sh[k].c = v[k].c * (12.5663706f / float(D))
+ *   samples = v.samples                                       (D * n_passes * samples_per_pixel, exact below 2^24)
+ * THE BASIS, with (x, y, z) = omega, in the order (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2):
+ *   Y0 = 0.282095f;  Y1 = 0.488603f * y;  Y2 = 0.488603f * z;  Y3 = 0.488603f * x;  Y4 = 1.092548f * (x * y);
+ *   Y5 = 1.092548f * (y * z);  Y6 = 0.315392f * fma(3, z * z, -1);  Y7 = 1.092548f * (x * z);  Y8 = 0.546274f * fma(x, x, -(y * y))
+ * INVALID ITEMS: an item with a non-finite position component — for pt_gather_irradiance also with a non-finite normal
+ * component or a normal of three zeros — is invalid.  That is decided on the device; its D rays are null rays (invalid rays of
+ * pt_query_radiance: nothing is traced, PtStats.segments does not move), and its record is all +0: samples == 0 is the mark.
+ * `points` / `probes` and `out` are host or device pointers (n of each), as pt_query_radiance takes them; the pads are not read.
+ * The calls are synchronous on the context's stream; n == 0 is PT_OK with nothing done.  Per batch of pt_query_batch(ctx) rays:
+ * the generator, pt_query_radiance's launch and fold, the reduce.  The first call puts a small buffer of the context's in place
+ * (the lanes' carried sums and the staging of a batch's items: 14 336 + 144 * (pt_query_batch / 64 + 2) bytes), kept until
+ * PT_OPT_RAY_QUERIES is turned off.
+ * ERRORS: pt_query_radiance's, checked in its order, then `directions`: PT_ERR_INVALID for a D outside the set above or
+ * n * D beyond 2^32 - 1.  PT_ERR_CAPACITY also where that buffer's allocation is refused (nothing is launched). */
+typedef struct PtGatherPoint {
+  float position[3];
+  float _pad0;
+  float normal[3];
+  float _pad1;
+} PtGatherPoint; /* 32 bytes */
+typedef struct PtIrradiance {
+  float e[3];
+  float samples;
+} PtIrradiance; /* 16 bytes */
+typedef struct PtProbeSH {
+  float sh[9][3];
+  float samples;
+} PtProbeSH; /* 112 bytes */
+int pt_gather_irradiance(pt_ctx* ctx, const PtGatherPoint* points, uint32_t n, uint32_t directions, uint32_t n_passes, PtIrradiance* out);
+int pt_bake_probes(pt_ctx* ctx, const PtGatherPoint* probes, uint32_t n, uint32_t directions, uint32_t n_passes, PtProbeSH* out);
+
 /* ---- exposure metering and tone-mapped read-out (build extension, opt-in: PT_OPT_TONEMAP) --------------------------------------
  * Every other read-out ends in sqrt and a clamp at 1: the reference's framebuffer.  A frame lit by PT_EMISSIVE spheres holds far
  * more range than that; these calls meter the frame on the device, keep an EXPOSURE there and read the frame out through a tone

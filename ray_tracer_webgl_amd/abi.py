@@ -278,6 +278,54 @@ class PtRayRadiance(C.Structure):
     ]
 
 
+class PtGatherPoint(C.Structure):
+    """include/ptrace.h PtGatherPoint: one item of pt_gather_irradiance / pt_bake_probes, 32 bytes; a probe's normal and the pads are not read."""
+
+    _fields_ = [
+        ("position", C.c_float * 3),
+        ("_pad0", C.c_float),
+        ("normal", C.c_float * 3),
+        ("_pad1", C.c_float),
+    ]
+
+
+class PtIrradiance(C.Structure):
+    """include/ptrace.h PtIrradiance: the record of one point of pt_gather_irradiance, 16 bytes; samples 0 marks an invalid item."""
+
+    _fields_ = [
+        ("e", C.c_float * 3),
+        ("samples", C.c_float),
+    ]
+
+
+class PtProbeSH(C.Structure):
+    """include/ptrace.h PtProbeSH: the record of one probe of pt_bake_probes, 112 bytes — nine real SH coefficients of bands 0 to 2
+    per channel, in the order (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2); samples 0 marks an invalid item."""
+
+    _fields_ = [
+        ("sh", (C.c_float * 3) * 9),
+        ("samples", C.c_float),
+    ]
+
+
+PT_GATHER_MIN_DIRECTIONS, PT_GATHER_MAX_DIRECTIONS = 64, 4096  # a multiple of 64 in between
+
+
+def sh_irradiance(sh, normals):
+    """The irradiance a probe's SH record gives a surface with unit normal n: the cosine convolution, band factors pi, 2 pi / 3
+    and pi / 4 on the nine coefficients in PtProbeSH's order.  `sh`: (..., 9, 3), `normals`: (..., 3), broadcast against each
+    other; (..., 3) float64 out.  Exact for light without a band above 2 (up to the probe's quadrature)."""
+    import numpy as np
+
+    sh = np.asarray(sh, np.float64)
+    n = np.asarray(normals, np.float64)
+    x, y, z = n[..., 0], n[..., 1], n[..., 2]
+    basis = np.stack([0.282095 * np.ones_like(x), 0.488603 * y, 0.488603 * z, 0.488603 * x, 1.092548 * x * y, 1.092548 * y * z,
+                      0.315392 * (3.0 * z * z - 1.0), 1.092548 * x * z, 0.546274 * (x * x - y * y)], axis=-1)
+    band = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+    return np.einsum("...k,...kc->...c", basis * band, sh)
+
+
 class PtMeterOptions(C.Structure):
     """include/ptrace.h PtMeterOptions: the rule of one pt_meter (and of pt_exposure_solve, which does not read the window),
     48 bytes.  The window {x0, y0, w, h} is in image coordinates, row 0 at the bottom; w == 0 or h == 0 is the whole frame."""

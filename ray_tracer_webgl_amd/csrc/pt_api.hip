@@ -41,6 +41,7 @@
 #include "pt_radiance.hpp"
 #include "pt_tone.hpp"
 #include "pt_glare.hpp"
+#include "pt_gather.hpp"
 #include "pt_buffers.hpp"
 #include "pt_ctx_state.hpp"
 
@@ -146,6 +147,8 @@ struct pt_ctx {
   ptbuf::HistorySet<float4> hist;
   ptbuf::ExposureSet expo;
   ptbuf::GlareSet<float4> glare;
+  // the gather queries' workspace (pt_gather_irradiance, pt_bake_probes): fitted by the first call, released with the query planes
+  ptbuf::GatherSet gather;
   uint32_t reserved_passes = 1;
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   PathTuner geom;
@@ -2140,7 +2143,7 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
     return set_buffer_option(c, value, "feature planes", c->feat, [&] { c->feat.release(); reproject_off(); },
                              pt_feature_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar)), uuids);
   if (key == PT_OPT_RAY_QUERIES)
-    return set_buffer_option(c, value, "ray queries", c->query, [c] { c->query.release(); }, pt_query_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar)), uuids);
+    return set_buffer_option(c, value, "ray queries", c->query, [c] { c->query.release(); c->gather.release(); }, pt_query_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar)), uuids);
   if (key == PT_OPT_REPROJECT) {
     if (value == 1 && !c->feat.on) return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_REPROJECT needs PT_OPT_FEATURES on (it reads the feature planes)");
     return set_buffer_option(c, value, "reprojection", c->hist, reproject_off, pt_reproject_kernel_handle(), [] { return PT_OK; });
@@ -2368,6 +2371,92 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
     PT_HIP(c, hipStreamSynchronize(c->stream));
   }
   return PT_OK;
+}
+
+// ---- gather queries (needs PT_OPT_RAY_QUERIES; include/ptrace.h has the contract) ------------------------------
+// The one function behind pt_gather_irradiance and pt_bake_probes: the n * D rays of the defining sentence in pt_query_radiance's
+// batches.  A batch: the items it touches into the workspace (a host array's; a device array is read in place), the generator
+// in stage_rays' place, pt_query_radiance's launch and fold as they are — the folded records wait in the query planes' first
+// plane, where a host call's wait for their copy — and the reduce over the items the batch touches: an item that ends in the
+// batch is written (straight into a device `out`, or into the workspace and copied from there), the one that goes on leaves its
+// lanes' partial sums in the workspace for the next batch.
+static int gather(pt_ctx* c, const char* who, int kind, const PtGatherPoint* points, uint32_t n, uint32_t D, uint32_t n_passes, void* out) {
+  if (!c) return PT_ERR_INVALID;
+  if (n == 0) return PT_OK;
+  if (int rc = query_ready(c, who, "radiance", points, out); rc != PT_OK) return rc;
+  if (n_passes == 0) return fail(c, PT_ERR_INVALID, "%s: n_passes == 0", who);
+  if (n_passes > c->reserved_passes)
+    return fail(c, PT_ERR_CAPACITY, "%s: %u passes > %u reserved (pt_reserve_passes)", who, n_passes, c->reserved_passes);
+  if (!ptgather::directions_valid(D))
+    return fail(c, PT_ERR_INVALID, "%s: %u directions (a multiple of 64 in [%d, %d])", who, D, (int)ptgather::kMinDirections, (int)ptgather::kMaxDirections);
+  const uint64_t total = ptgather::total_rays(n, D);
+  if (total == 0) return fail(c, PT_ERR_INVALID, "%s: %u items of %u directions are more than 2^32 - 1 rays", who, n, D);
+  const ptbuf::Extent e = extent_of(c);
+  if (!c->gather.in_place(e)) {
+    if (const ptbuf::Fit f = c->gather.fit(e); !f.ok())
+      return fail(c, PT_ERR_CAPACITY, "%s: the workspace's allocation for %zu local pixels failed: %s", who, e.pix, hipGetErrorString((hipError_t)f.err));
+  }
+  const uint32_t plane = (uint32_t)n_pixels(c);
+  const size_t record = kind == ptgather::PROBE ? sizeof(PtProbeSH) : sizeof(PtIrradiance);
+  const bool points_on_device = device_pointer(points), out_on_device = device_pointer(out);
+  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->query.planes.get());
+  PtRayRadiance* folded = reinterpret_cast<PtRayRadiance*>(planes + (size_t)PT_FEAT_ALBEDO * plane);
+  PtGatherPoint* staged_points = reinterpret_cast<PtGatherPoint*>(c->gather.points());
+  void* staged_out = c->gather.records(e);
+  const uint32_t batches = ptq::n_batches((uint32_t)total, plane);
+  for (uint32_t k = 0; k < batches; k++) {
+    uint32_t first = (uint32_t)((uint64_t)k * plane);
+    uint32_t m = ptq::batch_rays((uint32_t)total, plane, k);
+    uint32_t item0 = first / D, items = (uint32_t)(((uint64_t)first + m - 1u) / D) - item0 + 1u;  // the items the batch touches
+    // ... and those of them that end in it: [done0, done1)
+    const uint32_t done0 = item0, done1 = (uint32_t)(((uint64_t)first + m) / D);
+    // (items <= m / 64 + 2 <= GatherSet::items(e): D >= 64 and m <= plane — the workspace holds them)
+    const PtGatherPoint* pts = points + item0;
+    if (!points_on_device) {
+      PT_HIP(c, hipMemcpyAsync(staged_points, points + item0, (size_t)items * sizeof(PtGatherPoint), hipMemcpyHostToDevice, c->stream));
+      pts = staged_points;
+    }
+    {
+      uint32_t dirs = D, pl = plane;
+      int kd = kind;
+      void* kargs[] = {&pts, &item0, &first, &m, &dirs, &kd, &planes, &pl};
+      PT_HIP(c, hipLaunchKernel(pt_gather_kernel(PT_GATHER_RAYS), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+    }
+    LaunchUse use = batch_use(c, DOOR_RADIANCE, m);
+    use.who = who;
+    use.first_pass = ptr::batch_first_pass(c->params.first_pass, k, n_passes);
+    if (int rc = trace_once(c, n_passes, use); rc != PT_OK) return rc;
+    {
+      const ptq::F4* slab = reinterpret_cast<const ptq::F4*>(c->frame.slab.get());
+      const ptq::F4* staged = planes;
+      uint32_t pl = plane, np = n_passes;
+      void* kargs[] = {&slab, &pl, &np, &staged, &m, &folded};
+      PT_HIP(c, hipLaunchKernel(pt_radiance_fold_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+    }
+    {
+      const PtRayRadiance* rec = folded;
+      void* dst = out_on_device ? out : staged_out;
+      uint32_t out0 = out_on_device ? 0u : done0, dirs = D;
+      int kd = kind;
+      // (batch k writes the carry slot of its parity and reads the other, which batch k - 1 wrote: never one slot in one launch)
+      const float* carry_in = c->gather.carry(k + 1u);
+      float* carry_out = c->gather.carry(k);
+      void* kargs[] = {&rec, &pts, &item0, &items, &first, &m, &dirs, &kd, &carry_in, &carry_out, &dst, &out0};
+      PT_HIP(c, hipLaunchKernel(pt_gather_kernel(PT_GATHER_REDUCE), dim3((items + 3u) / 4u), dim3(256), kargs, 0, c->stream));
+      if (!out_on_device && done1 > done0)
+        PT_HIP(c, hipMemcpyAsync(static_cast<char*>(out) + (size_t)done0 * record, staged_out, (size_t)(done1 - done0) * record, hipMemcpyDeviceToHost, c->stream));
+    }
+    // (the next batch stages into the planes and the workspace this one reads)
+    PT_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return PT_OK;
+}
+
+PT_API int pt_gather_irradiance(pt_ctx* c, const PtGatherPoint* points, uint32_t n, uint32_t directions, uint32_t n_passes, PtIrradiance* out) {
+  return gather(c, "pt_gather_irradiance", ptgather::IRRADIANCE, points, n, directions, n_passes, out);
+}
+PT_API int pt_bake_probes(pt_ctx* c, const PtGatherPoint* probes, uint32_t n, uint32_t directions, uint32_t n_passes, PtProbeSH* out) {
+  return gather(c, "pt_bake_probes", ptgather::PROBE, probes, n, directions, n_passes, out);
 }
 
 // ---- exposure metering and the toned read-out (PT_OPT_TONEMAP; include/ptrace.h has the contract) -------------

@@ -14,6 +14,7 @@
 #include <utility>
 
 #include "../../include/ptrace.h"
+#include "pt_gather.hpp"
 #include "pt_glare.hpp"
 
 namespace ptbuf {
@@ -289,6 +290,33 @@ struct GlareSet {
     on = false;
     pyramid.release();
   }
+};
+
+// The gather queries' workspace (pt_gather_irradiance, pt_bake_probes; no option of its own: it lives under PT_OPT_RAY_QUERIES and
+// is released with the query planes): one allocation of floats — the 64 lanes' carried partial sums of the item that straddles a
+// batch boundary, in TWO slots of 64 * 28 (a batch's reduce reads the slot the batch before wrote and writes the other: reader
+// and writer are different waves of one launch), then the staging of the items one batch touches (K = pix / 64 + 2 of them: the PtGatherPoint going
+// up, 8 floats each, and the records coming down, 28 floats each, a PtProbeSH's size) — 14 336 + 144 K bytes.  Fitted by the
+// first call and again where the rows in place outgrew it; SCRATCH: nothing in it outlives a call, so it carries no validity and
+// has no row in the change table of pt_ctx_state.hpp, and it is not zeroed.
+struct GatherSet {
+  enum : uint32_t { WORK = 1 };
+  static constexpr size_t kSlot = (size_t)ptgather::kLanes * ptgather::kMaxAcc, kCarry = 2 * kSlot, kPoint = 8, kRecord = 28;
+  DevBuf<float> work;
+
+  static size_t items(const Extent& e) { return e.pix / ptgather::kMinDirections + 2; }
+  static size_t floats(const Extent& e) { return kCarry + (kPoint + kRecord) * items(e); }
+  Fit fit(const Extent& e) {
+    Fit f;
+    if (work.holds_at_least(floats(e))) return f;
+    refit(f, work, floats(e), WORK);
+    return f;
+  }
+  bool in_place(const Extent& e) const { return work.holds_at_least(floats(e)); }
+  float* carry(uint32_t slot) const { return work.get() + (slot & 1u) * kSlot; }  // the two slots: a batch writes its parity's
+  float* points() const { return work.get() + kCarry; }
+  float* records(const Extent& e) const { return work.get() + kCarry + kPoint * items(e); }
+  void release() { work.release(); }
 };
 
 // PT_OPT_NEXT_EVENT: the light table of the scene in place — n records (pt_nee.hpp Light), one allocation of at least max(n, 1).

@@ -102,6 +102,10 @@ extern "C" const void* pt_display_kernel(int id);
 // pt_kernels_glare.hip (a code object of its own): the glare pyramid's down, gather and composite kernels (PT_OPT_GLARE)
 enum { PT_G_DOWN = 0, PT_G_GATHER, PT_G_COMPOSITE, PT_G_COUNT };
 extern "C" const void* pt_glare_kernel(int id);
+// pt_kernels_gather.hip (a code object of its own): the gather queries' ray generator and reduce (pt_gather_irradiance,
+// pt_bake_probes)
+enum { PT_GATHER_RAYS = 0, PT_GATHER_REDUCE, PT_GATHER_COUNT };
+extern "C" const void* pt_gather_kernel(int id);
 // pt_kernels_nee.hip (a code object of its own): the next-event builds (PT_OPT_NEXT_EVENT), the twelve variant rows under the
 // adaptor Nee with the suffix _nee, by variant id.  No column of the trace table: the host keeps them in the side table
 // kNeeKernels (pt_nee_table.hpp) and takes a cell of it where a render launch's column would have been the plain build.

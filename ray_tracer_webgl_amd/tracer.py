@@ -519,6 +519,53 @@ class PathTracer:
             mean = np.where(samples[:, None] > 0, rec[:, 0:3] / np.maximum(samples, np.float32(1.0))[:, None], np.float32(0.0)).astype(np.float32)
         return {"sum": rec[:, 0:3], "samples": samples, "mean": mean}
 
+    # -- gather queries: irradiance at points and SH probes (include/ptrace.h pt_gather_irradiance, pt_bake_probes) --
+    def _gather(self, fn, what, positions, normals, directions, passes, floats):
+        """`fn` over n items: (n, floats) float32 records, numpy for numpy arrays and a torch device tensor for torch device
+        tensors under use_torch"""
+        if not (abi.PT_GATHER_MIN_DIRECTIONS <= int(directions) <= abi.PT_GATHER_MAX_DIRECTIONS and int(directions) % 64 == 0):
+            raise ValueError("%s: %d directions (a multiple of 64 in [%d, %d])" % (what, directions, abi.PT_GATHER_MIN_DIRECTIONS, abi.PT_GATHER_MAX_DIRECTIONS))
+        if self.use_torch and self._torch.is_tensor(positions) and positions.is_cuda:
+            torch = self._torch
+            three = lambda v: v.to(device=positions.device, dtype=torch.float32).reshape(-1, 3)
+            zeros = lambda shape: torch.zeros(shape, dtype=torch.float32, device=positions.device)
+            ptr = lambda a: C.c_void_p(a.data_ptr())
+        else:
+            three = lambda v: np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
+            zeros = lambda shape: np.zeros(shape, np.float32)
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        pos = three(positions)
+        n = int(pos.shape[0])
+        items = zeros((n, 8))  # PtGatherPoint: {position, pad, normal, pad}
+        items[:, 0:3] = pos
+        if normals is not None:
+            nrm = three(normals)
+            if nrm.shape != pos.shape:
+                raise ValueError("%s: %d positions, %d normals" % (what, n, nrm.shape[0]))
+            items[:, 4:7] = nrm
+        rec = zeros((n, floats))
+        if n:
+            self._check(fn(self._ctx, ptr(items), n, int(directions), int(passes), ptr(rec)))
+        return rec
+
+    def gather_irradiance(self, points, normals, directions=256, passes=1):
+        """The irradiance at each point of a surface with that normal (pt_gather_irradiance; needs ray_queries(True)):
+        `directions` cosine-weighted rays per point (a multiple of 64 in [64, 4096]), made, walked by query_radiance's plain
+        estimator and reduced on the device.  Two (n, 3) float32 arrays in (normals of any length), a dict out — "e": (n, 3)
+        float32, "samples": (n,) float32, 0 for an invalid item (a non-finite component, a normal of three zeros).  numpy
+        arrays give numpy arrays; under use_torch, torch device tensors give torch device tensors.  Synchronous; nothing else
+        of the context moves."""
+        rec = self._gather(self.lib.pt_gather_irradiance, "gather_irradiance", points, normals, directions, passes, 4)
+        return {"e": rec[:, 0:3], "samples": rec[:, 3]}
+
+    def bake_probes(self, positions, directions=256, passes=1):
+        """An SH probe of bands 0 to 2 at each position (pt_bake_probes; needs ray_queries(True)): `directions` rays over the
+        sphere per probe.  An (n, 3) float32 array in, a dict out — "sh": (n, 9, 3) float32 in abi.PtProbeSH's order,
+        "samples": (n,) float32, 0 for an invalid item.  abi.sh_irradiance(sh, normals) gives the irradiance the record holds
+        for a normal.  Arrays and tensors as gather_irradiance takes them."""
+        rec = self._gather(self.lib.pt_bake_probes, "bake_probes", positions, None, directions, passes, 28)
+        return {"sh": rec[:, 0:27].reshape(-1, 9, 3), "samples": rec[:, 27]}
+
     # -- exposure metering and the toned read-outs (include/ptrace.h PT_OPT_TONEMAP) -----------------
     def tone_mapping(self, on=True):
         """Put the exposure state in place (or release it: the exposure is forgotten).  Off by default; the image bits are the
