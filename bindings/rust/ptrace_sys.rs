@@ -185,6 +185,11 @@ extern "C" {
     pub fn pt_query_radiance(ctx: *mut PtCtx, rays: *const PtRay, n: u32, n_passes: u32, out: *mut PtRayRadiance) -> c_int;
     pub fn pt_gather_irradiance(ctx: *mut PtCtx, points: *const PtGatherPoint, n: u32, directions: u32, n_passes: u32, out: *mut PtIrradiance) -> c_int;
     pub fn pt_bake_probes(ctx: *mut PtCtx, probes: *const PtGatherPoint, n: u32, directions: u32, n_passes: u32, out: *mut PtProbeSH) -> c_int;
+    // the same three by the next-event estimator (PT_OPT_RAY_QUERIES and PT_OPT_NEXT_EVENT on): the caller's ray is a path's first
+    // segment, the light samples start at its first DIFFUSE hit; same arguments, records and batches as the namesakes
+    pub fn pt_query_radiance_nee(ctx: *mut PtCtx, rays: *const PtRay, n: u32, n_passes: u32, out: *mut PtRayRadiance) -> c_int;
+    pub fn pt_gather_irradiance_nee(ctx: *mut PtCtx, points: *const PtGatherPoint, n: u32, directions: u32, n_passes: u32, out: *mut PtIrradiance) -> c_int;
+    pub fn pt_bake_probes_nee(ctx: *mut PtCtx, probes: *const PtGatherPoint, n: u32, directions: u32, n_passes: u32, out: *mut PtProbeSH) -> c_int;
     // exposure metering and the toned read-outs (pt_set_option PT_OPT_TONEMAP 1): meter the frame on the device (src NULL: the
     // accumulation; else host or device linear RGBA f32 texels), keep the exposure record there, read the frame out through a tone
     // curve; pt_exposure_solve is the metering's second kernel on the host (ranks add their histograms, solve, pt_meter_set)

@@ -126,7 +126,9 @@ enum {
                              EXPECTATION is the plain estimator's, the samples differ.  0 (default): off, the table is released;
                              bit-exact against the oracle.  Excludes PT_OPT_RUSSIAN_ROULETTE, the debug overlay and
                              PT_OPT_COUNT_WORK (PT_ERR_INVALID, whichever comes second).  pt_render_features, pt_query_rays and
-                             pt_query_radiance stay the plain estimator.  The statements (csrc/pt_nee.hpp has each as one fp32
+                             pt_query_radiance stay the plain estimator (this estimator along the caller's rays has entry points
+                             of its own, which need the option on: pt_query_radiance_nee, pt_gather_irradiance_nee and
+                             pt_bake_probes_nee, below).  The statements (csrc/pt_nee.hpp has each as one fp32
                              operation; the order below is the contract):
                                LIGHTS  the spheres of the installed list with type == PT_EMISSIVE, a finite centre, a finite
                                        non-zero radius and a finite albedo, in list order; L of them.  The device table holds
@@ -917,6 +919,38 @@ typedef struct PtProbeSH {
 } PtProbeSH; /* 112 bytes */
 int pt_gather_irradiance(pt_ctx* ctx, const PtGatherPoint* points, uint32_t n, uint32_t directions, uint32_t n_passes, PtIrradiance* out);
 int pt_bake_probes(pt_ctx* ctx, const PtGatherPoint* probes, uint32_t n, uint32_t directions, uint32_t n_passes, PtProbeSH* out);
+
+/* ---- the same three calls by the NEXT-EVENT estimator (need PT_OPT_RAY_QUERIES and PT_OPT_NEXT_EVENT on; no option of their own) ----
+ * pt_query_radiance, pt_gather_irradiance and pt_bake_probes stay the plain estimator whatever the options say: they find the
+ * lamp of a closed room by chance only.  These three take the same arguments and walk the same rays by the estimator of
+ * PT_OPT_NEXT_EVENT: the same expectation per record, different samples, far less noise where a lamp is small.  The kernels are a
+ * code object of their own (csrc/pt_kernels_radiance_nee.hip: the radiance builds with the next-event shade, loaded at the first
+ * of these calls).
+ * pt_query_radiance_nee, THE RECORD of ray i:
+ *   - the batch b, the place j, the pixel centre (vx, vy) and the seed of pt_query_radiance's statement list: the seed of pass p
+ *     depends on first_pass + b * n_passes + p; NO jitter draw and NO lens draws are made;
+ *   - from that seed, samples_per_pixel CHAINED paths (the seed is carried from sample to sample) of the PT_OPT_NEXT_EVENT
+ *     estimator exactly as stated at the option above and in csrc/pt_nee.hpp, along the caller's ray;
+ *   - the caller's ray is a path's FIRST segment: no light sample precedes it, so an emissive sphere it hits adds its emission;
+ *   - from the first DIFFUSE hit on, the option's rules hold: the draw order (steps 1 to 4), the shadow segment (10 to 12), and
+ *     nothing added for a light that could have been sampled from the segment's origin (NO DOUBLE COUNTING);
+ *   - a sample's terms are added to the PASS's running sum s in the order they arise — s is carried across the samples of a
+ *     pass, as a render launch's per-item sum receives them (not c = ray_color(...); s = s + c);
+ *   - out.sum.c = out.sum.c + s.c per pass, in pass order;  out.samples = out.samples + float(samples_per_pixel).
+ * Records, the samples == 0 mark of an invalid ray, the batch size (pt_query_batch) and the host or device pointers are
+ * pt_query_radiance's.  PtStats.segments moves by the path segments PLUS the shadow segments, as a next-event render launch
+ * counts them.  Everything pt_query_radiance leaves alone stays alone (the accumulation, the estimate, the feature and history
+ * planes, first_pass, pt_last_trace_build, the geometry path, the tile orders).  With no light in the scene (L == 0) the records
+ * are pt_query_radiance's, bit for bit.
+ * pt_gather_irradiance_nee / pt_bake_probes_nee, THE DEFINING SENTENCE: item i is exactly what a caller gets who makes the n * D
+ * rays of the direction set above, calls pt_query_radiance_nee(ctx, rays, n * D, n_passes, rec) ONCE and reduces by the
+ * statement list above: the generator, the reduce and the workspace are pt_gather_irradiance's.  NO light sample is drawn AT
+ * the gather point itself: its D rays are first segments.
+ * ERRORS: the namesake's, in the namesake's order and words (for the gather calls through `directions`); then PT_ERR_NOT_READY
+ * while PT_OPT_NEXT_EVENT is off, and PT_ERR_CAPACITY where its light table is not in place after a failed allocation. */
+int pt_query_radiance_nee(pt_ctx* ctx, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out);
+int pt_gather_irradiance_nee(pt_ctx* ctx, const PtGatherPoint* points, uint32_t n, uint32_t directions, uint32_t n_passes, PtIrradiance* out);
+int pt_bake_probes_nee(pt_ctx* ctx, const PtGatherPoint* probes, uint32_t n, uint32_t directions, uint32_t n_passes, PtProbeSH* out);
 
 /* ---- exposure metering and tone-mapped read-out (build extension, opt-in: PT_OPT_TONEMAP) --------------------------------------
  * Every other read-out ends in sqrt and a clamp at 1: the reference's framebuffer.  A frame lit by PT_EMISSIVE spheres holds far

@@ -32,6 +32,7 @@
 #include "pt_launch_plan.hpp"
 #include "pt_trace_table.hpp"
 #include "pt_nee_table.hpp"
+#include "pt_rad_nee_table.hpp"
 #include "pt_nee.hpp"
 #include "pt_tile_order.hpp"
 #include "pt_error_plan.hpp"
@@ -354,11 +355,12 @@ int frame_buffers_ready(pt_ctx* c, const char* who) {
 }
 
 // an entry point (`who`) of an opt-in set that is off
-enum OptInSet { SET_ESTIMATE, SET_FEATURES, SET_QUERIES, SET_REPROJECT, SET_TONEMAP, SET_GLARE };
+enum OptInSet { SET_ESTIMATE, SET_FEATURES, SET_QUERIES, SET_REPROJECT, SET_TONEMAP, SET_GLARE, SET_NEXT_EVENT };
 int option_off(pt_ctx* c, const char* who, OptInSet set, int code = PT_ERR_NOT_READY) {
   static const char* const what[] = {"the error estimate is off (pt_set_option PT_OPT_ERROR_ESTIMATE)", "the feature planes are off (pt_set_option PT_OPT_FEATURES)",
                                      "ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)", "reprojection is off (pt_set_option PT_OPT_REPROJECT)",
-                                     "tone mapping is off (pt_set_option PT_OPT_TONEMAP)", "the glare is off (pt_set_option PT_OPT_GLARE)"};
+                                     "tone mapping is off (pt_set_option PT_OPT_TONEMAP)", "the glare is off (pt_set_option PT_OPT_GLARE)",
+                                     "next-event estimation is off (pt_set_option PT_OPT_NEXT_EVENT)"};
   return fail(c, code, "%s: %s", who, what[set]);
 }
 
@@ -489,10 +491,11 @@ Staging grid_build(const pt_ctx* c) {
 // kernel's dynamic-LDS limit, once per device and id; the main kernels' limit is lifted at pt_create, the small-list kernels need none.
 const void* cell_kernel(int device, const TraceCell& k) {
 #define PT_TRACE_ACCESSOR_OF(object, accessor, n_ids) accessor,
-  // (... and behind the table's objects the side table's: the next-event builds, pt_nee_table.hpp)
-  static const void* (*const accessors[OBJ_COUNT + 1])(int) = {PT_TRACE_OBJECTS(PT_TRACE_ACCESSOR_OF) pt_nee_kernel};
-  static_assert(OBJ_NEE == OBJ_COUNT, "the next-event object follows the trace table's");
-  static std::once_flag once[64][OBJ_COUNT + 1][PT_EXTRA_COUNT];  // (function attributes belong to a device: the context's is current here)
+  // (... and behind the table's objects the side tables': the next-event builds, pt_nee_table.hpp, and the radiance-query builds
+  // of that estimator, pt_rad_nee_table.hpp)
+  static const void* (*const accessors[OBJ_COUNT + 2])(int) = {PT_TRACE_OBJECTS(PT_TRACE_ACCESSOR_OF) pt_nee_kernel, pt_rad_nee_kernel};
+  static_assert(OBJ_NEE == OBJ_COUNT && OBJ_RAD_NEE == OBJ_COUNT + 1, "the next-event objects follow the trace table's");
+  static std::once_flag once[64][OBJ_COUNT + 2][PT_EXTRA_COUNT];  // (function attributes belong to a device: the context's is current here)
   static_assert(PT_EXTRA_COUNT >= PT_VARIANT_COUNT, "the extra object has the most ids");
   const void* fn = accessors[k.object](k.id);
   if (fn && k.object >= OBJ_EXTRA)
@@ -1102,7 +1105,10 @@ struct LaunchUse {
   //   DOOR_RADIANCE  pt_query_radiance: the PLAIN estimator on the caller's query_rays rays — n_passes passes of the uniforms'
   //                  samples and depth into the pass slabs, frame_ctr at the zero cell; the staged rays travel in
   //                  PtKernelArgs::uuid and the batch's first pass is `first_pass`; c->last_build is not stored
+  //   ... with next_event (set by pt_query_radiance_nee and the two _nee gather calls only, together with DOOR_RADIANCE): the
+  //                  PT_OPT_NEXT_EVENT estimator on those rays — the row's cell of kRadNeeKernels, the light table beside the rays
   Door door = DOOR_NONE;
+  bool next_event = false;
   uint32_t query_rays = 0;
   uint32_t first_pass = 0;
   // the entry point, for a refusal of prepare_launch's own (the frames' launches were asked under their names: frame_ready)
@@ -1132,7 +1138,9 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   const bool rr = !door && c->rr_min_depth > 0, dbg = !door && c->dbg_enable;
   // next-event estimation acts on render launches only; the doors stay the plain estimator
   const bool nee = !door && c->lights.on;
-  if (nee && !c->lights.in_place()) return fail(c, PT_ERR_CAPACITY, "%s: PT_OPT_NEXT_EVENT's light table is not in place (a failed allocation: install the scene or turn the option on again)", use.who);
+  // ... unless the entry point is one of the three that ask for the estimator by name (pt_rad_nee_table.hpp)
+  const bool rad_nee = rad && use.next_event;
+  if ((nee || rad_nee) && !c->lights.in_place()) return fail(c, PT_ERR_CAPACITY, "%s: PT_OPT_NEXT_EVENT's light table is not in place (a failed allocation: install the scene or turn the option on again)", use.who);
   if (rr && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and PT_OPT_RUSSIAN_ROULETTE exclude each other");
   if (dbg && c->count_work) return fail(c, PT_ERR_INVALID, "PT_OPT_COUNT_WORK and the debug overlay exclude each other");
   if (dbg && !c->state.uuid_valid) return fail(c, PT_ERR_NOT_READY, "debug overlay: the uuid arrays are not in place (pt_set_debug_overlay after a failed upload?)");
@@ -1188,7 +1196,16 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
     A.dbg_selected = (int32_t)c->lights.n;
     A.rr_min_depth = 0;
   }
-  const TraceCell& tk = nee_cell ? kNeeKernels[row] : kTraceKernels[row][build];
+  // (the radiance-query builds of the estimator: their rays and the ray count stay where `rad` put them, so the light table travels
+  // in slot_uuid, which both doors leave NULL, and its length as the bits of dbg_cursor[0], which neither reads — pt_kernel_args.h.
+  // reads_ring_layout is false of BUILD_RAD: the build of the row `grid` walks three axes over the plain cell array)
+  const bool rad_nee_cell = takes_rad_nee_cell(rad_nee, build);
+  if (rad_nee_cell) {
+    const uint32_t n_lights = c->lights.n;
+    A.slot_uuid = reinterpret_cast<const int32_t*>(c->lights.table.get());
+    memcpy(&A.dbg_cursor[0], &n_lights, sizeof n_lights);
+  }
+  const TraceCell& tk = rad_nee_cell ? kRadNeeKernels[row] : (nee_cell ? kNeeKernels[row] : kTraceKernels[row][build]);
   const void* kfn = cell_kernel(c->device, tk);
   if (!query && !rad) c->last_build = nee_cell ? (int)BUILD_NEXT_EVENT : build;  // (what pt_last_trace_build reports: a render or feature launch's column)
   const uint32_t block = walk ? walk_block_threads(kfn, tk.waves, scene, kWalkLdsMax, knobs.bvh_block) : list_block_threads(scene);
@@ -2282,6 +2299,16 @@ static int stage_rays(pt_ctx* c, const PtRay* rays, bool on_device, uint32_t m, 
   return PT_OK;
 }
 
+// What the three _nee entry points ask beyond their namesakes, after the namesake's own checks: the option on — refused the way
+// an off PT_OPT_RAY_QUERIES is — and its light table in place (prepare_launch's sentence, before anything is staged).  With the
+// option on the context has no roulette, overlay or twins (pt_set_option's exclusions): nothing else to exclude.
+static int estimator_ready(pt_ctx* c, const char* who, bool next_event) {
+  if (!next_event) return PT_OK;
+  if (!c->lights.on) return option_off(c, who, SET_NEXT_EVENT);
+  if (!c->lights.in_place()) return fail(c, PT_ERR_CAPACITY, "%s: PT_OPT_NEXT_EVENT's light table is not in place (a failed allocation: install the scene or turn the option on again)", who);
+  return PT_OK;
+}
+
 // The launch of a batch of m staged rays through `door`: over the tile rows the rays occupy, in the query planes' own tile order.
 static LaunchUse batch_use(const pt_ctx* c, Door door, uint32_t m) {
   LaunchUse use;
@@ -2338,13 +2365,16 @@ PT_API int pt_query_rays(pt_ctx* c, const PtRay* rays, uint32_t n, PtRayHit* hit
 // occupy — n_passes passes of the batch's own into the pass slabs — and ONE fold of those slabs into the records
 // (pt_radiance_fold_kernel): straight into a device `out`, or into the query planes' first plane (a record is a texel) and
 // copied from there.  Nothing is allocated per call but the host vector of a host batch's staging.
-PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out) {
+// Both estimators share the body: `next_event` is pt_query_radiance_nee's (its own precondition after the namesake's checks, its
+// own side table's cell at the launch: LaunchUse::next_event), and nothing else differs.
+static int query_radiance(pt_ctx* c, const char* who, bool next_event, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out) {
   if (!c) return PT_ERR_INVALID;
   if (n == 0) return PT_OK;
-  if (int rc = query_ready(c, "pt_query_radiance", "radiance", rays, out); rc != PT_OK) return rc;
-  if (n_passes == 0) return fail(c, PT_ERR_INVALID, "pt_query_radiance: n_passes == 0");
+  if (int rc = query_ready(c, who, "radiance", rays, out); rc != PT_OK) return rc;
+  if (n_passes == 0) return fail(c, PT_ERR_INVALID, "%s: n_passes == 0", who);
   if (n_passes > c->reserved_passes)
-    return fail(c, PT_ERR_CAPACITY, "pt_query_radiance: %u passes > %u reserved (pt_reserve_passes)", n_passes, c->reserved_passes);
+    return fail(c, PT_ERR_CAPACITY, "%s: %u passes > %u reserved (pt_reserve_passes)", who, n_passes, c->reserved_passes);
+  if (int rc = estimator_ready(c, who, next_event); rc != PT_OK) return rc;
   static_assert(sizeof(PtRayRadiance) == sizeof(ptq::F4), "a record is a texel: the fold's scratch is a plane");
   const uint32_t plane = (uint32_t)n_pixels(c);
   const bool rays_on_device = device_pointer(rays), out_on_device = device_pointer(out);
@@ -2356,6 +2386,8 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
     uint32_t m = ptq::batch_rays(n, plane, k);
     if (int rc = stage_rays(c, rays + first, rays_on_device, m, h_in); rc != PT_OK) return rc;
     LaunchUse use = batch_use(c, DOOR_RADIANCE, m);
+    use.who = who;
+    use.next_event = next_event;
     use.first_pass = ptr::batch_first_pass(c->params.first_pass, k, n_passes);
     if (int rc = trace_once(c, n_passes, use); rc != PT_OK) return rc;
     {
@@ -2373,6 +2405,13 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
   return PT_OK;
 }
 
+PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out) {
+  return query_radiance(c, "pt_query_radiance", false, rays, n, n_passes, out);
+}
+PT_API int pt_query_radiance_nee(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t n_passes, PtRayRadiance* out) {
+  return query_radiance(c, "pt_query_radiance_nee", true, rays, n, n_passes, out);
+}
+
 // ---- gather queries (needs PT_OPT_RAY_QUERIES; include/ptrace.h has the contract) ------------------------------
 // The one function behind pt_gather_irradiance and pt_bake_probes: the n * D rays of the defining sentence in pt_query_radiance's
 // batches.  A batch: the items it touches into the workspace (a host array's; a device array is read in place), the generator
@@ -2380,7 +2419,7 @@ PT_API int pt_query_radiance(pt_ctx* c, const PtRay* rays, uint32_t n, uint32_t 
 // plane, where a host call's wait for their copy — and the reduce over the items the batch touches: an item that ends in the
 // batch is written (straight into a device `out`, or into the workspace and copied from there), the one that goes on leaves its
 // lanes' partial sums in the workspace for the next batch.
-static int gather(pt_ctx* c, const char* who, int kind, const PtGatherPoint* points, uint32_t n, uint32_t D, uint32_t n_passes, void* out) {
+static int gather(pt_ctx* c, const char* who, int kind, bool next_event, const PtGatherPoint* points, uint32_t n, uint32_t D, uint32_t n_passes, void* out) {
   if (!c) return PT_ERR_INVALID;
   if (n == 0) return PT_OK;
   if (int rc = query_ready(c, who, "radiance", points, out); rc != PT_OK) return rc;
@@ -2391,6 +2430,7 @@ static int gather(pt_ctx* c, const char* who, int kind, const PtGatherPoint* poi
     return fail(c, PT_ERR_INVALID, "%s: %u directions (a multiple of 64 in [%d, %d])", who, D, (int)ptgather::kMinDirections, (int)ptgather::kMaxDirections);
   const uint64_t total = ptgather::total_rays(n, D);
   if (total == 0) return fail(c, PT_ERR_INVALID, "%s: %u items of %u directions are more than 2^32 - 1 rays", who, n, D);
+  if (int rc = estimator_ready(c, who, next_event); rc != PT_OK) return rc;
   const ptbuf::Extent e = extent_of(c);
   if (!c->gather.in_place(e)) {
     if (const ptbuf::Fit f = c->gather.fit(e); !f.ok())
@@ -2424,6 +2464,7 @@ static int gather(pt_ctx* c, const char* who, int kind, const PtGatherPoint* poi
     }
     LaunchUse use = batch_use(c, DOOR_RADIANCE, m);
     use.who = who;
+    use.next_event = next_event;
     use.first_pass = ptr::batch_first_pass(c->params.first_pass, k, n_passes);
     if (int rc = trace_once(c, n_passes, use); rc != PT_OK) return rc;
     {
@@ -2453,10 +2494,16 @@ static int gather(pt_ctx* c, const char* who, int kind, const PtGatherPoint* poi
 }
 
 PT_API int pt_gather_irradiance(pt_ctx* c, const PtGatherPoint* points, uint32_t n, uint32_t directions, uint32_t n_passes, PtIrradiance* out) {
-  return gather(c, "pt_gather_irradiance", ptgather::IRRADIANCE, points, n, directions, n_passes, out);
+  return gather(c, "pt_gather_irradiance", ptgather::IRRADIANCE, false, points, n, directions, n_passes, out);
 }
 PT_API int pt_bake_probes(pt_ctx* c, const PtGatherPoint* probes, uint32_t n, uint32_t directions, uint32_t n_passes, PtProbeSH* out) {
-  return gather(c, "pt_bake_probes", ptgather::PROBE, probes, n, directions, n_passes, out);
+  return gather(c, "pt_bake_probes", ptgather::PROBE, false, probes, n, directions, n_passes, out);
+}
+PT_API int pt_gather_irradiance_nee(pt_ctx* c, const PtGatherPoint* points, uint32_t n, uint32_t directions, uint32_t n_passes, PtIrradiance* out) {
+  return gather(c, "pt_gather_irradiance_nee", ptgather::IRRADIANCE, true, points, n, directions, n_passes, out);
+}
+PT_API int pt_bake_probes_nee(pt_ctx* c, const PtGatherPoint* probes, uint32_t n, uint32_t directions, uint32_t n_passes, PtProbeSH* out) {
+  return gather(c, "pt_bake_probes_nee", ptgather::PROBE, true, probes, n, directions, n_passes, out);
 }
 
 // ---- exposure metering and the toned read-out (PT_OPT_TONEMAP; include/ptrace.h has the contract) -------------

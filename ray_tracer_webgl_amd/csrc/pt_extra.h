@@ -118,6 +118,16 @@ constexpr int pt_nee_waves(int variant_id, int waves) {
   return variant_id == PT_VARIANT_ID(pt_trace_kernel_bvh_nodes) || variant_id == PT_VARIANT_ID(pt_trace_kernel_grid_cells) ? PT_WAVES_NEE_TIGHT : waves;
 }
 extern "C" const void* pt_nee_kernel(int id);
+// pt_kernels_radiance_nee.hip (a code object of its own): the radiance-query builds of the next-event estimator
+// (pt_query_radiance_nee and the two gather calls that walk through it), the twelve variant rows under the adaptor RadNee =
+// Nee<Rad<Row>> with the suffix _rad_nee, by variant id.  No column of the trace table either: the side table kRadNeeKernels
+// (pt_rad_nee_table.hpp), behind kNeeKernels.  Waves per SIMD a row's _rad_nee build is built for: its _nee build's figure — the
+// staged ray's place rides in st_s, which is parked with the path, and the ray count is read where the item is decoded, so RAD
+// adds no register that crosses a walk (the cross-compile's resource report: no scratch, no vector spill in any of the twelve;
+// DESIGN.md §4.8o has the registers).  A row that stops fitting gets its own lower figure HERE: one statement for the kernels'
+// attribute and the host's side table.
+constexpr int pt_rad_nee_waves(int variant_id, int waves) { return pt_nee_waves(variant_id, waves); }
+extern "C" const void* pt_rad_nee_kernel(int id);
 // pt_kernels_query.hip, beside its ray-query builds (PT_OPT_RAY_QUERIES, pt_query_rays): the two kernels that move a batch of
 // rays and records between the caller's device arrays and the query planes
 extern "C" const void* pt_query_pack_kernel_handle(void);

@@ -105,6 +105,12 @@ struct PtKernelArgs {
                                    // base of the query planes here — their staged rays: pt_refill.hpp RAD; the ray count in dbg_selected)
                                    // (the next-event builds, which never read a uuid either, find the LIGHT TABLE here — L records of
                                    // pt_nee.hpp Light, 32 bytes each — and L in dbg_selected: pt_shade.hpp NEE)
+                                   // (the builds that are BOTH, the _rad_nee kernels of pt_kernels_radiance_nee.hip, keep the staged
+                                   // rays and the ray count here and in dbg_selected, where RAD reads them at the decode and at
+                                   // every sample's start; their light table travels in slot_uuid, which both doors leave NULL,
+                                   // and L as the BITS of dbg_cursor[0], which neither reads: pt_scene.hpp nee_light_table /
+                                   // nee_light_count choose by `if constexpr (RAD)`.  No field is added: the layout, and with it
+                                   // every other kernel's argument offsets, stays)
   const int32_t* slot_uuid;        // n_slots: the slot's sphere's uuid (walk kernels, like slot_mat)
   float dbg_cursor[3];             // u_cursor_point, static/shader.frag:102
   int32_t dbg_selected;            // u_selected_object, :101

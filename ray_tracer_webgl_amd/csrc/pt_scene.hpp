@@ -85,6 +85,21 @@ struct NeeState<true> {
 template <bool NEE> struct NeeArgOf { typedef NeeState<false> type; };
 template <> struct NeeArgOf<true> { typedef NeeState<true>& type; };
 
+// WHERE a next-event build finds the light table and its length L in the kernarg segment (pt_kernel_args.h has the three notes):
+// behind `uuid` and in dbg_selected — unless the build is a radiance-query build as well (RAD && NEE, pt_kernels_radiance_nee.hip),
+// whose staged rays and ray count lie there: those find the table behind `slot_uuid` and L as the bits of dbg_cursor[0].  Read at
+// the point of use, like every kernarg of the shade.
+template <bool RAD>
+__device__ __forceinline__ const float4* nee_light_table(karg_t* K) {
+  if constexpr (RAD) return reinterpret_cast<const float4*>(K->slot_uuid);
+  else return reinterpret_cast<const float4*>(K->uuid);
+}
+template <bool RAD>
+__device__ __forceinline__ int nee_light_count(karg_t* K) {
+  if constexpr (RAD) return __float_as_int(K->dbg_cursor[0]);
+  else return K->dbg_selected;
+}
+
 // ---- wave-uniform work-queue state (pt_refill.hpp) ------------------------------------------------
 struct Queue {
   uint32_t pool_next = 0, pool_end = 0;  // this wave's reserved queue items

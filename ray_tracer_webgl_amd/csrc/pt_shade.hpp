@@ -27,7 +27,9 @@ namespace ptk {
 // NEE: the opt-in next-event build (PT_OPT_NEXT_EVENT; pt_kernels_nee.hip): one light sample at every DIFFUSE hit whose path goes
 // on, its shadow ray walked as the lane's next segment (pt_scene.hpp NeeState, pt_nee.hpp has the statements); the light table
 // travels in PtKernelArgs::uuid and L in dbg_selected (pt_kernel_args.h), read from the kernarg segment at the point of use
-template <typename S, bool RR, bool COUNT, bool DBG = false, bool FEAT = false, bool QRY = false, bool NEE = false>
+// RAD: read here only together with NEE (pt_kernels_radiance_nee.hip) and only for WHERE that table travels — a radiance-query
+// build's staged rays lie behind uuid, so its table comes behind slot_uuid (pt_scene.hpp nee_light_table); the shade is NEE's
+template <typename S, bool RR, bool COUNT, bool DBG = false, bool FEAT = false, bool QRY = false, bool NEE = false, bool RAD = false>
 __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, const Hit& h, const Carry& cw, Tally<COUNT>& tally, typename NeeArgOf<NEE>::type ne) {
   static_assert(!NEE || (!RR && !DBG && !FEAT && !COUNT), "next-event estimation excludes roulette, the overlay, the doors and the twins");
   tally.flag(PT_REG_SHADE_ANY);
@@ -50,7 +52,7 @@ __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, co
         if (hit >= 0 && hit_pos != 0xffffffffu) index = (int)A.bvh_slot_index[hit_pos];
       }
       karg_t* K = kargs();
-      const float4 l1 = reinterpret_cast<const float4*>(K->uuid)[2 * ne.light() + 1];  // albedo.xyz, list index
+      const float4 l1 = nee_light_table<RAD>(K)[2 * ne.light() + 1];  // albedo.xyz, list index
       if (hit >= 0 && index == __float_as_int(l1.w)) {
         float s3[3] = {sum.x, sum.y, sum.z};
         const float t3[3] = {col.x, col.y, col.z}, a3[3] = {l1.x, l1.y, l1.z};
@@ -285,14 +287,14 @@ __device__ __forceinline__ void shade_segment(const PtKernelArgs& A, Path& p, co
         // path goes on, when there is a light: one hash3, a light, a direction inside the cone the light subtends (pt_nee.hpp).
         // With cos_s > 0 the lane's next segment is the shadow ray; the scattered direction waits in ne.nd.
         karg_t* K = kargs();
-        const int n_lights = K->dbg_selected;
+        const int n_lights = nee_light_count<RAD>(K);
         const bool smp = !finished && mtype == 0 && n_lights > 0;
         ne.set_sampled(smp);
         if (smp) {
           float u0, u1, u2;
           hash3(seed, u0, u1, u2);
           const int k = ptnee::choose(u0, n_lights);
-          const float4 l0 = reinterpret_cast<const float4*>(K->uuid)[2 * k];  // centre, r * r
+          const float4 l0 = nee_light_table<RAD>(K)[2 * k];  // centre, r * r
           const float x3[3] = {o.x, o.y, o.z}, c3[3] = {l0.x, l0.y, l0.z};
           float w3[3], d2;
           if (ptnee::reach(x3, c3, l0.w, w3, d2)) {

@@ -1,10 +1,10 @@
-// pt_trace_body.hpp — the path-tracing kernel body shared by the eight device translation units that trace (each a gfx950
+// pt_trace_body.hpp — the path-tracing kernel body shared by the nine device translation units that trace (each a gfx950
 // code object of its own, loaded when one of its kernels is first asked for): pt_kernels.hip (list and walk
 // kernels), pt_kernels_small.hip (the small-list kernels, one per list length modulo four),
 // pt_kernels_extra.hip (the opt-in builds: the Russian-roulette kernels and the measuring twins),
 // pt_kernels_debug.hip (the opt-in debug-overlay builds), pt_kernels_features.hip (the opt-in first-hit feature builds),
-// pt_kernels_query.hip (the opt-in ray-query builds), pt_kernels_radiance.hip (the radiance-query builds) and pt_kernels_nee.hip
-// (the opt-in next-event builds).
+// pt_kernels_query.hip (the opt-in ray-query builds), pt_kernels_radiance.hip (the radiance-query builds), pt_kernels_nee.hip
+// (the opt-in next-event builds) and pt_kernels_radiance_nee.hip (the radiance-query builds of the next-event estimator).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +39,9 @@ using namespace ptd;
 //            and the shade, the sample loop and the slab store are the plain build's (pt_refill.hpp start_sample, radiance_admit)
 //   NEE      the opt-in next-event build (PT_OPT_NEXT_EVENT): the plain build with one light sample at every DIFFUSE hit whose path
 //            goes on, its shadow ray walked as the lane's next segment (pt_shade.hpp, pt_nee.hpp, pt_scene.hpp NeeState)
+//   RAD and NEE together (adaptor RadNee; pt_query_radiance_nee): RAD acts in the refill and the sample's start, NEE in the shade
+//            and the parking, and neither reads what the other writes — but both borrow the overlay's kernel arguments, so the
+//            light table moves (pt_scene.hpp nee_light_table)
 // Which kernel is which row under which adaptor is stated once, in the lists of pt_extra.h.
 // --------------------------------------------------------------------------------------------
 namespace ptb {
@@ -64,6 +67,7 @@ template <class Row> struct Feat : Row { static constexpr bool FEAT = true; };
 template <class Row> struct Qry : Row { static constexpr bool FEAT = true, QRY = true; };
 template <class Row> struct Rad : Row { static constexpr bool RAD = true; };
 template <class Row> struct Nee : Row { static constexpr bool NEE = true; };
+template <class Row> using RadNee = Nee<Rad<Row>>;  // both: the next-event estimator along the caller's rays (pt_kernels_radiance_nee.hip)
 }  // namespace ptb
 
 // One entry of a kernel list (pt_extra.h) as the kernel's definition and as the `case` of its object's accessor; a row of
@@ -175,7 +179,7 @@ __device__ __forceinline__ void pt_trace_body(const PtKernelArgs& A) {
     const bool shade = p.alive && !cw.carried;
     seg_count += (uint32_t)__popcll(pt_ballot(shade));
     tally.timebin(A, shade);
-    if (shade) shade_segment<S, RR, COUNT, DBG, FEAT, QRY, NEE>(A, p, h, cw, tally, ne);
+    if (shade) shade_segment<S, RR, COUNT, DBG, FEAT, QRY, NEE, RAD>(A, p, h, cw, tally, ne);
     tally.collect();
     tally.phase(7);
   }

@@ -480,13 +480,16 @@ class PathTracer:
             out[name] = col if b - a > 1 else col[:, 0]
         return out
 
-    def query_radiance(self, origins, directions, passes=1):
+    def query_radiance(self, origins, directions, passes=1, next_event=False):
         """The path-traced radiance along each of the caller's rays (pt_query_radiance; needs ray_queries(True)): `passes`
-        passes (at most those reserved) of the uniforms' samples_per_pixel samples per ray by the plain estimator.  Two (n, 3)
+        passes (at most those reserved) of the uniforms' samples_per_pixel samples per ray by the plain estimator — or, with
+        next_event=True (pt_query_radiance_nee; needs next_event(True) as well), by the next-event estimator: the caller's ray
+        is a path's first segment, the lamps are sampled from its first DIFFUSE hit on; the same expectation.  Two (n, 3)
         float32 arrays in (directions are not normalised), a dict out — "sum": (n, 3) float32, "samples": (n,) float32, "mean":
         (n, 3) float32 = sum / samples, 0 where samples is 0 (an invalid ray).  numpy arrays give numpy arrays; under
         use_torch, torch device tensors give torch device tensors.  Synchronous; nothing else of the context moves, first_pass
         included."""
+        fn = self.lib.pt_query_radiance_nee if next_event else self.lib.pt_query_radiance
         on_device = self.use_torch and self._torch.is_tensor(origins) and origins.is_cuda
         if on_device:
             torch = self._torch
@@ -500,7 +503,7 @@ class PathTracer:
             rays[:, 4:7] = d
             rec = torch.zeros((n, 4), dtype=torch.float32, device=o.device)
             if n:
-                self._check(self.lib.pt_query_radiance(self._ctx, C.c_void_p(rays.data_ptr()), n, int(passes), C.c_void_p(rec.data_ptr())))
+                self._check(fn(self._ctx, C.c_void_p(rays.data_ptr()), n, int(passes), C.c_void_p(rec.data_ptr())))
             samples = rec[:, 3]
             mean = torch.where(samples[:, None] > 0, rec[:, 0:3] / torch.clamp(samples, min=1.0)[:, None], torch.zeros_like(rec[:, 0:3]))
         else:
@@ -514,7 +517,7 @@ class PathTracer:
             rays[:, 4:7] = d
             rec = np.zeros((n, 4), np.float32)
             if n:
-                self._check(self.lib.pt_query_radiance(self._ctx, rays.ctypes.data_as(C.c_void_p), n, int(passes), rec.ctypes.data_as(C.c_void_p)))
+                self._check(fn(self._ctx, rays.ctypes.data_as(C.c_void_p), n, int(passes), rec.ctypes.data_as(C.c_void_p)))
             samples = rec[:, 3]
             mean = np.where(samples[:, None] > 0, rec[:, 0:3] / np.maximum(samples, np.float32(1.0))[:, None], np.float32(0.0)).astype(np.float32)
         return {"sum": rec[:, 0:3], "samples": samples, "mean": mean}
@@ -548,22 +551,23 @@ class PathTracer:
             self._check(fn(self._ctx, ptr(items), n, int(directions), int(passes), ptr(rec)))
         return rec
 
-    def gather_irradiance(self, points, normals, directions=256, passes=1):
+    def gather_irradiance(self, points, normals, directions=256, passes=1, next_event=False):
         """The irradiance at each point of a surface with that normal (pt_gather_irradiance; needs ray_queries(True)):
         `directions` cosine-weighted rays per point (a multiple of 64 in [64, 4096]), made, walked by query_radiance's plain
         estimator and reduced on the device.  Two (n, 3) float32 arrays in (normals of any length), a dict out — "e": (n, 3)
         float32, "samples": (n,) float32, 0 for an invalid item (a non-finite component, a normal of three zeros).  numpy
         arrays give numpy arrays; under use_torch, torch device tensors give torch device tensors.  Synchronous; nothing else
-        of the context moves."""
-        rec = self._gather(self.lib.pt_gather_irradiance, "gather_irradiance", points, normals, directions, passes, 4)
+        of the context moves.  next_event=True (pt_gather_irradiance_nee; needs next_event(True) as well): the rays are walked
+        by query_radiance's next-event estimator; no light sample is drawn at the point itself."""
+        rec = self._gather(self.lib.pt_gather_irradiance_nee if next_event else self.lib.pt_gather_irradiance, "gather_irradiance", points, normals, directions, passes, 4)
         return {"e": rec[:, 0:3], "samples": rec[:, 3]}
 
-    def bake_probes(self, positions, directions=256, passes=1):
+    def bake_probes(self, positions, directions=256, passes=1, next_event=False):
         """An SH probe of bands 0 to 2 at each position (pt_bake_probes; needs ray_queries(True)): `directions` rays over the
         sphere per probe.  An (n, 3) float32 array in, a dict out — "sh": (n, 9, 3) float32 in abi.PtProbeSH's order,
         "samples": (n,) float32, 0 for an invalid item.  abi.sh_irradiance(sh, normals) gives the irradiance the record holds
-        for a normal.  Arrays and tensors as gather_irradiance takes them."""
-        rec = self._gather(self.lib.pt_bake_probes, "bake_probes", positions, None, directions, passes, 28)
+        for a normal.  Arrays and tensors as gather_irradiance takes them; next_event=True (pt_bake_probes_nee) likewise."""
+        rec = self._gather(self.lib.pt_bake_probes_nee if next_event else self.lib.pt_bake_probes, "bake_probes", positions, None, directions, passes, 28)
         return {"sh": rec[:, 0:27].reshape(-1, 9, 3), "samples": rec[:, 27]}
 
     # -- exposure metering and the toned read-outs (include/ptrace.h PT_OPT_TONEMAP) -----------------

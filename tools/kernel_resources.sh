@@ -1,9 +1,9 @@
 #!/bin/bash
 # Compact per-kernel resource table (VGPRs, SGPRs, spills, scratch, waves/SIMD) + static instruction
-# counts of the kernels, from a cross-compile of the eight device translation units that trace (pt_kernels.hip: what every
+# counts of the kernels, from a cross-compile of the nine device translation units that trace (pt_kernels.hip: what every
 # context uses; pt_kernels_small.hip: the small-list kernels; pt_kernels_extra.hip: Russian-roulette builds, measuring
 # twins; pt_kernels_debug.hip: debug-overlay builds; pt_kernels_features.hip: first-hit feature builds; pt_kernels_query.hip:
-# ray-query builds with their pack and unpack kernels; pt_kernels_radiance.hip: radiance-query builds with their fold kernel; pt_kernels_nee.hip: next-event builds) and of the error
+# ray-query builds with their pack and unpack kernels; pt_kernels_radiance.hip: radiance-query builds with their fold kernel; pt_kernels_nee.hip: next-event builds; pt_kernels_radiance_nee.hip: the radiance-query builds of the next-event estimator) and of the error
 # estimate's (pt_kernels_error.hip: fold, read-out, tile and the two filter kernels) and the display kernels (pt_kernels_display.hip: metering,
 # exposure solve and the toned read-out) and the glare pyramid's (pt_kernels_glare.hip: down, gather, composite; its rows come last) for gfx950 (no GPU needed).
 # Usage: tools/kernel_resources.sh [outdir]   (default /tmp/ptres)
@@ -12,7 +12,7 @@ OUT=${1:-/tmp/ptres}
 mkdir -p "$OUT"
 cd "$(dirname "$(readlink -f "$0")")/../ray_tracer_webgl_amd/csrc"
 : > "$OUT/remarks.txt"
-for TU in pt_kernels pt_kernels_small pt_kernels_extra pt_kernels_debug pt_kernels_features pt_kernels_query pt_kernels_radiance pt_kernels_nee pt_kernels_error pt_kernels_display pt_kernels_glare; do
+for TU in pt_kernels pt_kernels_small pt_kernels_extra pt_kernels_debug pt_kernels_features pt_kernels_query pt_kernels_radiance pt_kernels_nee pt_kernels_radiance_nee pt_kernels_error pt_kernels_display pt_kernels_glare; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize \
     -fvisibility=hidden -Wall -Wno-unused-function $PT_EXTRA_FLAGS -Rpass-analysis=kernel-resource-usage \
     -save-temps=obj -c $TU.hip -o "$OUT/$TU.o" 2>> "$OUT/remarks.txt" || { cat "$OUT/remarks.txt"; exit 1; }
