@@ -83,6 +83,16 @@ pub struct PtProbeSH {           // the record of one probe of pt_bake_probes, 1
     pub sh: [[f32; 3]; 9], pub samples: f32,
 }
 
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtProbeLattice {      // a regular lattice of probes, 48 bytes: node (iz * ny + iy) * nx + ix at fma(i_c, step.c, origin.c)
+    pub origin: [f32; 3], pub nx: u32, pub step: [f32; 3], pub ny: u32, pub nz: u32, pub flags: u32, pub _pad: [u32; 2],
+}
+
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct PtProbeShadeOptions { // the rule of one pt_shade_probes, 16 bytes; NULL stands for {PT_PROBE_HALFSPACE, 0.0}
+    pub flags: u32, pub normal_bias: f32, pub _pad: [u32; 2],
+}
+
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct PtMeterOptions {      // the rule of one pt_meter, 48 bytes; the window is in image coordinates, w == 0 or h == 0: the whole frame
     pub key: f32, pub key_permille: u32, pub high_permille: u32, pub e_min: f32, pub e_max: f32, pub white_min: f32, pub rate: f32,
@@ -190,6 +200,11 @@ extern "C" {
     pub fn pt_query_radiance_nee(ctx: *mut PtCtx, rays: *const PtRay, n: u32, n_passes: u32, out: *mut PtRayRadiance) -> c_int;
     pub fn pt_gather_irradiance_nee(ctx: *mut PtCtx, points: *const PtGatherPoint, n: u32, directions: u32, n_passes: u32, out: *mut PtIrradiance) -> c_int;
     pub fn pt_bake_probes_nee(ctx: *mut PtCtx, probes: *const PtGatherPoint, n: u32, directions: u32, n_passes: u32, out: *mut PtProbeSH) -> c_int;
+    // probe lattices: bake the nodes first .. first + count - 1 of a lattice as pt_bake_probes (estimator 0) or pt_bake_probes_nee
+    // (estimator 1) bakes the same points, made on the device; shade the feature planes in place from a lattice's records into
+    // linear RGBA f32 texels (host or device pointers; alpha 0 marks a pixel without a usable probe)
+    pub fn pt_bake_lattice(ctx: *mut PtCtx, lattice: *const PtProbeLattice, first: u32, count: u32, directions: u32, n_passes: u32, estimator: c_int, out: *mut PtProbeSH) -> c_int;
+    pub fn pt_shade_probes(ctx: *mut PtCtx, lattice: *const PtProbeLattice, probes: *const PtProbeSH, options: *const PtProbeShadeOptions, rgba_out: *mut f32) -> c_int;
     // exposure metering and the toned read-outs (pt_set_option PT_OPT_TONEMAP 1): meter the frame on the device (src NULL: the
     // accumulation; else host or device linear RGBA f32 texels), keep the exposure record there, read the frame out through a tone
     // curve; pt_exposure_solve is the metering's second kernel on the host (ranks add their histograms, solve, pt_meter_set)
@@ -232,6 +247,8 @@ pub const PT_OPT_GLARE: c_int = 12;             // opt-in, 0 = off; scratch only
 pub const PT_TONE_CLAMP: i32 = 0;
 pub const PT_TONE_REINHARD: i32 = 1;
 pub const PT_TONE_FILMIC: i32 = 2;
+pub const PT_LATTICE_SKIP_BURIED: u32 = 1;       // PtProbeLattice.flags: a node inside a sphere that is not GLASS is an invalid item
+pub const PT_PROBE_HALFSPACE: u32 = 1;           // PtProbeShadeOptions.flags: drop the probes at or behind the pixel's tangent plane
 pub const PT_RAY_INVALID: i32 = -2;             // PtRayHit.index / uuid / type of an invalid ray
 pub const PT_REPROJECT_TOLERANCE_DEFAULT: f32 = 2.0;
 pub const PT_REPROJECT_CAP_DIFFUSE_DEFAULT: f32 = 32.0;

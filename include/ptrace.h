@@ -952,6 +952,87 @@ int pt_query_radiance_nee(pt_ctx* ctx, const PtRay* rays, uint32_t n, uint32_t n
 int pt_gather_irradiance_nee(pt_ctx* ctx, const PtGatherPoint* points, uint32_t n, uint32_t directions, uint32_t n_passes, PtIrradiance* out);
 int pt_bake_probes_nee(pt_ctx* ctx, const PtGatherPoint* probes, uint32_t n, uint32_t directions, uint32_t n_passes, PtProbeSH* out);
 
+/* ---- probe lattices: bake a regular lattice of SH probes, shade the feature planes from it (no option of their own) ----
+ * pt_bake_probes ends at the host; these two keep the chain on the device.  pt_bake_lattice makes the points of a regular
+ * lattice on the device and bakes them (needs PT_OPT_RAY_QUERIES, and PT_OPT_NEXT_EVENT for estimator 1); pt_shade_probes
+ * blends the eight records around every first hit of the feature planes into a linear RGBA frame (needs PT_OPT_FEATURES and
+ * a pt_render_features of the view): one feature launch plus one streaming kernel give a noise-free picture of the diffuse
+ * light transport at any camera.  The kernels are a code object of their own (csrc/pt_kernels_probe.hip, loaded at the first
+ * of these calls); the arithmetic is csrc/pt_probe.hpp, shared with the host.
+ * THE LATTICE: nx, ny, nz lie in [2, 256] and nx * ny * nz is at most 2^20; every step is finite and > 0; every origin
+ * component is finite; flags holds PT_LATTICE_SKIP_BURIED or nothing.  Anything else is PT_ERR_INVALID.
+ *   node i = (iz * ny + iy) * nx + ix
+ *   position.c = fma(float(i_c), step.c, origin.c)
+ * PT_LATTICE_SKIP_BURIED (off by default: a scene inside a dome sphere is legitimately inside a sphere): a node is BURIED if
+ * for some sphere of the installed list with type != PT_GLASS
+ *   w = position - centre;  d2 = fma(w.z, w.z, fma(w.y, w.y, w.x * w.x));  d2 < r * r
+ * with r * r the bits the kernels intersect.  The comparison is strict (a node on the surface is not buried), and
+ * a NaN centre never buries.  A buried node's position is written as NaN: by pt_bake_probes' own rule it is an invalid item,
+ * nothing is traced for it and its record is all +0 with samples == 0.
+ * pt_bake_lattice, THE DEFINING SENTENCE: out[k] is, bit for bit, item k of pt_bake_probes (estimator == 0) or
+ * pt_bake_probes_nee (estimator == 1) called ONCE on the `count` points made above for nodes first .. first + count - 1.
+ * AN ITEM'S INDEX, AND WITH IT ITS SEEDS, IS ITS INDEX IN THE CALL, NOT IN THE LATTICE:
+ * a sliced bake draws other samples than a whole one.  Errors (after the lattice's own), batches, PtStats and everything left alone are that call's.  first + count
+ * beyond nx * ny * nz, or an estimator other than 0 and 1: PT_ERR_INVALID; count == 0: PT_OK with nothing done.  `out` is a
+ * host or device pointer, as pt_bake_probes takes it.  The points are made by a generator kernel into a buffer of the
+ * context's (32 bytes per node of the slice, kept until PT_OPT_RAY_QUERIES is turned off; a refused allocation is
+ * PT_ERR_CAPACITY and nothing is launched).
+ * pt_shade_probes: `probes` are the records of all nx * ny * nz nodes in node order, on the host or the device; `rgba_out`
+ * holds local_rows * width linear RGBA fp32 texels on the host or the device, row 0 the lowest owned row — the layout
+ * pt_read_features uses and pt_meter, pt_glare and pt_resolve_toned accept as `src`.  options NULL: flags =
+ * PT_PROBE_HALFSPACE, normal_bias 0.  It needs valid feature planes, by pt_read_features' rule and errors (PT_ERR_NOT_READY
+ * while PT_OPT_FEATURES is off or the planes are stale; PT_ERR_INVALID under PT_OPT_COUNT_WORK or inside a capture), and it
+ * moves nothing of the context: not the accumulation, PtStats, first_pass, pt_last_trace_build or the planes.  A band that
+ * owns no rows: PT_OK.  Host records are staged in a buffer of the context's (112 bytes per node, kept until PT_OPT_FEATURES
+ * is turned off; a refused allocation is PT_ERR_CAPACITY and nothing is launched).  Synchronous where `probes` or `rgba_out`
+ * is a host pointer, asynchronous on the context's stream otherwise.
+ * PER PIXEL, fp32, one IEEE operation per statement; dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)), unit() is the
+ * gather section's unit normal (g, p, d2, i, z) and Y_j its basis; albedo, n, hp and ids are the feature planes' texels:
+ *   miss (ids.x < 0): {albedo-plane rgb, 1} — the background the path tracer returns
+ *   PT_EMISSIVE: {albedo, 1}
+ *   a type outside the four: {0, 0, 0, 1} — it absorbs
+ *   otherwise the look-up point and direction:
+ *   q.c = fma(normal_bias, n.c, hp.c)
+ *   g.c = (q.c - origin.c) / step.c
+ *   i.c = clamp(int(floor(g.c)), 0, n_c - 2)                 (outside the lattice the border cell answers; a NaN takes cell 0)
+ *   f.c = min(max(g.c - float(i.c), 0), 1)
+ *   DIFFUSE: omega = n; b = (3.14159265f, 2.09439510f x3, 0.785398163f x5)              (pi, 2 pi / 3, pi / 4)
+ *   METAL: v.c = hp.c - camera_origin.c; d = dot(v, n); k = 2 * d; m.c = k * n.c; r.c = v.c - m.c; omega = unit(r); b = 1
+ *   GLASS: omega = unit(v); b = 1                            (fuzz and refraction do not enter)
+ *   B_j = b_j * Y_j(omega)
+ *   corners k = 0 .. 7 in ascending order (bit 0 = x, bit 1 = y, bit 2 = z): wx = bit ? f.x : 1 - f.x, likewise wy, wz;
+ *   w_k = (wx * wy) * wz
+ *   a corner is KEPT iff w_k > 0, its record has samples > 0 and, under PT_PROBE_HALFSPACE, dot(pos_k - hp, n) > 0 (this
+ *   drops probes at or behind the tangent plane, every probe inside the convex ball the pixel lies on among them); then
+ *   E_k.c = fma(B_8, sh[8].c, ... fma(B_0, sh[0].c, +0))     (j ascending)
+ *   W = W + w_k
+ *   S.c = fma(w_k, E_k.c, S.c)
+ *   W > 0: v.c = max(S.c / W, 0); DIFFUSE: out.c = albedo.c * (v.c * 0.318309886f); METAL: out.c = albedo.c * v.c;
+ *          GLASS: out.c = v.c; alpha 1
+ *   W == 0: {0, 0, 0, 0} — alpha 0 is the mark of "no usable probe"
+ * OUT OF SCOPE: visibility-weighted or octahedral-depth probes (light leaks through thin walls); specular chains behind METAL
+ * and GLASS (one look-up along the mirror or the view direction stands for them); probes that follow a moving scene (bake
+ * again); a FrameLoop mode (the calls compose with it from outside); multi-rank baking beyond the first / count slice. */
+#define PT_LATTICE_SKIP_BURIED 1u
+#define PT_PROBE_HALFSPACE 1u
+typedef struct PtProbeLattice {
+  float origin[3];
+  uint32_t nx;
+  float step[3];
+  uint32_t ny;
+  uint32_t nz;
+  uint32_t flags; /* PT_LATTICE_SKIP_BURIED */
+  uint32_t _pad[2];
+} PtProbeLattice; /* 48 bytes */
+typedef struct PtProbeShadeOptions {
+  uint32_t flags; /* PT_PROBE_HALFSPACE */
+  float normal_bias;
+  uint32_t _pad[2];
+} PtProbeShadeOptions; /* 16 bytes */
+int pt_bake_lattice(pt_ctx* ctx, const PtProbeLattice* lattice, uint32_t first, uint32_t count, uint32_t directions, uint32_t n_passes,
+                    int estimator, PtProbeSH* out);
+int pt_shade_probes(pt_ctx* ctx, const PtProbeLattice* lattice, const PtProbeSH* probes, const PtProbeShadeOptions* options, float* rgba_out);
+
 /* ---- exposure metering and tone-mapped read-out (build extension, opt-in: PT_OPT_TONEMAP) --------------------------------------
  * Every other read-out ends in sqrt and a clamp at 1: the reference's framebuffer.  A frame lit by PT_EMISSIVE spheres holds far
  * more range than that; these calls meter the frame on the device, keep an EXPOSURE there and read the frame out through a tone

@@ -62,6 +62,16 @@ int pt_build_grid_runs(const PtSphere* spheres, uint32_t n, uint32_t* counts8, f
 int pt_debug_tile_order(pt_ctx* ctx, const uint32_t* cost, uint32_t n, uint32_t* order_out, uint32_t* cost_out);
 int pt_debug_partition_order(pt_ctx* ctx, const uint32_t* order, const uint32_t* flags, uint32_t n, uint32_t* part_out,
                              uint32_t* base_out);
+/* Which form of the shading kernel pt_shade_probes launches from now on (tools/probe_lit_compare.py, tests/test_gpu_probe_lit.py):
+ * form 0 — every lane loads its wanted corners' records itself; form 1 — a wave whose lit lanes share one cell stages the cell's
+ * eight records in LDS once and every other wave loads as form 0; form -1 — the library's default.  The texels are the same bits
+ * either way.  paths_dev: NULL, or a DEVICE pointer to one word per 8 x 8 tile of the local frame (tile ty * tiles_x + tx) that
+ * form 1 fills, for every wave with a lit lane, with 1 (it loaded as form 0) or 2 (it staged the cell); the caller keeps the
+ * memory alive while the form is in place and clears it.  THE POINTER IS KEPT AS GIVEN: every later pt_shade_probes of form 1 writes
+ * tiles_x * tiles_y words through it, nothing resets it — not pt_resize, not pt_set_params with another row partition, which change
+ * the tile count — so the caller takes it back (paths_dev NULL, or form -1) before the frame's size or partition changes.
+ * PT_ERR_INVALID for another form, or paths_dev with form 0. */
+int pt_debug_probe_form(pt_ctx* ctx, int form, uint32_t* paths_dev);
 
 #ifdef __cplusplus
 }

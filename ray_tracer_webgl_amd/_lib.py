@@ -76,6 +76,8 @@ SIGNATURES = {
     "pt_query_radiance_nee": (C.c_int, [_ctx, _vp, C.c_uint32, C.c_uint32, _vp]),
     "pt_gather_irradiance_nee": (C.c_int, [_ctx, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
     "pt_bake_probes_nee": (C.c_int, [_ctx, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    "pt_bake_lattice": (C.c_int, [_ctx, C.POINTER(abi.PtProbeLattice), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp]),
+    "pt_shade_probes": (C.c_int, [_ctx, C.POINTER(abi.PtProbeLattice), _vp, C.POINTER(abi.PtProbeShadeOptions), _vp]),
     "pt_meter": (C.c_int, [_ctx, _vp, C.POINTER(abi.PtMeterOptions)]),
     "pt_meter_read": (C.c_int, [_ctx, C.POINTER(abi.PtExposure), C.POINTER(C.c_uint32)]),
     "pt_meter_set": (C.c_int, [_ctx, C.POINTER(abi.PtExposure)]),
@@ -133,7 +135,7 @@ SIGNATURES = {
 # entry points added without a change of PT_ABI_VERSION (new functions only, no struct changed): the debug overlay, the error
 # estimate, adaptive sampling, the filtered read-out, the first-hit feature planes, the patch-wise filtered read-out, temporal
 # reprojection, temporal reprojection with the error estimate, ray queries, radiance queries, exposure metering and the toned
-# read-outs, the glare pyramid, gather queries, the radiance and gather queries of the next-event estimator
+# read-outs, the glare pyramid, gather queries, the radiance and gather queries of the next-event estimator, probe lattices
 ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_set_debugging", "pt_state_debug_overlay",
                       "pt_error_ptr", "pt_resolve_error", "pt_error_tiles", "pt_error_stats", "pt_render_until",
                       "pt_render_adaptive", "pt_adaptive_tiles", "pt_resolve_filtered", "pt_render_features", "pt_features_ptr",
@@ -141,7 +143,7 @@ ADDED_WITHIN_ABI_5 = ("pt_set_debug_overlay", "pt_last_trace_build", "pt_state_s
                       "pt_reproject_stats", "pt_reproject_constants", "pt_reproject_estimate", "pt_query_rays", "pt_query_batch",
                       "pt_query_radiance", "pt_meter", "pt_meter_read", "pt_meter_set", "pt_exposure_solve", "pt_resolve_toned",
                       "pt_resolve_toned_rgba8", "pt_glare", "pt_gather_irradiance", "pt_bake_probes", "pt_query_radiance_nee",
-                      "pt_gather_irradiance_nee", "pt_bake_probes_nee")
+                      "pt_gather_irradiance_nee", "pt_bake_probes_nee", "pt_bake_lattice", "pt_shade_probes")
 
 # include/ptrace_dev.h: developer diagnostics outside the versioned ABI, declared when the library in use has them (the other
 # pt_debug_* are declared where they are called, tracer.py and tools/)
@@ -149,6 +151,7 @@ _u32p = C.POINTER(C.c_uint32)
 DEV_SIGNATURES = {
     "pt_debug_tile_order": (C.c_int, [_ctx, _u32p, C.c_uint32, _u32p, _u32p]),
     "pt_debug_partition_order": (C.c_int, [_ctx, _u32p, _u32p, C.c_uint32, _u32p, _u32p]),
+    "pt_debug_probe_form": (C.c_int, [_ctx, C.c_int, _vp]),
 }
 
 

@@ -326,6 +326,72 @@ def sh_irradiance(sh, normals):
     return np.einsum("...k,...kc->...c", basis * band, sh)
 
 
+PT_LATTICE_SKIP_BURIED = 1  # PtProbeLattice.flags: a node inside a sphere that is not GLASS is an invalid item (NaN position)
+PT_PROBE_HALFSPACE = 1      # PtProbeShadeOptions.flags: drop the probes at or behind the pixel's tangent plane
+PT_LATTICE_MIN_NODES, PT_LATTICE_MAX_NODES, PT_LATTICE_MAX_TOTAL = 2, 256, 1 << 20  # per axis; nx * ny * nz
+
+
+class PtProbeLattice(C.Structure):
+    """include/ptrace.h PtProbeLattice: a regular lattice of probes, 48 bytes.  Node (iz * ny + iy) * nx + ix stands at
+    fma(float(i_c), step.c, origin.c); nx, ny, nz in [2, 256], their product at most 2^20, every step finite and > 0."""
+
+    _fields_ = [
+        ("origin", C.c_float * 3),
+        ("nx", C.c_uint32),
+        ("step", C.c_float * 3),
+        ("ny", C.c_uint32),
+        ("nz", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("_pad", C.c_uint32 * 2),
+    ]
+
+    def __init__(self, origin=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0), n=(2, 2, 2), flags=0):
+        super().__init__((C.c_float * 3)(*origin), n[0], (C.c_float * 3)(*step), n[1], n[2], flags, (C.c_uint32 * 2)(0, 0))
+
+    @property
+    def nodes(self):
+        return int(self.nx) * int(self.ny) * int(self.nz)
+
+    def copy(self):
+        out = PtProbeLattice()
+        C.memmove(C.byref(out), C.byref(self), C.sizeof(self))
+        return out
+
+
+class PtProbeShadeOptions(C.Structure):
+    """include/ptrace.h PtProbeShadeOptions: the rule of one pt_shade_probes, 16 bytes.  The default is the call's NULL."""
+
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("normal_bias", C.c_float),
+        ("_pad", C.c_uint32 * 2),
+    ]
+
+    def __init__(self, flags=PT_PROBE_HALFSPACE, normal_bias=0.0):
+        super().__init__(flags, normal_bias, (C.c_uint32 * 2)(0, 0))
+
+
+def probe_lattice_positions(lattice):
+    """(nx * ny * nz, 3) float32: the node positions of a lattice in node order, position.c = fma(float(i_c), step.c, origin.c)
+    with the device's bits.  The fp32 fma in numpy: the product of an index below 2^8 and a float32 is exact in float64; the sum
+    is rounded to odd there (two-sum finds the lost part, an inexact even result moves to its odd neighbour on that side), and a
+    53-bit round-to-odd value rounds to float32 as the exact sum does."""
+    import numpy as np
+
+    axes = []
+    for c, n in enumerate((lattice.nx, lattice.ny, lattice.nz)):
+        p = np.arange(int(n), dtype=np.float64) * np.float64(lattice.step[c])
+        o = np.full_like(p, np.float64(lattice.origin[c]))
+        s = p + o
+        t = s - p
+        lost = (p - (s - t)) + (o - t)
+        even = (s.view(np.int64) & 1) == 0
+        s = np.where((lost != 0) & even, np.nextafter(s, np.where(lost > 0, np.inf, -np.inf)), s)
+        axes.append(s.astype(np.float32))
+    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.ascontiguousarray(np.stack([x, y, z], axis=-1).reshape(-1, 3))
+
+
 class PtMeterOptions(C.Structure):
     """include/ptrace.h PtMeterOptions: the rule of one pt_meter (and of pt_exposure_solve, which does not read the window),
     48 bytes.  The window {x0, y0, w, h} is in image coordinates, row 0 at the bottom; w == 0 or h == 0 is the whole frame."""

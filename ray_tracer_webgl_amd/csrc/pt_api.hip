@@ -43,6 +43,7 @@
 #include "pt_tone.hpp"
 #include "pt_glare.hpp"
 #include "pt_gather.hpp"
+#include "pt_probe.hpp"
 #include "pt_buffers.hpp"
 #include "pt_ctx_state.hpp"
 
@@ -115,6 +116,10 @@ struct SceneBvh : SceneSlots { ptbvh::Bvh head; DevBuf<uint32_t> nodes; DevBuf<f
 // ring: a one-layer grid's records once more, in the ring layout the two-axis walk reads (pt_grid_records.hpp); entries: 16 B each
 struct SceneGrid : SceneSlots { ptgrid::Grid head; DevBuf<uint32_t> cells, ring; DevBuf<float> entries; };
 
+// pt_shade_probes' kernel form unless pt_debug_probe_form says otherwise: 0 straight loads, 1 the shared-cell way for coherent
+// waves (pt_kernels_probe.hip; profiles/r33_probe_lit.txt has the measurement that chose it)
+constexpr int kProbeFormDefault = 1;
+
 struct pt_ctx {
   int device = 0;
   uint32_t width = 0, height = 0;
@@ -150,6 +155,11 @@ struct pt_ctx {
   ptbuf::GlareSet<float4> glare;
   // the gather queries' workspace (pt_gather_irradiance, pt_bake_probes): fitted by the first call, released with the query planes
   ptbuf::GatherSet gather;
+  // the probe lattices' two buffers (pt_bake_lattice's points: released with the query planes; pt_shade_probes' staging of host
+  // records: released with the feature planes), each fitted by the first call that needs it; scratch
+  ptbuf::ProbeSet probe;
+  int probe_form = kProbeFormDefault;   // which shading kernel pt_shade_probes launches (include/ptrace_dev.h pt_debug_probe_form)
+  uint32_t* probe_paths = nullptr;      // ... and the caller's per-tile path words, form 1 only
   uint32_t reserved_passes = 1;
   // geometry path (include/ptrace.h PT_GEOM_*): policy, autotune state
   PathTuner geom;
@@ -2157,10 +2167,10 @@ PT_API int pt_set_option(pt_ctx* c, int key, int value) {
   if (key == PT_OPT_ERROR_ESTIMATE)
     return set_buffer_option(c, value, "error estimate", c->est, [c] { c->est.release(); }, pt_error_kernel(PT_E_FOLD), [c] { return clear_error(c); });
   if (key == PT_OPT_FEATURES)
-    return set_buffer_option(c, value, "feature planes", c->feat, [&] { c->feat.release(); reproject_off(); },
+    return set_buffer_option(c, value, "feature planes", c->feat, [&] { c->feat.release(); c->probe.release_stage(); reproject_off(); },
                              pt_feature_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar)), uuids);
   if (key == PT_OPT_RAY_QUERIES)
-    return set_buffer_option(c, value, "ray queries", c->query, [c] { c->query.release(); c->gather.release(); }, pt_query_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar)), uuids);
+    return set_buffer_option(c, value, "ray queries", c->query, [c] { c->query.release(); c->gather.release(); c->probe.release_points(); }, pt_query_kernel(PT_VARIANT_ID(pt_trace_kernel_scalar)), uuids);
   if (key == PT_OPT_REPROJECT) {
     if (value == 1 && !c->feat.on) return fail(c, PT_ERR_INVALID, "pt_set_option: PT_OPT_REPROJECT needs PT_OPT_FEATURES on (it reads the feature planes)");
     return set_buffer_option(c, value, "reprojection", c->hist, reproject_off, pt_reproject_kernel_handle(), [] { return PT_OK; });
@@ -2504,6 +2514,104 @@ PT_API int pt_gather_irradiance_nee(pt_ctx* c, const PtGatherPoint* points, uint
 }
 PT_API int pt_bake_probes_nee(pt_ctx* c, const PtGatherPoint* probes, uint32_t n, uint32_t directions, uint32_t n_passes, PtProbeSH* out) {
   return gather(c, "pt_bake_probes_nee", ptgather::PROBE, true, probes, n, directions, n_passes, out);
+}
+
+// ---- probe lattices (no option of their own; include/ptrace.h has the contract) ------------------------------
+// pt_bake_lattice: the lattice's own checks, what the gather call would refuse before anything is enqueued (so that no generator
+// runs for a call that is refused), the generator into the ProbeSet's point buffer, then the gather calls' one host body on that
+// DEVICE pointer: the defining sentence by construction, and no second copy of the bake loop.
+PT_API int pt_bake_lattice(pt_ctx* c, const PtProbeLattice* lattice, uint32_t first, uint32_t count, uint32_t directions, uint32_t n_passes, int estimator,
+                           PtProbeSH* out) {
+  if (!c) return PT_ERR_INVALID;
+  const char* who = "pt_bake_lattice";
+  if (!lattice) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
+  if (const char* why = ptprobe::lattice_error(*lattice)) return fail(c, PT_ERR_INVALID, "%s: %s", who, why);
+  if (estimator != 0 && estimator != 1) return fail(c, PT_ERR_INVALID, "%s: estimator %d (0: pt_bake_probes, 1: pt_bake_probes_nee)", who, estimator);
+  if (!ptprobe::slice_valid(*lattice, first, count))
+    return fail(c, PT_ERR_INVALID, "%s: nodes %u .. %u + %u of a lattice of %u", who, first, first, count, ptprobe::node_count(*lattice));
+  if (count == 0) return PT_OK;
+  const bool next_event = estimator == 1;
+  if (int rc = query_ready(c, who, "radiance", lattice, out); rc != PT_OK) return rc;
+  if (n_passes == 0) return fail(c, PT_ERR_INVALID, "%s: n_passes == 0", who);
+  if (n_passes > c->reserved_passes)
+    return fail(c, PT_ERR_CAPACITY, "%s: %u passes > %u reserved (pt_reserve_passes)", who, n_passes, c->reserved_passes);
+  if (!ptgather::directions_valid(directions))
+    return fail(c, PT_ERR_INVALID, "%s: %u directions (a multiple of 64 in [%d, %d])", who, directions, (int)ptgather::kMinDirections, (int)ptgather::kMaxDirections);
+  if (ptgather::total_rays(count, directions) == 0)
+    return fail(c, PT_ERR_INVALID, "%s: %u items of %u directions are more than 2^32 - 1 rays", who, count, directions);
+  if (int rc = estimator_ready(c, who, next_event); rc != PT_OK) return rc;
+  if (!c->probe.points_in_place(count)) {
+    PT_HIP(c, hipStreamSynchronize(c->stream));  // (nothing in flight reads what the fit frees)
+    if (const ptbuf::Fit f = c->probe.fit_points(count); !f.ok())
+      return fail(c, PT_ERR_CAPACITY, "%s: the point buffer's allocation for %u nodes failed: %s", who, count, hipGetErrorString((hipError_t)f.err));
+  }
+  PtGatherPoint* points = reinterpret_cast<PtGatherPoint*>(c->probe.points.get());
+  {
+    PtProbeLattice L = *lattice;
+    const float* geom = c->list.geom.get();
+    const PtMatRec* mat = c->list.mat.get();
+    uint32_t n_spheres = c->list.n;
+    void* kargs[] = {&L, &first, &count, &geom, &mat, &n_spheres, &points};
+    PT_HIP(c, hipLaunchKernel(pt_lattice_kernel(PT_PROBE_POINTS), dim3((count + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+  }
+  return gather(c, who, ptgather::PROBE, next_event, points, count, directions, n_passes, out);
+}
+
+PT_API int pt_debug_probe_form(pt_ctx* c, int form, uint32_t* paths_dev) {
+  if (!c) return PT_ERR_INVALID;
+  if (form == -1) form = kProbeFormDefault;
+  if (form != 0 && form != 1) return fail(c, PT_ERR_INVALID, "pt_debug_probe_form: form %d", form);
+  if (form == 0 && paths_dev) return fail(c, PT_ERR_INVALID, "pt_debug_probe_form: only form 1 reports its paths");
+  c->probe_form = form;
+  c->probe_paths = paths_dev;
+  return PT_OK;
+}
+
+// pt_shade_probes: one launch of the shading kernel over the feature planes in place.  Host records go through the ProbeSet's
+// staging, a host frame comes back through the read-outs' staging (scratch between calls, as pt_glare uses it); device pointers
+// are used in place and the call is then asynchronous.  No event pair, no counter, no flag of the context moves.
+PT_API int pt_shade_probes(pt_ctx* c, const PtProbeLattice* lattice, const PtProbeSH* probes, const PtProbeShadeOptions* options, float* rgba_out) {
+  if (!c) return PT_ERR_INVALID;
+  const char* who = "pt_shade_probes";
+  if (!lattice || !probes || !rgba_out) return fail(c, PT_ERR_INVALID, "%s: NULL argument", who);
+  if (const char* why = ptprobe::lattice_error(*lattice)) return fail(c, PT_ERR_INVALID, "%s: %s", who, why);
+  uint32_t flags = options ? options->flags : (uint32_t)PT_PROBE_HALFSPACE;
+  float bias = options ? options->normal_bias : 0.0f;
+  if (const char* why = ptprobe::options_error(flags, bias)) return fail(c, PT_ERR_INVALID, "%s: %s", who, why);
+  if (c->count_work) return fail(c, PT_ERR_INVALID, "%s: not with PT_OPT_COUNT_WORK", who);
+  if (!c->feat.on) return option_off(c, who, SET_FEATURES);
+  if (!c->feat.valid)
+    return fail(c, PT_ERR_NOT_READY, "%s: no pt_render_features since the scene, the uniforms or the size last changed", who);
+  PT_HIP(c, hipSetDevice(c->device));
+  if (is_capturing(c)) return fail(c, PT_ERR_INVALID, "%s: not inside a stream capture", who);
+  if (c->local_rows == 0) return PT_OK;  // this band owns no rows
+  if (!c->feat.in_place(extent_of(c))) return fail(c, PT_ERR_CAPACITY, "%s: the planes are not allocated for the rows in place (an earlier allocation failed)", who);
+  const uint32_t nodes = ptprobe::node_count(*lattice);
+  const bool probes_on_device = device_pointer(probes), out_on_device = device_pointer(rgba_out);
+  if (!out_on_device) PT_TRY(frame_buffers_ready(c, who));  // (the read-outs' staging holds a host caller's frame)
+  const float* records = reinterpret_cast<const float*>(probes);
+  if (!probes_on_device) {
+    if (!c->probe.stage_in_place(nodes)) {
+      PT_HIP(c, hipStreamSynchronize(c->stream));  // (nothing in flight reads what the fit frees)
+      if (const ptbuf::Fit f = c->probe.fit_stage(nodes); !f.ok())
+        return fail(c, PT_ERR_CAPACITY, "%s: the staging's allocation for %u records failed: %s", who, nodes, hipGetErrorString((hipError_t)f.err));
+    }
+    PT_HIP(c, hipMemcpyAsync(c->probe.stage.get(), probes, (size_t)nodes * sizeof(PtProbeSH), hipMemcpyHostToDevice, c->stream));
+    records = c->probe.stage.get();
+  }
+  {
+    const float4* planes = c->feat.planes.get();
+    uint32_t plane = (uint32_t)n_pixels(c), width = c->width, rows = c->local_rows;
+    PtProbeLattice L = *lattice;
+    float cx = c->params.camera_origin[0], cy = c->params.camera_origin[1], cz = c->params.camera_origin[2];
+    float* dst = out_on_device ? rgba_out : reinterpret_cast<float*>(c->frame.resolve.get());
+    uint32_t* paths = c->probe_paths;
+    void* kargs[] = {&planes, &plane, &width, &rows, &L, &flags, &bias, &cx, &cy, &cz, &records, &dst, &paths};  // (form 0 reads the first twelve)
+    PT_HIP(c, hipLaunchKernel(pt_lattice_kernel(c->probe_form == 1 ? PT_PROBE_SHADE_SHARED : PT_PROBE_SHADE), dim3((n_tiles(c) + 3u) / 4u), dim3(256), kargs, 0, c->stream));
+    if (!out_on_device) PT_HIP(c, hipMemcpyAsync(rgba_out, dst, n_pixels(c) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (!probes_on_device || !out_on_device) PT_HIP(c, hipStreamSynchronize(c->stream));
+  return PT_OK;
 }
 
 // ---- exposure metering and the toned read-out (PT_OPT_TONEMAP; include/ptrace.h has the contract) -------------

@@ -319,6 +319,34 @@ struct GatherSet {
   void release() { work.release(); }
 };
 
+// The probe lattices' two buffers (pt_bake_lattice, pt_shade_probes; no option of their own).  `points`: the generator's
+// PtGatherPoint per node of a bake's slice (8 floats each) — it lives under PT_OPT_RAY_QUERIES and is released with the query
+// planes.  `stage`: the staging of a HOST `probes` array of pt_shade_probes (28 floats per node, a PtProbeSH's size) — it lives
+// under PT_OPT_FEATURES and is released with the feature planes.  Each is sized by the LATTICE of the call, not by the rows: fitted
+// by the first call that needs it and again where a call's nodes outgrew it, in place for those nodes or refused.  SCRATCH, like
+// the glare pyramid: every call writes all it reads, so neither carries validity, has a row in the change table of
+// pt_ctx_state.hpp or is zeroed.
+struct ProbeSet {
+  enum : uint32_t { POINTS = 1, STAGE = 2 };
+  static constexpr size_t kPoint = 8, kRecord = 28;
+  DevBuf<float> points, stage;
+
+  Fit fit_points(size_t nodes) {
+    Fit f;
+    if (!points.holds_at_least(kPoint * (nodes ? nodes : 1))) refit(f, points, kPoint * (nodes ? nodes : 1), POINTS);
+    return f;
+  }
+  Fit fit_stage(size_t nodes) {
+    Fit f;
+    if (!stage.holds_at_least(kRecord * (nodes ? nodes : 1))) refit(f, stage, kRecord * (nodes ? nodes : 1), STAGE);
+    return f;
+  }
+  bool points_in_place(size_t nodes) const { return points.holds_at_least(kPoint * (nodes ? nodes : 1)); }
+  bool stage_in_place(size_t nodes) const { return stage.holds_at_least(kRecord * (nodes ? nodes : 1)); }
+  void release_points() { points.release(); }
+  void release_stage() { stage.release(); }
+};
+
 // PT_OPT_NEXT_EVENT: the light table of the scene in place — n records (pt_nee.hpp Light), one allocation of at least max(n, 1).
 // It is sized by the SCENE, not by the rows: no resize and no repartition touches it; pt_set_spheres rebuilds it while the option
 // is on, and turning the option on over an installed scene builds it.  `n` speaks for the table only while it is in place: a

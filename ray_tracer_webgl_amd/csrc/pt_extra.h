@@ -106,6 +106,10 @@ extern "C" const void* pt_glare_kernel(int id);
 // pt_bake_probes)
 enum { PT_GATHER_RAYS = 0, PT_GATHER_REDUCE, PT_GATHER_COUNT };
 extern "C" const void* pt_gather_kernel(int id);
+// pt_kernels_probe.hip (a code object of its own): the probe lattices' point generator and shading kernel (pt_bake_lattice,
+// pt_shade_probes)
+enum { PT_PROBE_POINTS = 0, PT_PROBE_SHADE, PT_PROBE_SHADE_SHARED, PT_PROBE_COUNT };
+extern "C" const void* pt_lattice_kernel(int id);
 // pt_kernels_nee.hip (a code object of its own): the next-event builds (PT_OPT_NEXT_EVENT), the twelve variant rows under the
 // adaptor Nee with the suffix _nee, by variant id.  No column of the trace table: the host keeps them in the side table
 // kNeeKernels (pt_nee_table.hpp) and takes a cell of it where a render launch's column would have been the plain build.

@@ -7,6 +7,7 @@ src/dom.rs:126-143, without a browser).
     python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.02 --adaptive --samples-out cover_samples.png
     python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.05 --denoise --out cover_filtered.png
     python -m ray_tracer_webgl_amd.render --config config2 --noise-target 0.05 --denoise-patch --out cover_patch_filtered.png
+    python -m ray_tracer_webgl_amd.render --config config4 --probe-lit 8,8,10 --next-event --tone filmic --out room_probe_lit.png
 """
 import argparse
 import math
@@ -30,6 +31,64 @@ def glare_options(strength, levels, threshold):
     used = base[:levels]
     total = sum(used)
     return abi.PtGlareOptions(strength, threshold, levels, [w / total for w in used])
+
+
+def lattice_over(spheres, n, flags=0):
+    """abi.PtProbeLattice of n = (nx, ny, nz) nodes over the bounding box of the spheres whose radius is below 100 (the walls and
+    the ground of the BASELINE scenes are spheres of radius 100 and more: they are what the lattice stands IN, not what it spans)."""
+    small = [s for s in spheres if abs(float(s["radius"])) < 100.0]
+    if not small:
+        raise ValueError("no sphere of a radius below 100 to span a lattice over")
+    lo = np.min([np.asarray(s["center"], np.float64) - abs(float(s["radius"])) for s in small], axis=0)
+    hi = np.max([np.asarray(s["center"], np.float64) + abs(float(s["radius"])) for s in small], axis=0)
+    step = np.maximum((hi - lo) / (np.asarray(n, np.float64) - 1.0), 1e-6)
+    return abi.PtProbeLattice(origin=tuple(lo), step=tuple(step), n=tuple(int(v) for v in n), flags=flags)
+
+
+def probe_lit(sc, args, geom, lattice_n, curve, exposure, glare):
+    """--probe-lit: bake a lattice over the scene once, shade the camera's first hits from it (pt_bake_lattice, pt_shade_probes)
+    and take the linear frame through the read-outs --tone / --glare name (without --tone: the square root and the clamp)."""
+    p = sc.params.copy()
+    p.time_step = abi.PT_TIME_STEP_DECORRELATED
+    p.samples_per_pixel = 1
+    pt = PathTracer(p.width, p.height, device=args.device)
+    pt.set_geometry_path(geom)
+    pt.set_spheres(sc.spheres)
+    pt.feature_planes(True)
+    pt.ray_queries(True)
+    if args.next_event:
+        pt.next_event(True)
+    pt.set_params(p)
+    lat = lattice_over(sc.spheres, lattice_n, abi.PT_LATTICE_SKIP_BURIED)
+    t0 = time.perf_counter()
+    rec = pt.bake_lattice(lat, directions=args.probe_directions, passes=1, next_event=args.next_event)
+    t_bake = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    pt.render_features()
+    frame = pt.probe_lit_image(lat, rec)
+    t_frame = time.perf_counter() - t0
+    empty = int((frame[..., 3] == 0).sum())
+    frame[..., 3] = 1.0  # (alpha 0 marked the pixels without a usable probe: they stay black)
+    print("probe-lit: lattice %dx%dx%d from (%.3g, %.3g, %.3g) in steps of (%.3g, %.3g, %.3g), %d of %d nodes buried, %d directions, %s estimator: "
+          "bake %.1f ms, frame (features + shading) %.2f ms, %d pixels without a usable probe" % (
+              lat.nx, lat.ny, lat.nz, *lat.origin, *lat.step, int((rec["samples"] == 0).sum()), lat.nodes, args.probe_directions,
+              "next-event" if args.next_event else "plain", t_bake * 1e3, t_frame * 1e3, empty))
+    if curve is None:
+        frame[..., :3] = np.sqrt(np.clip(frame[..., :3], 0.0, 1.0))
+    else:
+        pt.tone_mapping(True)
+        if glare is not None:
+            pt.glare(True)
+            frame = pt.glared_image(src=frame, options=glare)
+        pt.meter(abi.PtMeterOptions(), src=frame)
+        rec_e, _ = pt.exposure()
+        opt = abi.PtToneOptions(curve, 1, 0.0, 1.0)
+        if exposure is not None:
+            opt = abi.PtToneOptions(curve, 1, exposure, max(rec_e.y_high * exposure, 1.0))
+        frame = pt.toned_image(opt, src=frame)
+    image_io.write_png(args.out, frame)
+    print("%s: %dx%d, %d spheres, probe-lit -> %s" % (sc.name, p.width, p.height, len(sc.spheres), args.out))
+    pt.close()
 
 
 def main(argv=None):
@@ -91,6 +150,14 @@ def main(argv=None):
     ap.add_argument("--next-event", action="store_true",
                     help="next-event estimation (PT_OPT_NEXT_EVENT): sample the scene's emissive spheres at every diffuse hit; the same "
                          "expectation as the plain estimator with far less noise where a lamp is small (config4); not with --debug-overlay")
+    ap.add_argument("--probe-lit", metavar="NX,NY,NZ",
+                    help="instead of path tracing the frame: bake an SH probe lattice of NX x NY x NZ nodes (each 2 .. 256) over the "
+                         "bounding box of the spheres whose radius is below 100 (pt_bake_lattice; nodes inside a sphere are skipped) and "
+                         "shade the camera's first hits from it (pt_render_features, pt_shade_probes): a noise-free picture of the "
+                         "diffuse light transport.  With --next-event the bake uses that estimator; --tone, --exposure and --glare "
+                         "read the linear frame out as they read a path-traced one")
+    ap.add_argument("--probe-directions", type=int, default=256, metavar="D",
+                    help="with --probe-lit: rays per probe, a multiple of 64 in 64 .. 4096 (default 256)")
     ap.add_argument("--out", default="render.png")
     ap.add_argument("--checkpoint", help="also save the fp32 accumulation buffer (.npz)")
     args = ap.parse_args(argv)
@@ -159,6 +226,20 @@ def main(argv=None):
         glare = glare_options(args.glare, args.glare_levels, args.glare_threshold)
         if glare is None:
             ap.error("--glare: a strength in 0 .. 1, --glare-levels 1 .. %d, --glare-threshold finite and >= 0" % abi.PT_GLARE_MAX_LEVELS)
+    if args.probe_lit is not None:
+        try:
+            lattice_n = tuple(int(v) for v in args.probe_lit.split(","))
+        except ValueError:
+            lattice_n = ()
+        if len(lattice_n) != 3 or not all(abi.PT_LATTICE_MIN_NODES <= v <= abi.PT_LATTICE_MAX_NODES for v in lattice_n) or \
+                lattice_n[0] * lattice_n[1] * lattice_n[2] > abi.PT_LATTICE_MAX_TOTAL:
+            ap.error("--probe-lit: NX,NY,NZ, each 2 .. 256, at most 2^20 nodes in all")
+        if not (abi.PT_GATHER_MIN_DIRECTIONS <= args.probe_directions <= abi.PT_GATHER_MAX_DIRECTIONS and args.probe_directions % 64 == 0):
+            ap.error("--probe-directions: a multiple of 64 in 64 .. 4096")
+        if overlay is not None or args.noise_target is not None or args.error_out or denoise is not None or denoise_patch is not None or args.checkpoint:
+            ap.error("--probe-lit shades from probes: it has no accumulation to measure, filter, overlay or checkpoint")
+        curve = None if args.tone is None else {"clamp": abi.PT_TONE_CLAMP, "reinhard": abi.PT_TONE_REINHARD, "filmic": abi.PT_TONE_FILMIC}[args.tone]
+        return probe_lit(sc, args, geom, lattice_n, curve, exposure, glare)
     if args.noise_target is not None or args.error_out:
         if overlay is not None:
             ap.error("--noise-target / --error-out measure the frame's noise: not with --debug-overlay")

@@ -570,6 +570,62 @@ class PathTracer:
         rec = self._gather(self.lib.pt_bake_probes_nee if next_event else self.lib.pt_bake_probes, "bake_probes", positions, None, directions, passes, 28)
         return {"sh": rec[:, 0:27].reshape(-1, 9, 3), "samples": rec[:, 27]}
 
+    # -- probe lattices: bake a lattice of SH probes, shade the feature planes from it (include/ptrace.h pt_bake_lattice) --
+    def bake_lattice(self, lattice, directions=256, passes=1, next_event=False, first=0, count=None):
+        """The SH probes of nodes first .. first + count - 1 of an abi.PtProbeLattice (pt_bake_lattice; needs ray_queries(True),
+        and next_event(True) for next_event=True): the points are made on the device and baked as bake_probes bakes them — the
+        records of item k are bake_probes' for the k-th point of the slice, bit for bit; an item's seeds follow its index in
+        the call, so a sliced bake draws other samples than a whole one.  count=None: every node from `first` on.  The
+        bake_probes dict out — "sh": (count, 9, 3) float32, "samples": (count,) float32 — as numpy arrays, or as torch device
+        tensors under use_torch (the records never leave the device: probe_lit_image takes them)."""
+        if not (abi.PT_GATHER_MIN_DIRECTIONS <= int(directions) <= abi.PT_GATHER_MAX_DIRECTIONS and int(directions) % 64 == 0):
+            raise ValueError("bake_lattice: %d directions (a multiple of 64 in [%d, %d])" % (directions, abi.PT_GATHER_MIN_DIRECTIONS, abi.PT_GATHER_MAX_DIRECTIONS))
+        lat = lattice.copy()
+        n = lat.nodes - int(first) if count is None else int(count)
+        if n < 0:
+            raise ValueError("bake_lattice: first %d beyond the lattice's %d nodes" % (first, lat.nodes))
+        if self.use_torch:
+            rec = self._torch.zeros((n, 28), dtype=self._torch.float32, device="cuda:%d" % self.device)
+            ptr = C.c_void_p(rec.data_ptr())
+        else:
+            rec = np.zeros((n, 28), np.float32)
+            ptr = rec.ctypes.data_as(C.c_void_p)
+        # (count == 0 too: the call says whether the lattice and the slice are valid)
+        self._check(self.lib.pt_bake_lattice(self._ctx, C.byref(lat), int(first), n, int(directions), int(passes), 1 if next_event else 0, ptr))
+        return {"sh": rec[:, 0:27].reshape(-1, 9, 3), "samples": rec[:, 27]}
+
+    def probe_lit_image(self, lattice, probes, options=None):
+        """(local_rows, width, 4) fp32: the feature planes in place shaded from a lattice's records (pt_shade_probes; needs
+        feature_planes(True) and a render_features() of the view) — linear RGBA, alpha 0 where no probe was usable; what
+        meter(src=...), glared_image(src=...) and toned_image(src=...) take next.  `probes`: the records of every node in node
+        order — a bake_lattice dict, or (nodes, 28) float32 — as numpy arrays (a numpy image out) or, under use_torch, torch
+        device tensors (a torch device tensor out, nothing crosses the bus).  `options`: abi.PtProbeShadeOptions (default:
+        the half-space test on, no bias)."""
+        lat = lattice.copy()
+        on_device = self.use_torch and self._torch.is_tensor(probes["sh"] if isinstance(probes, dict) else probes)
+        if on_device:
+            torch = self._torch
+            if isinstance(probes, dict):
+                rec = torch.cat([probes["sh"].reshape(-1, 27), probes["samples"].reshape(-1, 1)], dim=1)
+            else:
+                rec = probes
+            rec = rec.to(device="cuda:%d" % self.device, dtype=torch.float32).contiguous()
+            out = torch.empty((self.local_rows, self.width, 4), dtype=torch.float32, device=rec.device)
+            pr, po = C.c_void_p(rec.data_ptr()), C.c_void_p(out.data_ptr())
+        else:
+            if isinstance(probes, dict):
+                rec = np.concatenate([np.asarray(probes["sh"], np.float32).reshape(-1, 27), np.asarray(probes["samples"], np.float32).reshape(-1, 1)], axis=1)
+            else:
+                rec = probes
+            rec = np.ascontiguousarray(rec, dtype=np.float32)
+            out = np.empty((self.local_rows, self.width, 4), np.float32)
+            pr, po = rec.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+        if tuple(rec.shape) != (lat.nodes, 28):
+            raise ValueError("probe_lit_image: records of shape %s for a lattice of %d nodes" % (tuple(rec.shape), lat.nodes))
+        opt = C.byref(options) if options is not None else None
+        self._check(self.lib.pt_shade_probes(self._ctx, C.byref(lat), pr, opt, po))
+        return out
+
     # -- exposure metering and the toned read-outs (include/ptrace.h PT_OPT_TONEMAP) -----------------
     def tone_mapping(self, on=True):
         """Put the exposure state in place (or release it: the exposure is forgotten).  Off by default; the image bits are the
