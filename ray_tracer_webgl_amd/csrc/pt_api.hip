@@ -27,6 +27,7 @@
 #include "pt_grid_records.hpp"
 #include "pt_scene_image.hpp"
 #include "pt_extra.h"
+#include "pt_sigs.h"
 #include "pt_kernel_args.h"
 #include "pt_geom_plan.hpp"
 #include "pt_launch_plan.hpp"
@@ -1234,6 +1235,15 @@ static int prepare_launch(pt_ctx* c, uint32_t n_passes, const LaunchUse& use, La
   return PT_OK;
 }
 
+// THE launch of every kernel that lives in a unit of its own and is no trace kernel: `sig` is the kernel's parameter list
+// (pt_sigs.h), `kernel` its handle (pt_extra.h), the arguments go by value and are checked against the list at compile time
+// (pt_call.hpp has the rule) before they become the array of pointers.  Capture-safe: a launch only.
+template <class... P, class... A>
+static hipError_t call(ptcall::Sig<P...> sig, const void* kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, A... args) {
+  return ptcall::call([](const void* k, dim3 g, dim3 b, void** slots, size_t l, hipStream_t s) { return hipLaunchKernel(k, g, b, slots, l, s); },
+                      sig, kernel, grid, block, lds, stream, args...);
+}
+
 // the trace kernel of a prepared launch (capture-safe: a launch only)
 static int launch_trace(pt_ctx* c, const Launch& L) {
   void* kargs[] = {const_cast<PtKernelArgs*>(&L.A)};
@@ -1332,12 +1342,8 @@ PT_API int pt_render_passes(pt_ctx* c, uint32_t n_passes) {
 
   uint32_t n_pix = (uint32_t)n_pixels(c);
   if (estimate) {  // the same adds into accum, and the estimate's update beside them (pt_kernels_error.hip)
-    float4* accum = c->frame.accum;
-    float4* est = c->est.state.get();
-    const float4* slab = c->frame.slab.get();
-    uint32_t passes = n_passes;
-    void* kargs[] = {&accum, &est, &slab, &n_pix, &passes};
-    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
+    PT_HIP(c, call(ptsig::FoldError{}, pt_error_kernel(PT_E_FOLD), dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream,
+                   c->frame.accum, c->est.state.get(), c->frame.slab.get(), n_pix, n_passes));
     c->est.spp = p.samples_per_pixel;
   } else {
     hipLaunchKernelGGL(pt_accumulate_kernel, dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream,
@@ -1674,6 +1680,13 @@ PT_API int pt_debug_tile_order(pt_ctx* c, const uint32_t* cost, uint32_t n, uint
   return PT_OK;
 }
 
+// the partition kernel: `order` split by `flags` into part[0, n) — the flagged tiles first, both halves in order's order — and
+// base; one workgroup; enqueued, not awaited
+static int launch_partition(pt_ctx* c, const uint32_t* order, const uint32_t* flags, uint32_t* part, uint32_t* base, uint32_t n) {
+  PT_HIP(c, call(ptsig::PartitionOrder{}, pt_error_kernel(PT_E_PARTITION), dim3(1), dim3(1024), 0, c->stream, order, flags, part, base, n));
+  return PT_OK;
+}
+
 PT_API int pt_debug_partition_order(pt_ctx* c, const uint32_t* order, const uint32_t* flags, uint32_t n, uint32_t* part_out,
                                     uint32_t* base_out) {
   if (!c || !order || !flags || !part_out || !base_out || n == 0)
@@ -1687,15 +1700,7 @@ PT_API int pt_debug_partition_order(pt_ctx* c, const uint32_t* order, const uint
   PT_HIP(c, hipMemcpyAsync(d_in.get(), order, bytes, hipMemcpyHostToDevice, c->stream));
   PT_HIP(c, hipMemcpyAsync(d_in.get() + n, flags, bytes, hipMemcpyHostToDevice, c->stream));
   PT_HIP(c, hipMemsetAsync(d_out.get(), 0xFF, 2 * bytes, c->stream));
-  {
-    const uint32_t* od = d_in.get();
-    const uint32_t* fl = d_in.get() + n;
-    uint32_t* part = d_out.get();
-    uint32_t* base = d_out.get() + n;
-    uint32_t tiles = n;
-    void* kargs[] = {&od, &fl, &part, &base, &tiles};
-    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_PARTITION), dim3(1), dim3(1024), kargs, 0, c->stream));
-  }
+  PT_TRY(launch_partition(c, d_in.get(), d_in.get() + n, d_out.get(), d_out.get() + n, n));
   PT_HIP(c, hipMemcpyAsync(part_out, d_out.get(), bytes, hipMemcpyDeviceToHost, c->stream));
   PT_HIP(c, hipMemcpyAsync(base_out, d_out.get() + n, bytes, hipMemcpyDeviceToHost, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1766,10 +1771,8 @@ PT_API int pt_resolve_error(pt_ctx* c, float* rgba_out) {
   PT_HIP(c, hipSetDevice(c->device));
   uint32_t n_pix = (uint32_t)n_pixels(c);
   if (n_pix == 0) return PT_OK;
-  const float4* est = c->est.state.get();
-  float4* out = c->frame.resolve.get();
-  void* kargs[] = {&est, &out, &n_pix};
-  PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_RESOLVE), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, call(ptsig::ResolveError{}, pt_error_kernel(PT_E_RESOLVE), dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream,
+                 c->est.state.get(), c->frame.resolve.get(), n_pix));
   PT_HIP(c, hipMemcpyAsync(rgba_out, c->frame.resolve.get(), (size_t)n_pix * sizeof(float4), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
@@ -1789,17 +1792,13 @@ static int resolve_filtered(pt_ctx* c, const char* who, float* rgba_out, uint32_
   if (n_pix == 0) return PT_OK;
   const float4* est = c->est.state.get();
   float4* out = c->frame.resolve.get();
-  uint32_t width = c->width, rows = c->local_rows;
-  uint32_t band_rows = ptstate::Partition(c->params).rows;  // (0: no band, every local row is a neighbour)
+  const uint32_t width = c->width, rows = c->local_rows;
+  const uint32_t band_rows = ptstate::Partition(c->params).rows;  // (0: no band, every local row is a neighbour)
   const dim3 grid((width + 31u) / 32u, (rows + 7u) / 8u);
-  if (patch) {
-    uint32_t P = *patch;
-    void* kargs[] = {&est, &out, &width, &rows, &band_rows, &radius, &P, &kappa, &gamma};
-    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FILTER_PATCH), grid, dim3(256), kargs, 0, c->stream));
-  } else {
-    void* kargs[] = {&est, &out, &width, &rows, &band_rows, &radius, &kappa, &gamma};
-    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FILTER), grid, dim3(256), kargs, 0, c->stream));
-  }
+  if (patch)
+    PT_HIP(c, call(ptsig::FilterPatch{}, pt_error_kernel(PT_E_FILTER_PATCH), grid, dim3(256), 0, c->stream, est, out, width, rows, band_rows, radius, *patch, kappa, gamma));
+  else
+    PT_HIP(c, call(ptsig::Filter{}, pt_error_kernel(PT_E_FILTER), grid, dim3(256), 0, c->stream, est, out, width, rows, band_rows, radius, kappa, gamma));
   PT_HIP(c, hipMemcpyAsync(rgba_out, c->frame.resolve.get(), (size_t)n_pix * sizeof(float4), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
@@ -1817,12 +1816,9 @@ PT_API int pt_resolve_filtered_patch(pt_ctx* c, float* rgba_out, uint32_t radius
 static int launch_error_tiles(pt_ctx* c) {
   uint32_t tiles_n = n_tiles(c);
   if (tiles_n == 0) return PT_OK;
-  const float4* est = c->est.state.get();
   float4* tiles = c->est.tiles.get();
-  float4* aux = tiles + tiles_n;
-  uint32_t width = c->width, rows = c->local_rows, tx = tiles_x(c);
-  void* kargs[] = {&est, &tiles, &aux, &width, &rows, &tx, &tiles_n};
-  PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_TILES), dim3(tile_grid(tiles_n)), dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, call(ptsig::ErrorTiles{}, pt_error_kernel(PT_E_TILES), dim3(tile_grid(tiles_n)), dim3(256), 0, c->stream,
+                 c->est.state.get(), tiles, tiles + tiles_n, c->width, c->local_rows, tiles_x(c), tiles_n));
   return PT_OK;
 }
 
@@ -1929,13 +1925,7 @@ int partial_round(pt_ctx* c, uint32_t k, uint32_t tiles, uint32_t n_active, uint
     c->order.order_kernel_ran();
   }
   PT_HIP(c, hipMemcpyAsync(flags, c->h_adapt_flags.data(), (size_t)tiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  {
-    const uint32_t* order = c->frame.tile_order.get();
-    const uint32_t* fl = flags;
-    uint32_t n = tiles;
-    void* kargs[] = {&order, &fl, &part, &base, &n};
-    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_PARTITION), dim3(1), dim3(1024), kargs, 0, c->stream));
-  }
+  PT_TRY(launch_partition(c, c->frame.tile_order.get(), flags, part, base, tiles));
   LaunchUse use;
   use.feedback = LaunchUse::OFF;  // a partial launch keeps the order it finds, as a frame does
   use.n_first_tiles = n_active;
@@ -1943,15 +1933,8 @@ int partial_round(pt_ctx* c, uint32_t k, uint32_t tiles, uint32_t n_active, uint
   use.who = "pt_render_adaptive";
   TimedSpan span;
   if (int rc = trace_once(c, k, use, &span); rc != PT_OK) return rc;
-  {
-    float4* accum = c->frame.accum;
-    float4* est = c->est.state.get();
-    const float4* slab = c->frame.slab.get();
-    const uint32_t* order = part;
-    uint32_t na = n_active, width = c->width, rows = c->local_rows, tx = tiles_x(c), passes = k;
-    void* kargs[] = {&accum, &est, &slab, &order, &na, &width, &rows, &tx, &passes};
-    PT_HIP(c, hipLaunchKernel(pt_error_kernel(PT_E_FOLD_TILES), dim3(tile_grid(n_active)), dim3(256), kargs, 0, c->stream));
-  }
+  PT_HIP(c, call(ptsig::FoldErrorTiles{}, pt_error_kernel(PT_E_FOLD_TILES), dim3(tile_grid(n_active)), dim3(256), 0, c->stream,
+                 c->frame.accum, c->est.state.get(), c->frame.slab.get(), part, n_active, c->width, c->local_rows, tiles_x(c), k));
   c->est.spp = p.samples_per_pixel;
   changed(*c, ptstate::PARTIAL_ROUND_DONE);
   c->adapt_tiles = tiles;
@@ -2296,10 +2279,9 @@ static int query_ready(pt_ctx* c, const char* who, const char* build, const void
 // packed into h_in (the caller's, so that nothing is allocated per batch) and copied plane by plane.
 static int stage_rays(pt_ctx* c, const PtRay* rays, bool on_device, uint32_t m, std::vector<ptq::F4>& h_in) {
   ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->query.planes.get());
-  uint32_t plane = (uint32_t)n_pixels(c);
+  const uint32_t plane = (uint32_t)n_pixels(c);
   if (on_device) {
-    void* kargs[] = {&rays, &m, &planes, &plane};
-    PT_HIP(c, hipLaunchKernel(pt_query_pack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+    PT_HIP(c, call(ptsig::QueryPack{}, pt_query_pack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), 0, c->stream, rays, m, planes, plane));
     return PT_OK;
   }
   h_in.resize(2 * (size_t)m);
@@ -2344,15 +2326,11 @@ PT_API int pt_query_rays(pt_ctx* c, const PtRay* rays, uint32_t n, PtRayHit* hit
   const uint32_t batches = ptq::n_batches(n, plane);
   for (uint32_t k = 0; k < batches; k++) {
     const size_t first = (size_t)k * plane;
-    uint32_t m = ptq::batch_rays(n, plane, k);
+    const uint32_t m = ptq::batch_rays(n, plane, k);
     if (int rc = stage_rays(c, rays + first, rays_on_device, m, h_in); rc != PT_OK) return rc;
     if (int rc = trace_once(c, 1, batch_use(c, DOOR_QUERY, m)); rc != PT_OK) return rc;
     if (hits_on_device) {
-      const ptq::F4* src = planes;
-      PtRayHit* dst = hits + first;
-      uint32_t pl = plane;
-      void* kargs[] = {&src, &pl, &m, &dst};
-      PT_HIP(c, hipLaunchKernel(pt_query_unpack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
+      PT_HIP(c, call(ptsig::QueryUnpack{}, pt_query_unpack_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), 0, c->stream, planes, plane, m, hits + first));
     } else {
       h_out.resize(PT_FEAT_PLANES * (size_t)m);
       for (int q = 0; q < PT_FEAT_PLANES; q++)
@@ -2370,10 +2348,32 @@ PT_API int pt_query_rays(pt_ctx* c, const PtRay* rays, uint32_t n, PtRayHit* hit
 }
 
 // ---- radiance queries (needs PT_OPT_RAY_QUERIES; include/ptrace.h has the contract) ---------------------------
+// n_passes of a radiance or gather call: not zero, and no more than the pass slabs hold
+static int passes_ready(pt_ctx* c, const char* who, uint32_t n_passes) {
+  if (n_passes == 0) return fail(c, PT_ERR_INVALID, "%s: n_passes == 0", who);
+  if (n_passes > c->reserved_passes)
+    return fail(c, PT_ERR_CAPACITY, "%s: %u passes > %u reserved (pt_reserve_passes)", who, n_passes, c->reserved_passes);
+  return PT_OK;
+}
+
+// THE RADIANCE BATCH of pt_query_radiance and the gather calls: batch k's m rays, which the caller has staged in the query
+// planes, through ONE launch of the row's radiance build and ONE fold of its pass slabs into `dst`, m records on the device.
+// Enqueued, not awaited.
+static int radiance_batch(pt_ctx* c, const char* who, bool next_event, uint32_t k, uint32_t m, uint32_t n_passes, PtRayRadiance* dst) {
+  LaunchUse use = batch_use(c, DOOR_RADIANCE, m);
+  use.who = who;
+  use.next_event = next_event;
+  use.first_pass = ptr::batch_first_pass(c->params.first_pass, k, n_passes);
+  if (int rc = trace_once(c, n_passes, use); rc != PT_OK) return rc;
+  PT_HIP(c, call(ptsig::RadianceFold{}, pt_radiance_fold_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), 0, c->stream,
+                 c->frame.slab.get(), (uint32_t)n_pixels(c), n_passes, c->query.planes.get(), m, dst));
+  return PT_OK;
+}
+
 // n rays in batches of the local pixel count, as pt_query_rays deals them; a batch: stage the rays into the point and normal
 // planes of the query planes (pt_query_rays' own staging), ONE launch of the row's radiance build over the tile rows the rays
 // occupy — n_passes passes of the batch's own into the pass slabs — and ONE fold of those slabs into the records
-// (pt_radiance_fold_kernel): straight into a device `out`, or into the query planes' first plane (a record is a texel) and
+// (radiance_batch): straight into a device `out`, or into the query planes' first plane (a record is a texel) and
 // copied from there.  Nothing is allocated per call but the host vector of a host batch's staging.
 // Both estimators share the body: `next_event` is pt_query_radiance_nee's (its own precondition after the namesake's checks, its
 // own side table's cell at the launch: LaunchUse::next_event), and nothing else differs.
@@ -2381,34 +2381,21 @@ static int query_radiance(pt_ctx* c, const char* who, bool next_event, const PtR
   if (!c) return PT_ERR_INVALID;
   if (n == 0) return PT_OK;
   if (int rc = query_ready(c, who, "radiance", rays, out); rc != PT_OK) return rc;
-  if (n_passes == 0) return fail(c, PT_ERR_INVALID, "%s: n_passes == 0", who);
-  if (n_passes > c->reserved_passes)
-    return fail(c, PT_ERR_CAPACITY, "%s: %u passes > %u reserved (pt_reserve_passes)", who, n_passes, c->reserved_passes);
+  if (int rc = passes_ready(c, who, n_passes); rc != PT_OK) return rc;
   if (int rc = estimator_ready(c, who, next_event); rc != PT_OK) return rc;
   static_assert(sizeof(PtRayRadiance) == sizeof(ptq::F4), "a record is a texel: the fold's scratch is a plane");
   const uint32_t plane = (uint32_t)n_pixels(c);
   const bool rays_on_device = device_pointer(rays), out_on_device = device_pointer(out);
-  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->query.planes.get());
+  PtRayRadiance* scratch = reinterpret_cast<PtRayRadiance*>(c->query.planes.get() + (size_t)PT_FEAT_ALBEDO * plane);
   std::vector<ptq::F4> h_in;  // host rays only: the two planes going up
   const uint32_t batches = ptq::n_batches(n, plane);
   for (uint32_t k = 0; k < batches; k++) {
     const size_t first = (size_t)k * plane;
-    uint32_t m = ptq::batch_rays(n, plane, k);
+    const uint32_t m = ptq::batch_rays(n, plane, k);
     if (int rc = stage_rays(c, rays + first, rays_on_device, m, h_in); rc != PT_OK) return rc;
-    LaunchUse use = batch_use(c, DOOR_RADIANCE, m);
-    use.who = who;
-    use.next_event = next_event;
-    use.first_pass = ptr::batch_first_pass(c->params.first_pass, k, n_passes);
-    if (int rc = trace_once(c, n_passes, use); rc != PT_OK) return rc;
-    {
-      const ptq::F4* slab = reinterpret_cast<const ptq::F4*>(c->frame.slab.get());
-      const ptq::F4* staged = planes;
-      PtRayRadiance* dst = out_on_device ? out + first : reinterpret_cast<PtRayRadiance*>(planes + (size_t)PT_FEAT_ALBEDO * plane);
-      uint32_t pl = plane, np = n_passes;
-      void* kargs[] = {&slab, &pl, &np, &staged, &m, &dst};
-      PT_HIP(c, hipLaunchKernel(pt_radiance_fold_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
-      if (!out_on_device) PT_HIP(c, hipMemcpyAsync(out + first, dst, (size_t)m * sizeof(PtRayRadiance), hipMemcpyDeviceToHost, c->stream));
-    }
+    PtRayRadiance* dst = out_on_device ? out + first : scratch;
+    if (int rc = radiance_batch(c, who, next_event, k, m, n_passes, dst); rc != PT_OK) return rc;
+    if (!out_on_device) PT_HIP(c, hipMemcpyAsync(out + first, dst, (size_t)m * sizeof(PtRayRadiance), hipMemcpyDeviceToHost, c->stream));
     // (the next batch stages into the planes this one's fold reads, and a host batch's vector is packed again)
     PT_HIP(c, hipStreamSynchronize(c->stream));
   }
@@ -2423,84 +2410,67 @@ PT_API int pt_query_radiance_nee(pt_ctx* c, const PtRay* rays, uint32_t n, uint3
 }
 
 // ---- gather queries (needs PT_OPT_RAY_QUERIES; include/ptrace.h has the contract) ------------------------------
-// The one function behind pt_gather_irradiance and pt_bake_probes: the n * D rays of the defining sentence in pt_query_radiance's
-// batches.  A batch: the items it touches into the workspace (a host array's; a device array is read in place), the generator
-// in stage_rays' place, pt_query_radiance's launch and fold as they are — the folded records wait in the query planes' first
-// plane, where a host call's wait for their copy — and the reduce over the items the batch touches: an item that ends in the
-// batch is written (straight into a device `out`, or into the workspace and copied from there), the one that goes on leaves its
-// lanes' partial sums in the workspace for the next batch.
-static int gather(pt_ctx* c, const char* who, int kind, bool next_event, const PtGatherPoint* points, uint32_t n, uint32_t D, uint32_t n_passes, void* out) {
-  if (!c) return PT_ERR_INVALID;
-  if (n == 0) return PT_OK;
-  if (int rc = query_ready(c, who, "radiance", points, out); rc != PT_OK) return rc;
-  if (n_passes == 0) return fail(c, PT_ERR_INVALID, "%s: n_passes == 0", who);
-  if (n_passes > c->reserved_passes)
-    return fail(c, PT_ERR_CAPACITY, "%s: %u passes > %u reserved (pt_reserve_passes)", who, n_passes, c->reserved_passes);
+// What every gather call asks before anything is enqueued: pt_query_radiance's checks in its order, with the direction count
+// and the ray total between the passes and the estimator.  `in` is the caller's array of items (pt_bake_lattice: its lattice).
+static int gather_ready(pt_ctx* c, const char* who, bool next_event, const void* in, uint32_t n, uint32_t D, uint32_t n_passes, const void* out) {
+  if (int rc = query_ready(c, who, "radiance", in, out); rc != PT_OK) return rc;
+  if (int rc = passes_ready(c, who, n_passes); rc != PT_OK) return rc;
   if (!ptgather::directions_valid(D))
     return fail(c, PT_ERR_INVALID, "%s: %u directions (a multiple of 64 in [%d, %d])", who, D, (int)ptgather::kMinDirections, (int)ptgather::kMaxDirections);
-  const uint64_t total = ptgather::total_rays(n, D);
-  if (total == 0) return fail(c, PT_ERR_INVALID, "%s: %u items of %u directions are more than 2^32 - 1 rays", who, n, D);
-  if (int rc = estimator_ready(c, who, next_event); rc != PT_OK) return rc;
+  if (ptgather::total_rays(n, D) == 0) return fail(c, PT_ERR_INVALID, "%s: %u items of %u directions are more than 2^32 - 1 rays", who, n, D);
+  return estimator_ready(c, who, next_event);
+}
+
+// The batches of a gather call that gather_ready has passed (n > 0), behind pt_gather_irradiance, pt_bake_probes and
+// pt_bake_lattice: the workspace in place, then the n * D rays of the defining sentence in pt_query_radiance's batches.  A batch:
+// the items it touches into the workspace (a host array's; a device array is read in place), the generator in stage_rays' place,
+// pt_query_radiance's launch and fold as they are (radiance_batch) — the folded records wait in the query planes' first plane,
+// where a host call's wait for their copy — and the reduce over the items the batch touches: an item that ends in the batch is
+// written (straight into a device `out`, or into the workspace and copied from there), the one that goes on leaves its lanes'
+// partial sums in the workspace for the next batch.
+static int gather_batches(pt_ctx* c, const char* who, int kind, bool next_event, const PtGatherPoint* points, uint32_t n, uint32_t D, uint32_t n_passes, void* out) {
   const ptbuf::Extent e = extent_of(c);
   if (!c->gather.in_place(e)) {
     if (const ptbuf::Fit f = c->gather.fit(e); !f.ok())
       return fail(c, PT_ERR_CAPACITY, "%s: the workspace's allocation for %zu local pixels failed: %s", who, e.pix, hipGetErrorString((hipError_t)f.err));
   }
-  const uint32_t plane = (uint32_t)n_pixels(c);
+  const uint32_t plane = (uint32_t)n_pixels(c), total = (uint32_t)ptgather::total_rays(n, D);
   const size_t record = kind == ptgather::PROBE ? sizeof(PtProbeSH) : sizeof(PtIrradiance);
   const bool points_on_device = device_pointer(points), out_on_device = device_pointer(out);
-  ptq::F4* planes = reinterpret_cast<ptq::F4*>(c->query.planes.get());
-  PtRayRadiance* folded = reinterpret_cast<PtRayRadiance*>(planes + (size_t)PT_FEAT_ALBEDO * plane);
+  PtRayRadiance* folded = reinterpret_cast<PtRayRadiance*>(c->query.planes.get() + (size_t)PT_FEAT_ALBEDO * plane);
   PtGatherPoint* staged_points = reinterpret_cast<PtGatherPoint*>(c->gather.points());
   void* staged_out = c->gather.records(e);
-  const uint32_t batches = ptq::n_batches((uint32_t)total, plane);
+  const uint32_t batches = ptq::n_batches(total, plane);
   for (uint32_t k = 0; k < batches; k++) {
-    uint32_t first = (uint32_t)((uint64_t)k * plane);
-    uint32_t m = ptq::batch_rays((uint32_t)total, plane, k);
-    uint32_t item0 = first / D, items = (uint32_t)(((uint64_t)first + m - 1u) / D) - item0 + 1u;  // the items the batch touches
-    // ... and those of them that end in it: [done0, done1)
-    const uint32_t done0 = item0, done1 = (uint32_t)(((uint64_t)first + m) / D);
-    // (items <= m / 64 + 2 <= GatherSet::items(e): D >= 64 and m <= plane — the workspace holds them)
-    const PtGatherPoint* pts = points + item0;
+    const uint32_t first = (uint32_t)((uint64_t)k * plane), m = ptq::batch_rays(total, plane, k);
+    // the items the batch touches — no more than the workspace holds (ptgather::items_per_batch: m <= plane) — and those of
+    // them that end in it
+    const ptgather::ItemSpan s = ptgather::item_span(first, m, D);
+    const PtGatherPoint* pts = points + s.item0;
     if (!points_on_device) {
-      PT_HIP(c, hipMemcpyAsync(staged_points, points + item0, (size_t)items * sizeof(PtGatherPoint), hipMemcpyHostToDevice, c->stream));
+      PT_HIP(c, hipMemcpyAsync(staged_points, pts, (size_t)s.items * sizeof(PtGatherPoint), hipMemcpyHostToDevice, c->stream));
       pts = staged_points;
     }
-    {
-      uint32_t dirs = D, pl = plane;
-      int kd = kind;
-      void* kargs[] = {&pts, &item0, &first, &m, &dirs, &kd, &planes, &pl};
-      PT_HIP(c, hipLaunchKernel(pt_gather_kernel(PT_GATHER_RAYS), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
-    }
-    LaunchUse use = batch_use(c, DOOR_RADIANCE, m);
-    use.who = who;
-    use.next_event = next_event;
-    use.first_pass = ptr::batch_first_pass(c->params.first_pass, k, n_passes);
-    if (int rc = trace_once(c, n_passes, use); rc != PT_OK) return rc;
-    {
-      const ptq::F4* slab = reinterpret_cast<const ptq::F4*>(c->frame.slab.get());
-      const ptq::F4* staged = planes;
-      uint32_t pl = plane, np = n_passes;
-      void* kargs[] = {&slab, &pl, &np, &staged, &m, &folded};
-      PT_HIP(c, hipLaunchKernel(pt_radiance_fold_kernel_handle(), dim3((m + 255u) / 256u), dim3(256), kargs, 0, c->stream));
-    }
-    {
-      const PtRayRadiance* rec = folded;
-      void* dst = out_on_device ? out : staged_out;
-      uint32_t out0 = out_on_device ? 0u : done0, dirs = D;
-      int kd = kind;
-      // (batch k writes the carry slot of its parity and reads the other, which batch k - 1 wrote: never one slot in one launch)
-      const float* carry_in = c->gather.carry(k + 1u);
-      float* carry_out = c->gather.carry(k);
-      void* kargs[] = {&rec, &pts, &item0, &items, &first, &m, &dirs, &kd, &carry_in, &carry_out, &dst, &out0};
-      PT_HIP(c, hipLaunchKernel(pt_gather_kernel(PT_GATHER_REDUCE), dim3((items + 3u) / 4u), dim3(256), kargs, 0, c->stream));
-      if (!out_on_device && done1 > done0)
-        PT_HIP(c, hipMemcpyAsync(static_cast<char*>(out) + (size_t)done0 * record, staged_out, (size_t)(done1 - done0) * record, hipMemcpyDeviceToHost, c->stream));
-    }
+    PT_HIP(c, call(ptsig::GatherRays{}, pt_gather_kernel(PT_GATHER_RAYS), dim3((m + 255u) / 256u), dim3(256), 0, c->stream,
+                   pts, s.item0, first, m, D, kind, c->query.planes.get(), plane));
+    if (int rc = radiance_batch(c, who, next_event, k, m, n_passes, folded); rc != PT_OK) return rc;
+    // (batch k writes the carry slot of its parity and reads the other, which batch k - 1 wrote: never one slot in one launch)
+    PT_HIP(c, call(ptsig::GatherReduce{}, pt_gather_kernel(PT_GATHER_REDUCE), dim3((s.items + 3u) / 4u), dim3(256), 0, c->stream,
+                   folded, pts, s.item0, s.items, first, m, D, kind, c->gather.carry(k + 1u), c->gather.carry(k),
+                   out_on_device ? out : staged_out, out_on_device ? 0u : s.done0));
+    if (!out_on_device && s.done1 > s.done0)
+      PT_HIP(c, hipMemcpyAsync(static_cast<char*>(out) + (size_t)s.done0 * record, staged_out, (size_t)(s.done1 - s.done0) * record, hipMemcpyDeviceToHost, c->stream));
     // (the next batch stages into the planes and the workspace this one reads)
     PT_HIP(c, hipStreamSynchronize(c->stream));
   }
   return PT_OK;
+}
+
+static int gather(pt_ctx* c, const char* who, int kind, bool next_event, const PtGatherPoint* points, uint32_t n, uint32_t D, uint32_t n_passes, void* out) {
+  if (!c) return PT_ERR_INVALID;
+  if (n == 0) return PT_OK;
+  if (int rc = gather_ready(c, who, next_event, points, n, D, n_passes, out); rc != PT_OK) return rc;
+  return gather_batches(c, who, kind, next_event, points, n, D, n_passes, out);
 }
 
 PT_API int pt_gather_irradiance(pt_ctx* c, const PtGatherPoint* points, uint32_t n, uint32_t directions, uint32_t n_passes, PtIrradiance* out) {
@@ -2517,9 +2487,9 @@ PT_API int pt_bake_probes_nee(pt_ctx* c, const PtGatherPoint* probes, uint32_t n
 }
 
 // ---- probe lattices (no option of their own; include/ptrace.h has the contract) ------------------------------
-// pt_bake_lattice: the lattice's own checks, what the gather call would refuse before anything is enqueued (so that no generator
-// runs for a call that is refused), the generator into the ProbeSet's point buffer, then the gather calls' one host body on that
-// DEVICE pointer: the defining sentence by construction, and no second copy of the bake loop.
+// pt_bake_lattice: the lattice's own checks, the gather calls' (gather_ready, once: no generator runs for a call that is
+// refused), the generator into the ProbeSet's point buffer, then the gather calls' batches on that DEVICE pointer: the defining
+// sentence by construction, and no second copy of the bake loop.
 PT_API int pt_bake_lattice(pt_ctx* c, const PtProbeLattice* lattice, uint32_t first, uint32_t count, uint32_t directions, uint32_t n_passes, int estimator,
                            PtProbeSH* out) {
   if (!c) return PT_ERR_INVALID;
@@ -2531,30 +2501,16 @@ PT_API int pt_bake_lattice(pt_ctx* c, const PtProbeLattice* lattice, uint32_t fi
     return fail(c, PT_ERR_INVALID, "%s: nodes %u .. %u + %u of a lattice of %u", who, first, first, count, ptprobe::node_count(*lattice));
   if (count == 0) return PT_OK;
   const bool next_event = estimator == 1;
-  if (int rc = query_ready(c, who, "radiance", lattice, out); rc != PT_OK) return rc;
-  if (n_passes == 0) return fail(c, PT_ERR_INVALID, "%s: n_passes == 0", who);
-  if (n_passes > c->reserved_passes)
-    return fail(c, PT_ERR_CAPACITY, "%s: %u passes > %u reserved (pt_reserve_passes)", who, n_passes, c->reserved_passes);
-  if (!ptgather::directions_valid(directions))
-    return fail(c, PT_ERR_INVALID, "%s: %u directions (a multiple of 64 in [%d, %d])", who, directions, (int)ptgather::kMinDirections, (int)ptgather::kMaxDirections);
-  if (ptgather::total_rays(count, directions) == 0)
-    return fail(c, PT_ERR_INVALID, "%s: %u items of %u directions are more than 2^32 - 1 rays", who, count, directions);
-  if (int rc = estimator_ready(c, who, next_event); rc != PT_OK) return rc;
+  if (int rc = gather_ready(c, who, next_event, lattice, count, directions, n_passes, out); rc != PT_OK) return rc;
   if (!c->probe.points_in_place(count)) {
     PT_HIP(c, hipStreamSynchronize(c->stream));  // (nothing in flight reads what the fit frees)
     if (const ptbuf::Fit f = c->probe.fit_points(count); !f.ok())
       return fail(c, PT_ERR_CAPACITY, "%s: the point buffer's allocation for %u nodes failed: %s", who, count, hipGetErrorString((hipError_t)f.err));
   }
   PtGatherPoint* points = reinterpret_cast<PtGatherPoint*>(c->probe.points.get());
-  {
-    PtProbeLattice L = *lattice;
-    const float* geom = c->list.geom.get();
-    const PtMatRec* mat = c->list.mat.get();
-    uint32_t n_spheres = c->list.n;
-    void* kargs[] = {&L, &first, &count, &geom, &mat, &n_spheres, &points};
-    PT_HIP(c, hipLaunchKernel(pt_lattice_kernel(PT_PROBE_POINTS), dim3((count + 255u) / 256u), dim3(256), kargs, 0, c->stream));
-  }
-  return gather(c, who, ptgather::PROBE, next_event, points, count, directions, n_passes, out);
+  PT_HIP(c, call(ptsig::ProbePoints{}, pt_lattice_kernel(PT_PROBE_POINTS), dim3((count + 255u) / 256u), dim3(256), 0, c->stream,
+                 *lattice, first, count, c->list.geom.get(), c->list.mat.get(), c->list.n, points));
+  return gather_batches(c, who, ptgather::PROBE, next_event, points, count, directions, n_passes, out);
 }
 
 PT_API int pt_debug_probe_form(pt_ctx* c, int form, uint32_t* paths_dev) {
@@ -2601,13 +2557,16 @@ PT_API int pt_shade_probes(pt_ctx* c, const PtProbeLattice* lattice, const PtPro
   }
   {
     const float4* planes = c->feat.planes.get();
-    uint32_t plane = (uint32_t)n_pixels(c), width = c->width, rows = c->local_rows;
-    PtProbeLattice L = *lattice;
-    float cx = c->params.camera_origin[0], cy = c->params.camera_origin[1], cz = c->params.camera_origin[2];
+    const uint32_t plane = (uint32_t)n_pixels(c);
+    const float* cam = c->params.camera_origin;
     float* dst = out_on_device ? rgba_out : reinterpret_cast<float*>(c->frame.resolve.get());
-    uint32_t* paths = c->probe_paths;
-    void* kargs[] = {&planes, &plane, &width, &rows, &L, &flags, &bias, &cx, &cy, &cz, &records, &dst, &paths};  // (form 0 reads the first twelve)
-    PT_HIP(c, hipLaunchKernel(pt_lattice_kernel(c->probe_form == 1 ? PT_PROBE_SHADE_SHARED : PT_PROBE_SHADE), dim3((n_tiles(c) + 3u) / 4u), dim3(256), kargs, 0, c->stream));
+    const dim3 grid((n_tiles(c) + 3u) / 4u);
+    if (c->probe_form == 1)
+      PT_HIP(c, call(ptsig::ProbeShadeShared{}, pt_lattice_kernel(PT_PROBE_SHADE_SHARED), grid, dim3(256), 0, c->stream,
+                     planes, plane, c->width, c->local_rows, *lattice, flags, bias, cam[0], cam[1], cam[2], records, dst, c->probe_paths));
+    else
+      PT_HIP(c, call(ptsig::ProbeShade{}, pt_lattice_kernel(PT_PROBE_SHADE), grid, dim3(256), 0, c->stream,
+                     planes, plane, c->width, c->local_rows, *lattice, flags, bias, cam[0], cam[1], cam[2], records, dst));
     if (!out_on_device) PT_HIP(c, hipMemcpyAsync(rgba_out, dst, n_pixels(c) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   }
   if (!probes_on_device || !out_on_device) PT_HIP(c, hipStreamSynchronize(c->stream));
@@ -2651,18 +2610,14 @@ PT_API int pt_meter(pt_ctx* c, const float* src, const PtMeterOptions* opt) {
   PT_TRY(tone_source(c, "pt_meter", src, s));
   if (!c->expo.in_place()) return fail(c, PT_ERR_CAPACITY, "pt_meter: the exposure state is not allocated (an earlier allocation failed)");
   uint32_t* state = c->expo.state.get();
-  uint32_t n_pix = (uint32_t)n_pixels(c), width = c->width;
+  const uint32_t n_pix = (uint32_t)n_pixels(c);
   const ptstate::Partition part(c->params);
-  pttone::Window win = {opt->x0, opt->y0, opt->w, opt->h, part.rows, part.index, part.count};
+  const pttone::Window win = {opt->x0, opt->y0, opt->w, opt->h, part.rows, part.index, part.count};
   PT_HIP(c, hipMemsetAsync(state, 0, pttone::kTallies * sizeof(uint32_t), c->stream));
   if (n_pix) {  // (a band without rows: N == 0 on the device)
-    void* kargs[] = {&s.texels, &s.from_accum, &n_pix, &width, &win, &state};
-    PT_HIP(c, hipLaunchKernel(pt_display_kernel(PT_D_METER), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
+    PT_HIP(c, call(ptsig::Meter{}, pt_display_kernel(PT_D_METER), dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream, s.texels, s.from_accum, n_pix, c->width, win, state));
   }
-  PtMeterOptions rule = *opt;
-  int was_valid = c->expo.valid ? 1 : 0;
-  void* kargs[] = {&state, &rule, &was_valid};
-  PT_HIP(c, hipLaunchKernel(pt_display_kernel(PT_D_EXPOSURE), dim3(1), dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, call(ptsig::Exposure{}, pt_display_kernel(PT_D_EXPOSURE), dim3(1), dim3(256), 0, c->stream, state, *opt, c->expo.valid ? 1 : 0));
   c->expo.valid = true;
   if (s.staged) PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
@@ -2723,12 +2678,9 @@ static int resolve_toned(pt_ctx* c, const char* who, const float* src, const PtT
   uint32_t n_pix = (uint32_t)n_pixels(c);
   if (n_pix == 0) return PT_OK;
   void* out = c->frame.resolve.get();
-  int32_t curve = opt->curve;
-  int gamma = opt->gamma;
-  float exposure = opt->exposure, white = opt->white;
   const PtExposure* record = from_record ? reinterpret_cast<const PtExposure*>(c->expo.state.get() + pttone::kTallies) : nullptr;
-  void* kargs[] = {&s.texels, &s.from_accum, &out, &bytes, &n_pix, &curve, &gamma, &exposure, &white, &record};
-  PT_HIP(c, hipLaunchKernel(pt_display_kernel(PT_D_TONE), dim3(pixel_grid(n_pix)), dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, call(ptsig::Tone{}, pt_display_kernel(PT_D_TONE), dim3(pixel_grid(n_pix)), dim3(256), 0, c->stream,
+                 s.texels, s.from_accum, out, bytes, n_pix, opt->curve, opt->gamma, opt->exposure, opt->white, record));
   PT_HIP(c, hipMemcpyAsync(rgba_out, out, (size_t)n_pix * (bytes ? 4 : sizeof(float4)), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
@@ -2774,25 +2726,22 @@ PT_API int pt_glare(pt_ctx* c, const float* src, const PtGlareOptions* opt, floa
     level[k] = next;
     next += (size_t)lw[k] * lh[k];
   }
-  float threshold = opt->threshold, strength = opt->strength;
   for (uint32_t k = 1; k <= opt->levels; k++) {
     const pttone::F4* from = k == 1 ? s.texels : level[k - 1];
-    int mode = k == 1 ? (s.from_accum ? 2 : 1) : 0;
-    void* kargs[] = {&from, &mode, &threshold, &lw[k - 1], &lh[k - 1], &level[k], &lw[k], &lh[k]};
-    PT_HIP(c, hipLaunchKernel(pt_glare_kernel(PT_G_DOWN), dim3(glare_tile_grid(lw[k], lh[k])), dim3(256), kargs, 0, c->stream));
+    const int mode = k == 1 ? (s.from_accum ? 2 : 1) : 0;
+    PT_HIP(c, call(ptsig::GlareDown{}, pt_glare_kernel(PT_G_DOWN), dim3(glare_tile_grid(lw[k], lh[k])), dim3(256), 0, c->stream,
+                   from, mode, opt->threshold, lw[k - 1], lh[k - 1], level[k], lw[k], lh[k]));
   }
   for (uint32_t k = opt->levels; k >= 1; k--) {
     const bool top = k == opt->levels;
     const pttone::F4* above = top ? nullptr : level[k + 1];
-    uint32_t W = top ? 0u : lw[k + 1], H = top ? 0u : lh[k + 1];
-    float weight = opt->weight[k - 1];
-    void* kargs[] = {&level[k], &lw[k], &lh[k], &weight, &above, &W, &H};
-    PT_HIP(c, hipLaunchKernel(pt_glare_kernel(PT_G_GATHER), dim3(pixel_grid(lw[k] * lh[k])), dim3(256), kargs, 0, c->stream));
+    const uint32_t W = top ? 0u : lw[k + 1], H = top ? 0u : lh[k + 1];
+    PT_HIP(c, call(ptsig::GlareGather{}, pt_glare_kernel(PT_G_GATHER), dim3(pixel_grid(lw[k] * lh[k])), dim3(256), 0, c->stream,
+                   level[k], lw[k], lh[k], opt->weight[k - 1], above, W, H));
   }
-  pttone::F4* out = reinterpret_cast<pttone::F4*>(c->frame.resolve.get());
-  const pttone::F4* u1 = level[1];
-  void* kargs[] = {&s.texels, &s.from_accum, &threshold, &strength, &u1, &lw[1], &lh[1], &out, &w, &h};
-  PT_HIP(c, hipLaunchKernel(pt_glare_kernel(PT_G_COMPOSITE), dim3(pixel_grid(w * h)), dim3(256), kargs, 0, c->stream));
+  float4* out = c->frame.resolve.get();
+  PT_HIP(c, call(ptsig::GlareComposite{}, pt_glare_kernel(PT_G_COMPOSITE), dim3(pixel_grid(w * h)), dim3(256), 0, c->stream,
+                 s.texels, s.from_accum, opt->threshold, opt->strength, level[1], lw[1], lh[1], out, w, h));
   PT_HIP(c, hipMemcpyAsync(rgba_out, out, (size_t)w * h * sizeof(float4), hipMemcpyDefault, c->stream));
   PT_HIP(c, hipStreamSynchronize(c->stream));
   return PT_OK;
@@ -2886,7 +2835,7 @@ static int reproject_call(pt_ctx* c, const PtReprojectOptions* opt, const char* 
   K.cap_diffuse = opt->cap_diffuse;
   K.cap_other = opt->cap_other;
   const ptstate::Partition part(c->params);
-  ptrep::Frame F = {c->width, c->height, c->local_rows, part.rows, part.index, part.count};
+  const ptrep::Frame F = {c->width, c->height, c->local_rows, part.rows, part.index, part.count};
   const float4* cur_ids = c->feat.planes.get() + (size_t)PT_FEAT_IDS * pix;
   const float4* cur_pnt = c->feat.planes.get() + (size_t)PT_FEAT_POINT * pix;
   const float4* hist_ids = c->hist.planes.get();
@@ -2896,8 +2845,7 @@ static int reproject_call(pt_ctx* c, const PtReprojectOptions* opt, const char* 
   unsigned long long* tally = c->hist.tally.get();
   const dim3 grid((c->width + 31u) / 32u, (c->local_rows + 7u) / 8u);
   if (!carry) {
-    void* kargs[] = {&cur_ids, &cur_pnt, &hist_ids, &hist_pnt, &accum, &out, &K, &F, &tally};
-    PT_HIP(c, hipLaunchKernel(pt_reproject_kernel_handle(), grid, dim3(256), kargs, 0, c->stream));
+    PT_HIP(c, call(ptsig::Reproject{}, pt_reproject_kernel_handle(), grid, dim3(256), 0, c->stream, cur_ids, cur_pnt, hist_ids, hist_pnt, accum, out, K, F, tally));
     PT_HIP(c, hipMemcpyAsync(c->frame.accum, out, pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     return clear_error(c);  // (history is sums, not the passes they came from: as pt_load_accum)
   }
@@ -2905,8 +2853,8 @@ static int reproject_call(pt_ctx* c, const PtReprojectOptions* opt, const char* 
   const ptrep::EstConsts E = ptrep::est_consts(c->est.spp, opt->cap_diffuse, opt->cap_other);
   const float4* err = c->est.state.get();
   float4* out_err = c->est.stage.get();
-  void* kargs[] = {&cur_ids, &cur_pnt, &hist_ids, &hist_pnt, &accum, &err, &out, &out_err, &K, (void*)&E, &F, &tally};
-  PT_HIP(c, hipLaunchKernel(pt_reproject_estimate_kernel_handle(), grid, dim3(256), kargs, 0, c->stream));
+  PT_HIP(c, call(ptsig::ReprojectEstimate{}, pt_reproject_estimate_kernel_handle(), grid, dim3(256), 0, c->stream,
+                 cur_ids, cur_pnt, hist_ids, hist_pnt, accum, err, out, out_err, K, E, F, tally));
   PT_HIP(c, hipMemcpyAsync(c->frame.accum, out, pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
   PT_HIP(c, hipMemcpyAsync(c->est.state.get(), out_err, 2 * pix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
   return PT_OK;

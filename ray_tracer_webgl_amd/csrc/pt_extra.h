@@ -11,6 +11,11 @@
 // PT_VARIANT_ACCESSOR(pt_<name>_kernel, _<suffix>, <Adaptor>), added to the Makefile's SRCS; one entry in PT_TRACE_OBJECTS
 // here; and in pt_trace_table.hpp one value of TraceBuild, one cell expansion, one suffix in PT_TABLE_ROW and who names the
 // column: the option's place in trace_build() for a render launch's, a Door and its line in door_build() for an entry point's.
+//
+// HOW TO ADD A SMALL KERNEL (any kernel that is no trace kernel and lives outside pt_kernels.hip): its accessor or its id below,
+// beside its unit's; its parameter list, once, in pt_sigs.h; in its unit the handle through ptcall::handle(ptsig::Name{}, kernel),
+// which compiles only while the two agree; in pt_api.hip the launch through call(ptsig::Name{}, handle, ...), which checks the
+// arguments against the same list (pt_call.hpp has the rule).
 #pragma once
 
 // pt_kernels.hip (compiled into pt_api.hip's object): the list and walk kernels

@@ -64,6 +64,17 @@ PT_GTH_HD uint64_t total_rays(uint32_t n, uint32_t D) {
 }
 // the items a batch of at most `batch` rays can touch: whole ones, and a straddling one at either end
 PT_GTH_HD uint32_t items_per_batch(uint32_t batch) { return batch / kMinDirections + 2u; }
+// The items of D rays each that the batch of rays [first, first + m) touches (m >= 1, first + m <= 2^32 - 1: the sum is taken in
+// 64 bits all the same): `items` of them from item0 on, at most items_per_batch(m), of which [done0, done1) END in the batch —
+// their records are written; the last one touched goes on into the next batch where done1 < item0 + items.
+struct ItemSpan {
+  uint32_t item0, items, done0, done1;
+};
+PT_GTH_HD ItemSpan item_span(uint32_t first, uint32_t m, uint32_t D) {
+  const uint64_t end = (uint64_t)first + m;
+  const uint32_t item0 = first / D;
+  return {item0, (uint32_t)((end - 1u) / D) - item0 + 1u, item0, (uint32_t)(end / D)};
+}
 
 // THE VALIDITY PREDICATE of an item: a non-finite position component; for irradiance also a non-finite normal component or a
 // normal of three zeros of either sign

@@ -18,6 +18,7 @@
 
 #include "pt_tone.hpp"
 #include "pt_extra.h"
+#include "pt_sigs.h"
 
 namespace {
 
@@ -111,9 +112,9 @@ extern "C" __global__ __launch_bounds__(256) void pt_tone_kernel(const pttone::F
 
 extern "C" const void* pt_display_kernel(int id) {
   switch (id) {
-    case PT_D_METER: return reinterpret_cast<const void*>(pt_meter_kernel);
-    case PT_D_EXPOSURE: return reinterpret_cast<const void*>(pt_exposure_kernel);
-    case PT_D_TONE: return reinterpret_cast<const void*>(pt_tone_kernel);
+    case PT_D_METER: return ptcall::handle(ptsig::Meter{}, pt_meter_kernel);
+    case PT_D_EXPOSURE: return ptcall::handle(ptsig::Exposure{}, pt_exposure_kernel);
+    case PT_D_TONE: return ptcall::handle(ptsig::Tone{}, pt_tone_kernel);
   }
   return nullptr;
 }

@@ -19,6 +19,7 @@
 
 #include "pt_error_plan.hpp"
 #include "pt_extra.h"
+#include "pt_sigs.h"
 
 // state per pixel i: est[2 i] = A = {mean.r, mean.g, mean.b, n}, est[2 i + 1] = B = {M2.r, M2.g, M2.b, k}
 // (n passes folded, k their samples: both live in the buffer, like accum.w, so a hipGraph replay keeps them right)
@@ -390,13 +391,13 @@ extern "C" __global__ __launch_bounds__(256) void pt_filter_patch_kernel(const f
 
 extern "C" const void* pt_error_kernel(int id) {
   switch (id) {
-    case PT_E_FILTER_PATCH: return reinterpret_cast<const void*>(pt_filter_patch_kernel);
-    case PT_E_FILTER: return reinterpret_cast<const void*>(pt_filter_kernel);
-    case PT_E_FOLD: return reinterpret_cast<const void*>(pt_fold_error_kernel);
-    case PT_E_RESOLVE: return reinterpret_cast<const void*>(pt_resolve_error_kernel);
-    case PT_E_TILES: return reinterpret_cast<const void*>(pt_error_tiles_kernel);
-    case PT_E_FOLD_TILES: return reinterpret_cast<const void*>(pt_fold_error_tiles_kernel);
-    case PT_E_PARTITION: return reinterpret_cast<const void*>(pt_partition_order_kernel);
+    case PT_E_FILTER_PATCH: return ptcall::handle(ptsig::FilterPatch{}, pt_filter_patch_kernel);
+    case PT_E_FILTER: return ptcall::handle(ptsig::Filter{}, pt_filter_kernel);
+    case PT_E_FOLD: return ptcall::handle(ptsig::FoldError{}, pt_fold_error_kernel);
+    case PT_E_RESOLVE: return ptcall::handle(ptsig::ResolveError{}, pt_resolve_error_kernel);
+    case PT_E_TILES: return ptcall::handle(ptsig::ErrorTiles{}, pt_error_tiles_kernel);
+    case PT_E_FOLD_TILES: return ptcall::handle(ptsig::FoldErrorTiles{}, pt_fold_error_tiles_kernel);
+    case PT_E_PARTITION: return ptcall::handle(ptsig::PartitionOrder{}, pt_partition_order_kernel);
     default: return nullptr;
   }
 }

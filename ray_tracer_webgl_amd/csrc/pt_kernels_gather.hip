@@ -22,6 +22,7 @@
 
 #include "pt_arith.hpp"
 #include "pt_extra.h"
+#include "pt_sigs.h"
 #include "pt_gather.hpp"
 #include "pt_query.hpp"
 
@@ -133,8 +134,8 @@ extern "C" __global__ __launch_bounds__(256) void pt_gather_reduce_kernel(const 
 
 extern "C" const void* pt_gather_kernel(int id) {
   switch (id) {
-    case PT_GATHER_RAYS: return reinterpret_cast<const void*>(pt_gather_rays_kernel);
-    case PT_GATHER_REDUCE: return reinterpret_cast<const void*>(pt_gather_reduce_kernel);
+    case PT_GATHER_RAYS: return ptcall::handle(ptsig::GatherRays{}, pt_gather_rays_kernel);
+    case PT_GATHER_REDUCE: return ptcall::handle(ptsig::GatherReduce{}, pt_gather_reduce_kernel);
   }
   return nullptr;
 }

@@ -23,6 +23,7 @@
 
 #include "pt_glare.hpp"
 #include "pt_extra.h"
+#include "pt_sigs.h"
 
 namespace {
 
@@ -122,9 +123,9 @@ extern "C" __global__ __launch_bounds__(256) void pt_glare_composite_kernel(cons
 
 extern "C" const void* pt_glare_kernel(int id) {
   switch (id) {
-    case PT_G_DOWN: return reinterpret_cast<const void*>(pt_glare_down_kernel);
-    case PT_G_GATHER: return reinterpret_cast<const void*>(pt_glare_gather_kernel);
-    case PT_G_COMPOSITE: return reinterpret_cast<const void*>(pt_glare_composite_kernel);
+    case PT_G_DOWN: return ptcall::handle(ptsig::GlareDown{}, pt_glare_down_kernel);
+    case PT_G_GATHER: return ptcall::handle(ptsig::GlareGather{}, pt_glare_gather_kernel);
+    case PT_G_COMPOSITE: return ptcall::handle(ptsig::GlareComposite{}, pt_glare_composite_kernel);
   }
   return nullptr;
 }

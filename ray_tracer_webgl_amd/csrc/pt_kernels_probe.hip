@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "pt_extra.h"
+#include "pt_sigs.h"
 #include "pt_kernel_args.h"
 #include "pt_probe.hpp"
 
@@ -161,9 +162,9 @@ extern "C" __global__ __launch_bounds__(256) void pt_probe_shade_shared_kernel(c
 
 extern "C" const void* pt_lattice_kernel(int id) {
   switch (id) {
-    case PT_PROBE_POINTS: return reinterpret_cast<const void*>(pt_probe_points_kernel);
-    case PT_PROBE_SHADE: return reinterpret_cast<const void*>(pt_probe_shade_kernel);
-    case PT_PROBE_SHADE_SHARED: return reinterpret_cast<const void*>(pt_probe_shade_shared_kernel);
+    case PT_PROBE_POINTS: return ptcall::handle(ptsig::ProbePoints{}, pt_probe_points_kernel);
+    case PT_PROBE_SHADE: return ptcall::handle(ptsig::ProbeShade{}, pt_probe_shade_kernel);
+    case PT_PROBE_SHADE_SHARED: return ptcall::handle(ptsig::ProbeShadeShared{}, pt_probe_shade_shared_kernel);
   }
   return nullptr;
 }

@@ -10,6 +10,7 @@
 //   pt_query_pack_kernel     PtRay[m] -> origins into PT_FEAT_POINT's plane, directions into PT_FEAT_NORMAL's
 //   pt_query_unpack_kernel   the four planes -> PtRayHit[m]
 #include "pt_trace_body.hpp"
+#include "pt_sigs.h"
 
 PT_VARIANT_ROWS(PT_TRACE_VARIANT, _qry, Qry)
 PT_VARIANT_ACCESSOR(pt_query_kernel, _qry, Qry)
@@ -25,5 +26,5 @@ extern "C" __global__ __launch_bounds__(256) void pt_query_unpack_kernel(const p
   if (i < m) ptq::unpack_at(planes, plane, i, hits);
 }
 
-extern "C" const void* pt_query_pack_kernel_handle(void) { return reinterpret_cast<const void*>(pt_query_pack_kernel); }
-extern "C" const void* pt_query_unpack_kernel_handle(void) { return reinterpret_cast<const void*>(pt_query_unpack_kernel); }
+extern "C" const void* pt_query_pack_kernel_handle(void) { return ptcall::handle(ptsig::QueryPack{}, pt_query_pack_kernel); }
+extern "C" const void* pt_query_unpack_kernel_handle(void) { return ptcall::handle(ptsig::QueryUnpack{}, pt_query_unpack_kernel); }

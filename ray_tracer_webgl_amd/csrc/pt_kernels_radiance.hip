@@ -9,6 +9,7 @@
 // The thirteenth folds a batch, one thread per ray, by the statements of pt_radiance.hpp:
 //   pt_radiance_fold_kernel   n_passes slab texels of place i -> PtRayRadiance out[i]; the zero record where the staged ray is invalid
 #include "pt_trace_body.hpp"
+#include "pt_sigs.h"
 #include "pt_radiance.hpp"
 
 PT_VARIANT_ROWS(PT_TRACE_VARIANT, _rad, Rad)
@@ -21,4 +22,4 @@ extern "C" __global__ __launch_bounds__(256) void pt_radiance_fold_kernel(const 
   if (i < m) ptr::fold_at(slab, plane, n_passes, rays, i, out);
 }
 
-extern "C" const void* pt_radiance_fold_kernel_handle(void) { return reinterpret_cast<const void*>(pt_radiance_fold_kernel); }
+extern "C" const void* pt_radiance_fold_kernel_handle(void) { return ptcall::handle(ptsig::RadianceFold{}, pt_radiance_fold_kernel); }

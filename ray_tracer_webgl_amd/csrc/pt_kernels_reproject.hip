@@ -18,6 +18,7 @@
 
 #include "pt_reproject.hpp"
 #include "pt_extra.h"
+#include "pt_sigs.h"
 
 namespace {
 
@@ -133,5 +134,5 @@ extern "C" __global__ __launch_bounds__(256) void pt_reproject_estimate_kernel(c
   }
 }
 
-extern "C" const void* pt_reproject_kernel_handle(void) { return reinterpret_cast<const void*>(pt_reproject_kernel); }
-extern "C" const void* pt_reproject_estimate_kernel_handle(void) { return reinterpret_cast<const void*>(pt_reproject_estimate_kernel); }
+extern "C" const void* pt_reproject_kernel_handle(void) { return ptcall::handle(ptsig::Reproject{}, pt_reproject_kernel); }
+extern "C" const void* pt_reproject_estimate_kernel_handle(void) { return ptcall::handle(ptsig::ReprojectEstimate{}, pt_reproject_estimate_kernel); }

@@ -20,6 +20,48 @@ class PtError(RuntimeError):
         self.code = code
 
 
+class _Arrays:
+    """The array library of one call, chosen once: numpy on the host (`torch` None), or torch on `device`.  What the entry points
+    that take or give arrays need of either: a contiguous float32 copy of an input where it must live (`f32`; `rows`: as
+    (n, k)), fresh arrays (`zeros`, `empty`: numpy dtypes name the element type for both), the pointer the library takes
+    (`ptr`), a reinterpreting view (`view`), and `cat`, `where` and `at_least` (an element-wise lower bound)."""
+
+    def __init__(self, torch=None, device=None):
+        self.torch, self.device = torch, device
+
+    def _dtype(self, dtype):
+        return getattr(self.torch, np.dtype(dtype).name) if self.torch else dtype
+
+    def f32(self, v):
+        if self.torch:
+            return v.to(device=self.device, dtype=self.torch.float32).contiguous()
+        return np.ascontiguousarray(v, dtype=np.float32)
+
+    def rows(self, v, k=3):
+        return self.f32(v).reshape(-1, k)
+
+    def zeros(self, shape, dtype=np.float32):
+        return self.torch.zeros(shape, dtype=self._dtype(dtype), device=self.device) if self.torch else np.zeros(shape, dtype)
+
+    def empty(self, shape, dtype=np.float32):
+        return self.torch.empty(shape, dtype=self._dtype(dtype), device=self.device) if self.torch else np.empty(shape, dtype)
+
+    def ptr(self, a):
+        return C.c_void_p(a.data_ptr()) if self.torch else a.ctypes.data_as(C.c_void_p)
+
+    def view(self, a, dtype):
+        return a.view(self._dtype(dtype))
+
+    def cat(self, parts):
+        return self.torch.cat(parts, dim=1) if self.torch else np.concatenate(parts, axis=1)
+
+    def where(self, cond, a, b):
+        return (self.torch or np).where(cond, a, b)
+
+    def at_least(self, a, low):
+        return self.torch.clamp(a, min=low) if self.torch else np.maximum(a, np.float32(low))
+
+
 class PathTracer:
     def __init__(self, width, height, device=0, use_torch=False):
         self.lib = load()
@@ -78,6 +120,24 @@ class PathTracer:
 
     def __exit__(self, *exc):
         self.close()
+
+    def _arrays(self, device=None):
+        """the array library of a call: torch on `device` (a torch.device or its name), numpy for None"""
+        return _Arrays(self._torch, device) if device is not None else _Arrays()
+
+    def _device_of(self, v):
+        """the device of a torch device tensor under use_torch; None for anything else: a host array"""
+        return v.device if self.use_torch and self._torch.is_tensor(v) and v.is_cuda else None
+
+    def _rays(self, what, xp, origins, directions):
+        """the (n, 8) float32 PtRay records {origin, pad, direction, pad} of two (n, 3) inputs"""
+        o, d = xp.rows(origins), xp.rows(directions)
+        if o.shape != d.shape:
+            raise ValueError("%s: %d origins, %d directions" % (what, o.shape[0], d.shape[0]))
+        rays = xp.zeros((int(o.shape[0]), 8))
+        rays[:, 0:3] = o
+        rays[:, 4:7] = d
+        return rays
 
     # -- scene / uniforms -----------------------------------------------------------------------
     def set_spheres(self, spheres):
@@ -446,34 +506,13 @@ class PathTracer:
         -1 and the background in "albedo"; an invalid ray (a non-finite component, a direction of three zeros) has index
         abi.PT_RAY_INVALID.  numpy arrays give numpy arrays; under use_torch, torch device tensors give torch device tensors
         (no host copy, ordered on torch's stream).  Synchronous; nothing else of the context moves."""
-        on_device = self.use_torch and self._torch.is_tensor(origins) and origins.is_cuda
-        if on_device:
-            torch = self._torch
-            o = origins.to(torch.float32).reshape(-1, 3)
-            d = directions.to(device=o.device, dtype=torch.float32).reshape(-1, 3)
-            if o.shape != d.shape:
-                raise ValueError("query_rays: %d origins, %d directions" % (o.shape[0], d.shape[0]))
-            n = int(o.shape[0])
-            rays = torch.zeros((n, 8), dtype=torch.float32, device=o.device)
-            rays[:, 0:3] = o
-            rays[:, 4:7] = d
-            hits = torch.zeros((n, 16), dtype=torch.int32, device=o.device)
-            if n:
-                self._check(self.lib.pt_query_rays(self._ctx, C.c_void_p(rays.data_ptr()), n, C.c_void_p(hits.data_ptr())))
-            fl = hits.view(torch.float32)
-        else:
-            o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
-            d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
-            if o.shape != d.shape:
-                raise ValueError("query_rays: %d origins, %d directions" % (o.shape[0], d.shape[0]))
-            n = int(o.shape[0])
-            rays = np.zeros((n, 8), np.float32)
-            rays[:, 0:3] = o
-            rays[:, 4:7] = d
-            hits = np.zeros((n, 16), np.int32)
-            if n:
-                self._check(self.lib.pt_query_rays(self._ctx, rays.ctypes.data_as(C.c_void_p), n, hits.ctypes.data_as(C.c_void_p)))
-            fl = hits.view(np.float32)
+        xp = self._arrays(self._device_of(origins))
+        rays = self._rays("query_rays", xp, origins, directions)
+        n = int(rays.shape[0])
+        hits = xp.zeros((n, 16), np.int32)
+        if n:
+            self._check(self.lib.pt_query_rays(self._ctx, xp.ptr(rays), n, xp.ptr(hits)))
+        fl = xp.view(hits, np.float32)
         out = {}
         for name, a, b, integer in self._HIT_FIELDS:
             col = (hits if integer else fl)[:, a:b]
@@ -490,36 +529,14 @@ class PathTracer:
         use_torch, torch device tensors give torch device tensors.  Synchronous; nothing else of the context moves, first_pass
         included."""
         fn = self.lib.pt_query_radiance_nee if next_event else self.lib.pt_query_radiance
-        on_device = self.use_torch and self._torch.is_tensor(origins) and origins.is_cuda
-        if on_device:
-            torch = self._torch
-            o = origins.to(torch.float32).reshape(-1, 3)
-            d = directions.to(device=o.device, dtype=torch.float32).reshape(-1, 3)
-            if o.shape != d.shape:
-                raise ValueError("query_radiance: %d origins, %d directions" % (o.shape[0], d.shape[0]))
-            n = int(o.shape[0])
-            rays = torch.zeros((n, 8), dtype=torch.float32, device=o.device)
-            rays[:, 0:3] = o
-            rays[:, 4:7] = d
-            rec = torch.zeros((n, 4), dtype=torch.float32, device=o.device)
-            if n:
-                self._check(fn(self._ctx, C.c_void_p(rays.data_ptr()), n, int(passes), C.c_void_p(rec.data_ptr())))
-            samples = rec[:, 3]
-            mean = torch.where(samples[:, None] > 0, rec[:, 0:3] / torch.clamp(samples, min=1.0)[:, None], torch.zeros_like(rec[:, 0:3]))
-        else:
-            o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
-            d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
-            if o.shape != d.shape:
-                raise ValueError("query_radiance: %d origins, %d directions" % (o.shape[0], d.shape[0]))
-            n = int(o.shape[0])
-            rays = np.zeros((n, 8), np.float32)
-            rays[:, 0:3] = o
-            rays[:, 4:7] = d
-            rec = np.zeros((n, 4), np.float32)
-            if n:
-                self._check(fn(self._ctx, rays.ctypes.data_as(C.c_void_p), n, int(passes), rec.ctypes.data_as(C.c_void_p)))
-            samples = rec[:, 3]
-            mean = np.where(samples[:, None] > 0, rec[:, 0:3] / np.maximum(samples, np.float32(1.0))[:, None], np.float32(0.0)).astype(np.float32)
+        xp = self._arrays(self._device_of(origins))
+        rays = self._rays("query_radiance", xp, origins, directions)
+        n = int(rays.shape[0])
+        rec = xp.zeros((n, 4))
+        if n:
+            self._check(fn(self._ctx, xp.ptr(rays), n, int(passes), xp.ptr(rec)))
+        samples = rec[:, 3]
+        mean = xp.where(samples[:, None] > 0, rec[:, 0:3] / xp.at_least(samples, 1.0)[:, None], xp.zeros((n, 3)))
         return {"sum": rec[:, 0:3], "samples": samples, "mean": mean}
 
     # -- gather queries: irradiance at points and SH probes (include/ptrace.h pt_gather_irradiance, pt_bake_probes) --
@@ -528,27 +545,19 @@ class PathTracer:
         tensors under use_torch"""
         if not (abi.PT_GATHER_MIN_DIRECTIONS <= int(directions) <= abi.PT_GATHER_MAX_DIRECTIONS and int(directions) % 64 == 0):
             raise ValueError("%s: %d directions (a multiple of 64 in [%d, %d])" % (what, directions, abi.PT_GATHER_MIN_DIRECTIONS, abi.PT_GATHER_MAX_DIRECTIONS))
-        if self.use_torch and self._torch.is_tensor(positions) and positions.is_cuda:
-            torch = self._torch
-            three = lambda v: v.to(device=positions.device, dtype=torch.float32).reshape(-1, 3)
-            zeros = lambda shape: torch.zeros(shape, dtype=torch.float32, device=positions.device)
-            ptr = lambda a: C.c_void_p(a.data_ptr())
-        else:
-            three = lambda v: np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
-            zeros = lambda shape: np.zeros(shape, np.float32)
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        pos = three(positions)
+        xp = self._arrays(self._device_of(positions))
+        pos = xp.rows(positions)
         n = int(pos.shape[0])
-        items = zeros((n, 8))  # PtGatherPoint: {position, pad, normal, pad}
+        items = xp.zeros((n, 8))  # PtGatherPoint: {position, pad, normal, pad}
         items[:, 0:3] = pos
         if normals is not None:
-            nrm = three(normals)
+            nrm = xp.rows(normals)
             if nrm.shape != pos.shape:
                 raise ValueError("%s: %d positions, %d normals" % (what, n, nrm.shape[0]))
             items[:, 4:7] = nrm
-        rec = zeros((n, floats))
+        rec = xp.zeros((n, floats))
         if n:
-            self._check(fn(self._ctx, ptr(items), n, int(directions), int(passes), ptr(rec)))
+            self._check(fn(self._ctx, xp.ptr(items), n, int(directions), int(passes), xp.ptr(rec)))
         return rec
 
     def gather_irradiance(self, points, normals, directions=256, passes=1, next_event=False):
@@ -584,14 +593,10 @@ class PathTracer:
         n = lat.nodes - int(first) if count is None else int(count)
         if n < 0:
             raise ValueError("bake_lattice: first %d beyond the lattice's %d nodes" % (first, lat.nodes))
-        if self.use_torch:
-            rec = self._torch.zeros((n, 28), dtype=self._torch.float32, device="cuda:%d" % self.device)
-            ptr = C.c_void_p(rec.data_ptr())
-        else:
-            rec = np.zeros((n, 28), np.float32)
-            ptr = rec.ctypes.data_as(C.c_void_p)
+        xp = self._arrays("cuda:%d" % self.device if self.use_torch else None)
+        rec = xp.zeros((n, 28))
         # (count == 0 too: the call says whether the lattice and the slice are valid)
-        self._check(self.lib.pt_bake_lattice(self._ctx, C.byref(lat), int(first), n, int(directions), int(passes), 1 if next_event else 0, ptr))
+        self._check(self.lib.pt_bake_lattice(self._ctx, C.byref(lat), int(first), n, int(directions), int(passes), 1 if next_event else 0, xp.ptr(rec)))
         return {"sh": rec[:, 0:27].reshape(-1, 9, 3), "samples": rec[:, 27]}
 
     def probe_lit_image(self, lattice, probes, options=None):
@@ -603,27 +608,15 @@ class PathTracer:
         the half-space test on, no bias)."""
         lat = lattice.copy()
         on_device = self.use_torch and self._torch.is_tensor(probes["sh"] if isinstance(probes, dict) else probes)
-        if on_device:
-            torch = self._torch
-            if isinstance(probes, dict):
-                rec = torch.cat([probes["sh"].reshape(-1, 27), probes["samples"].reshape(-1, 1)], dim=1)
-            else:
-                rec = probes
-            rec = rec.to(device="cuda:%d" % self.device, dtype=torch.float32).contiguous()
-            out = torch.empty((self.local_rows, self.width, 4), dtype=torch.float32, device=rec.device)
-            pr, po = C.c_void_p(rec.data_ptr()), C.c_void_p(out.data_ptr())
-        else:
-            if isinstance(probes, dict):
-                rec = np.concatenate([np.asarray(probes["sh"], np.float32).reshape(-1, 27), np.asarray(probes["samples"], np.float32).reshape(-1, 1)], axis=1)
-            else:
-                rec = probes
-            rec = np.ascontiguousarray(rec, dtype=np.float32)
-            out = np.empty((self.local_rows, self.width, 4), np.float32)
-            pr, po = rec.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+        xp = self._arrays("cuda:%d" % self.device if on_device else None)
+        if isinstance(probes, dict):
+            probes = xp.cat([xp.f32(probes["sh"]).reshape(-1, 27), xp.f32(probes["samples"]).reshape(-1, 1)])
+        rec = xp.f32(probes)
+        out = xp.empty((self.local_rows, self.width, 4))
         if tuple(rec.shape) != (lat.nodes, 28):
             raise ValueError("probe_lit_image: records of shape %s for a lattice of %d nodes" % (tuple(rec.shape), lat.nodes))
         opt = C.byref(options) if options is not None else None
-        self._check(self.lib.pt_shade_probes(self._ctx, C.byref(lat), pr, opt, po))
+        self._check(self.lib.pt_shade_probes(self._ctx, C.byref(lat), xp.ptr(rec), opt, xp.ptr(out)))
         return out
 
     # -- exposure metering and the toned read-outs (include/ptrace.h PT_OPT_TONEMAP) -----------------
@@ -690,15 +683,10 @@ class PathTracer:
     def _toned(self, fn, dtype, options, src):
         opt = options if options is not None else abi.PtToneOptions()
         ptr, keep = self._tone_src(src)
-        if keep is not None and not isinstance(keep, np.ndarray):
-            out = self._torch.empty((self.local_rows, self.width, 4), dtype=self._torch.float32 if dtype == np.float32 else self._torch.uint8,
-                                    device=keep.device)
-            if out.numel():
-                self._check(fn(self._ctx, ptr, C.byref(opt), C.c_void_p(out.data_ptr())))
-            return out
-        out = np.empty((self.local_rows, self.width, 4), dtype=dtype)
-        if out.size:
-            self._check(fn(self._ctx, ptr, C.byref(opt), out.ctypes.data_as(C.c_void_p)))
+        xp = self._arrays(keep.device if keep is not None and not isinstance(keep, np.ndarray) else None)
+        out = xp.empty((self.local_rows, self.width, 4), dtype)
+        if self.local_rows * self.width:
+            self._check(fn(self._ctx, ptr, C.byref(opt), xp.ptr(out)))
         return out
 
     def toned_image(self, options=None, src=None):

@@ -1,7 +1,8 @@
 // gather_main.cpp — a stand-alone program over csrc/pt_gather.hpp for -fsanitize=address,undefined: the sweep of
 // tests/gather_sweep.hpp — every j of every direction count, every normal, the reduction over exactly sized heap arrays with
 // mixed signs, a zero and a NaN — through the functions the kernels compile.  A direction that is not finite or not of unit
-// length, a read past an item's records or an index past the accumulators is a report, not a wrong bit.
+// length, a read past an item's records or an index past the accumulators is a report, not a wrong bit.  And the item span of a
+// gather batch (item_span) against the enumeration ray by ray, with the bound that keeps a batch's items inside the workspace.
 // tests/test_gather_ref.py builds it and runs it as a child; nothing sanitized is loaded into Python.
 #include <cmath>
 #include <cstdio>
@@ -17,7 +18,36 @@ static bool unit(const float w[3]) {
   return std::fabs(l2 - 1.0) < 1e-5;
 }
 
+// item_span against the enumeration ray by ray of the batch [first, first + m) of items of D rays
+static bool span_ok(uint32_t first, uint32_t m, uint32_t D, uint32_t plane) {
+  const ptgather::ItemSpan s = ptgather::item_span(first, m, D);
+  uint32_t lo = 0, hi = 0, done_lo = 0, done_n = 0;
+  for (uint64_t ray = first; ray < (uint64_t)first + m; ray++) {
+    const uint32_t item = (uint32_t)(ray / D);
+    if (ray == first) lo = item;
+    hi = item;
+    if (ray % D == D - 1u) {
+      if (!done_n) done_lo = item;
+      done_n++;
+    }
+  }
+  if (!done_n) done_lo = lo;  // (an empty range starts at the first item touched)
+  const bool same = s.item0 == lo && s.items == hi - lo + 1u && s.done0 == done_lo && s.done1 == done_lo + done_n;
+  const bool fits = s.items <= ptgather::items_per_batch(plane) && s.items <= plane / ptgather::kMinDirections + 2u && s.done0 == s.item0 && s.done1 <= s.item0 + s.items;
+  if (!same || !fits) std::printf("gather: item_span(%u, %u, %u) = {%u, %u, %u, %u}, plane %u\n", first, m, D, s.item0, s.items, s.done0, s.done1, plane);
+  return same && fits;
+}
+
 int main() {
+  // every batch of calls of 1 to 5 items, and the last batch (the 64-bit sum) of the largest call there is
+  for (uint32_t plane : {64u, 72u, 100u, 4096u})
+    for (uint32_t D : {64u, 128u, 256u, 4096u}) {
+      for (uint32_t n = 1; n <= 5; n++)
+        for (uint32_t first = 0; first < n * D; first += plane)
+          if (!span_ok(first, n * D - first < plane ? n * D - first : plane, D, plane)) return 1;
+      const uint32_t total = 0xffffffffu / D * D, last = (total - 1u) / plane * plane;
+      if (!span_ok(last, total - last, D, plane)) return 1;
+    }
   for (uint32_t D : {0u, 63u, 64u, 65u, 128u, 4096u, 4160u})
     if (ptgather::directions_valid(D) != (D == 64u || D == 128u || D == 4096u)) { std::printf("gather: directions_valid(%u)\n", D); return 1; }
   if (ptgather::total_rays(0x4000000u, 64u) != 0ull || ptgather::total_rays(0x3ffffffu, 64u) != 0xffffffc0ull) { std::printf("gather: total_rays\n"); return 1; }

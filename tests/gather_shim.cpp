@@ -33,6 +33,11 @@ extern "C" {
 int gth_directions_valid(uint32_t D) { return ptgather::directions_valid(D) ? 1 : 0; }
 uint64_t gth_total_rays(uint32_t n, uint32_t D) { return ptgather::total_rays(n, D); }
 uint32_t gth_items_per_batch(uint32_t batch) { return ptgather::items_per_batch(batch); }
+// the items the batch of rays [first, first + m) touches: {item0, items, done0, done1}
+void gth_item_span(uint32_t first, uint32_t m, uint32_t D, uint32_t out[4]) {
+  const ptgather::ItemSpan s = ptgather::item_span(first, m, D);
+  out[0] = s.item0; out[1] = s.items; out[2] = s.done0; out[3] = s.done1;
+}
 int gth_item_valid(const PtGatherPoint* p, int kind) { return ptgather::item_valid(*p, kind) ? 1 : 0; }
 float gth_stratum(uint32_t j, uint32_t D) { return ptgather::stratum(j, D); }
 float gth_turn(uint32_t j) { return ptgather::turn(j); }

@@ -66,6 +66,7 @@ def shim():
     lib.gth_directions_valid.argtypes = [u32]
     lib.gth_total_rays.restype, lib.gth_total_rays.argtypes = u64, [u32, u32]
     lib.gth_items_per_batch.restype, lib.gth_items_per_batch.argtypes = u32, [u32]
+    lib.gth_item_span.restype, lib.gth_item_span.argtypes = None, [u32, u32, u32, C.POINTER(u32)]
     lib.gth_item_valid.argtypes = [vp, C.c_int]
     lib.gth_stratum.restype, lib.gth_stratum.argtypes = C.c_float, [u32, u32]
     lib.gth_turn.restype, lib.gth_turn.argtypes = C.c_float, [u32]
@@ -386,11 +387,12 @@ def test_the_header_carries_the_contract():
 
 def test_the_error_wording_and_their_order_in_the_source():
     api = open(os.path.join(ROOT, "ray_tracer_webgl_amd", "csrc", "pt_api.hip")).read()
-    body = api[api.index("static int gather("):api.index("PT_API int pt_gather_irradiance")]
-    order = ["query_ready(c, who", "n_passes == 0", "passes > %u reserved", "directions (a multiple of 64 in", "are more than 2^32 - 1 rays", "c->gather.fit(e)",
-             "hipLaunchKernel"]
+    body = api[api.index("static int passes_ready("):api.index("static int radiance_batch(")] + api[api.index("static int gather_ready("):api.index("PT_API int pt_gather_irradiance")]
+    order = ["n_passes == 0", "passes > %u reserved", "query_ready(c, who", "passes_ready(c, who", "directions (a multiple of 64 in", "are more than 2^32 - 1 rays",
+             "estimator_ready(c, who", "static int gather_batches(", "c->gather.fit(e)", "call(ptsig::GatherRays{}", "static int gather(", "gather_ready(c, who", "return gather_batches("]
     at = [body.index(s) for s in order]
     assert at == sorted(at), "pt_query_radiance's checks in its order, then directions, then the workspace, then the first launch"
+    assert api.count("directions (a multiple of 64 in") == api.count("are more than 2^32 - 1 rays") == api.count("passes > %u reserved (pt_reserve_passes)\", who") == 1, "stated once"
     assert "unknown key %d" in api and not re.search(r"#define\s+PT_OPT_\w+\s+14\b", open(HEADER).read()), "no new option key"
     assert 14 not in [v for k, v in vars(abi).items() if k.startswith("PT_OPT_")]
 
@@ -412,6 +414,58 @@ def test_counts_and_batches(shim):
     for B in (1, 63, 64, 240, 512, 777):
         worst = max((first + B - 1) // D - first // D + 1 for D in (64, 128, 4096) for first in range(0, 3 * D))
         assert worst <= shim.gth_items_per_batch(B) == B // 64 + 2, (B, worst)
+
+
+def item_span(shim, first, m, D):
+    out = (C.c_uint32 * 4)()
+    shim.gth_item_span(first, m, D, out)
+    return tuple(out)
+
+
+def span_by_enumeration(first, m, D):
+    """{item0, items, done0, done1} of the batch of rays [first, first + m), ray by ray: the items the rays belong to, and those
+    whose last ray is among them (a range from the first item touched on: an item that started earlier ends first)"""
+    rays = np.arange(first, first + m, dtype=np.uint64)
+    items = rays // np.uint64(D)
+    done = items[rays % np.uint64(D) == D - 1]
+    assert (np.diff(items) <= 1).all() and (len(done) == 0 or done[0] == items[0])
+    return int(items[0]), int(items[-1] - items[0]) + 1, int(items[0]), int(items[0]) + len(done)
+
+
+def test_the_item_span_of_every_batch_equals_the_enumeration(shim):
+    """csrc/pt_gather.hpp item_span, which sizes what a gather batch stages, reduces and copies (pt_api.hip gather_batches):
+    every batch of calls of 1 to 5 items over the planes and direction counts below, ray by ray; and the bound that keeps the
+    staged points and records inside GatherSet::work — never more items than plane / kMinDirections + 2, GatherSet::items'
+    own expression."""
+    assert "return e.pix / ptgather::kMinDirections + 2;" in open(os.path.join(ROOT, "ray_tracer_webgl_amd", "csrc", "pt_buffers.hpp")).read()
+    most = 0
+    for plane in (64, 72, 100, 4096):
+        for D in (64, 128, 256, 4096):
+            for n in range(1, 6):
+                for first in range(0, n * D, plane):
+                    m = min(plane, n * D - first)
+                    got = item_span(shim, first, m, D)
+                    assert got == span_by_enumeration(first, m, D), (plane, D, n, first)
+                    assert got[1] <= plane // abi.PT_GATHER_MIN_DIRECTIONS + 2 == shim.gth_items_per_batch(plane), (plane, D, n, first)
+                    most = max(most, got[1] - plane // 64)
+    assert most == 2, "the bound is met: whole items and a straddling one at either end"
+    assert abi.PT_GATHER_MIN_DIRECTIONS == 64
+    # an item that straddles two batches (item 1 of D = 64 over planes of 100): touched by both, ends in the second
+    assert item_span(shim, 0, 100, 64) == (0, 2, 0, 1)
+    # ... whose first item only reads the carry and whose last only writes it: items 1 .. 3, of which 1 and 2 end
+    assert item_span(shim, 100, 100, 64) == (1, 3, 1, 3)
+    # an item that fills a whole batch and ends in neither it nor the one before: nothing is written
+    assert item_span(shim, 64, 64, 256) == (0, 1, 0, 0) and item_span(shim, 128, 64, 256) == (0, 1, 0, 0) and item_span(shim, 192, 64, 256) == (0, 1, 0, 1)
+    # a short last batch: 28 rays of 2 items of 64 over planes of 100
+    assert item_span(shim, 100, 28, 64) == (1, 1, 1, 2)
+    # the last batch of the largest call there is (67108863 items of 64: 2^32 - 64 rays) over planes of 4096 ...
+    total = 67108863 * 64
+    first = (total - 1) // 4096 * 4096
+    assert first + (total - first) > 2 ** 32 - 1 - 64
+    assert item_span(shim, first, total - first, 64) == (first // 64, 63, first // 64, 67108863) == span_by_enumeration(first, total - first, 64)
+    # ... and a batch that ends at ray 2^32 itself: first + m in 32 bits would be 0
+    assert item_span(shim, 2 ** 32 - 64, 64, 64) == (2 ** 26 - 1, 1, 2 ** 26 - 1, 2 ** 26)
+    assert item_span(shim, 2 ** 32 - 100, 99, 4096) == (2 ** 20 - 1, 1, 2 ** 20 - 1, 2 ** 20 - 1)
 
 
 def test_the_workspace_is_in_place_or_refused(shim):

@@ -273,14 +273,18 @@ def test_the_lattice_and_option_checks_and_their_wording(shim):
         assert (got.decode() if got else None) == want == P.options_error(flags, bias)
     api = open(os.path.join(ROOT, "ray_tracer_webgl_amd", "csrc", "pt_api.hip")).read()
     body = api[api.index("PT_API int pt_bake_lattice("):api.index("PT_API int pt_shade_probes(")]
-    order = ["ptprobe::lattice_error", "estimator %d", "ptprobe::slice_valid", "count == 0", "query_ready(c, who", "n_passes == 0", "passes > %u reserved",
-             "directions (a multiple of 64 in", "estimator_ready(c, who", "c->probe.fit_points", "hipLaunchKernel", "return gather(c, who, ptgather::PROBE"]
+    order = ["ptprobe::lattice_error", "estimator %d", "ptprobe::slice_valid", "count == 0", "gather_ready(c, who, next_event, lattice", "c->probe.fit_points",
+             "call(ptsig::ProbePoints{}", "return gather_batches(c, who, ptgather::PROBE"]
     at = [body.index(s) for s in order]
     assert at == sorted(at), "the lattice's own checks, the gather call's, the point buffer, the generator, then the one bake loop"
-    assert body.count("hipLaunchKernel") == 1, "no second copy of the bake loop"
+    assert body.count("call(ptsig::") == 1 and "query_ready" not in body and "passes_ready" not in body, "no second copy of the bake loop or of the gather calls' checks"
+    ready = api[api.index("static int gather_ready("):api.index("static int gather_batches(")]
+    order = ["query_ready(c, who", "passes_ready(c, who", "directions (a multiple of 64 in", "are more than 2^32 - 1 rays", "estimator_ready(c, who"]
+    at = [ready.index(s) for s in order]
+    assert at == sorted(at), "what pt_bake_lattice refuses before its generator runs: the gather calls' checks in their order"
     body = api[api.index("PT_API int pt_shade_probes("):]
     order = ["ptprobe::lattice_error", "ptprobe::options_error", "not with PT_OPT_COUNT_WORK", "SET_FEATURES", "c->feat.valid", "is_capturing", "c->local_rows == 0",
-             "c->probe.fit_stage", "hipLaunchKernel"]
+             "c->probe.fit_stage", "call(ptsig::ProbeShadeShared{}", "call(ptsig::ProbeShade{}"]
     at = [body.index(s) for s in order]
     assert at == sorted(at)
     assert "unknown key %d" in api and not re.search(r"#define\s+PT_OPT_\w+\s+14\b", open(HEADER).read()), "no new option key"

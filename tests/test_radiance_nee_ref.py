@@ -284,12 +284,18 @@ def test_the_launch_text_that_must_stay_and_the_transport():
     # one body each: the estimator is a parameter
     assert api.count("static int query_radiance(") == 1 and api.count("static int gather(") == 1
     body = api[api.index("static int query_radiance("):api.index("PT_API int pt_query_radiance(")]
-    order = ["query_ready(c, who", "n_passes == 0", "passes > %u reserved", "estimator_ready(c, who, next_event)", "stage_rays(", "trace_once("]
+    order = ["query_ready(c, who", "passes_ready(c, who", "estimator_ready(c, who, next_event)", "stage_rays(", "radiance_batch(c, who, next_event"]
     at = [body.index(s) for s in order]
     assert at == sorted(at), "the namesake's checks in its order, then the option"
-    body = api[api.index("static int gather("):api.index("PT_API int pt_gather_irradiance")]
-    order = ["query_ready(c, who", "n_passes == 0", "passes > %u reserved", "directions (a multiple of 64 in", "are more than 2^32 - 1 rays", "estimator_ready(c, who, next_event)",
-             "c->gather.fit(e)", "hipLaunchKernel"]
+    passes = api[api.index("static int passes_ready("):api.index("static int radiance_batch(")]
+    assert passes.index("n_passes == 0") < passes.index("passes > %u reserved")
+    # one batch body for both estimators and both families: the estimator reaches the launch through it
+    batch = api[api.index("static int radiance_batch("):api.index("static int query_radiance(")]
+    assert "use.next_event = next_event;" in batch and api.count("use.next_event = next_event;") == 1 and batch.index("trace_once(") < batch.index("call(ptsig::RadianceFold{}")
+    body = api[api.index("static int gather_ready("):api.index("PT_API int pt_gather_irradiance")]
+    order = ["query_ready(c, who", "passes_ready(c, who", "directions (a multiple of 64 in", "are more than 2^32 - 1 rays", "estimator_ready(c, who, next_event)",
+             "static int gather_batches(", "c->gather.fit(e)", "call(ptsig::GatherRays{}", "radiance_batch(c, who, next_event", "static int gather(", "gather_ready(c, who, next_event",
+             "return gather_batches("]
     at = [body.index(s) for s in order]
     assert at == sorted(at)
     assert '"next-event estimation is off (pt_set_option PT_OPT_NEXT_EVENT)"' in api and '"ray queries are off (pt_set_option PT_OPT_RAY_QUERIES)"' in api
